@@ -9,10 +9,17 @@ keyframe, LiDAR + IMU + GNSS DD-pseudorange/Doppler + marginalization prior, syn
 the timed region starts.  The sliding window does not shard ("replicas only"), so with
 --gpus N every rank solves its own window and `value` is the aggregate (weak scaling).
 
-The line also carries: `roofline` for the dominant kernel (K3: 40 algorithmic bytes per LiDAR residual,
+A plain run sets up, warms up, times the --steps solves and prints the headline line only.  With --full
+the line also carries: `roofline` for the dominant kernel (K3: 40 algorithmic bytes per LiDAR residual,
 timed with HIP events on the context's stream), `cpu_baseline` (the CPU oracle = a restatement of the
-reference's Ceres path, 1 thread, timed on this box on a bounded sample; N=1 only) and the per-stage
-timings of the correspondence search (BASELINE config C3) for information.
+reference's Ceres path, 1 thread, timed on this box on a bounded sample; N=1 only), the per-stage
+timings of the correspondence search (BASELINE config C3) and the other sections for information, and
+the complete record goes to bench_full.json.
+
+--dump-outputs DIR writes what the last timed solve returned (rank 0's window): DIR/trans.npy [W][3],
+quat.npy [W][4], speed_bias.npy [W][9], rcv_ddt.npy [n_ddt] and summary.npy (the glio_summary fields in
+their C order: iterations, successful_steps, termination, n_lidar_residuals, initial_cost, final_cost,
+final_radius, gradient_max_norm), all float64.  The inputs depend only on the arguments.
 """
 import argparse
 import json
@@ -49,13 +56,18 @@ def main():
     ap.add_argument("--no-bassoc", action="store_true")
     ap.add_argument("--no-c5", action="store_true")
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: the ranks only rendezvous (gloo) and rank 0 prints a line (CPU test of the launcher)")
+    ap.add_argument("--full", action="store_true", help="after the headline, every informational section (CPU baselines, other sizes and configurations, "
+                                                        "roofline and per-kernel timings, ...) and the complete record in bench_full.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed solve returned as float64 .npy files under DIR")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # `python bench.py --gpus N` without a launcher around it: be the launcher (one process per GPU, RCCL rendezvous on 127.0.0.1)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))
     if args.dry_run:
-        return dry_run()
+        return dry_run(args.full)
 
     # exactly ONE line on stdout: libraries print there too (RCCL's version banner when a communicator is created, from C stdio at exit), so the
     # process's stdout descriptor points at stderr for the whole run and the JSON line goes to a private copy of the original descriptor
@@ -133,6 +145,27 @@ def main():
     total_steps = args.steps * world
     value = total_steps / elapsed
     ms_per_step = 1e3 * elapsed / args.steps
+    line = {
+        "metric": "sliding-window solves/sec (64k pts, 20 keyframes)", "value": round(value, 3), "unit": "solves/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"C2: {args.window}-keyframe window x {args.points} surf pts/keyframe, LiDAR+IMU+GNSS(DD-psr,Doppler)+prior, "
+                               "prior = device marginalization of the previous window (steady state), correspondences resident (pre-associated), Huber(1.0), dogleg, <=15 iterations",
+                   "lidar_residuals": n_res, "unknowns": 15 * win.W + state.n_ddt, "parallelism": f"replicas x{world}"},
+        "iterations": int(summ.iterations), "ms_per_iteration": round(ms_per_step / max(1, int(summ.iterations)), 4),
+        "termination": int(summ.termination), "solver_path": {0: "dense", 1: "arrow", 2: "keyframe chain"}.get(int(capi.load().glio_debug_solver_path(ctx._h)), "?"),
+    }
+    if share_gpu:
+        line["shared_gpu"] = f"{world} processes on ONE GPU, gloo through the host (GLIO_BENCH_SHARE_GPU=1): a test of the N-process path, not a scaling measurement"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sol, summ)
+    if not args.full:
+        if rank == 0:
+            os.write(out_fd, (json.dumps(_strict(line), allow_nan=False, separators=(",", ":")) + "\n").encode())
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     batch_info = None
     if not args.no_batch:
@@ -408,15 +441,7 @@ def main():
         pass
     roofline["others"] = others
 
-    line = {
-        "metric": "sliding-window solves/sec (64k pts, 20 keyframes)", "value": round(value, 3), "unit": "solves/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"C2: {args.window}-keyframe window x {args.points} surf pts/keyframe, LiDAR+IMU+GNSS(DD-psr,Doppler)+prior, "
-                               "prior = device marginalization of the previous window (steady state), correspondences resident (pre-associated), Huber(1.0), dogleg, <=15 iterations",
-                   "lidar_residuals": n_res, "unknowns": 15 * win.W + state.n_ddt, "parallelism": f"replicas x{world}"},
-        "iterations": int(summ.iterations), "ms_per_iteration": round(ms_per_step / max(1, int(summ.iterations)), 4),
-        "termination": int(summ.termination), "solver_path": {0: "dense", 1: "arrow", 2: "keyframe chain"}.get(int(capi.load().glio_debug_solver_path(ctx._h)), "?"),
+    line.update({
         "dense_prior_variant": dense_variant,
         "window_sizes": window_sizes, "concurrent_windows_one_gpu": concurrent,
         "kernels_us": {"lidar_linearize": round(k3_ms * 1e3, 2), "full_linearize": round(lin_ms * 1e3, 2), "tr_step": round(trs_ms * 1e3, 2), "tr_step_later_iterations": round(trs_steady_ms * 1e3, 2),
@@ -424,7 +449,7 @@ def main():
         "roofline": roofline, "cpu_baseline": cpu, "cpu_baselines_other_configs": cpu_more, "pose_vs_oracle": pose_err, "association": assoc,
         "association_c3": c3_info, "c5_stress": c5_info, "batch_stage": batch_info, "batch_association": bassoc_info, "local_map": localmap_info, "front_end_odometry": odometry_info, "keyframe_pipeline": pipeline_info,
         "released_config": released_info,
-    }
+    })
     # The whole reference function per keyframe (optimizeSlidingWindowWithLandMark from the new scan to the end of batchFeatureAssociation), driven from C++:
     # the figure to hold next to `value`, which times the solve of a pre-associated window only (BASELINE config 2)
     try:
@@ -440,8 +465,6 @@ def main():
                 "solve_only_share_of_the_cycle": round(ms_per_step / cppk["cycle_ms"], 3)}
     except (KeyError, TypeError, ZeroDivisionError):
         pass
-    if share_gpu:
-        line["shared_gpu"] = f"{world} processes on ONE GPU, gloo through the host (GLIO_BENCH_SHARE_GPU=1): a test of the N-process path, not a scaling measurement"
     if c3_info:
         c3_info.pop("_cpu_sample", None)
     if cpu and "value" in cpu:
@@ -482,6 +505,19 @@ def _strict(o):
 
 def _pick(d, keys):
     return {k: d[k] for k in keys if isinstance(d, dict) and k in d}
+
+
+HEADLINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
+                 "iterations", "ms_per_iteration", "termination", "solver_path", "shared_gpu")
+
+
+def dump_outputs(out_dir, sol, summ):
+    """--dump-outputs: what glio_solve returned in the last timed step (the solved window state and its summary), as float64 .npy files"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"trans": sol.trans, "quat": sol.quat, "speed_bias": sol.speed_bias, "rcv_ddt": sol.rcv_ddt[:sol.n_ddt],
+              "summary": [float(getattr(summ, k)) for k, _ in summ._fields_]}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def write_full_record(line):
@@ -690,8 +726,9 @@ def launch_ranks(n):
     return rc
 
 
-def dry_run():
-    """The launcher's CPU test: every rank joins a gloo group, an all-reduce proves they see each other, rank 0 prints a line."""
+def dry_run(full=False):
+    """The launcher's CPU test: every rank joins a gloo group, an all-reduce proves they see each other, rank 0 prints a line
+    (the headline keys of a plain run; with `full` the line of a --full run)."""
     import torch
     import torch.distributed as dist
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
@@ -717,7 +754,7 @@ def dry_run():
         if isinstance(rec.get("batch_stage"), dict):
             rec["batch_stage"]["rccl_ranks_seen"] = 0        # gloo here: RCCL saw nobody
             rec["batch_stage"]["n1_reference"] = n1_reference(rec["batch_stage"].get("constraints_total"))
-        short = json.loads(compact_line(rec))
+        short = json.loads(compact_line(rec)) if full else _strict({k: rec[k] for k in HEADLINE_KEYS if k in rec})
         short.update({"dry_run": True, "rank_sum": float(t.item())})
         print(json.dumps(short, allow_nan=False, separators=(",", ":")))
     if world > 1:

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 for CNT in FETCH_SIZE WRITE_SIZE; do
   OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$CNT
   rm -rf $OUT; mkdir -p $OUT
-  rocprofv3 --pmc $CNT --output-format csv -d $OUT -o pmc -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-batch --no-c5 --no-bassoc > gpurun_out/pmc_$CNT.log 2>&1
+  rocprofv3 --pmc $CNT --output-format csv -d $OUT -o pmc -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-batch --no-c5 --no-bassoc > "$(dirname $OUT)/pmc_$CNT.log" 2>&1
   f=$(find $OUT -name "*counter_collection.csv" | head -1)
   python - "$f" $CNT <<'PY' | tee -a gpurun_out/k3_pmc.txt
 import csv, sys, collections, json, os
@@ -55,7 +55,7 @@ out = {"lidar_residuals": line["config"]["lidar_residuals"] if line else None, "
        "algorithmic_bytes_per_launch": line["roofline"]["bytes_per_launch"] if line else None,
        "linearize_all_launches_averaged": len(lav), "linearize_all_fetch_bytes_per_launch": la_fetch,
        "linearize_all_hbm_bytes_per_launch": (la_fetch + la_write) if la_fetch else None,
-       "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `python bench.py --steps 3 --warmup 1 "
+       "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `python bench.py --full --steps 3 --warmup 1 "
                  "--no-cpu-baseline --no-batch --no-c5 --no-bassoc`; FETCH_SIZE x2 (gfx950 wide-read correction), KB -> bytes"}
 json.dump(out, open("gpurun_out/k3_pmc.json", "w"), indent=1)
 print(json.dumps(out))

@@ -3,11 +3,11 @@
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-python bench.py --steps 50 --warmup 5 > gpurun_out/r06_bench_line.json 2> gpurun_out/r06_bench_line.err
-cp bench_full.json gpurun_out/r06_bench_full.json      # (the profiled runs below write their own bench_full.json)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o trace -- python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-c5 > gpurun_out/prof_bench.log 2>&1
+python bench.py --full --steps 50 --warmup 5 > "$(dirname $OUT)/r06_bench_line.json" 2> "$(dirname $OUT)/r06_bench_line.err"
+cp bench_full.json "$(dirname $OUT)/r06_bench_full.json"      # (the profiled runs below write their own bench_full.json)
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o trace -- python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-c5 > "$(dirname $OUT)/prof_bench.log" 2>&1
 for f in $(find $OUT -name "*kernel_stats.csv"); do cp $f gpurun_out/r06_bench_kernel_stats.csv; done
 rm -rf $OUT
 bash scripts/gpu_pmc.sh > gpurun_out/pmc_run.log 2>&1

@@ -113,9 +113,37 @@ def test_the_stdout_line_is_small_strict_json():
 def test_n2_line_carries_the_batch_stage_at_top_level_and_no_projection():
     """N > 1: the number a scaling record is about is the batch stage's strong-scaling time (the sliding window only replicates), so the compact line
     holds it at the top level together with the number of ranks RCCL saw; the 8-rank projection is not part of it."""
-    line = _run(None, "--gpus", "2", "--dry-run")
+    line = _run(None, "--gpus", "2", "--dry-run", "--full")
     bs = line["batch_stage"]
     for k in ("scaling", "ranks", "rccl_ranks_seen", "ms_solve", "ms_solve_per_group", "kernel_groups", "constraints_total"):
         assert k in bs, k
     assert bs["ranks"] == 2 and bs["scaling"] == "strong" and bs["rccl_ranks_seen"] == 0
     assert "projection" not in json.dumps(line) and "projected" not in json.dumps(line)
+
+
+def test_plain_line_is_the_headline_only():
+    """without --full the line holds the headline keys and nothing measured beside them (those sections need --full)"""
+    line = _run(None, "--gpus", "2", "--dry-run")
+    b = _bench_module()
+    assert set(line) - {"dry_run", "rank_sum"} <= set(b.HEADLINE_KEYS)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus"):
+        assert k in line, k
+    assert "roofline" not in line and "cpu_baseline" not in line and "batch_stage" not in line
+
+
+def test_dump_outputs_writes_the_solve_result_as_float64(tmp_path):
+    """--dump-outputs: one float64 .npy per array glio_solve returns, the summary in the C struct's field order"""
+    import numpy as np
+    from glio_amd import ctypes_types as T
+    b = _bench_module()
+    sol = T.WindowState(5, n_ddt=3)
+    sol.trans[:] = np.arange(15.0).reshape(5, 3)
+    sol.rcv_ddt[:] = [1.5, 2.5, 3.5]
+    summ = T.GlioSummary(iterations=4, termination=1, n_lidar_residuals=1000, final_cost=2.25)
+    b.dump_outputs(str(tmp_path / "out"), sol, summ)
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert sorted(got) == ["quat", "rcv_ddt", "speed_bias", "summary", "trans"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert got["trans"].shape == (5, 3) and np.array_equal(got["trans"], sol.trans) and got["quat"].shape == (5, 4) and got["speed_bias"].shape == (5, 9)
+    assert np.array_equal(got["rcv_ddt"], [1.5, 2.5, 3.5])
+    assert np.array_equal(got["summary"], [4, 0, 1, 1000, 0.0, 2.25, 0.0, 0.0])
