@@ -114,7 +114,16 @@ int glio_create(int device, const glio_opts* opts, glio_ctx** out) {
     const int W = opts->window;
     if (W < 1 || W > GLIO_MAX_WINDOW || opts->max_points_per_scan < 1) { glio_set_error("bad window / capacity"); return GLIO_E_ARG; }
     const int n_max = 15 * W + std::max(0, opts->max_ddt_epochs);
-    if (glio_tr_step_lds_bytes(n_max) > 160 * 1024) { glio_set_error("15*W + ddt = %d unknowns exceed the single-CU solver (LDS)", n_max); return GLIO_E_ARG; }
+    if (n_max > GLIO_MAX_UNKNOWNS || glio_tr_step_lds_bytes(n_max) > 160 * 1024) {
+        const int nd = std::max(0, opts->max_ddt_epochs), w_fit = (GLIO_MAX_UNKNOWNS - nd) / 15;
+        if (w_fit >= 1)
+            glio_set_error("15*W + ddt = 15*%d + %d = %d unknowns exceed GLIO_MAX_UNKNOWNS = %d (the dense solver's LDS): W <= %d with this many epochs",
+                           W, nd, n_max, GLIO_MAX_UNKNOWNS, w_fit);
+        else
+            glio_set_error("15*W + ddt = 15*%d + %d = %d unknowns exceed GLIO_MAX_UNKNOWNS = %d (the dense solver's LDS): %d epochs leave no room "
+                           "for a single keyframe (at most %d epochs with W = 1)", W, nd, n_max, GLIO_MAX_UNKNOWNS, nd, GLIO_MAX_UNKNOWNS - 15);
+        return GLIO_E_ARG;
+    }
     GLIO_HIP_CHECK(hipSetDevice(device));
     glio_ctx* c = new glio_ctx();
     memset(c, 0, sizeof *c);

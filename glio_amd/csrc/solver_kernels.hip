@@ -149,7 +149,7 @@ typedef double v2f64 __attribute__((ext_vector_type(2)));
 extern __shared__ __attribute__((aligned(16))) unsigned char tr_lds[];
 
 // LDS carve of the factor kernel
-__device__ __host__ __forceinline__ int bp_stride(int n) { return ((n + 15) & ~15) + 2; }   // even -> 16-B aligned rows
+__device__ __host__ __forceinline__ constexpr int bp_stride(int n) { return ((n + 15) & ~15) + 2; }   // even -> 16-B aligned rows
 
 // ------------------------------------------------------------------------------------------------
 // Blocked left-looking Cholesky of the leading n x n block of the (n+1) x n row-major matrix A (lower
@@ -2396,7 +2396,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_solve(const ChainArgs a, c
 #endif
     if ((bad || a.force_fail) && lane == 0) misc[0] = 1;
     __syncthreads();
-    if (misc[0]) { if (tid == 0) atomicOr(a.flag, 1); return; }
+    if (misc[0]) { if (tid == 0) { atomicOr(a.flag, 1); if (a.dbg) a.dbg[301] += 1; } return; }     // (slot 301: breakdowns handed to the dense fallback)
     // back substitution: meeting keyframe, then the two halves in parallel:  L_ii^T z_i = y_i - L_{nbr,i}^T z_nbr
     auto back = [&](const int i, const int nbr) {
         const double* Bi = Blk + (size_t)i * KC_BLK;
@@ -2461,7 +2461,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_solve(const ChainArgs a, c
     if (bd2 != 0.0) misc[0] = 1;
     __syncthreads();
     AR_STAMP(46);
-    if (tid == 0) { if (misc[0]) atomicOr(a.flag, 1); else *a.flag = 2; }
+    if (tid == 0) { if (misc[0]) { atomicOr(a.flag, 1); if (a.dbg) a.dbg[301] += 1; } else *a.flag = 2; }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2476,7 +2476,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_solve(const ChainArgs a, c
 // blocks (ChainBuilder) and factors it with the generic blocked Cholesky and Ceres' mu retries -- the outcome is the dense
 // one in every case, as before.
 // ------------------------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ size_t tr_step_lds_doubles(int n) {
+__host__ __device__ __forceinline__ constexpr size_t tr_step_lds_doubles(int n) {
     size_t d = (size_t)TR_NB * bp_stride(n);
     d += 16 * 256;
     d += (TR_NB + 1) * TR_PS;
@@ -2484,6 +2484,9 @@ __host__ __device__ __forceinline__ size_t tr_step_lds_doubles(int n) {
     d += 32 + 16;
     return d;
 }
+// the header's GLIO_MAX_UNKNOWNS is exactly the largest system this carve fits in 160 KiB of LDS
+static_assert(tr_step_lds_doubles(GLIO_MAX_UNKNOWNS) * 8 <= 160 * 1024 && tr_step_lds_doubles(GLIO_MAX_UNKNOWNS + 1) * 8 > 160 * 1024,
+              "GLIO_MAX_UNKNOWNS (glio_types.h) must be the largest n whose dense trust-region step fits the LDS");
 // byte offset of the gather tables inside k_chain_step's dynamic LDS: behind both carves that use the front of the array
 __host__ __device__ __forceinline__ size_t chain_step_tabs_offset(int W, int nd, int n) {
     const size_t a = chain_lds_doubles(W, nd) * 8, b = tr_step_lds_doubles(n) * 8;
@@ -3758,7 +3761,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
         GLIO_BLOCK_LDS_SYNC();
     }
     fast_tail = (a.fast & 1) && !misc[0];
-    if (tid == 0) { *a.flag = misc[0] ? 1 : 2; }
+    if (tid == 0) { *a.flag = misc[0] ? 1 : 2; if (misc[0] && a.dbg) a.dbg[301] += 1; }     // (slot 301: steps whose chain factorisation broke down -> dense rebuild)
     if (fast_tail) GLIO_BLOCK_LDS_SYNC(); else { __threadfence(); __syncthreads(); }      // (the generic tail reads t, z and the record back from global memory)
     AR_STAMP(49);
     }   // !dec.reuse
@@ -3939,6 +3942,8 @@ int glio_chain_kind(const glio_ctx* c, int n_ddt) {
     if (c->W >= KC_F4_MIN_W && chain_lds_doubles_g(c->W, n_ddt) * 8 + 8 * 1024 <= 158 * 1024) return 3;
     return 0;
 }
+// test hook: the chain kernel a step of this context would take with n_ddt clock-drift epochs (glio_chain_kind's numbering)
+extern "C" int glio_debug_chain_kind(const glio_ctx* c, int n_ddt) { return c ? glio_chain_kind(c, n_ddt) : -1; }
 // the linearisation must also build the dense H (k_assemble) unless the step is k_chain_step
 int glio_solver_needs_dense_H(const glio_ctx* c, int n_ddt) { return glio_chain_kind(c, n_ddt) != 1; }
 

@@ -159,9 +159,13 @@ inline void writeBackState(int W, const double* tmpTrans, const double* tmpQuat,
 
 // featureSelection (Estimator.cpp:3894-3992), the draws only: which of `count` correspondences of a slot stay.  Returns false when nothing changes
 // (count - 1 < feature_res_num: the early return at :3906-3909, quirk Q9 -- the set is kept WHOLE, not cut to feature_res_num); otherwise `kept` holds
-// the original indices in draw order: feature_res_num draws, each uniform over the records still left (the reference builds a no-repeat random array
-// over the remaining records and takes its LAST element, :3948-3957, then erases that record, :3964-3978 -- i.e. one uniform draw per kept record,
-// whatever rand_set_num is); random_select == false empties the slot (:3945 never enters the loop, :3981-3987 install the empty sets).
+// the original indices in draw order: feature_res_num draws.  The reference shuffles geneRandArrayNoRepeat(0, size - 1, rand_set_num)
+// (random_generator.hpp:79-93), i.e. the indices 0 .. size - 2 of the `size` records still left, takes element rand_set_num - 1 of the shuffle
+// (:3948-3957) and erases that record (:3964-3978): one draw uniform over the first size - 1 records left, whatever rand_set_num is -- the LAST record
+// still left is never drawn.  random_select == false empties the slot (:3945 never enters the loop, :3981-3987 install the empty sets).
+// The one count where the reference has no defined draw: count = feature_res_num + 1 with rand_set_num > 1 clamps rand_set_num to 0 (:3914-3916),
+// the shuffle is never read and selected_id stays -1 (a read before the first record).  This port does not reproduce that: it draws there as for
+// every other count (uniform over the first size - 1 records left), so parity is claimed for count > feature_res_num + 1 only.
 // rand_below(n): uniform integer in [0, n) -- the reference seeds from std::random_device (random_generator.hpp:58), so the generator is the caller's.
 // The Python twin is glio_amd/sliding.py::feature_selection_draws: same generator in, same indices out (tests/test_host_cpp.py).
 template <typename RandBelow>
@@ -169,12 +173,12 @@ inline bool featureSelectionDraws(int64_t count, int feature_res_num, RandBelow&
     kept.clear();
     if (count < 1 || count - 1 < (int64_t)feature_res_num) return false;
     if (!random_select) return true;
-    // the d-th draw picks the k-th record STILL LEFT (k uniform below count - d): its original index is k advanced past every removed index <= it.
+    // the d-th draw picks the k-th record STILL LEFT (k uniform below count - d - 1): its original index is k advanced past every removed index <= it.
     // `gone` stays sorted: O(feature_res_num^2) whatever the count (erasing from a 64k-element list per draw would be O(count) each)
     std::vector<int32_t> gone;
     gone.reserve((size_t)feature_res_num);
     for (int d = 0; d < feature_res_num; ++d) {
-        int64_t v = (int64_t)rand_below((uint64_t)(count - d));
+        int64_t v = (int64_t)rand_below((uint64_t)(count - d - 1));
         size_t pos = 0;
         while (pos < gone.size() && (int64_t)gone[pos] <= v) { ++v; ++pos; }
         gone.insert(gone.begin() + (std::ptrdiff_t)pos, (int32_t)v);

@@ -24,19 +24,23 @@ def unify_quaternions(state):
 def feature_selection_draws(count, feature_res_num, rng, random_select=True):
     """The index sequence `featureSelection` (Estimator.cpp:3894-3992) keeps, for `count` correspondences: nothing
     changes when count - 1 < feature_res_num (early return :3906-3909, quirk Q9); otherwise feature_res_num draws, each
-    uniform over the records still left (the reference builds a no-repeat random array and takes its last element,
-    :3948-3957, then erases the record, :3964-3978); with random_select == false the set is emptied (:3945,3981-3987).
+    uniform over the first size - 1 of the `size` records still left: the reference shuffles geneRandArrayNoRepeat(0,
+    size - 1, rand_set_num) = the indices 0 .. size - 2 (random_generator.hpp:79-93), takes element rand_set_num - 1
+    (:3948-3957) and erases that record (:3964-3978), so the last record still left is never drawn.  With
+    random_select == false the set is emptied (:3945,3981-3987).  At count = feature_res_num + 1 the reference clamps
+    rand_set_num to 0 (:3914-3916) and reads record -1; this port draws there as for any other count, and claims parity
+    for count > feature_res_num + 1 only (glio::featureSelectionDraws decides the same).
     Returns None for "keep all", else the kept original indices in draw order."""
     if count < 1 or count - 1 < feature_res_num:
         return None
     if not random_select:
         return np.zeros(0, np.int32)
-    # the d-th draw picks the k-th record STILL LEFT, k uniform below count - d; its original index is k advanced past every removed index <= it
+    # the d-th draw picks the k-th record STILL LEFT, k uniform below count - d - 1; its original index is k advanced past every removed index <= it
     # (the same as popping from the list of remaining records, without building a list of `count` entries per slot; glio::featureSelectionDraws
     # in glio_backend.hpp is this loop in C++: same generator in, same indices out)
     gone, out = [], []
     for d in range(feature_res_num):
-        v = int(rng.integers(0, int(count) - d))
+        v = int(rng.integers(0, int(count) - d - 1))
         pos = 0
         while pos < len(gone) and gone[pos] <= v:
             v += 1; pos += 1

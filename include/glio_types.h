@@ -26,7 +26,12 @@ extern "C" {
 
 #define GLIO_POSE_LOCAL 15      /* local (tangent) size of one keyframe: dt3 dtheta3 dv3 dba3 dbg3 */
 #define GLIO_DD_MAX_SAT 20      /* dd_psr_factor_20: psr_size_20, dd_psr_factor.hpp:12 */
+/* GLIO_MAX_WINDOW sizes the static per-slot tables (and the prior's limits); it is NOT the largest window glio_create accepts.
+ * The trust-region step factors the 15 W + max_ddt_epochs unknowns densely inside one workgroup's 160 KiB of LDS, which
+ * holds at most GLIO_MAX_UNKNOWNS of them: W <= 61 without clock-drift epochs, in general 15 W + max_ddt_epochs <= 928.
+ * glio_create refuses a larger context with GLIO_E_ARG and an error that names the unknown count. */
 #define GLIO_MAX_WINDOW 64
+#define GLIO_MAX_UNKNOWNS 928
 enum { GLIO_STRATEGY_DOGLEG = 0, GLIO_STRATEGY_LM = 1 };
 
 /* Options that shape the hot path.  Defaults (glio_opts_default) are the shipped yaml /

@@ -336,3 +336,47 @@ def test_feature_selection_draws_cpp_equals_python(tmp_path):
         else:
             assert out[0] == "1" and [int(v) for v in out[1:]] == want.tolist(), (count, res, rs)
             assert len(set(want.tolist())) == len(want) and (len(want) == 0 or (0 <= want.min() and want.max() < count))
+
+
+def test_feature_selection_draw_rule_enumerated(tmp_path):
+    """Every draw of featureSelection is uniform over the FIRST size - 1 of the `size` records still left: the reference shuffles
+    geneRandArrayNoRepeat(0, size - 1, rand_set_num), the indices 0 .. size - 2 (random_generator.hpp:79-93), so the last record left is never
+    drawn.  Enumerated over every table of draws for small counts (each table entry runs up to size - 1, the one value an off-by-one rule would
+    turn into the last record): the kept indices equal popping record k mod (size - 1) off the remaining list, the last record left is never
+    drawn, every other one is, and glio::featureSelectionDraws (C++) returns the same indices as sliding.feature_selection_draws.
+    count = feature_res_num + 1 is included as the port's own decision, not as parity: there the reference clamps rand_set_num to 0
+    (Estimator.cpp:3914-3916) and reads record -1; the port draws as for every other count."""
+    import itertools
+    from glio_amd import sliding
+    here = os.path.join(ROOT, "glio_amd", "host")
+    src = tmp_path / "fs_enum.cpp"
+    src.write_text('#include "glio_backend.hpp"\n#include <cstdio>\n'
+                   'int main(int argc, char** argv) { FILE* f = fopen(argv[1], "r"); long count; int res;\n'
+                   '  while (fscanf(f, "%ld %d", &count, &res) == 2) { std::vector<unsigned long long> t(res); for (int d = 0; d < res; ++d) if (fscanf(f, "%llu", &t[d]) != 1) return 2;\n'
+                   '    size_t k = 0; std::vector<int32_t> kept;\n'
+                   '    const bool changed = glio::featureSelectionDraws(count, res, [&](uint64_t n) -> uint64_t { return t[k++ % t.size()] % n; }, true, kept);\n'
+                   '    printf("%d", changed ? 1 : 0); for (int32_t v : kept) printf(" %d", v); printf("\\n"); }\n  return 0; }\n')
+    exe = str(tmp_path / "fs_enum")
+    subprocess.check_call(["g++", "-std=c++14", "-O1", str(src), "-I" + here, "-I" + os.path.join(ROOT, "include"), "-o", exe])
+    cases, wants = [], []
+    for count in range(2, 8):
+        for res in range(1, count):
+            seen = [set() for _ in range(res)]          # per draw d: the positions (in the list still left) that some table drew
+            for table in itertools.product(*[range(count - d) for d in range(res)]):
+                got = sliding.feature_selection_draws(count, res, sliding.TableRng(np.array(table, np.uint64)))
+                rem, want = list(range(count)), []
+                for d, t in enumerate(table):
+                    k = t % (len(rem) - 1)
+                    assert got[d] != rem[-1], (count, res, table, "the last record left was drawn")
+                    seen[d].add(rem.index(int(got[d])))
+                    want.append(rem.pop(k))
+                assert got.tolist() == want, (count, res, table)
+                cases.append((count, res, table)); wants.append(want)
+            for d in range(res):
+                assert seen[d] == set(range(count - d - 1)), (count, res, d, "a record other than the last one left is never drawn")
+    inp = tmp_path / "cases.txt"
+    inp.write_text("".join(f"{c} {r} " + " ".join(map(str, t)) + "\n" for c, r, t in cases))
+    out = subprocess.run([exe, str(inp)], capture_output=True, text=True, check=True).stdout.splitlines()
+    assert len(out) == len(cases)
+    for line, (c, r, t), want in zip(out, cases, wants):
+        assert line.split() == ["1"] + [str(v) for v in want], (c, r, t)
