@@ -93,6 +93,41 @@ class Context:
     def set_map(self, map_pts):
         _check(load().glio_set_map(self._h, T.fptr(map_pts), len(map_pts)))
 
+    # ---- LiDAR features from the raw scan (Preprocessing::cloudHandler on the device; glio_features_*)
+    def features_config(self, opts=None):
+        if opts is None:
+            from . import features
+            opts = features.default_opts()
+        _check(load().glio_features_config(self._h, C.byref(opts)))
+        self.feat_opts = opts
+
+    def features_extract(self, raw, q_imu, ioff=12):
+        """raw: [n][4] float32 (x y z intensity) or records of any stride (x y z floats at 0, the intensity float at ioff).  Returns glio_feat_counts."""
+        pts, ptr, n, stride = self._raw(raw)
+        if pts.dtype == np.float32 and pts.ndim == 2:
+            stride = 4 * pts.shape[1]
+        q = np.ascontiguousarray(q_imu, np.float64)
+        cnt = T.GlioFeatCounts()
+        _check(load().glio_features_extract_strided(self._h, ptr if n else None, n, stride, ioff, T.dptr(q), C.byref(cnt)))
+        return cnt
+
+    def features_read(self, which):
+        n = C.c_int(0)
+        _check(load().glio_features_read(self._h, int(which), None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 4), np.float32)
+        _check(load().glio_features_read(self._h, int(which), T.fptr(out), n.value, C.byref(n)))
+        return out[:n.value].copy()
+
+    def features_to_scan(self, slot, leaf):
+        n = C.c_int(0)
+        _check(load().glio_features_to_scan(self._h, int(slot), C.c_float(leaf), C.byref(n)))
+        return n.value
+
+    def features_last_device_ms(self):
+        ms = C.c_float(0)
+        _check(load().glio_features_last_device_ms(self._h, C.byref(ms)))
+        return ms.value
+
     # ---- strided point input: clouds as records of `stride` bytes (x y z floats at 0, intensity float at `ioff`); pcl::PointXYZI = PCL_XYZI
     @staticmethod
     def _raw(points):

@@ -249,6 +249,7 @@ struct glio_ctx {
                                                     // batch association's stream): the next write to a scan row, and glio_destroy, come behind this event
     int prior_device_made;                    // the installed prior is glio_marginalize_keep's own product: block diagonal with EXACT zeros (a caller's prior is only held to a tolerance)
     int n_cu;                                 // compute units of THIS context's device (the helper workgroups of k_chain_step need 2 (1 + W) of them)
+    struct FeatWork* features;                // raw-scan feature extraction (feature_kernels.hip), created by glio_features_config
 };
 
 static inline int glio_x_size(int W, int n_ddt) { return 16 * W + n_ddt; }
@@ -431,6 +432,7 @@ int glio_assoc_run_window(glio_ctx* c, const double* quats, const double* trans,
 int glio_assoc_run_window_async(glio_ctx* c, const double* quats, const double* trans);
 int glio_assoc_finish_pending(glio_ctx* c);
 void glio_localmap_destroy(glio_ctx* c);
+void glio_features_destroy(glio_ctx* c);          // feature_kernels.hip
 // solver_kernels.hip
 void glio_launch_tr_step(glio_ctx* c, int n_ddt);
 void glio_chain_tabs_upload(glio_ctx* c);

@@ -102,6 +102,26 @@ class GlioSummary(C.Structure):
         return d
 
 
+class GlioFeatOpts(C.Structure):
+    """glio_feat_opts (include/glio_types.h): Preprocessing's parameters"""
+    _fields_ = [("n_scans", C.c_int32), ("ds_rate", C.c_int32), ("edge_threshold", C.c_double), ("surf_threshold", C.c_double),
+                ("ds_leaf", C.c_float), ("min_range", C.c_float), ("q_lb", C.c_double * 4), ("max_raw_points", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
+class GlioFeatCounts(C.Structure):
+    """glio_feat_counts: point counts of the last extraction"""
+    _fields_ = [("in_", C.c_int32), ("kept", C.c_int32), ("cut", C.c_int32), ("sharp", C.c_int32), ("less_sharp", C.c_int32),
+                ("flat", C.c_int32), ("surf", C.c_int32), ("reserved_", C.c_int32)]
+
+    def as_dict(self):
+        return {"in": self.in_, "kept": self.kept, "cut": self.cut, "sharp": self.sharp, "less_sharp": self.less_sharp, "flat": self.flat, "surf": self.surf}
+
+
+FEAT_SURF, FEAT_EDGE_LESS_SHARP, FEAT_SHARP, FEAT_FLAT, FEAT_CUT_CLOUD, FEAT_LAST_SCAN = range(6)
+FEAT_MAX_RAW_POINTS = 400000
+
+
 def dptr(a):
     assert a.dtype == np.float64 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(c_double_p)

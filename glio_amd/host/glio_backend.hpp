@@ -424,6 +424,69 @@ private:
     glio_ctx* ctx_ = nullptr;
 };
 
+// qIMU of Preprocessing (GLIO/src/Preprocessing.cpp): imuHandler (:260-292), processIMU (:223-259) with solveRotation (:202-207) and the
+// NON-normalised deltaQ of math_tools.h (w = 1, xyz = theta / 2), the NaN guard (:415-417) and the reset after each cloud (:675).  addImu per IMU
+// message; forScan(t_scan_next, q) per cloud (t_scan_next: the stamp of the NEXT cloud in the queue, :356-371) gives the q_imu of
+// glio_features_extract, or returns false where the reference waits for IMU data (:373-377) and drops the cloud.  The Python twin is
+// glio_amd/features.py::ScanRotation (tests/test_host_scan_rotation.py holds the two to each other).
+class ScanRotation {
+public:
+    void addImu(double t, const double gyro[3]) {
+        buf_.push_back({{t, gyro[0], gyro[1], gyro[2]}});
+        if (current_time_imu_ < 0) current_time_imu_ = t;                          // the first sample's dt is 0
+        if (!first_imu_) { first_imu_ = true; gyr0_[0] = gyro[0]; gyr0_[1] = gyro[1]; gyr0_[2] = gyro[2]; }
+    }
+    bool forScan(double t_scan_next, double q_out[4]) {
+        const size_t tmp = idx_imu_ > 0 ? idx_imu_ - 1 : 0;
+        if (buf_.empty() || buf_[tmp][0] > t_scan_next) return false;
+        if (first_imu_) process(t_scan_next);
+        if (std::isnan(q_[0]) || std::isnan(q_[1]) || std::isnan(q_[2]) || std::isnan(q_[3])) { q_[0] = 1; q_[1] = q_[2] = q_[3] = 0; }
+        for (int k = 0; k < 4; ++k) q_out[k] = q_[k];
+        q_[0] = 1; q_[1] = q_[2] = q_[3] = 0;
+        return true;
+    }
+private:
+    void solve(double dt, const double w[3]) {
+        double dq[4] = {1.0, 0, 0, 0};
+        for (int k = 0; k < 3; ++k) { const double un = 0.5 * (gyr0_[k] + w[k]); const double th = un * dt; dq[1 + k] = th / 2.0; }
+        const double a[4] = {q_[0], q_[1], q_[2], q_[3]};
+        q_[0] = a[0] * dq[0] - a[1] * dq[1] - a[2] * dq[2] - a[3] * dq[3];
+        q_[1] = a[0] * dq[1] + a[1] * dq[0] + a[2] * dq[3] - a[3] * dq[2];
+        q_[2] = a[0] * dq[2] + a[2] * dq[0] + a[3] * dq[1] - a[1] * dq[3];
+        q_[3] = a[0] * dq[3] + a[3] * dq[0] + a[1] * dq[2] - a[2] * dq[1];
+        for (int k = 0; k < 3; ++k) gyr0_[k] = w[k];
+    }
+    void process(double t_cur) {
+        double r[3] = {0, 0, 0};
+        size_t i = idx_imu_;
+        if (i >= buf_.size()) i--;
+        while (buf_[i][0] < t_cur) {
+            const double t = buf_[i][0];
+            if (current_time_imu_ < 0) current_time_imu_ = t;
+            const double dt = t - current_time_imu_;
+            current_time_imu_ = buf_[i][0];
+            r[0] = buf_[i][1]; r[1] = buf_[i][2]; r[2] = buf_[i][3];
+            solve(dt, r);
+            i++;
+            if (i >= buf_.size()) break;
+        }
+        if (i < buf_.size()) {                                                      // the interpolated last step at t_cur
+            const double dt1 = t_cur - current_time_imu_, dt2 = buf_[i][0] - t_cur;
+            const double w1 = dt2 / (dt1 + dt2), w2 = dt1 / (dt1 + dt2);
+            for (int k = 0; k < 3; ++k) r[k] = w1 * r[k] + w2 * buf_[i][1 + k];
+            solve(dt1, r);
+        }
+        current_time_imu_ = t_cur;
+        idx_imu_ = i;
+    }
+    std::vector<std::array<double, 4>> buf_;
+    size_t idx_imu_ = 0;
+    double current_time_imu_ = -1;
+    double gyr0_[3] = {0, 0, 0};
+    double q_[4] = {1, 0, 0, 0};
+    bool first_imu_ = false;
+};
+
 // ---- (3) the front end -------------------------------------------------------------------------------
 // LidarOdometry (GLIO/src/LidarOdometry.cpp): scan-to-map odometry on the same C-ABI with a one-keyframe window.  Per scan, run() (:661-699):
 //   poseInitialization (:405-432)  abs_pose <- abs_pose o rel_pose
@@ -482,7 +545,7 @@ public:
         std::array<double, 7> p = pose;
         if (rounds) rounds->clear();
         if (map_points_ < 10) return p;                                             // "Not enough feature points from the map" (:477-480)
-        check(glio_set_scan(ctx_, 0, surf_last_ds, n), "glio_set_scan");
+        if (surf_last_ds) check(glio_set_scan(ctx_, 0, surf_last_ds, n), "glio_set_scan");      // (null: already resident in slot 0, runRaw)
         double sb[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int it = 0; it < match_cnt; ++it) {
             int kept = 0;
@@ -524,7 +587,57 @@ public:
         abs_pose = update(surf_last_ds, n, abs_pose, poses_ < 2 ? 8 : scan_match_cnt_, rounds);
         const std::array<double, 7> prev = last_pose_;
         savePoses(surf_last_ds, n);
-        // computeRelative: rel = prev^-1 o abs
+        computeRelative(prev);
+        return abs_pose;
+    }
+    // run() from the RAW scan: Preprocessing::cloudHandler on the device (glio_features_extract; the context configured with featuresConfig), then the
+    // surf features voxel-filtered at 0.2 m on the device into slot 0 (glio_features_to_scan: down_size_filter_surf, :306-314).  The previous scan is
+    // pushed into the 20-frame ring from slot 0 BEFORE the new one overwrites it; then the same update rounds as run() without glio_set_scan.  After
+    // the first two scans only counts cross PCIe.  glio_amd/odometry.py::ScanToMapOdometry.run_raw is the Python twin.
+    void featuresConfig(const glio_feat_opts& o) { check(glio_features_config(ctx_, &o), "glio_features_config"); }
+    std::array<double, 7> runRaw(const void* raw, int n, PointLayout l, const double q_imu[4], std::vector<Round>* rounds = nullptr, glio_feat_counts* counts = nullptr) {
+        if (rounds) rounds->clear();
+        glio_feat_counts cnt;
+        check(glio_features_extract_strided(ctx_, raw, n, l.stride_bytes, l.intensity_offset, q_imu, &cnt), "glio_features_extract_strided");
+        if (counts) *counts = cnt;
+        const float zero[3] = {0.f, 0.f, 0.f};
+        if (poses_ >= 2) check(glio_localmap_push_scan(ctx_, 0, zero, &last_pose_[0], &last_pose_[4]), "glio_localmap_push_scan");
+        int ns = 0;
+        check(glio_features_to_scan(ctx_, 0, 0.2f, &ns), "glio_features_to_scan");
+        if (poses_ == 0) { last_pose_ = abs_pose; ++poses_; return abs_pose; }
+        {
+            double t[3], q[4];
+            rotate(&abs_pose[0], &rel_pose[4], t);
+            for (int k = 0; k < 3; ++k) t[k] += abs_pose[4 + k];
+            qmul(&abs_pose[0], &rel_pose[0], q);
+            for (int k = 0; k < 4; ++k) abs_pose[k] = q[k];
+            for (int k = 0; k < 3; ++k) abs_pose[4 + k] = t[k];
+        }
+        if (poses_ <= 1) {                                                          // the scan is its own map: read back once
+            std::vector<float> cloud((size_t)ns * 4 + 4);
+            int got = 0;
+            check(glio_features_read(ctx_, GLIO_FEAT_LAST_SCAN, cloud.data(), ns, &got), "glio_features_read");
+            setMap(cloud.data(), got);
+        } else {
+            int pts = 0;
+            check(glio_localmap_build(ctx_, &pts), "glio_localmap_build");
+            map_points_ = pts;
+        }
+        abs_pose = update(nullptr, ns, abs_pose, poses_ < 2 ? 8 : scan_match_cnt_, rounds);
+        const std::array<double, 7> prev = last_pose_;
+        last_pose_ = abs_pose;
+        ++poses_;
+        computeRelative(prev);
+        return abs_pose;
+    }
+    int frames() const { return poses_; }
+    int mapPoints() const { return map_points_; }
+
+    std::array<double, 7> abs_pose, rel_pose;          // q (w,x,y,z), t -- the reference's abs_pose[7] / rel_pose[7]
+
+private:
+    // computeRelative: rel = prev^-1 o abs
+    void computeRelative(const std::array<double, 7>& prev) {
         {
             const double qi[4] = {prev[0], -prev[1], -prev[2], -prev[3]};           // (unit quaternions: the inverse is the conjugate, as Eigen's inverse() of a normalised one)
             const double n2 = prev[0] * prev[0] + prev[1] * prev[1] + prev[2] * prev[2] + prev[3] * prev[3];
@@ -535,14 +648,7 @@ public:
             for (int k = 0; k < 4; ++k) rel_pose[k] = q[k];
             for (int k = 0; k < 3; ++k) rel_pose[4 + k] = t[k];
         }
-        return abs_pose;
     }
-    int frames() const { return poses_; }
-    int mapPoints() const { return map_points_; }
-
-    std::array<double, 7> abs_pose, rel_pose;          // q (w,x,y,z), t -- the reference's abs_pose[7] / rel_pose[7]
-
-private:
     void savePoses(const float* cloud, int n) {
         last_pose_ = abs_pose;
         last_cloud_.assign(cloud, cloud + 4 * (size_t)n);

@@ -227,3 +227,42 @@ def run_demo_odometry(path, device=0, env=None):
             rows.append({"rounds": int(w[9]), "kept": int(w[10]), "iterations": int(w[11]), "final_cost": float(w[12]), "map_points": int(w[13])})
     info = json.loads(next(ln for ln in r.stdout.splitlines() if ln.startswith("{")))
     return np.array(poses), rows, info
+
+
+DEMO_FRONTEND_RAW = os.path.join(HERE, "host_demo_frontend_raw")
+
+
+def build_demo_frontend_raw(force=False):
+    """The C++ front end from raw scans (host_demo_frontend_raw.cpp over glio::ScanToMapOdometry::runRaw); built on demand by its test."""
+    src = [os.path.join(HERE, "host_demo_frontend_raw.cpp"), os.path.join(HERE, "glio_backend.hpp")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_FRONTEND_RAW) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_FRONTEND_RAW) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_FRONTEND_RAW])
+    return DEMO_FRONTEND_RAW
+
+
+def write_frontend_raw_stream(path, opts, feat_opts, scans, q_imus, scan_match_cnt=1, ioff=12):
+    """opts | feat_opts | n_scans scan_match_cnt stride ioff | per scan: n, q_imu[4], raw records (all scans of one stride)"""
+    recs = [np.ascontiguousarray(s) for s in scans]
+    stride = 4 * recs[0].shape[1] if recs[0].dtype == np.float32 and recs[0].ndim == 2 else recs[0].dtype.itemsize
+    with open(path, "wb") as f:
+        f.write(bytes(opts)); f.write(bytes(feat_opts))
+        f.write(np.array([len(recs), scan_match_cnt, stride, ioff], np.int32).tobytes())
+        for r, q in zip(recs, q_imus):
+            f.write(np.array([len(r)], np.int32).tobytes()); f.write(np.ascontiguousarray(q, np.float64).tobytes()); f.write(r.tobytes())
+
+
+def run_demo_frontend_raw(path, device=0, env=None):
+    """-> (poses [n][7] q then t, per-scan dicts, {"ms_per_scan": ...})"""
+    import json
+    r = subprocess.run([build_demo_frontend_raw(), path, str(device)], capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError("host_demo_frontend_raw failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
+    poses, rows = [], []
+    for ln in r.stdout.splitlines():
+        if ln.startswith("pose "):
+            w = ln.split()
+            poses.append([float(x) for x in w[2:9]])
+            rows.append({"rounds": int(w[9]), "kept": int(w[10]), "iterations": int(w[11]), "final_cost": float(w[12]), "map_points": int(w[13]), "surf": int(w[14])})
+    info = json.loads(next(ln for ln in r.stdout.splitlines() if ln.startswith("{")))
+    return np.array(poses), rows, info

@@ -91,6 +91,43 @@ class ScanToMapOdometry:
         self.rel_pose = np.r_[_qmul(qin, self.abs_pose[:4]), _rotate(qin, self.abs_pose[4:] - prev[4:])]
         return self.abs_pose.copy(), rounds
 
+    def run_raw(self, raw, q_imu, stride=16, ioff=12, max_points=None):
+        """One RAW scan: Preprocessing::cloudHandler on the device (glio_features_extract, the backend configured with features_config), then
+        run() with the surf features voxel-filtered at 0.2 m on the device (glio_features_to_scan into slot 0: downSampleCloud, :306-314).  The
+        previous scan is pushed into the 20-frame ring from slot 0 BEFORE the new one overwrites it; after the first two scans only counts
+        cross PCIe.  raw: [n][stride/4] float32 or records of `stride` bytes.  Returns (abs_pose, rounds, glio_feat_counts)."""
+        raw = np.ascontiguousarray(raw)
+        if raw.dtype == np.float32 and raw.ndim == 2:
+            assert raw.shape[1] * 4 == stride
+        cnt = self.be.features_extract(raw, q_imu, ioff=ioff)
+        if not self._ring:
+            self.be.localmap_config(LOCAL_MAP_WIDTH, LOCAL_MAP_LEAF, max_points or self.be.opts.max_points_per_scan)
+            self._ring = True
+        if self.poses >= 2:                               # the previous scan, still resident in slot 0
+            self.be.localmap_push_scan(0, np.zeros(3, np.float32), self._last_pose[:4], self._last_pose[4:])
+        n = self.be.features_to_scan(0, LOCAL_MAP_LEAF)
+        if self.poses == 0:
+            self._last_pose = self.abs_pose.copy()
+            self.poses += 1
+            return self.abs_pose.copy(), [], cnt
+        a, r = self.abs_pose, self.rel_pose
+        t = _rotate(a[:4], r[4:]) + a[4:]
+        self.abs_pose = np.r_[_qmul(a[:4], r[:4]), t]
+        if self.poses <= 1:
+            self.be.set_map(self.be.features_read(T.FEAT_LAST_SCAN)); self.map_points = n
+        else:
+            self.map_points = self.be.localmap_build()
+        rounds = []
+        if self.map_points >= 10:
+            self.abs_pose, rounds = self.update(None, self.abs_pose, match_cnt=8 if self.poses < 2 else self.scan_match_cnt)
+        prev = self._last_pose
+        self._last_pose = self.abs_pose.copy()
+        self.poses += 1
+        n2 = float(prev[0] * prev[0] + prev[1] * prev[1] + prev[2] * prev[2] + prev[3] * prev[3])
+        qin = np.array([prev[0], -prev[1], -prev[2], -prev[3]]) / n2
+        self.rel_pose = np.r_[_qmul(qin, self.abs_pose[:4]), _rotate(qin, self.abs_pose[4:] - prev[4:])]
+        return self.abs_pose.copy(), rounds, cnt
+
     def set_map(self, surf_from_map_ds):
         self.be.set_map(surf_from_map_ds)           # kd_tree_surf_last->setInputCloud (:482)
 
@@ -105,7 +142,8 @@ class ScanToMapOdometry:
         self.be.set_prior(None)
         self.be.set_gnss(None, [], [])
         rounds = []
-        self.be.set_scan(0, surf_last_ds)
+        if surf_last_ds is not None:                # (None: the scan is already resident in slot 0, run_raw)
+            self.be.set_scan(0, surf_last_ds)
         for _ in range(match_cnt):
             kept = self.be.associate_resident(0, st.quat[0], st.trans[0])
             st, summ = self.be.solve(st)

@@ -383,6 +383,33 @@ int glio_bassoc_select(glio_bassoc* b, int64_t n_keep, const int64_t* src_index,
 int glio_bassoc_select_range(glio_bassoc* b, int64_t first, int64_t n_keep, const int64_t* src_index, int64_t n_current);
 int glio_bassoc_read(glio_bassoc* b, int64_t first, int64_t n, float* cp, double* norm_cent, double* score);
 
+/* ---- LiDAR features from the raw scan: Preprocessing::cloudHandler (GLIO/src/Preprocessing.cpp:353-681) on the device.
+ * The IMU rotation of the sweep (processIMU / solveRotation, :202-259) stays with the caller (glio_amd/features.py::ScanRotation,
+ * glio::ScanRotation): q_imu is the qIMU the reference holds when the scan is handled, after the NaN guard (:415-417). */
+void glio_feat_opts_default(glio_feat_opts* o);
+/* sizeof() of glio_feat_opts, glio_feat_counts; returns how many there are (2) */
+int glio_feat_struct_sizes(int32_t* out, int n);
+/* allocates the extraction's buffers for opts->max_raw_points raw points (a context that never calls it allocates nothing for it);
+ * GLIO_E_ARG for n_scans not in {16, 32, 64}, ds_rate < 1, ds_leaf <= 0 or max_raw_points outside [1, GLIO_FEAT_MAX_RAW_POINTS] */
+int glio_features_config(glio_ctx* ctx, const glio_feat_opts* opts);
+/* removeNaNFromPointCloud + removeClosedPointCloud (:144-168, :396-397), startOri / endOri (:401-410), ring, orientation, relTime and
+ * undistortion(point, qIMU) per point (:176-200, :424-515), the stable ring bucketing (:517-526), the curvature (:529-538), the six sectors
+ * of every ring with their edge / flat picks and the less-flat points (:540-646), the per-ring VoxelGrid at ds_leaf (:648-654).
+ * Records of stride_bytes (a multiple of 4, >= 16: x y z floats at 0, the intensity float at intensity_offset; the intensity is not read).
+ * Returns when the caller's buffer has been read and the counts are known.  n > max_raw_points: GLIO_E_ARG, nothing written; before
+ * glio_features_config: GLIO_E_STATE.  A scan without survivors gives zero counts and GLIO_OK (the reference would read points[0] of
+ * an empty cloud at :401). */
+int glio_features_extract_strided(glio_ctx* ctx, const void* raw, int n, int stride_bytes, int intensity_offset, const double q_imu[4], glio_feat_counts* counts);
+int glio_features_extract(glio_ctx* ctx, const float* xyzi, int n, const double q_imu[4], glio_feat_counts* counts);
+/* one output of the last extraction (GLIO_FEAT_*), [n][4] x y z intensity; *n = its size (out may be null to ask for it); capacity too small: GLIO_E_ARG */
+int glio_features_read(glio_ctx* ctx, int which, float* out_xyzi, int capacity, int* n);
+/* LidarOdometry's downSampleCloud (LidarOdometry.cpp:306-314): the surf features of the last extraction, voxel-filtered at `leaf` on the device
+ * (pcl::VoxelGrid, one segment; leaf <= 0: as they are), written into window slot `slot` as glio_set_scan would and presorted -- no host round trip.
+ * *n = the points written; more than max_points_per_scan: GLIO_E_ARG, the slot untouched. */
+int glio_features_to_scan(glio_ctx* ctx, int slot, float leaf, int* n);
+/* device time of the last extraction's kernels (HIP events around them, after the raw upload), ms */
+int glio_features_last_device_ms(glio_ctx* ctx, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

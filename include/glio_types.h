@@ -211,6 +211,35 @@ typedef struct glio_batch_opts {
     double lm_lambda;        /* fixed Levenberg damping used by the restated batch solve */
 } glio_batch_opts;
 
+/* LiDAR feature extraction from a raw scan (Preprocessing::cloudHandler, GLIO/src/Preprocessing.cpp:353-681).
+ * Defaults (glio_feat_opts_default): config_urban_hk.yaml:14-18,90-93 and the node's members. */
+typedef struct glio_feat_opts {
+    int32_t n_scans;         /* line_num: 16, 32 or 64 (yaml: 32) */
+    int32_t ds_rate;         /* rings with i % ds_rate != 0 are skipped (:542; yaml: 1) */
+    double edge_threshold;   /* edgeThreshold (yaml: 1.0), compared as double (:566) */
+    double surf_threshold;   /* surfThreshold (yaml: 0.1), compared as double (:607) */
+    float ds_leaf;           /* ds_v = 0.4: the member default (:14), never read from the yaml */
+    float min_range;         /* removeClosedPointCloud(.., 3.0) (:397), a float threshold squared in float */
+    double q_lb[4];          /* ql2b_w/x/y/z (w,x,y,z; yaml: identity) */
+    int32_t max_raw_points;  /* capacity of one raw scan: at most 400000, the node's static arrays (:9-12) */
+    int32_t reserved_;
+} glio_feat_opts;
+
+/* point counts of the last glio_features_extract* */
+typedef struct glio_feat_counts {
+    int32_t in;              /* raw points handed in */
+    int32_t kept;            /* finite and not inside min_range (removeNaNFromPointCloud + removeClosedPointCloud) */
+    int32_t cut;             /* with a valid ring: /lidar_cloud_cutted */
+    int32_t sharp;           /* cornerPointsSharp */
+    int32_t less_sharp;      /* cornerPointsLessSharp: /edge_features */
+    int32_t flat;            /* surfPointsFlat */
+    int32_t surf;            /* surfPointsLessFlat after the per-ring VoxelGrid: /surf_features */
+    int32_t reserved_;
+} glio_feat_counts;
+enum { GLIO_FEAT_SURF = 0, GLIO_FEAT_EDGE_LESS_SHARP = 1, GLIO_FEAT_SHARP = 2, GLIO_FEAT_FLAT = 3, GLIO_FEAT_CUT_CLOUD = 4,
+       GLIO_FEAT_LAST_SCAN = 5 /* the cloud the last glio_features_to_scan wrote into its slot */ };
+#define GLIO_FEAT_MAX_RAW_POINTS 400000
+
 #ifdef __cplusplus
 }
 #endif
