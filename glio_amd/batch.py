@@ -81,12 +81,13 @@ def make_poses(K, seed=20260930, perturb=(0.05, 0.003)):
 BATCH_KF_DT = 0.125          # seconds between batch keyframes (1 m spacing at 8 m/s)
 
 
-def make_batch_imu(K, seed=20260930, rate_per_kf=10, kf_dt=BATCH_KF_DT, perturb_v=0.05, noise=True):
+def make_batch_imu(K, seed=20260930, rate_per_kf=10, kf_dt=BATCH_KF_DT, perturb_v=0.05, noise=True, return_raw=False):
     """The IMU chain of the batch problem (Estimator.cpp:2990-3001): one pre-integration per pair of consecutive keyframes
     of make_poses' track, from IMU samples of the analytic trajectory (position p(s), yaw(s), s = t / kf_dt), midpoint
     pre-integrated on the host exactly as the window generator does (synth.preintegrate = class Preintegration restated).
     Returns (preints [K - 1] dicts, speed_bias_gt [K][9], speed_bias_init [K][9]).  Edge k spans keyframes k .. k + 1
-    (the consistent interval; the reference's own indexing looks off by one there)."""
+    (the consistent interval; the reference's own indexing looks off by one there).
+    return_raw: a fourth value, the samples the edges were integrated from, [(acc [n + 1][3], gyr [n + 1][3], dts [n])] per edge."""
     from . import synth
     rng = np.random.default_rng(seed + 31)
 
@@ -102,7 +103,7 @@ def make_batch_imu(K, seed=20260930, rate_per_kf=10, kf_dt=BATCH_KF_DT, perturb_
 
     n = rate_per_kf
     dts = np.full(n, kf_dt / n)
-    preints = []
+    preints, raw = [], []
     for k in range(K - 1):
         acc, gyr = np.zeros((n + 1, 3)), np.zeros((n + 1, 3))
         for i in range(n + 1):
@@ -114,11 +115,14 @@ def make_batch_imu(K, seed=20260930, rate_per_kf=10, kf_dt=BATCH_KF_DT, perturb_
         if noise:
             acc += rng.normal(0, synth.ACC_N, acc.shape); gyr += rng.normal(0, synth.GYR_N, gyr.shape)
         preints.append(synth.preintegrate(acc, gyr, dts, np.zeros(3), np.zeros(3)))
+        raw.append((acc, gyr, dts.copy()))
     sb_gt = np.zeros((K, 9))
     for k in range(K):
         sb_gt[k, :3] = pos_d(float(k))[0] / kf_dt
     sb_init = sb_gt.copy()
     sb_init[:, :3] += rng.normal(0, perturb_v, (K, 3))
+    if return_raw:
+        return preints, sb_gt, sb_init, raw
     return preints, sb_gt, sb_init
 
 
@@ -784,6 +788,12 @@ class BatchStage:
                 synth.fill_preint(arr[k], d)
         capi._check(capi.load().glio_batch_set_imu(self._h, len(preints), arr if preints else None, C.c_double(synth.GRAVITY if gravity is None else gravity)))
         self.n_imu = len(preints)
+
+    def set_imu_from_store(self, store, first_edge=0, gravity=None):
+        """The ImuFactor chain from an imu.ImuStore on the same device: its edges first_edge .. first_edge + K - 2 (glio_batch_set_imu_from_store)."""
+        from . import synth
+        capi._check(capi.load().glio_batch_set_imu_from_store(self._h, store._h, int(first_edge), C.c_double(synth.GRAVITY if gravity is None else gravity)))
+        self.n_imu = self.K - 1
 
     def _hook(self, dist, on_allreduce=None):
         """The all-reduce hook of the library for torch.distributed: the collective is issued on the library's stream (made

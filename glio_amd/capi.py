@@ -278,6 +278,13 @@ class Context:
     def set_imu(self, preints, slots=None):
         self.set_imu_marshalled(self.marshal_imu(preints, slots))
 
+    def set_imu_from_store(self, store, edges, slots=None):
+        """glio_set_imu with the edges taken from an imu.ImuStore on the same device: edges[k] links slots slots[k], slots[k] + 1 (default k)"""
+        edges = np.ascontiguousarray(edges, np.int32)
+        n = len(edges)
+        slots = np.arange(max(n, 1), dtype=np.int32) if slots is None else np.ascontiguousarray(slots, np.int32)
+        _check(load().glio_set_imu_from_store(self._h, store._h, n, T.iptr(edges) if n else None, T.iptr(slots) if n else None))
+
     def set_prior(self, prior):
         ps = synth.prior_struct(prior)
         self._keep = [prior]          # glio_set_prior copies synchronously; only the latest is held (for the caller's convenience)

@@ -1176,6 +1176,27 @@ int glio_batch_set_imu(glio_batch* b, int n_edges, const glio_preint* edges, dou
     return GLIO_OK;
 }
 
+// The same chain from a glio_imu store on the same device: edges first_edge .. first_edge + K - 2, copied on the device on the batch stream behind
+// the store's last integration (an event, no host wait); every reader of the table is enqueued on that stream or forks from it.
+int glio_batch_set_imu_from_store(glio_batch* b, glio_imu* st, int first_edge, double gravity) {
+    if (!b || !st || first_edge < 0) return GLIO_E_ARG;
+    const int n_edges = b->K - 1;
+    if (st->device != b->device) { glio_set_error("the IMU store lives on device %d, the batch stage on device %d", st->device, b->device); return GLIO_E_ARG; }
+    if (n_edges < 1 || (long long)first_edge + n_edges > st->max_edges) { glio_set_error("IMU edges %d .. %d of a store of %d", first_edge, first_edge + n_edges - 1, st->max_edges); return GLIO_E_ARG; }
+    { const int bad = glio_imu_known_flag(st, first_edge, n_edges, nullptr); if (bad >= 0) { glio_set_error("IMU edge %d: flagged by the store (non-finite input or covariance not invertible)", bad); return GLIO_E_NUMERIC; } }
+    BT_CHECK(hipSetDevice(b->device));
+    { const int rc = small_ensure(b); if (rc) return rc; }
+    BatchSmall* s = b->small;
+    if (!s->d_imu) {
+        BT_CHECK(hipMalloc((void**)&s->d_imu, (size_t)(b->K - 1) * sizeof(ImuEdgeDev)));
+        for (int k = 0; k < 2; ++k) BT_CHECK(hipMalloc((void**)&s->d_rec[k], (size_t)(b->K - 1) * sizeof(PairBlock)));
+    }
+    BT_CHECK(hipStreamWaitEvent(b->stream, st->ev_done, 0));
+    glio_imu_launch_gather_range(b->stream, st, first_edge, n_edges, s->d_imu);
+    s->n_imu = n_edges; s->gravity = gravity;
+    return GLIO_OK;
+}
+
 int glio_batch_set_small_factors(glio_batch* b, const glio_gnss_frame* frame, int n_dq, const int32_t* dq_i, const int32_t* dq_j, const double* dq_const,
                                  int n_dd, const glio_dd_psr* dd) {
     if (!b || n_dq < 0 || n_dd < 0 || (n_dq > 0 && (!dq_i || !dq_j || !dq_const)) || (n_dd > 0 && (!dd || !frame))) return GLIO_E_ARG;

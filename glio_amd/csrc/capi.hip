@@ -780,6 +780,47 @@ int glio_set_imu(glio_ctx* c, int n_edges, const glio_preint* edges, const int32
     return GLIO_OK;
 }
 
+// glio_set_imu with the edges taken from a glio_imu store on the same device (imu_kernels.hip): the digested records are copied on the device.
+// The copy is the writer of the IMU table and runs where glio_set_imu's installing kernel runs (the upload stream, ahead of the context's stream
+// through ev_up; the context's stream when GLIO_EARLY_UPLOAD=0), behind the store's last integration through its event -- the host waits for nothing.
+int glio_set_imu_from_store(glio_ctx* c, glio_imu* st, int n_edges, const int32_t* edge, const int32_t* slot_i) {
+    if (!c || !st || n_edges < 0 || n_edges > c->W - 1 + (c->W == 1) || n_edges > GLIO_MAX_WINDOW || (n_edges > 0 && (!edge || !slot_i))) { glio_set_error("bad IMU edge count"); return GLIO_E_ARG; }
+    if (st->device != c->device) { glio_set_error("the IMU store lives on device %d, the context on device %d", st->device, c->device); return GLIO_E_ARG; }
+    for (int k = 0; k < n_edges; ++k) {
+        if (slot_i[k] < 0 || slot_i[k] + 1 >= c->W) { glio_set_error("IMU edge slot out of range"); return GLIO_E_ARG; }
+        if (edge[k] < 0 || edge[k] >= st->max_edges) { glio_set_error("IMU edge %d of a store of %d", edge[k], st->max_edges); return GLIO_E_ARG; }
+    }
+    { const int bad = glio_imu_known_flag(st, 0, n_edges, edge); if (bad >= 0) { glio_set_error("IMU edge %d: flagged by the store (non-finite input or covariance not invertible)", bad); return GLIO_E_NUMERIC; } }
+    { const int rp = marg_pending_done(c); if (rp) return rp; }
+    GLIO_HIP_CHECK(hipSetDevice(c->device));
+    CtxExtra* ex = extra_of(c);
+    if (n_edges) {
+        if (stage_early_enabled(ex)) {
+            if (!ex->up_stream) {          // as stage_begin_early makes it
+                int least = 0, greatest = 0;
+                if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) GLIO_HIP_CHECK(hipStreamCreateWithPriority(&ex->up_stream, hipStreamNonBlocking, greatest));
+                else GLIO_HIP_CHECK(hipStreamCreateWithFlags(&ex->up_stream, hipStreamNonBlocking));
+                GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_up, hipEventDisableTiming));
+            }
+            GLIO_HIP_CHECK(hipStreamWaitEvent(ex->up_stream, st->ev_done, 0));
+            glio_imu_launch_gather_list(ex->up_stream, st, n_edges, edge, slot_i, c->d_imu);
+            GLIO_HIP_CHECK(hipEventRecord(ex->ev_up, ex->up_stream));
+            GLIO_HIP_CHECK(hipStreamWaitEvent(c->stream, ex->ev_up, 0));
+        } else {
+            GLIO_HIP_CHECK(hipStreamWaitEvent(c->stream, st->ev_done, 0));
+            glio_imu_launch_gather_list(c->stream, st, n_edges, edge, slot_i, c->d_imu);
+        }
+    }
+    ex->imu_raw.clear(); ex->imu_dig.clear();          // glio_set_imu's cache of digested edges describes another table now
+    c->n_imu = n_edges;
+    for (int k = 0; k < n_edges; ++k) c->h_imu_slot[k] = slot_i[k];
+    c->chain_tabs_dirty = 1; c->h_band_clean = 0;
+    ex->imu_edge0 = -1;
+    for (int k = 0; k < n_edges; ++k) if (slot_i[k] == 0) ex->imu_edge0 = k;
+    if (n_edges) c->have_factors = 1;
+    return GLIO_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- prior
 int glio_set_prior(glio_ctx* c, const glio_prior* p) {
     if (!c) return GLIO_E_ARG;

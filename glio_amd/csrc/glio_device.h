@@ -451,6 +451,29 @@ int glio_assoc_build_map(glio_ctx* c, const void* map_points, int n, int stride,
 int glio_assoc_run(glio_ctx* c, int slot, const double q[4], const double t[3], int* out_count);
 void glio_assoc_time_hooks(glio_ctx* c, int which, int reps, float* ms);
 
+// imu_kernels.hip: the device-resident store of IMU pre-integrations (glio_imu_*)
+struct glio_imu {
+    int device;
+    hipStream_t stream;
+    hipEvent_t ev_done;                 // the end of the last glio_imu_integrate: what a consumer's stream waits for
+    hipEvent_t ev_t0, ev_t1;            // around the last integration kernel
+    hipEvent_t ev_copied; bool copying; // the last upload out of the pinned block
+    int max_edges, max_samples, timed;
+    glio_imu_noise noise;
+    glio_preint* d_pre;                 // [max_edges] the host view (glio_imu_read)
+    ImuEdgeDev* d_dig;                  // [max_edges] the digested form the factor kernels read (slot_i = 0: the consumer's copy sets it)
+    int* d_flag; int* h_flag;           // [max_edges] 0 = fine, 1 = non-finite, 2 = covariance not invertible / not SPD; h_flag pinned, as of the last wait
+    char* h_up; char* d_up; size_t up_cap;      // pinned block [offsets | start values | samples] and its device mirror
+};
+#define GLIO_IMU_FLAG_NONFINITE 1
+#define GLIO_IMU_FLAG_SINGULAR 2
+// dst[k] = the store's edge edge[k] with slot_i = slot[k] (n <= GLIO_MAX_WINDOW), on `stream`
+void glio_imu_launch_gather_list(hipStream_t stream, const glio_imu* s, int n, const int32_t* edge, const int32_t* slot, ImuEdgeDev* dst);
+// dst[k] = the store's edge first + k with slot_i = k
+void glio_imu_launch_gather_range(hipStream_t stream, const glio_imu* s, int first, int n, ImuEdgeDev* dst);
+// the first edge of [first, first + n) that the host knows to be flagged (as of the store's last wait), or -1
+int glio_imu_known_flag(const glio_imu* s, int first, int n, const int32_t* list);
+
 void glio_set_error(const char* fmt, ...);
 // roctx range around a C-ABI entry point (SURVEY section 5 "tracing"): visible in rocprofv3 --marker-trace when GLIO_ROCTX=1 (libroctx64 is
 // opened with dlopen: no link dependency, no cost when the switch is off)

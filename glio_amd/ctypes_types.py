@@ -118,6 +118,16 @@ class GlioFeatCounts(C.Structure):
         return {"in": self.in_, "kept": self.kept, "cut": self.cut, "sharp": self.sharp, "less_sharp": self.less_sharp, "flat": self.flat, "surf": self.surf}
 
 
+class GlioImuNoise(C.Structure):
+    """glio_imu_noise: acc_n, gyr_n, acc_w, gyr_w of class Preintegration (Preintegration.h:48-51)"""
+    _fields_ = [("acc_n", C.c_double), ("gyr_n", C.c_double), ("acc_w", C.c_double), ("gyr_w", C.c_double)]
+
+
+class GlioImuSample(C.Structure):
+    """glio_imu_sample: one push_back(dt, acc, gyr); a [n][7] float64 array has the same bytes"""
+    _fields_ = [("dt", C.c_double), ("acc", C.c_double * 3), ("gyr", C.c_double * 3)]
+
+
 FEAT_SURF, FEAT_EDGE_LESS_SHARP, FEAT_SHARP, FEAT_FLAT, FEAT_CUT_CLOUD, FEAT_LAST_SCAN = range(6)
 FEAT_MAX_RAW_POINTS = 400000
 

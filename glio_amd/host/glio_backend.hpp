@@ -255,6 +255,12 @@ public:
         for (size_t k = 0; k < pre.size(); ++k) slots[k] = (int32_t)k;
         check(glio_set_imu(ctx_, (int)pre.size(), pre.data(), slots.data()), "glio_set_imu");
     }
+    // the same with the edges taken from an ImuStore on the same device: edges[k] links slots k, k + 1 (glio_set_imu_from_store)
+    void setImuFactorsFromStore(glio_imu* store, const std::vector<int32_t>& edges) {
+        std::vector<int32_t> slots(edges.size());
+        for (size_t k = 0; k < edges.size(); ++k) slots[k] = (int32_t)k;
+        check(glio_set_imu_from_store(ctx_, store, (int)edges.size(), edges.data(), slots.data()), "glio_set_imu_from_store");
+    }
     void setMarginalizationPrior(const glio_prior* prior) { check(glio_set_prior(ctx_, prior), "glio_set_prior"); }
     void setGnss(const glio_gnss_frame* frame, const std::vector<glio_dd_psr>& dd, const std::vector<glio_doppler>& dop) {
         check(glio_set_gnss(ctx_, frame, (int)dd.size(), dd.data(), (int)dop.size(), dop.data()), "glio_set_gnss");
@@ -486,6 +492,116 @@ private:
     double q_[4] = {1, 0, 0, 0};
     bool first_imu_ = false;
 };
+
+// ---- raw IMU input ------------------------------------------------------------------------------------
+// One push_back(dt, acc, gyr) is a glio_imu_sample.  keyframeImuSamples is the sample preparation of saveKeyFramesAndFactors (Estimator.cpp:4162-4229):
+// from the time-stamped IMU buffer (stamps / acc / gyr [n]), the running index idx_imu and cur_time_imu, the list processIMU is called with for the
+// keyframe at kf_time -- every sample from idx_imu with a stamp strictly before kf_time (dt against cur_time_imu, 0 for the very first sample; acc clamped
+// to +-15 / +-15 / +-18, :4176-4182), up to the buffer's end (the early break, :4194), then the closing sample interpolated between the last one taken and the
+// next (w1 = dt2 / (dt1 + dt2), w2 = dt1 / (dt1 + dt2), clamped again, :4199-4227), none when the buffer ended.  idx_imu / cur_time_imu are left as the
+// reference leaves them (:4243, :4229).  The Python twin is glio_amd/imu.py::keyframe_samples: the same doubles, bit for bit (tests/test_imu_host_cpu.py).
+inline double clampImuAcc(double v, double lim) { if (v > lim) v = lim; if (v < -lim) v = -lim; return v; }
+inline std::vector<glio_imu_sample> keyframeImuSamples(const std::vector<double>& stamps, const std::vector<std::array<double, 3>>& acc,
+                                                       const std::vector<std::array<double, 3>>& gyr, size_t& idx_imu, double& cur_time_imu, double kf_time) {
+    static const double lim[3] = {15.0, 15.0, 18.0};
+    std::vector<glio_imu_sample> out;
+    const size_t n = stamps.size();
+    size_t i = idx_imu;
+    double d[3] = {0, 0, 0}, r[3] = {0, 0, 0};
+    while (i < n && stamps[i] < kf_time) {
+        const double t = stamps[i];
+        if (cur_time_imu < 0) cur_time_imu = t;
+        glio_imu_sample s;
+        s.dt = t - cur_time_imu;
+        cur_time_imu = t;
+        for (int k = 0; k < 3; ++k) { d[k] = clampImuAcc(acc[i][k], lim[k]); r[k] = gyr[i][k]; s.acc[k] = d[k]; s.gyr[k] = r[k]; }
+        out.push_back(s);
+        i++;
+        if (i >= n) break;
+    }
+    if (i < n) {
+        const double dt1 = kf_time - cur_time_imu, dt2 = stamps[i] - kf_time;
+        const double w1 = dt2 / (dt1 + dt2), w2 = dt1 / (dt1 + dt2);
+        glio_imu_sample s;
+        s.dt = dt1;
+        for (int k = 0; k < 3; ++k) {
+            d[k] = clampImuAcc(w1 * d[k] + w2 * acc[i][k], lim[k]);
+            r[k] = w1 * r[k] + w2 * gyr[i][k];
+            s.acc[k] = d[k]; s.gyr[k] = r[k];
+        }
+        out.push_back(s);
+    }
+    cur_time_imu = kf_time;
+    idx_imu = i;
+    return out;
+}
+// Rs / Ps / Vs of processIMU (Estimator.cpp:1592-1598) over the samples of one edge, beside the pre-integration (which the store does on the device):
+// midpoint propagation in the world frame with deltaQ(un_gyr dt) = (1, un_gyr dt / 2) turned into a matrix by Eigen's toRotationMatrix() without
+// normalisation.  R [9] row-major, P, V [3] in/out; acc0 / gyr0 [3] in/out (acc_0 / gyr_0 of the estimator); g = the gravity vector.  ~30 flops per sample,
+// and the caller needs the result at once: this stays on the host.  Python twin: imu.propagate_state.
+inline void propagateImuState(double R[9], double P[3], double V[3], const double ba[3], const double bg[3], double acc0[3], double gyr0[3],
+                              const std::vector<glio_imu_sample>& samples, const double g[3]) {
+    for (const glio_imu_sample& s : samples) {
+        const double dt = s.dt;
+        double e0[3], un0[3], ug[3], e1[3], un1[3];
+        for (int k = 0; k < 3; ++k) e0[k] = acc0[k] - ba[k];
+        for (int i = 0; i < 3; ++i) un0[i] = R[i * 3 + 0] * e0[0] + R[i * 3 + 1] * e0[1] + R[i * 3 + 2] * e0[2] - g[i];
+        for (int k = 0; k < 3; ++k) ug[k] = 0.5 * (gyr0[k] + s.gyr[k]) - bg[k];
+        const double qw = 1.0, qx = ug[0] * dt / 2.0, qy = ug[1] * dt / 2.0, qz = ug[2] * dt / 2.0;
+        const double tx = 2 * qx, ty = 2 * qy, tz = 2 * qz;
+        const double twx = tx * qw, twy = ty * qw, twz = tz * qw;
+        const double txx = tx * qx, txy = ty * qx, txz = tz * qx;
+        const double tyy = ty * qy, tyz = tz * qy, tzz = tz * qz;
+        const double D[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
+        double Rn[9];
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j) Rn[i * 3 + j] = R[i * 3 + 0] * D[0 * 3 + j] + R[i * 3 + 1] * D[1 * 3 + j] + R[i * 3 + 2] * D[2 * 3 + j];
+        for (int k = 0; k < 9; ++k) R[k] = Rn[k];
+        for (int k = 0; k < 3; ++k) e1[k] = s.acc[k] - ba[k];
+        for (int i = 0; i < 3; ++i) un1[i] = R[i * 3 + 0] * e1[0] + R[i * 3 + 1] * e1[1] + R[i * 3 + 2] * e1[2] - g[i];
+        for (int k = 0; k < 3; ++k) {
+            const double un = 0.5 * (un0[k] + un1[k]);
+            P[k] = P[k] + (dt * V[k] + 0.5 * dt * dt * un);
+            V[k] = V[k] + dt * un;
+        }
+        for (int k = 0; k < 3; ++k) { acc0[k] = s.acc[k]; gyr0[k] = s.gyr[k]; }
+    }
+}
+// The pre_integrations vector (Estimator.cpp:1582-1600) on the device: processIMU's `new Preintegration(acc_0, gyr_0, Bas.back(), Bgs.back())` + push_back per
+// sample become ONE integrate() per keyframe with the list keyframeImuSamples made.  Edges are addressed by index (a ring, if the
+// caller wishes); SlidingWindowBackend::setImuFactorsFromStore and BatchBackend::setImuFromStore take them without a trip through the host.
+class ImuStore {
+public:
+    struct Start { double acc0[3], gyr0[3], linearized_ba[3], linearized_bg[3]; };
+    ImuStore(int max_edges, int max_samples_per_edge, const glio_imu_noise* noise = nullptr, int device = 0) {
+        glio_imu_noise n;
+        if (noise) n = *noise; else glio_imu_noise_default(&n);
+        check(glio_imu_create(device, max_edges, max_samples_per_edge, &n, &h_), "glio_imu_create");
+    }
+    ~ImuStore() { glio_imu_destroy(h_); }
+    ImuStore(const ImuStore&) = delete;
+    ImuStore& operator=(const ImuStore&) = delete;
+    glio_imu* handle() const { return h_; }
+    // one edge (asynchronous: returns when the samples have been copied)
+    void integrate(int edge, const Start& start, const std::vector<glio_imu_sample>& samples) {
+        const int32_t off[2] = {0, (int32_t)samples.size()};
+        check(glio_imu_integrate(h_, edge, 1, off, samples.empty() ? nullptr : samples.data(), start.acc0), "glio_imu_integrate");
+    }
+    // edges first_edge .. in one launch: sample_offset [n_edges + 1] into samples, start [n_edges]
+    void integrate(int first_edge, const std::vector<int32_t>& sample_offset, const std::vector<glio_imu_sample>& samples, const std::vector<Start>& start) {
+        check(glio_imu_integrate(h_, first_edge, (int)start.size(), sample_offset.data(), samples.empty() ? nullptr : samples.data(),
+                                 start.empty() ? nullptr : start[0].acc0), "glio_imu_integrate");
+    }
+    std::vector<glio_preint> read(int first_edge, int n) {
+        std::vector<glio_preint> out((size_t)n);
+        check(glio_imu_read(h_, first_edge, n, out.data()), "glio_imu_read");
+        return out;
+    }
+    float lastDeviceMs() { float ms = 0; check(glio_imu_last_device_ms(h_, &ms), "glio_imu_last_device_ms"); return ms; }
+private:
+    glio_imu* h_ = nullptr;
+};
+static_assert(sizeof(ImuStore::Start) == 12 * sizeof(double), "glio_imu_integrate takes start values as [n][12] doubles");
 
 // ---- (3) the front end -------------------------------------------------------------------------------
 // LidarOdometry (GLIO/src/LidarOdometry.cpp): scan-to-map odometry on the same C-ABI with a one-keyframe window.  Per scan, run() (:661-699):

@@ -150,6 +150,11 @@ public:
         check(glio_batch_set_imu(h_, (int)edges.size(), edges.empty() ? nullptr : edges.data(), gravity), "glio_batch_set_imu");
         have_imu_ = !edges.empty();
     }
+    // the same chain from a glio_imu store on the same device (glio::ImuStore::handle()): its edges first_edge .. first_edge + K - 2
+    void setImuFromStore(glio_imu* store, int first_edge, double gravity) {
+        check(glio_batch_set_imu_from_store(h_, store, first_edge, gravity), "glio_batch_set_imu_from_store");
+        have_imu_ = true;
+    }
     // ceres::Solve of the batch problem (Estimator.cpp:3275-3284), device resident; speed_bias [K][9] travels with the IMU chain
     glio_summary solveTrustRegion(std::vector<double>& poses, const glio_batch_tr_opts& opts, std::vector<double>* speed_bias = nullptr) {
         glio_summary s;

@@ -82,6 +82,15 @@ def feature_selection_window(backend, counts, feature_res_num, rng, random_selec
 MIN_MAP_POINTS = 50        # `if (surf_local_map_ds->points.size() > 50)` guards the correspondence search, Estimator.cpp:2221,2244
 
 
+def set_imu_edges(backend, preints):
+    """The window's IMU edges (Estimator.cpp:2182-2192): a list of pre-integrations (host path, glio_set_imu), or a pair
+    (imu.ImuStore, edge indices) -- edge_indices[s] is the store's edge between slots s and s + 1 -- taken on the device (glio_set_imu_from_store)."""
+    if isinstance(preints, tuple) and len(preints) == 2 and hasattr(preints[0], "integrate_raw"):
+        backend.set_imu_from_store(preints[0], preints[1])
+    else:
+        backend.set_imu(preints)
+
+
 class SlidingWindowDriver:
     def __init__(self, backend, opts, lidar_pose=capi.lidar_pose):
         self.be, self.opts, self.W = backend, opts, opts.window
@@ -99,7 +108,8 @@ class SlidingWindowDriver:
 
     def step(self, map_pts, scans, preints):
         """One optimizeSlidingWindowWithLandMark() call.  scans[s] / preints[s] are those of window slot s
-        (preints[s] links slots s and s+1).  Returns (solved state, summary, correspondence counts)."""
+        (preints[s] links slots s and s+1; or preints = (imu.ImuStore, edge indices), see set_imu_edges).  Returns (solved state, summary,
+        correspondence counts)."""
         be, W = self.be, self.W
         be.set_map(map_pts)
         counts = []
@@ -110,7 +120,7 @@ class SlidingWindowDriver:
                 continue
             q2, t2 = self.lidar_pose(self.opts, self.state.quat[s], self.state.trans[s])
             counts.append(be.associate(s, scans[s], q2, t2))
-        be.set_imu(preints)
+        set_imu_edges(be, preints)
         be.set_prior(self.prior)
         be.set_gnss(None, [], [])
         sol, summ = be.solve(self.state)
@@ -163,7 +173,7 @@ class ResidentSlidingWindow:
             counts = [0] * W
         else:
             counts = ctx.associate_window(np.array([p[0] for p in poses]), np.array([p[1] for p in poses]))
-        ctx.set_imu(preints)
+        set_imu_edges(ctx, preints)
         sol, summ = ctx.solve(self.state)
         unify_quaternions(sol)
         ctx.marginalize_keep(sol)

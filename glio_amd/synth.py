@@ -312,6 +312,7 @@ class Window:
     dop: list = field(default_factory=list)       # GlioDoppler
     frame: T.GlioGnssFrame = None
     prior: dict = None
+    imu_raw: list = field(default_factory=list)   # per edge (acc [n + 1][3], gyr [n + 1][3], dts [n]): what preints[s] was integrated from
 
 
 def default_opts(W=5, pts=65536, map_pts=1 << 21, n_ddt=0):
@@ -391,6 +392,7 @@ def make_window(W=5, pts_per_scan=2048, seed=SEED_BASE, with_gnss=False, with_pr
         acc = np.array([traj.specific_force(t) for t in ts]) + rng_imu.normal(0, ACC_N, (n + 1, 3))
         gyr = np.array([traj.omega_body(t) for t in ts]) + rng_imu.normal(0, GYR_N, (n + 1, 3))
         win.preints.append(preintegrate(acc, gyr, np.full(n, 1.0 / imu_rate), np.zeros(3), np.zeros(3)))
+        win.imu_raw.append((acc, gyr, np.full(n, 1.0 / imu_rate)))
 
     if with_gnss:
         n_ddt = _make_gnss(win, traj, seed, epoch_dt=gnss_epoch_dt)
@@ -476,7 +478,8 @@ def sub_window(long, lo, W):
             st.rcv_ddt[new] = src.rcv_ddt[old]
     win = Window(opts=None, W=W, gt=gt, init=init, kf_times=long.kf_times[lo:lo + W], scans=long.scans[lo:lo + W],
                  scan_plane_id=long.scan_plane_id[lo:lo + W], map_pts=long.map_pts, scene=long.scene,
-                 preints=long.preints[lo:lo + W - 1], dd=dd, dop=dop, frame=long.frame if (dd or dop) else None)
+                 preints=long.preints[lo:lo + W - 1], dd=dd, dop=dop, frame=long.frame if (dd or dop) else None,
+                 imu_raw=long.imu_raw[lo:lo + W - 1])
     win.opts = default_opts(W, pts=max(max(len(sc) for sc in win.scans), 64), map_pts=max(len(long.map_pts), 64), n_ddt=n_ddt)
     return win
 

@@ -410,6 +410,37 @@ int glio_features_to_scan(glio_ctx* ctx, int slot, float leaf, int* n);
 /* device time of the last extraction's kernels (HIP events around them, after the raw upload), ms */
 int glio_features_last_device_ms(glio_ctx* ctx, float* ms);
 
+/* ---- IMU pre-integration from raw samples: class Preintegration (GLIO/include/factors/Preintegration.h:29-194) on the device.
+ * A glio_imu is the reference's pre_integrations vector (Estimator.cpp:1582-1600) kept on the device: edge e is built from its start values and
+ * its run of samples (one wavefront per edge, any number of edges per call), digested there into the form the ImuFactor kernels read
+ * (sqrt_info = LLT(covariance^-1).L^T, ImuFactor.h:44-45), and handed to a sliding-window context or a batch stage on the same device without
+ * crossing PCIe again.  A store owns one HIP stream and is not thread-safe.  An edge whose samples hold a non-finite number, or whose covariance
+ * does not invert, is flagged on the device: glio_imu_read of a range that holds it returns GLIO_E_NUMERIC (glio_last_error names the edge; the
+ * other edges of the range are delivered), and so does a glio_*_from_store call that is given an edge already known to be flagged. */
+typedef struct glio_imu glio_imu;
+/* config_urban_hk.yaml:7-10 */
+void glio_imu_noise_default(glio_imu_noise* n);
+/* sizeof() of glio_imu_noise, glio_imu_sample; returns how many there are (2) */
+int glio_imu_struct_sizes(int32_t* out, int n);
+int glio_imu_create(int device, int max_edges, int max_samples_per_edge, const glio_imu_noise* noise, glio_imu** out);
+void glio_imu_destroy(glio_imu* s);
+/* Preintegration(acc0, gyr0, linearized_ba, linearized_bg) + one push_back per sample, in order (Estimator::processIMU, Estimator.cpp:1581-1604),
+ * for edges [first_edge, first_edge + n_edges): edge first_edge + e owns samples[sample_offset[e] .. sample_offset[e + 1]) (sample_offset has
+ * n_edges + 1 non-decreasing entries; an edge without samples is the constructor's state) and start[e] = acc0[3], gyr0[3], linearized_ba[3],
+ * linearized_bg[3].  Returns when the caller's buffers have been copied; the kernels run on the store's stream.  GLIO_E_ARG (nothing launched) for
+ * an edge outside [0, max_edges), more than max_samples_per_edge samples in an edge, negative counts or a missing pointer. */
+int glio_imu_integrate(glio_imu* s, int first_edge, int n_edges, const int32_t* sample_offset, const glio_imu_sample* samples,
+                       const double* start /* [n_edges][12] */);
+/* the host view of edges [first_edge, first_edge + n_edges) (waits for the store's stream) */
+int glio_imu_read(glio_imu* s, int first_edge, int n_edges, glio_preint* out);
+/* device time of the last glio_imu_integrate's kernel (HIP events around it, after the upload), ms; waits */
+int glio_imu_last_device_ms(glio_imu* s, float* ms);
+/* glio_set_imu (Estimator.cpp:2182-2192) with the edges taken from the store: edge[k] links slots slot_i[k] and slot_i[k] + 1.  The context's
+ * stream waits for the store's through an event, not the host; afterwards the context is as after glio_set_imu with the same edges. */
+int glio_set_imu_from_store(glio_ctx* ctx, glio_imu* s, int n_edges, const int32_t* edge, const int32_t* slot_i);
+/* glio_batch_set_imu (Estimator.cpp:2990-3001) with store edges first_edge .. first_edge + K - 2 as the chain */
+int glio_batch_set_imu_from_store(glio_batch* b, glio_imu* s, int first_edge, double gravity);
+
 #ifdef __cplusplus
 }
 #endif

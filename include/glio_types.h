@@ -236,6 +236,18 @@ typedef struct glio_feat_counts {
     int32_t surf;            /* surfPointsLessFlat after the per-ring VoxelGrid: /surf_features */
     int32_t reserved_;
 } glio_feat_counts;
+
+/* ---- raw IMU input: the pre_integrations vector on the device (glio_imu_*).
+ * The process noise densities of class Preintegration (Preintegration.h:48-51, 64-70); /IMU/acc_n ... of the yaml. */
+typedef struct glio_imu_noise {
+    double acc_n, gyr_n, acc_w, gyr_w;
+} glio_imu_noise;
+/* one push_back(dt, acc, gyr) (Preintegration.h:73-78) */
+typedef struct glio_imu_sample {
+    double dt;
+    double acc[3];
+    double gyr[3];
+} glio_imu_sample;
 enum { GLIO_FEAT_SURF = 0, GLIO_FEAT_EDGE_LESS_SHARP = 1, GLIO_FEAT_SHARP = 2, GLIO_FEAT_FLAT = 3, GLIO_FEAT_CUT_CLOUD = 4,
        GLIO_FEAT_LAST_SCAN = 5 /* the cloud the last glio_features_to_scan wrote into its slot */ };
 #define GLIO_FEAT_MAX_RAW_POINTS 400000
