@@ -2472,6 +2472,13 @@ void glio_bassoc_destroy(glio_bassoc* b) {
 }
 
 static int bassoc_drain(glio_bassoc* b);
+}  // extern "C"
+int glio_bassoc_view(glio_bassoc* b, GlioBassocView* out) {
+    if (!b || !out) return GLIO_E_ARG;
+    out->device = b->device; out->K = b->K; out->cap = b->cap; out->d_local = b->d_local; out->h_n = b->h_n; out->stream = b->stream;
+    return GLIO_OK;
+}
+extern "C" {
 int glio_bassoc_set_frame(glio_bassoc* b, int k, const float* scan_xyzi, int n) { return glio_bassoc_set_frame_strided(b, k, scan_xyzi, n, 16, 12); }
 int glio_bassoc_set_frame_strided(glio_bassoc* b, int k, const void* scan, int n, int stride_bytes, int intensity_offset) {
     if (!b || k < 0 || k >= b->K || n < 0 || n > b->cap || (n > 0 && !scan)) { glio_set_error("bad keyframe cloud (k %d, n %d)", k, n); return GLIO_E_ARG; }

@@ -433,6 +433,12 @@ int glio_assoc_run_window_async(glio_ctx* c, const double* quats, const double* 
 int glio_assoc_finish_pending(glio_ctx* c);
 void glio_localmap_destroy(glio_ctx* c);
 void glio_features_destroy(glio_ctx* c);          // feature_kernels.hip
+// localmap_kernels.hip: the local map's VoxelGrid (float accumulation in concatenation order) over a list of device-resident clouds, without a context.
+// poses [n_frames][7] = t, q; the filtered cloud goes to `out` (nothing is copied when *nv_out > out_cap).  Waits for `stream` once, inside.
+struct LocalMap;
+int glio_vg_create(int width, int cap, float leaf, int max_vox, hipStream_t stream, LocalMap** out);
+void glio_vg_destroy(LocalMap* m);
+int glio_vg_build(LocalMap* m, hipStream_t stream, int n_frames, const float4* const* src, const int* n_src, const double* poses, float4* out, int out_cap, int* nv_out);
 // solver_kernels.hip
 void glio_launch_tr_step(glio_ctx* c, int n_ddt);
 void glio_chain_tabs_upload(glio_ctx* c);
@@ -450,6 +456,10 @@ void glio_assoc_destroy(glio_ctx* c);
 int glio_assoc_build_map(glio_ctx* c, const void* map_points, int n, int stride, int ioff);
 int glio_assoc_run(glio_ctx* c, int slot, const double q[4], const double t[3], int* out_count);
 void glio_assoc_time_hooks(glio_ctx* c, int which, int reps, float* ms);
+// what a glio_loop (loop_kernels.hip) needs of the batch association it is created on: the resident keyframe clouds [K][cap] with their sizes (a host array
+// the association keeps up to date) and the stream their copies are enqueued on
+struct GlioBassocView { int device, K, cap; const float4* d_local; const int* h_n; hipStream_t stream; };
+int glio_bassoc_view(glio_bassoc* b, GlioBassocView* out);
 
 // imu_kernels.hip: the device-resident store of IMU pre-integrations (glio_imu_*)
 struct glio_imu {

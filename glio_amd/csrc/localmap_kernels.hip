@@ -435,8 +435,7 @@ __global__ void k_lm_emit_float(const int* __restrict__ vslot_sorted, const int 
 #define LM_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { glio_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); return GLIO_E_HIP; } } while (0)
 static int lm_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
-void glio_localmap_destroy(glio_ctx* c) {
-    LocalMap* m = c->localmap;
+static void lm_free(LocalMap* m) {
     if (!m) return;
     void* p[] = {m->d_slot_bbox, m->d_nkeys, m->d_n, m->d_ring, m->d_keys, m->d_sum, m->d_cnt, m->d_bbox, m->d_nvox, m->d_vkey, m->d_vkey_sorted, m->d_vslot, m->d_vslot_sorted, m->d_sort_tmp, m->d_out, m->d_fill, m->d_slot_start, m->d_plist, m->d_bm, m->d_bm_pre, m->d_bm_blk, m->d_bm_over};
     for (void* q : p) if (q) hipFree(q);
@@ -444,20 +443,15 @@ void glio_localmap_destroy(glio_ctx* c) {
     if (m->h_pub) hipHostFree(m->h_pub);
     delete[] m->h_n;
     delete m;
+}
+void glio_localmap_destroy(glio_ctx* c) {
+    lm_free(c->localmap);
     c->localmap = nullptr;
 }
 
-extern "C" {
-
-int glio_localmap_config(glio_ctx* c, int width, float leaf, int max_points_per_keyframe) {
-    if (!c || width < 1 || !(leaf > 0.f) || max_points_per_keyframe < 1) return GLIO_E_ARG;
-    LM_CHECK(hipSetDevice(c->device));
-    const int keep_accumulation = c->localmap ? c->localmap->accumulation : 0;      // (the centroid arithmetic is a property of the context, not of one ring)
-    glio_localmap_destroy(c);
-    LocalMap* m = new LocalMap();
-    memset(m, 0, sizeof *m);
-    m->width = width; m->cap = max_points_per_keyframe; m->leaf = leaf;
-    m->max_vox = c->opts.max_map_points > 0 ? c->opts.max_map_points : 1;
+// the buffers of a ring of m->width x m->cap points and of a voxel table for m->max_vox voxels (width, cap, leaf, max_vox set by the caller), cleared on `stream`
+static int lm_alloc(LocalMap* m, hipStream_t stream) {
+    const int width = m->width;
     m->table_cap = lm_pow2(2 * m->max_vox);
     m->h_n = new int[width]();
     LM_CHECK(hipMalloc((void**)&m->d_n, (size_t)width * 4));
@@ -478,16 +472,39 @@ int glio_localmap_config(glio_ctx* c, int width, float leaf, int max_points_per_
         const char* e = getenv("GLIO_LM_SORT");
         m->force_sort = e && atoi(e) != 0;
         LM_CHECK(hipMalloc((void**)&m->d_bm_over, 4));
-        LM_CHECK(hipMemsetAsync(m->d_bm_over, 0, 4, c->stream));
+        LM_CHECK(hipMemsetAsync(m->d_bm_over, 0, 4, stream));
         if (!m->force_sort) {
             const size_t words = (size_t)(BM_MAX_BITS / 32);
             LM_CHECK(hipMalloc((void**)&m->d_bm, words * 4)); LM_CHECK(hipMalloc((void**)&m->d_bm_pre, words * 4)); LM_CHECK(hipMalloc((void**)&m->d_bm_blk, 4096 * 4));
-            LM_CHECK(hipMemsetAsync(m->d_bm, 0, words * 4, c->stream));
+            LM_CHECK(hipMemsetAsync(m->d_bm, 0, words * 4, stream));
         }
     }
-    hipLaunchKernelGGL(k_lm_clear, dim3((m->table_cap + 255) / 256), dim3(256), 0, c->stream, m->d_keys, m->d_sum, m->d_cnt, m->table_cap, m->d_nkeys);
-    LM_CHECK(hipMemsetAsync(m->d_n, 0, (size_t)width * 4, c->stream));
-    LM_CHECK(hipStreamSynchronize(c->stream));
+    hipLaunchKernelGGL(k_lm_clear, dim3((m->table_cap + 255) / 256), dim3(256), 0, stream, m->d_keys, m->d_sum, m->d_cnt, m->table_cap, m->d_nkeys);
+    LM_CHECK(hipMemsetAsync(m->d_n, 0, (size_t)width * 4, stream));
+    LM_CHECK(hipStreamSynchronize(stream));
+    return GLIO_OK;
+}
+static int lm_set_accumulation(LocalMap* m, int mode) {
+    if (mode == 1 && !m->d_plist) {
+        LM_CHECK(hipMalloc((void**)&m->d_fill, (size_t)m->table_cap * 4)); LM_CHECK(hipMalloc((void**)&m->d_slot_start, (size_t)m->table_cap * 4));
+        LM_CHECK(hipMalloc((void**)&m->d_plist, (size_t)m->width * m->cap * 4));
+    }
+    m->accumulation = mode;
+    return GLIO_OK;
+}
+
+extern "C" {
+
+int glio_localmap_config(glio_ctx* c, int width, float leaf, int max_points_per_keyframe) {
+    if (!c || width < 1 || !(leaf > 0.f) || max_points_per_keyframe < 1) return GLIO_E_ARG;
+    LM_CHECK(hipSetDevice(c->device));
+    const int keep_accumulation = c->localmap ? c->localmap->accumulation : 0;      // (the centroid arithmetic is a property of the context, not of one ring)
+    glio_localmap_destroy(c);
+    LocalMap* m = new LocalMap();
+    memset(m, 0, sizeof *m);
+    m->width = width; m->cap = max_points_per_keyframe; m->leaf = leaf;
+    m->max_vox = c->opts.max_map_points > 0 ? c->opts.max_map_points : 1;
+    { const int ra = lm_alloc(m, c->stream); if (ra != GLIO_OK) { lm_free(m); return ra; } }
     c->localmap = m;
     if (keep_accumulation) return glio_localmap_set_accumulation(c, keep_accumulation);
     return GLIO_OK;
@@ -596,39 +613,37 @@ static bool lm_wait_published(LocalMap* m, int* out8) {
     }
 }
 
-int glio_localmap_build(glio_ctx* c, int* out_points) {
-    GLIO_TRACE("K1 glio_localmap_build (voxel grid + hash)");
-    if (!c || !c->localmap) { glio_set_error("glio_localmap_config first"); return GLIO_E_STATE; }
-    LocalMap* m = c->localmap;
-    LM_CHECK(hipSetDevice(c->device));
+// pcl::VoxelGrid of the ring's concatenation into m->d_out on `stream` (the whole of the down-sampling: glio_localmap_build hands the result to K1, a
+// loop-closure submap -- glio_vg_build below -- keeps it as it is); *nv_out = the voxels
+static int lm_voxelize(LocalMap* m, hipStream_t stream, int* nv_out) {
     const float inv_leaf = 1.0f / m->leaf;
     // (the slots' point counts are on the device already: every push records its own, k_lm_bbox_init)
     if (m->nkeys_seen > m->table_cap / 2) {               // too many tombstones: rebuild the table from the ring once
-        hipLaunchKernelGGL(k_lm_clear, dim3((m->table_cap + 255) / 256), dim3(256), 0, c->stream, m->d_keys, m->d_sum, m->d_cnt, m->table_cap, m->d_nkeys);
+        hipLaunchKernelGGL(k_lm_clear, dim3((m->table_cap + 255) / 256), dim3(256), 0, stream, m->d_keys, m->d_sum, m->d_cnt, m->table_cap, m->d_nkeys);
         for (int k = 0; k < m->count; ++k) {
             const int slot = (m->head + k) % m->width, n = m->h_n[slot];
-            if (n > 0) hipLaunchKernelGGL(k_lm_accumulate, dim3((n + 255) / 256), dim3(256), 0, c->stream, m->d_ring + (size_t)slot * m->cap, n, inv_leaf, +1,
+            if (n > 0) hipLaunchKernelGGL(k_lm_accumulate, dim3((n + 255) / 256), dim3(256), 0, stream, m->d_ring + (size_t)slot * m->cap, n, inv_leaf, +1,
                                           m->d_keys, m->d_sum, m->d_cnt, m->table_cap, m->d_nkeys);
         }
     }
     if (m->d_bm && m->bm_dirty) {          // a build that ended between k_lm_list and its emit kernel (an error return) left bits behind
-        LM_CHECK(hipMemsetAsync(m->d_bm, 0, (size_t)(BM_MAX_BITS / 32) * 4, c->stream));
+        LM_CHECK(hipMemsetAsync(m->d_bm, 0, (size_t)(BM_MAX_BITS / 32) * 4, stream));
         m->bm_dirty = 0;
     }
-    hipLaunchKernelGGL(k_lm_bbox_union, dim3(1), dim3(64), 0, c->stream, m->d_slot_bbox, m->d_n, m->width, m->d_bbox, m->d_bm_over, m->d_nvox);
-    hipLaunchKernelGGL(k_lm_list, dim3((m->table_cap + 1023) / 1024), dim3(1024), 0, c->stream, m->d_keys, m->d_cnt, m->table_cap, inv_leaf, m->d_bbox,
+    hipLaunchKernelGGL(k_lm_bbox_union, dim3(1), dim3(64), 0, stream, m->d_slot_bbox, m->d_n, m->width, m->d_bbox, m->d_bm_over, m->d_nvox);
+    hipLaunchKernelGGL(k_lm_list, dim3((m->table_cap + 1023) / 1024), dim3(1024), 0, stream, m->d_keys, m->d_cnt, m->table_cap, inv_leaf, m->d_bbox,
                        m->d_nvox, m->d_vkey, m->d_vslot, m->max_vox, m->d_bm, (unsigned long long)BM_MAX_BITS, m->d_bm_over);
     LM_CHECK(hipGetLastError());
     if (m->d_bm) m->bm_dirty = 1;
     m->pub_seq = m->pub_seq == 0xffffffffu ? 1u : m->pub_seq + 1u;
-    hipLaunchKernelGGL(k_lm_publish, dim3(1), dim3(64), 0, c->stream, m->d_nvox, m->d_nkeys, m->d_bbox, m->d_bm_over, m->d_h_pub, m->pub_seq);
+    hipLaunchKernelGGL(k_lm_publish, dim3(1), dim3(64), 0, stream, m->d_nvox, m->d_nkeys, m->d_bbox, m->d_bm_over, m->d_h_pub, m->pub_seq);
     LM_CHECK(hipGetLastError());
     if (!lm_wait_published(m, m->h_pin)) {
-        LM_CHECK(hipMemcpyAsync(m->h_pin, m->d_nvox, 4, hipMemcpyDeviceToHost, c->stream));
-        LM_CHECK(hipMemcpyAsync(m->h_pin + 1, m->d_nkeys, 4, hipMemcpyDeviceToHost, c->stream));
-        LM_CHECK(hipMemcpyAsync(m->h_pin + 2, m->d_bbox, 24, hipMemcpyDeviceToHost, c->stream));
-        LM_CHECK(hipMemcpyAsync(m->h_pin + 8, m->d_bm_over, 4, hipMemcpyDeviceToHost, c->stream));
-        LM_CHECK(hipStreamSynchronize(c->stream));
+        LM_CHECK(hipMemcpyAsync(m->h_pin, m->d_nvox, 4, hipMemcpyDeviceToHost, stream));
+        LM_CHECK(hipMemcpyAsync(m->h_pin + 1, m->d_nkeys, 4, hipMemcpyDeviceToHost, stream));
+        LM_CHECK(hipMemcpyAsync(m->h_pin + 2, m->d_bbox, 24, hipMemcpyDeviceToHost, stream));
+        LM_CHECK(hipMemcpyAsync(m->h_pin + 8, m->d_bm_over, 4, hipMemcpyDeviceToHost, stream));
+        LM_CHECK(hipStreamSynchronize(stream));
         if (m->h_pin[8]) m->h_pin[1] |= 0x20000000;
     }
     const bool bm_over = (m->h_pin[1] & 0x20000000) != 0;
@@ -649,9 +664,9 @@ int glio_localmap_build(glio_ctx* c, int* out_points) {
         const bool by_rank = m->d_bm && !bm_over && span <= (double)BM_MAX_BITS;
         if (by_rank) {
             const int nwords = (int)(((unsigned long long)span + 31ull) / 32ull), nblk = (nwords + 1023) / 1024;
-            hipLaunchKernelGGL(k_bm_scan1, dim3(nblk), dim3(1024), 0, c->stream, m->d_bm, nwords, m->d_bm_pre, m->d_bm_blk);
-            hipLaunchKernelGGL(k_bm_scan2, dim3(1), dim3(1024), 0, c->stream, m->d_bm_blk, nblk);
-            hipLaunchKernelGGL(k_bm_rank, dim3((nv + 255) / 256), dim3(256), 0, c->stream, m->d_vkey, m->d_vslot, nv, m->d_bm, m->d_bm_pre, m->d_bm_blk, m->d_vslot_sorted);
+            hipLaunchKernelGGL(k_bm_scan1, dim3(nblk), dim3(1024), 0, stream, m->d_bm, nwords, m->d_bm_pre, m->d_bm_blk);
+            hipLaunchKernelGGL(k_bm_scan2, dim3(1), dim3(1024), 0, stream, m->d_bm_blk, nblk);
+            hipLaunchKernelGGL(k_bm_rank, dim3((nv + 255) / 256), dim3(256), 0, stream, m->d_vkey, m->d_vslot, nv, m->d_bm, m->d_bm_pre, m->d_bm_blk, m->d_vslot_sorted);
             va = m->d_vslot_sorted;
         } else {
             int bits = 1;
@@ -661,26 +676,37 @@ int glio_localmap_build(glio_ctx* c, int* out_points) {
             int* vb = m->d_vslot_sorted;
             int* hist = reinterpret_cast<int*>(m->d_sort_tmp);
             for (int p = 0; p < passes; ++p) {
-                hipLaunchKernelGGL(k_rs_hist, dim3(nt), dim3(64), 0, c->stream, ka, nv, 8 * p, nt, hist);
-                hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, c->stream, hist, nt);
-                hipLaunchKernelGGL(k_rs_scatter, dim3(nt), dim3(64), 0, c->stream, ka, va, nv, 8 * p, nt, hist, kb, vb);
+                hipLaunchKernelGGL(k_rs_hist, dim3(nt), dim3(64), 0, stream, ka, nv, 8 * p, nt, hist);
+                hipLaunchKernelGGL(k_rs_scan, dim3(1), dim3(1024), 0, stream, hist, nt);
+                hipLaunchKernelGGL(k_rs_scatter, dim3(nt), dim3(64), 0, stream, ka, va, nv, 8 * p, nt, hist, kb, vb);
                 std::swap(ka, kb); std::swap(va, vb);
             }
             keys_final = ka;
         }
         LM_CHECK(hipGetLastError());
         if (m->accumulation == 1) {
-            hipLaunchKernelGGL(k_lm_starts, dim3(1), dim3(1024), 0, c->stream, va, nv, m->d_cnt, m->d_slot_start);
-            LM_CHECK(hipMemsetAsync(m->d_fill, 0, (size_t)m->table_cap * 4, c->stream));
-            hipLaunchKernelGGL(k_lm_scatter_idx, dim3((m->cap + 255) / 256, m->width), dim3(256), 0, c->stream, m->d_ring, m->d_n, m->cap, m->width, m->head, m->count,
+            hipLaunchKernelGGL(k_lm_starts, dim3(1), dim3(1024), 0, stream, va, nv, m->d_cnt, m->d_slot_start);
+            LM_CHECK(hipMemsetAsync(m->d_fill, 0, (size_t)m->table_cap * 4, stream));
+            hipLaunchKernelGGL(k_lm_scatter_idx, dim3((m->cap + 255) / 256, m->width), dim3(256), 0, stream, m->d_ring, m->d_n, m->cap, m->width, m->head, m->count,
                                inv_leaf, m->d_keys, m->table_cap, m->d_slot_start, m->d_fill, m->d_plist);
-            hipLaunchKernelGGL(k_lm_emit_float, dim3((nv + 255) / 256), dim3(256), 0, c->stream, va, nv, m->d_cnt, m->d_slot_start, m->d_plist, m->d_ring, m->cap, m->width,
+            hipLaunchKernelGGL(k_lm_emit_float, dim3((nv + 255) / 256), dim3(256), 0, stream, va, nv, m->d_cnt, m->d_slot_start, m->d_plist, m->d_ring, m->cap, m->width,
                                m->head, m->d_out, m->d_bm, keys_final, (unsigned long long)BM_MAX_BITS);
         } else
-        hipLaunchKernelGGL(k_lm_emit, dim3((nv + 255) / 256), dim3(256), 0, c->stream, va, nv, m->d_sum, m->d_cnt, m->d_out, m->d_bm, keys_final,
+        hipLaunchKernelGGL(k_lm_emit, dim3((nv + 255) / 256), dim3(256), 0, stream, va, nv, m->d_sum, m->d_cnt, m->d_out, m->d_bm, keys_final,
                            (unsigned long long)BM_MAX_BITS);     // (va: the sorted side after the last swap)
         m->bm_dirty = 0;
     } else m->bm_dirty = 0;
+    *nv_out = nv;
+    return GLIO_OK;
+}
+
+int glio_localmap_build(glio_ctx* c, int* out_points) {
+    GLIO_TRACE("K1 glio_localmap_build (voxel grid + hash)");
+    if (!c || !c->localmap) { glio_set_error("glio_localmap_config first"); return GLIO_E_STATE; }
+    LocalMap* m = c->localmap;
+    LM_CHECK(hipSetDevice(c->device));
+    int nv = 0;
+    { const int rv = lm_voxelize(m, c->stream, &nv); if (rv != GLIO_OK) return rv; }
     const int rc = glio_assoc_build_map_dev(c, m->d_out, nv);          // K1: replaces setInputCloud(surf_local_map_ds) (:2056)
     if (rc) return rc;
     // (no wait here: the map's size is known since the synchronisation above, and everything that reads the map -- the searches, glio_localmap_read --
@@ -696,12 +722,7 @@ int glio_localmap_set_accumulation(glio_ctx* c, int mode) {
     if (!c || !c->localmap || (mode != 0 && mode != 1)) { glio_set_error("glio_localmap_config first; mode 0 or 1"); return GLIO_E_ARG; }
     LocalMap* m = c->localmap;
     LM_CHECK(hipSetDevice(c->device));
-    if (mode == 1 && !m->d_plist) {
-        LM_CHECK(hipMalloc((void**)&m->d_fill, (size_t)m->table_cap * 4)); LM_CHECK(hipMalloc((void**)&m->d_slot_start, (size_t)m->table_cap * 4));
-        LM_CHECK(hipMalloc((void**)&m->d_plist, (size_t)m->width * m->cap * 4));
-    }
-    m->accumulation = mode;
-    return GLIO_OK;
+    return lm_set_accumulation(m, mode);
 }
 
 int glio_localmap_read(glio_ctx* c, float* out_xyzi, int capacity, int* out_n) {
@@ -718,3 +739,46 @@ int glio_localmap_read(glio_ctx* c, float* out_xyzi, int capacity, int* out_n) {
 }
 
 }  // extern "C"
+
+// ---- the same VoxelGrid for a caller that is not a context: a list of device-resident clouds, each moved by transformCloud (k_lm_transform), concatenated in
+// list order and filtered with the float accumulation (accumulation = 1: pcl::VoxelGrid's arithmetic and output order, the oracle's bit for bit).  The ring is
+// used as a plain array of `width` slots, refilled by every build.  For the loop-closure submaps (loop_kernels.hip).
+int glio_vg_create(int width, int cap, float leaf, int max_vox, hipStream_t stream, LocalMap** out) {
+    LocalMap* m = new LocalMap();
+    memset(m, 0, sizeof *m);
+    m->width = width; m->cap = cap; m->leaf = leaf; m->max_vox = max_vox > 0 ? max_vox : 1;
+    int rc = lm_alloc(m, stream);
+    if (rc == GLIO_OK) rc = lm_set_accumulation(m, 1);
+    if (rc != GLIO_OK) { lm_free(m); return rc; }
+    *out = m;
+    return GLIO_OK;
+}
+void glio_vg_destroy(LocalMap* m) { lm_free(m); }
+int glio_vg_build(LocalMap* m, hipStream_t stream, int n_frames, const float4* const* src, const int* n_src, const double* poses, float4* out, int out_cap, int* nv_out) {
+    if (n_frames < 1 || n_frames > m->width) return GLIO_E_ARG;
+    const float inv_leaf = 1.0f / m->leaf;
+    hipLaunchKernelGGL(k_lm_clear, dim3((m->table_cap + 255) / 256), dim3(256), 0, stream, m->d_keys, m->d_sum, m->d_cnt, m->table_cap, m->d_nkeys);
+    LM_CHECK(hipMemsetAsync(m->d_n, 0, (size_t)m->width * 4, stream));
+    m->head = 0; m->count = n_frames; m->nkeys_seen = 0;
+    for (int f = 0; f < m->width; ++f) m->h_n[f] = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        const int n = n_src[f];
+        if (n < 0 || n > m->cap) return GLIO_E_ARG;
+        const double* ps = poses + 7 * f;            // t[3], q[4] (w first)
+        float4* dst = m->d_ring + (size_t)f * m->cap;
+        hipLaunchKernelGGL(k_lm_bbox_init, dim3(1), dim3(64), 0, stream, m->d_slot_bbox + 6 * f, m->d_n + f, n);
+        if (n > 0) {
+            hipLaunchKernelGGL(k_lm_transform, dim3((n + 255) / 256), dim3(256), 0, stream, src[f], n, ps[3], ps[4], ps[5], ps[6], ps[0], ps[1], ps[2], dst);
+            hipLaunchKernelGGL(k_lm_bbox, dim3(std::min(64, (n + 1023) / 1024)), dim3(1024), 0, stream, dst, n, m->d_slot_bbox + 6 * f);
+            hipLaunchKernelGGL(k_lm_accumulate, dim3((n + 255) / 256), dim3(256), 0, stream, dst, n, inv_leaf, +1, m->d_keys, m->d_sum, m->d_cnt, m->table_cap, m->d_nkeys);
+        }
+        m->h_n[f] = n;
+    }
+    LM_CHECK(hipGetLastError());
+    int nv = 0;
+    { const int rv = lm_voxelize(m, stream, &nv); if (rv != GLIO_OK) return rv; }
+    *nv_out = nv;
+    if (nv > out_cap) return GLIO_OK;                 // (the caller reports it)
+    if (nv > 0) LM_CHECK(hipMemcpyAsync(out, m->d_out, (size_t)nv * 16, hipMemcpyDeviceToDevice, stream));
+    return GLIO_OK;
+}

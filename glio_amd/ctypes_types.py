@@ -132,6 +132,30 @@ FEAT_SURF, FEAT_EDGE_LESS_SHARP, FEAT_SHARP, FEAT_FLAT, FEAT_CUT_CLOUD, FEAT_LAS
 FEAT_MAX_RAW_POINTS = 400000
 
 
+class GlioLoopOpts(C.Structure):
+    """glio_loop_opts (include/glio_types.h): the submaps' leaf, pcl::IterativeClosestPoint's settings of Estimator.cpp:5197-5200, capacities"""
+    _fields_ = [("max_corr_dist", C.c_double), ("transformation_eps", C.c_double), ("fitness_eps", C.c_double), ("abs_mse_eps", C.c_double),
+                ("leaf", C.c_float), ("max_iterations", C.c_int32), ("min_correspondences", C.c_int32), ("max_source_points", C.c_int32),
+                ("max_target_points", C.c_int32), ("max_frames_per_submap", C.c_int32)]
+
+
+class GlioLoopResult(C.Structure):
+    """glio_loop_result: icp.align + hasConverged + getFitnessScore + getFinalTransformation"""
+    _fields_ = [("fitness", C.c_double), ("last_mse", C.c_double), ("transform", C.c_float * 16), ("converged", C.c_int32), ("state", C.c_int32),
+                ("iterations", C.c_int32), ("last_n_corr", C.c_int32), ("rank_deficient", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class GlioLoopStepResult(C.Structure):
+    """glio_loop_step_result: one round"""
+    _fields_ = [("mse", C.c_double), ("transform", C.c_float * 16), ("n_corr", C.c_int32), ("state", C.c_int32), ("n_fallback", C.c_int32),
+                ("rank_deficient", C.c_int32)]
+
+
+LOOP_SOURCE, LOOP_TARGET = 0, 1
+LOOP_NOT_CONVERGED, LOOP_ITERATIONS, LOOP_TRANSFORM, LOOP_ABS_MSE, LOOP_REL_MSE, LOOP_NO_CORRESPONDENCES = range(6)
+LOOP_STATE_NAMES = ("NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE", "NO_CORRESPONDENCES")
+
+
 def dptr(a):
     assert a.dtype == np.float64 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(c_double_p)

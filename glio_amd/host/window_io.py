@@ -266,3 +266,64 @@ def run_demo_frontend_raw(path, device=0, env=None):
             rows.append({"rounds": int(w[9]), "kept": int(w[10]), "iterations": int(w[11]), "final_cost": float(w[12]), "map_points": int(w[13]), "surf": int(w[14])})
     info = json.loads(next(ln for ln in r.stdout.splitlines() if ln.startswith("{")))
     return np.array(poses), rows, info
+
+
+DEMO_LOOP = os.path.join(HERE, "host_demo_loop")
+
+
+def build_demo_loop(force=False):
+    """The C++ loop-closure sequence (host_demo_loop.cpp over glio::LoopClosure and the host mirrors of glio_loop_backend.hpp)."""
+    src = [os.path.join(HERE, "host_demo_loop.cpp"), os.path.join(HERE, "glio_loop_backend.hpp")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_LOOP) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_LOOP) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_LOOP])
+    return DEMO_LOOP
+
+
+def write_loop_case(path, opts, cap, clouds, src_frames, src_pose_info, tgt_frames, tgt_pose_info, q_bl, t_bl, icp_thres, src_points=None, tgt_points=None):
+    """K cap n_src_frames n_tgt_frames n_src_points n_tgt_points 0 0 | glio_loop_opts | icp_thres | K x (n, cloud) | src frames, pose_info | tgt frames, pose_info
+    | q_bl t_bl | ready submaps (used when a frame list is empty)"""
+    sp = np.zeros((0, 4), np.float32) if src_points is None else np.ascontiguousarray(src_points, np.float32).reshape(-1, 4)
+    tp = np.zeros((0, 4), np.float32) if tgt_points is None else np.ascontiguousarray(tgt_points, np.float32).reshape(-1, 4)
+    with open(path, "wb") as f:
+        f.write(np.array([len(clouds), cap, len(src_frames), len(tgt_frames), len(sp), len(tp), 0, 0], np.int32).tobytes())
+        f.write(bytes(opts)); f.write(np.array([icp_thres], np.float64).tobytes())
+        for c in clouds:
+            c = np.ascontiguousarray(c, np.float32).reshape(-1, 4)
+            f.write(np.array([len(c)], np.int32).tobytes()); f.write(c.tobytes())
+        f.write(np.ascontiguousarray(src_frames, np.int32).tobytes()); f.write(np.ascontiguousarray(src_pose_info, np.float64).tobytes())
+        f.write(np.ascontiguousarray(tgt_frames, np.int32).tobytes()); f.write(np.ascontiguousarray(tgt_pose_info, np.float64).tobytes())
+        f.write(np.ascontiguousarray(q_bl, np.float64).tobytes()); f.write(np.ascontiguousarray(t_bl, np.float64).tobytes())
+        f.write(sp.tobytes()); f.write(tp.tobytes())
+
+
+def loop_checksum(cloud):
+    """FNV-1a over the 32-bit words of a float cloud, as host_demo_loop prints it"""
+    h = 1469598103934665603
+    for u in np.ascontiguousarray(cloud, np.float32).view(np.uint32).ravel().tolist():
+        h = ((h ^ u) * 1099511628211) & 0xffffffffffffffff
+    return h
+
+
+def run_demo_loop(path, device=0, env=None):
+    """-> dict(n_src, src_sum, n_tgt, tgt_sum, converged, state, iterations, last_n_corr, rank_deficient, fitness, last_mse, transform (float32 [4][4]),
+    constraint (None or (relative [7], variance)), align_device_ms)"""
+    import json
+    r = subprocess.run([build_demo_loop(), path, str(device)], capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError("host_demo_loop failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
+    out = {}
+    for ln in r.stdout.splitlines():
+        w = ln.split()
+        if w[0] == "submap":
+            out.update(n_src=int(w[1]), src_sum=int(w[2], 16), n_tgt=int(w[3]), tgt_sum=int(w[4], 16))
+        elif w[0] == "result":
+            out.update(converged=bool(int(w[1])), state=int(w[2]), iterations=int(w[3]), last_n_corr=int(w[4]), rank_deficient=bool(int(w[5])),
+                       fitness=float.fromhex(w[6]), last_mse=float.fromhex(w[7]))
+        elif w[0] == "transform":
+            out["transform"] = np.array([int(x, 16) for x in w[1:]], np.uint32).view(np.float32).reshape(4, 4)
+        elif w[0] == "constraint":
+            out["constraint"] = None if w[1] == "none" else (np.array([float.fromhex(x) for x in w[1:8]]), float.fromhex(w[8]))
+        elif ln.startswith("{"):
+            out.update(json.loads(ln))
+    return out

@@ -441,6 +441,60 @@ int glio_set_imu_from_store(glio_ctx* ctx, glio_imu* s, int n_edges, const int32
 /* glio_batch_set_imu (Estimator.cpp:2990-3001) with store edges first_edge .. first_edge + K - 2 as the chain */
 int glio_batch_set_imu_from_store(glio_batch* b, glio_imu* s, int first_edge, double gravity);
 
+/* ---- loop closure: detectLoopClosure's submaps and performLoopClosure's ICP (Estimator.cpp:5101-5273) on the device.
+ * A glio_loop is created on a glio_bassoc, whose resident keyframe clouds (glio_bassoc_set_frame*) it reads; it lives on the same device, owns one HIP
+ * stream, and every call orders itself behind the association's pending frame copies with an event -- never behind the host.  It changes nothing the
+ * association holds.  Not thread-safe by itself; meant for the reference's 1 Hz loop thread beside the keyframe cycle.
+ *
+ * The registration restates pcl::IterativeClosestPoint of PCL 1.8.1 (the version of the reference's docker image).  PCL is not part of the reference
+ * tree, so these rules are UNPINNED: restated from the published source, never run against PCL here.  With cur = source,
+ * final = I, prev_mse = DBL_MAX every round
+ *   1. finds for every point of cur its exact nearest target point: float d2 = dx*dx + dy*dy + dz*dz without contraction, ties to the lowest target
+ *      index; the pair is kept when (double) d2 <= max_corr_dist^2;
+ *   2. stops with converged = 0, NO_CORRESPONDENCES when fewer than min_correspondences pairs are kept;
+ *   3. fits the rigid transform of the kept pairs (Umeyama without scale: means, Sigma = 1/n sum (t - mu_t)(s - mu_s)^T, SVD,
+ *      R = U diag(1, 1, det U det V) V^T, t = mu_t - R mu_s) and rounds it to a float 4x4.  DELIBERATE DEVIATION: PCL accumulates in float; here the sums
+ *      are fp64 in a fixed order (bit-identical from run to run) and the SVD is fp64;
+ *   4. cur <- T cur and final <- T final in float (((a*x + b*y) + c*z) + d per row, no contraction), iterations += 1;
+ *   5. tests, in this order: iterations >= max_iterations (ITERATIONS); 0.5 (trace R - 1) >= 1 - transformation_eps and |t|^2 <= transformation_eps
+ *      (TRANSFORM); mse = mean of the kept d2 in double: |mse - prev_mse| < abs_mse_eps (ABS_MSE); |mse - prev_mse| / prev_mse < fitness_eps (REL_MSE);
+ *      otherwise prev_mse = mse and the next round;
+ *   6. fitness = the mean over ALL final cur points of the float squared 1-NN distance, summed in double (getFitnessScore's cap defaults to DBL_MAX).
+ * Pairs that are collinear (Sigma of rank < 2) determine no rotation: the round changes nothing, the alignment ends NOT_CONVERGED with rank_deficient = 1.
+ * setRANSACIterations(5) (:5194) has no effect in the reference: no correspondence rejector is installed. */
+typedef struct glio_loop glio_loop;
+void glio_loop_opts_default(glio_loop_opts* o);
+/* sizeof() of glio_loop_opts, glio_loop_result, glio_loop_step_result; returns how many there are (3) */
+int glio_loop_struct_sizes(int32_t* out, int n);
+int glio_loop_create(glio_bassoc* b, const glio_loop_opts* opts, glio_loop** out);
+void glio_loop_destroy(glio_loop* lp);
+/* one submap (which = GLIO_LOOP_SOURCE / GLIO_LOOP_TARGET) from resident keyframes: cloud frame_idx[f] moved by transformCloud with poses[f] = t[3], q[4]
+ * (as glio_bassoc_run takes them; Estimator.cpp:1548-1568), concatenated in list order, pcl::VoxelGrid at opts.leaf with PCL's float sums in
+ * concatenation order and PCL's output order (the arithmetic of glio_localmap_set_accumulation(ctx, 1)).  The result stays on the device;
+ * *n_points = its size.  GLIO_E_ARG: n_frames outside [1, max_frames_per_submap], a frame index outside [0, K), a frame that was never set (or holds no
+ * point), more voxels than the submap's capacity. */
+int glio_loop_build_submap(glio_loop* lp, int which, int n_frames, const int32_t* frame_idx, const double* poses /* [n_frames][7] */, int* n_points);
+/* a ready cloud [n][4] as a submap; GLIO_E_ARG for n < 1 or n above the capacity */
+int glio_loop_set_submap(glio_loop* lp, int which, const float* xyzi, int n);
+/* *n = the submap's size (out may be null to ask for it); capacity too small: GLIO_E_ARG */
+int glio_loop_read_submap(glio_loop* lp, int which, float* out_xyzi, int capacity, int* n);
+/* the whole alignment from "source as set".  Every round is enqueued ahead and turns into a no-op once the device has decided convergence; the call
+ * then BLOCKS on one event behind the result's copy into pinned memory (no spinning: it runs on a 1 Hz thread and must not take a core from the keyframe
+ * cycle).  GLIO_E_STATE before both submaps exist. */
+int glio_loop_align(glio_loop* lp, glio_loop_result* result);
+/* one round from the object's current state (the same kernels glio_loop_align enqueues); glio_loop_reset_current returns to "source as set" */
+int glio_loop_reset_current(glio_loop* lp);
+int glio_loop_step(glio_loop* lp, glio_loop_step_result* step);
+/* the last search's answer per source point: target index (-1 beyond max_corr_dist) and float squared distance to the NEAREST target point */
+int glio_loop_read_correspondences(glio_loop* lp, int32_t* idx_out, float* d2_out);
+/* the current cloud (source moved by the rounds so far), [n_source][4] */
+int glio_loop_read_current(glio_loop* lp, float* out_xyzi, int capacity, int* n);
+/* per round of the last glio_loop_align: the queries the brute-force scan answered ([0, iterations) and one more entry for the fitness search);
+ * *n = entries written */
+int glio_loop_read_fallbacks(glio_loop* lp, int32_t* out, int capacity, int* n);
+/* device time of the last glio_loop_align (HIP events around its kernels), ms */
+int glio_loop_last_device_ms(glio_loop* lp, float* ms);
+
 #ifdef __cplusplus
 }
 #endif

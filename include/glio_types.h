@@ -252,6 +252,48 @@ enum { GLIO_FEAT_SURF = 0, GLIO_FEAT_EDGE_LESS_SHARP = 1, GLIO_FEAT_SHARP = 2, G
        GLIO_FEAT_LAST_SCAN = 5 /* the cloud the last glio_features_to_scan wrote into its slot */ };
 #define GLIO_FEAT_MAX_RAW_POINTS 400000
 
+/* ---- loop closure: the submaps of detectLoopClosure and the pcl::IterativeClosestPoint of performLoopClosure (Estimator.cpp:5101-5273) on the
+ * device (glio_loop_*).  Defaults (glio_loop_opts_default): Estimator.cpp:855 (the 0.4 m leaf of ds_filter_surf_map),  :5197-5201
+ * (setMaxCorrespondenceDistance(30), setMaximumIterations(100), setTransformationEpsilon(1e-6), setEuclideanFitnessEpsilon(1e-6)) and PCL 1.8.1's
+ * DefaultConvergenceCriteria (absolute MSE 1e-12) and min_number_correspondences_ (3). */
+typedef struct glio_loop_opts {
+    double max_corr_dist;          /* 30: a pair is kept when (double) d2 <= max_corr_dist^2 */
+    double transformation_eps;     /* 1e-6 */
+    double fitness_eps;            /* 1e-6: the relative MSE threshold (setEuclideanFitnessEpsilon) */
+    double abs_mse_eps;            /* 1e-12 */
+    float leaf;                    /* 0.4: VoxelGrid leaf of glio_loop_build_submap */
+    int32_t max_iterations;        /* 100 */
+    int32_t min_correspondences;   /* 3 */
+    int32_t max_source_points;     /* capacity of the filtered source submap (65536) */
+    int32_t max_target_points;     /* capacity of the filtered target submap (262144) */
+    int32_t max_frames_per_submap; /* 64 */
+} glio_loop_opts;
+enum { GLIO_LOOP_SOURCE = 0, GLIO_LOOP_TARGET = 1 };
+/* pcl::registration::DefaultConvergenceCriteria::ConvergenceState, by name */
+enum { GLIO_LOOP_NOT_CONVERGED = 0, GLIO_LOOP_ITERATIONS = 1, GLIO_LOOP_TRANSFORM = 2, GLIO_LOOP_ABS_MSE = 3, GLIO_LOOP_REL_MSE = 4,
+       GLIO_LOOP_NO_CORRESPONDENCES = 5 };
+/* icp.align + hasConverged + getFitnessScore + getFinalTransformation */
+typedef struct glio_loop_result {
+    double fitness;                /* mean squared 1-NN distance of the final source to the target, no distance cap */
+    double last_mse;               /* mean squared distance of the last round's kept pairs */
+    float transform[16];           /* row major Matrix4f */
+    int32_t converged;
+    int32_t state;                 /* GLIO_LOOP_* */
+    int32_t iterations;
+    int32_t last_n_corr;
+    int32_t rank_deficient;        /* 1: the last round's pairs were collinear (or one point); the transform of the rounds before is kept */
+    int32_t reserved_;
+} glio_loop_result;
+/* one round (glio_loop_step) */
+typedef struct glio_loop_step_result {
+    double mse;
+    float transform[16];           /* the round's incremental transform, row major */
+    int32_t n_corr;
+    int32_t state;                 /* what the convergence test of this round says (GLIO_LOOP_NOT_CONVERGED: go on) */
+    int32_t n_fallback;            /* queries of this round's search that the grid could not certify and the brute-force scan answered */
+    int32_t rank_deficient;
+} glio_loop_step_result;
+
 #ifdef __cplusplus
 }
 #endif
