@@ -170,6 +170,23 @@ class Context:
         _check(load().glio_localmap_build(self._h, C.byref(n)))
         return n.value
 
+    def localmap_rebuild_from_frames(self, assoc, frames, poses):
+        """the ring rebuilt from the resident keyframe clouds `frames` (oldest first) of a batch.BatchAssociation at poses [n][7] = t, q (loop.frame_poses):
+        buildLocalMapWithLandMark's rebuild branch (Estimator.cpp:3545-3579) + the build; returns the map size"""
+        frames = np.ascontiguousarray(frames, np.int32)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        assert len(poses) == len(frames)
+        n = C.c_int()
+        _check(load().glio_localmap_rebuild_from_frames(self._h, assoc._h, len(frames), T.iptr(frames) if len(frames) else None,
+                                                        T.dptr(poses) if len(frames) else None, C.byref(n)))
+        return n.value
+
+    def localmap_last_rebuild_device_ms(self):
+        """device ms of the last rebuild's own two launches; needs GLIO_LM_REBUILD_TIMING=1 in the environment when the ring is first rebuilt"""
+        ms = C.c_float(0)
+        _check(load().glio_localmap_last_rebuild_device_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def localmap_read(self):
         n = C.c_int()
         _check(load().glio_localmap_read(self._h, None, 0, C.byref(n)))

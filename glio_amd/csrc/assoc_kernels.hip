@@ -2196,6 +2196,8 @@ struct glio_bassoc {
     int device; hipStream_t stream;
     int prep_nb, prep_todo[64], prep_n[64], prep_tc[64];      // glio_bassoc_prepare_async: the first batch of search frames whose descriptors are on the device and whose tables are cleared
     hipEvent_t ev_scan;             // glio_bassoc_set_frame_from_scan: the point of the context's stream the copy of its scan waits for (no host wait)
+    hipEvent_t ev_ext_read; int ext_read_pending;   // another object's stream is still READING the resident clouds (glio_localmap_rebuild_from_frames transforms them on the
+                                                    // context's stream): the next write to a cloud, and glio_bassoc_destroy, come behind this event (glio_ctx::ev_ext_read, the other way)
     int K, cap; long long max_con;
     float inv_cell, cell;
     float4* d_local;                // [K][cap] keyframe-local clouds
@@ -2460,6 +2462,7 @@ void glio_bassoc_destroy(glio_bassoc* b) {
     if (b->raw_stage.d) hipFree(b->raw_stage.d);
     delete[] b->h_n; delete[] b->frames;
     if (b->ev_scan) hipEventDestroy(b->ev_scan);
+    if (b->ev_ext_read) { if (b->ext_read_pending) hipEventSynchronize(b->ev_ext_read); hipEventDestroy(b->ev_ext_read); }
     if (b->ev_sel) hipEventDestroy(b->ev_sel);
     if (b->ev_fb) hipEventDestroy(b->ev_fb);
     if (b->ev_raws) hipEventDestroy(b->ev_raws);
@@ -2478,6 +2481,17 @@ int glio_bassoc_view(glio_bassoc* b, GlioBassocView* out) {
     out->device = b->device; out->K = b->K; out->cap = b->cap; out->d_local = b->d_local; out->h_n = b->h_n; out->stream = b->stream;
     return GLIO_OK;
 }
+int glio_bassoc_external_read(glio_bassoc* b, hipStream_t reader) {
+    if (!b->ev_ext_read) BA_CHECK(hipEventCreateWithFlags(&b->ev_ext_read, hipEventDisableTiming));
+    BA_CHECK(hipEventRecord(b->ev_ext_read, reader));
+    b->ext_read_pending = 1;
+    return GLIO_OK;
+}
+// (before a resident cloud is overwritten on the object's stream)
+static int bassoc_behind_external_read(glio_bassoc* b) {
+    if (b->ext_read_pending) { BA_CHECK(hipStreamWaitEvent(b->stream, b->ev_ext_read, 0)); b->ext_read_pending = 0; }
+    return GLIO_OK;
+}
 extern "C" {
 int glio_bassoc_set_frame(glio_bassoc* b, int k, const float* scan_xyzi, int n) { return glio_bassoc_set_frame_strided(b, k, scan_xyzi, n, 16, 12); }
 int glio_bassoc_set_frame_strided(glio_bassoc* b, int k, const void* scan, int n, int stride_bytes, int intensity_offset) {
@@ -2485,6 +2499,7 @@ int glio_bassoc_set_frame_strided(glio_bassoc* b, int k, const void* scan, int n
     if (!glio_point_layout_ok(stride_bytes, intensity_offset)) { glio_set_error("bad point layout (stride %d, intensity at %d)", stride_bytes, intensity_offset); return GLIO_E_ARG; }
     BA_CHECK(hipSetDevice(b->device));
     { const int rf = bassoc_drain(b); if (rf != GLIO_OK) return rf; }      // (an asynchronous run may still read the clouds)
+    { const int re = bassoc_behind_external_read(b); if (re != GLIO_OK) return re; }
     { const int ru = glio_upload_points(b->stream, &b->raw_stage, scan, n, stride_bytes, intensity_offset, b->d_local + (size_t)k * b->cap); if (ru != GLIO_OK) return ru; }
     enqueue_presort(b->stream, b->kb, b->d_local + (size_t)k * b->cap, n, b->d_local_ps + (size_t)k * b->cap);
     BA_CHECK(hipGetLastError());
@@ -2855,6 +2870,7 @@ int glio_bassoc_set_frame_from_scan(glio_bassoc* b, int k, glio_ctx* c, int slot
     if (!b->ev_scan) BA_CHECK(hipEventCreateWithFlags(&b->ev_scan, hipEventDisableTiming));
     BA_CHECK(hipEventRecord(b->ev_scan, c->stream));
     BA_CHECK(hipStreamWaitEvent(b->stream, b->ev_scan, 0));
+    { const int re = bassoc_behind_external_read(b); if (re != GLIO_OK) return re; }
     // the context presorted this scan when it was uploaded: its presorted copy (same points, w = index in the scan) is taken over with the same offset instead
     // of presorting the cloud a second time (any spatially compact order serves: results are written at the original indices)
     if (n > 0) {

@@ -452,6 +452,13 @@ int glio_localmap_push_scan_ahead_and_build(glio_ctx* c, const float lidar_offse
     GLIO_HIP_CHECK(e);
     return GLIO_OK;
 }
+}  // extern "C"
+int glio_order_behind_ahead(glio_ctx* c) {
+    CtxExtra* ex = extra_of(c);
+    if (ex && ex->ahead_valid && ex->ev_ahead) GLIO_HIP_CHECK(hipStreamWaitEvent(c->stream, ex->ev_ahead, 0));
+    return GLIO_OK;
+}
+extern "C" {
 int glio_associate_resident(glio_ctx* c, int slot, const double q[4], const double t[3], int* out_count) {
     GLIO_TRACE("K2 glio_associate_resident");
     if (!c || slot < 0 || slot >= c->W) return GLIO_E_ARG;

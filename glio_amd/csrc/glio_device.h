@@ -460,6 +460,11 @@ void glio_assoc_time_hooks(glio_ctx* c, int which, int reps, float* ms);
 // the association keeps up to date) and the stream their copies are enqueued on
 struct GlioBassocView { int device, K, cap; const float4* d_local; const int* h_n; hipStream_t stream; };
 int glio_bassoc_view(glio_bassoc* b, GlioBassocView* out);
+// `reader` (another object's stream) has just been given work that reads the resident clouds: the association's next write to one of them waits for this point
+int glio_bassoc_external_read(glio_bassoc* b, hipStream_t reader);
+// capi.hip: a scan / map sent ahead on the upload stream (glio_set_scan_ahead, glio_localmap_push_scan_ahead_and_build) is still pending -> the context's
+// stream waits for it (the next glio_slide_window still takes the scan over)
+int glio_order_behind_ahead(glio_ctx* c);
 
 // imu_kernels.hip: the device-resident store of IMU pre-integrations (glio_imu_*)
 struct glio_imu {

@@ -13,6 +13,10 @@
 // (bit for bit, whatever the atomic order) -- insert/evict costs two keyframes of traffic instead of re-streaming the
 // whole ring (3.3 M points).  Emptied voxels stay as tombstones (count 0) until they fill half the table, then the table
 // is rebuilt once.  PCL's float accumulation (whose order std::sort leaves unspecified) is matched to ~1e-6 m.
+//
+// A push is the reference's steady state (:3580-3610).  Its other branch (:3545-3579: the deque below local_map_width -- the first 50 keyframes and, SURVEY Q17,
+// every call after a loop closure -- is thrown away and refilled from surf_frames at the CURRENT poses) is glio_localmap_rebuild_from_frames: ring and table
+// rebuilt from the keyframe clouds resident in a batch association, two launches whatever the number of keyframes (k_lm_rebuild_*).
 #include <cfloat>
 #include <algorithm>
 #include <cstring>
@@ -53,7 +57,13 @@ struct LocalMap {
     // does) -- instead of the exact fixed-point sums.  Same voxels, same output order; the centroids then equal the oracle's bit for bit.
     int accumulation;
     int* d_fill; int* d_slot_start; int* d_plist;      // [table_cap], [table_cap], [width * cap]: per-voxel fill counters, list starts, point lists
+    // glio_localmap_rebuild_from_frames: the frame table [width] (pinned, its device mirror, the event of its last upload) and the event that orders the context's
+    // stream behind the frame copies of the batch association
+    struct LmFrame* h_frames; struct LmFrame* d_frames; hipEvent_t ev_frames; int frames_in_flight; hipEvent_t ev_dep;
+    hipEvent_t ev_rb0, ev_rb1; int time_rebuild, have_rebuild_ms;      // GLIO_LM_REBUILD_TIMING=1: timing events around the rebuild's two launches (glio_localmap_last_rebuild_device_ms)
 };
+// one keyframe of a rebuild: its own-frame cloud (resident in a batch association), its size and transformCloud's pose
+struct LmFrame { const float4* src; int n, pad_; double q[4], t[3]; };
 
 #define LM_EMPTY (~0ull)
 #define LM_FIX 1048576.0            /* 2^20: fixed-point scale of the voxel sums */
@@ -432,6 +442,91 @@ __global__ void k_lm_emit_float(const int* __restrict__ vslot_sorted, const int 
     out[v] = make_float4(ax / c, ay / c, az / c, aw / c);
 }
 
+// ------------------------------------------------------------------------------------------------
+// Rebuild of the whole ring from resident keyframe clouds (glio_localmap_rebuild_from_frames): what n_frames pushes into a fresh ring do -- per frame a slot
+// initialisation, transformCloud, the row's bounding box and the voxel accumulation, three to four launches each -- in TWO launches whatever n_frames is:
+//   k_lm_rebuild_clear    the voxel table emptied; every slot's box and count initialised (slots behind n_frames: empty)
+//   k_lm_rebuild_frames   blockIdx.y = frame: k_lm_transform's arithmetic from the frame's cloud into ring row blockIdx.y, the row's box (one set of six atomics
+//                         per workgroup), k_lm_accumulate's insertion.  The sums are exact integers: whatever order the frames' workgroups run in, the table
+//                         holds what the pushes would have left (keys may sit in other slots of the table: no reader depends on where).
+// ------------------------------------------------------------------------------------------------
+typedef float lm_v4f __attribute__((ext_vector_type(4)));
+#define LM_RB_THREADS 256
+#define LM_RB_PER 4            /* points per thread: a workgroup covers 1024 points of one frame */
+__global__ void k_lm_rebuild_clear(unsigned long long* keys, long long* sum, int* cnt, int cap, int* nkeys, const LmFrame* __restrict__ fr, int n_frames, int width,
+                                   int* slot_bbox, int* ns) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < cap) { keys[i] = LM_EMPTY; cnt[i] = 0; sum[4 * (size_t)i] = 0; sum[4 * (size_t)i + 1] = 0; sum[4 * (size_t)i + 2] = 0; sum[4 * (size_t)i + 3] = 0; }
+    if (i == 0) *nkeys = 0;
+    if (i < 6 * width) slot_bbox[i] = (i % 6) < 3 ? 0x7fffffff : (int)0x80000000;
+    if (i < width) ns[i] = i < n_frames ? fr[i].n : 0;
+}
+__global__ __launch_bounds__(LM_RB_THREADS) void k_lm_rebuild_frames(const LmFrame* __restrict__ fr, float4* __restrict__ ring, const int ring_cap, const float inv_leaf,
+                                                                     unsigned long long* keys, long long* sum, int* cnt, const int cap, int* nkeys, int* slot_bbox) {
+    __shared__ int s_mn[LM_RB_THREADS / 64][3], s_mx[LM_RB_THREADS / 64][3];
+    const int f = blockIdx.y;
+    const LmFrame d = fr[f];                                     // (uniform over the workgroup)
+    const int base = blockIdx.x * (LM_RB_THREADS * LM_RB_PER);
+    if (base >= d.n) return;                                     // (the whole workgroup: the grid is sized for the largest frame)
+    float4* __restrict__ row = ring + (size_t)f * ring_cap;
+    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+    float4 p[LM_RB_PER];
+    // the clouds are read once: all of a thread's loads in flight together, past the caches' retention
+#pragma unroll
+    for (int k = 0; k < LM_RB_PER; ++k) {
+        const int i = base + k * LM_RB_THREADS + (int)threadIdx.x;
+        if (i < d.n) { const lm_v4f r = __builtin_nontemporal_load(reinterpret_cast<const lm_v4f*>(d.src + i)); p[k] = make_float4(r.x, r.y, r.z, r.w); }
+    }
+#pragma unroll
+    for (int k = 0; k < LM_RB_PER; ++k) {
+        const int i = base + k * LM_RB_THREADS + (int)threadIdx.x;
+        if (i >= d.n) continue;
+        // transformCloud exactly as k_lm_transform forms it (double q * v + t, products kept separate, float store)
+        const double v[3] = {(double)p[k].x, (double)p[k].y, (double)p[k].z};
+        double uv[3] = {d.q[2] * v[2] - d.q[3] * v[1], d.q[3] * v[0] - d.q[1] * v[2], d.q[1] * v[1] - d.q[2] * v[0]};
+        uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
+        const double uuv[3] = {d.q[2] * uv[2] - d.q[3] * uv[1], d.q[3] * uv[0] - d.q[1] * uv[2], d.q[1] * uv[1] - d.q[2] * uv[0]};
+        const float4 g = make_float4((float)((v[0] + d.q[0] * uv[0] + uuv[0]) + d.t[0]), (float)((v[1] + d.q[0] * uv[1] + uuv[1]) + d.t[1]),
+                                     (float)((v[2] + d.q[0] * uv[2] + uuv[2]) + d.t[2]), p[k].w);
+        row[i] = g;
+        const int o[3] = {f2ord(g.x), f2ord(g.y), f2ord(g.z)};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { mn[c] = min(mn[c], o[c]); mx[c] = max(mx[c], o[c]); }
+        // k_lm_accumulate with sign = +1
+        const unsigned long long key = lm_key((int)floorf(g.x * inv_leaf), (int)floorf(g.y * inv_leaf), (int)floorf(g.z * inv_leaf));
+        unsigned s = lm_hash(key) & (cap - 1);
+        int probes = 0;
+        bool full = false;
+        for (;;) {
+            const unsigned long long kk = atomicCAS(keys + s, LM_EMPTY, key);
+            if (kk == LM_EMPTY) { atomicAdd(nkeys, 1); break; }
+            if (kk == key) break;
+            s = (s + 1) & (cap - 1);
+            if (++probes >= cap) { atomicOr(nkeys, 0x40000000); full = true; break; }          // table full: reported by the build
+        }
+        if (full) continue;
+        const long long fx[4] = {llrint((double)g.x * LM_FIX), llrint((double)g.y * LM_FIX), llrint((double)g.z * LM_FIX), llrint((double)g.w * LM_FIX)};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) atomicAdd(reinterpret_cast<unsigned long long*>(sum + 4 * (size_t)s + c), (unsigned long long)fx[c]);
+        atomicAdd(cnt + s, 1);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { mn[c] = min(mn[c], __shfl_xor(mn[c], off, 64)); mx[c] = max(mx[c], __shfl_xor(mx[c], off, 64)); }
+    }
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { s_mn[threadIdx.x >> 6][c] = mn[c]; s_mx[threadIdx.x >> 6][c] = mx[c]; }
+    }
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        const int c = threadIdx.x % 3;
+        if (threadIdx.x < 3) { int v = 0x7fffffff; for (int w = 0; w < LM_RB_THREADS / 64; ++w) v = min(v, s_mn[w][c]); atomicMin(slot_bbox + 6 * f + c, v); }
+        else { int v = (int)0x80000000; for (int w = 0; w < LM_RB_THREADS / 64; ++w) v = max(v, s_mx[w][c]); atomicMax(slot_bbox + 6 * f + 3 + c, v); }
+    }
+}
+
 #define LM_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { glio_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); return GLIO_E_HIP; } } while (0)
 static int lm_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
@@ -441,6 +536,12 @@ static void lm_free(LocalMap* m) {
     for (void* q : p) if (q) hipFree(q);
     if (m->h_pin) hipHostFree(m->h_pin);
     if (m->h_pub) hipHostFree(m->h_pub);
+    if (m->h_frames) hipHostFree(m->h_frames);
+    if (m->d_frames) hipFree(m->d_frames);
+    if (m->ev_frames) hipEventDestroy(m->ev_frames);
+    if (m->ev_dep) hipEventDestroy(m->ev_dep);
+    if (m->ev_rb0) hipEventDestroy(m->ev_rb0);
+    if (m->ev_rb1) hipEventDestroy(m->ev_rb1);
     delete[] m->h_n;
     delete m;
 }
@@ -715,6 +816,78 @@ int glio_localmap_build(glio_ctx* c, int* out_points) {
     return GLIO_OK;
 }
 
+// buildLocalMapWithLandMark's rebuild branch (Estimator.cpp:3545-3579): the ring becomes the keyframes frame_idx[0..n) of `frames`' resident clouds at the caller's
+// poses -- what n_frames glio_localmap_push of those clouds into a fresh ring and a glio_localmap_build leave, bit for bit -- in two launches (k_lm_rebuild_*)
+// and the build's chain.  Everything that can be refused is refused before the first launch: the ring is never left half-written.
+int glio_localmap_rebuild_from_frames(glio_ctx* c, glio_bassoc* frames, int n_frames, const int32_t* frame_idx, const double* poses, int* out_points) {
+    GLIO_TRACE("K1 glio_localmap_rebuild_from_frames");
+    if (!c || !c->localmap) { glio_set_error("glio_localmap_config first"); return GLIO_E_STATE; }
+    LocalMap* m = c->localmap;
+    GlioBassocView v;
+    if (!frames || glio_bassoc_view(frames, &v) != GLIO_OK) { glio_set_error("glio_localmap_rebuild_from_frames: no batch association"); return GLIO_E_ARG; }
+    if (v.device != c->device) { glio_set_error("glio_localmap_rebuild_from_frames: the batch association is on device %d, the context on %d", v.device, c->device); return GLIO_E_ARG; }
+    if (n_frames < 1 || n_frames > m->width) { glio_set_error("glio_localmap_rebuild_from_frames: %d frames, the ring holds 1 .. %d", n_frames, m->width); return GLIO_E_ARG; }
+    if (!frame_idx || !poses) { glio_set_error("glio_localmap_rebuild_from_frames: null frame list / poses"); return GLIO_E_ARG; }
+    int max_n = 0;
+    for (int f = 0; f < n_frames; ++f) {
+        const int k = frame_idx[f];
+        if (k < 0 || k >= v.K) { glio_set_error("glio_localmap_rebuild_from_frames: frame %d outside [0, %d)", k, v.K); return GLIO_E_ARG; }
+        if (v.h_n[k] < 1) { glio_set_error("glio_localmap_rebuild_from_frames: frame %d was never set (or holds no point)", k); return GLIO_E_ARG; }
+        if (v.h_n[k] > m->cap) { glio_set_error("glio_localmap_rebuild_from_frames: frame %d has %d points, the ring takes %d", k, v.h_n[k], m->cap); return GLIO_E_ARG; }
+        for (int e = 0; e < 7; ++e) if (!(fabs(poses[7 * f + e]) <= DBL_MAX)) { glio_set_error("glio_localmap_rebuild_from_frames: pose %d is not finite", f); return GLIO_E_ARG; }
+        if (v.h_n[k] > max_n) max_n = v.h_n[k];
+    }
+    LM_CHECK(hipSetDevice(c->device));
+    if (!m->h_frames) {
+        LM_CHECK(hipHostMalloc((void**)&m->h_frames, (size_t)m->width * sizeof(LmFrame))); LM_CHECK(hipMalloc((void**)&m->d_frames, (size_t)m->width * sizeof(LmFrame)));
+        LM_CHECK(hipEventCreateWithFlags(&m->ev_frames, hipEventDisableTiming)); LM_CHECK(hipEventCreateWithFlags(&m->ev_dep, hipEventDisableTiming));
+        const char* e = getenv("GLIO_LM_REBUILD_TIMING");
+        m->time_rebuild = e && atoi(e) != 0;
+        if (m->time_rebuild) { LM_CHECK(hipEventCreate(&m->ev_rb0)); LM_CHECK(hipEventCreate(&m->ev_rb1)); }
+    }
+    if (m->frames_in_flight) { LM_CHECK(hipEventSynchronize(m->ev_frames)); m->frames_in_flight = 0; }      // (the pinned table is rewritten only behind its last upload)
+    for (int f = 0; f < n_frames; ++f) {
+        LmFrame& d = m->h_frames[f];
+        const int k = frame_idx[f];
+        const double* ps = poses + 7 * f;                        // t[3], q[4] (w first)
+        d.src = v.d_local + (size_t)k * v.cap; d.n = v.h_n[k]; d.pad_ = 0;
+        for (int e = 0; e < 4; ++e) d.q[e] = ps[3 + e];
+        for (int e = 0; e < 3; ++e) d.t[e] = ps[e];
+    }
+    // a scan / map sent ahead on the upload stream still writes the ring and the table: behind it (the rebuild supersedes that map; the scan stays for the next slide)
+    { const int ra = glio_order_behind_ahead(c); if (ra != GLIO_OK) return ra; }
+    // the association's pending frame copies come first -- for the context's stream, not for the host
+    LM_CHECK(hipEventRecord(m->ev_dep, v.stream));
+    LM_CHECK(hipStreamWaitEvent(c->stream, m->ev_dep, 0));
+    LM_CHECK(hipMemcpyAsync(m->d_frames, m->h_frames, (size_t)n_frames * sizeof(LmFrame), hipMemcpyHostToDevice, c->stream));
+    LM_CHECK(hipEventRecord(m->ev_frames, c->stream));
+    m->frames_in_flight = 1;
+    const float inv_leaf = 1.0f / m->leaf;
+    if (m->time_rebuild) LM_CHECK(hipEventRecord(m->ev_rb0, c->stream));
+    hipLaunchKernelGGL(k_lm_rebuild_clear, dim3((std::max(m->table_cap, 6 * m->width) + 255) / 256), dim3(256), 0, c->stream, m->d_keys, m->d_sum, m->d_cnt, m->table_cap, m->d_nkeys,
+                       m->d_frames, n_frames, m->width, m->d_slot_bbox, m->d_n);
+    hipLaunchKernelGGL(k_lm_rebuild_frames, dim3((max_n + LM_RB_THREADS * LM_RB_PER - 1) / (LM_RB_THREADS * LM_RB_PER), n_frames), dim3(LM_RB_THREADS), 0, c->stream, m->d_frames,
+                       m->d_ring, m->cap, inv_leaf, m->d_keys, m->d_sum, m->d_cnt, m->table_cap, m->d_nkeys, m->d_slot_bbox);
+    LM_CHECK(hipGetLastError());
+    if (m->time_rebuild) { LM_CHECK(hipEventRecord(m->ev_rb1, c->stream)); m->have_rebuild_ms = 1; }
+    // ... and the association must not overwrite a cloud before this has read it
+    { const int re = glio_bassoc_external_read(frames, c->stream); if (re != GLIO_OK) return re; }
+    m->head = 0; m->count = n_frames; m->pushed = n_frames; m->nkeys_seen = 0;          // a fresh ring after n_frames pushes: no tombstones
+    for (int f = 0; f < m->width; ++f) m->h_n[f] = f < n_frames ? m->h_frames[f].n : 0;
+    return glio_localmap_build(c, out_points);
+}
+
+// device time of the last rebuild's own two launches (table clear + the multi-frame kernel), ms -- only in a process started with GLIO_LM_REBUILD_TIMING=1
+// (the events are not recorded otherwise: two event records per call are launch-rate money); GLIO_E_STATE without it or before a rebuild
+int glio_localmap_last_rebuild_device_ms(glio_ctx* c, float* ms) {
+    if (!c || !ms) return GLIO_E_ARG;
+    LocalMap* m = c->localmap;
+    if (!m || !m->time_rebuild || !m->have_rebuild_ms) { glio_set_error("no timed rebuild (GLIO_LM_REBUILD_TIMING=1, then glio_localmap_rebuild_from_frames)"); return GLIO_E_STATE; }
+    LM_CHECK(hipSetDevice(c->device));
+    LM_CHECK(hipEventSynchronize(m->ev_rb1));
+    LM_CHECK(hipEventElapsedTime(ms, m->ev_rb0, m->ev_rb1));
+    return GLIO_OK;
+}
 // 0 (default): exact fixed-point voxel sums (insert / evict without re-streaming the ring, bit-reproducible whatever the atomic order);
 // 1: pcl::VoxelGrid's own arithmetic -- float sums over the voxel's points in the order of the concatenated cloud (the oracle's restatement): the centroids
 // then equal the oracle's BIT FOR BIT, at the price of one pass over the ring per build.  For A/B runs of the 1.5e-5 m difference between the two.

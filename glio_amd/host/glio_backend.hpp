@@ -194,6 +194,35 @@ struct PointLayout {
     static PointLayout pclXYZI() { return {32, 16}; }        // pcl::PointXYZI, the reference's PointType (GLIO/include/utils/common.h)
 };
 
+// buildLocalMapWithLandMark's bookkeeping (Estimator.cpp:3545-3610) without the clouds: what the call does to recent_surf_keyframes when the deque holds
+// recent_size clouds, pose_keyframe n_keyframes poses and local_map_width = width.
+//   MAP_REBUILD  the deque is thrown away and refilled with `frames` (oldest first) at their CURRENT poses (:3545-3579): whenever recent_size < width.  With
+//                n_keyframes > width the loop's guard `i <= size - local_map_width` (:3550) ends it after width - 1 frames, so the deque never reaches `width`
+//                again and EVERY later call rebuilds (quirk Q17: the permanent state after the first loop closure, whose correctPoses clears the deque,
+//                :4660); with n_keyframes <= width it takes them all.  latest_frame_idx is not touched in this branch.
+//   MAP_PUSH     the deque is full: the oldest cloud leaves, keyframe n_keyframes - 1 (= frames[0]) enters at the pose it has now (:3582-3609)
+//   MAP_NOTHING  full and no new keyframe since the last push (:3582), or no keyframe yet (:3531-3543: the initial map is the caller's)
+// The Python twin is sliding.local_map_plan (tests/test_map_schedule_host_cpu.py).
+enum { MAP_NOTHING = 0, MAP_PUSH = 1, MAP_REBUILD = 2 };
+struct LocalMapPlan { int action; std::vector<int32_t> frames; int recent_size, latest_frame_idx; };
+inline LocalMapPlan localMapPlan(int recent_size, int n_keyframes, int width, int latest_frame_idx) {
+    LocalMapPlan p{MAP_NOTHING, {}, recent_size, latest_frame_idx};
+    const int n = n_keyframes;
+    if (n < 1) return p;
+    if (recent_size < width) {
+        p.action = MAP_REBUILD;
+        for (int i = n - 1; i >= 0; --i) {
+            if (n > width && i <= n - width) break;
+            p.frames.insert(p.frames.begin(), (int32_t)i);
+            if ((int)p.frames.size() >= width) break;
+        }
+        p.recent_size = (int)p.frames.size();
+        return p;
+    }
+    if (latest_frame_idx != n - 1) { p.action = MAP_PUSH; p.frames.push_back((int32_t)(n - 1)); p.latest_frame_idx = n - 1; }
+    return p;
+}
+
 class SlidingWindowBackend {
 public:
     explicit SlidingWindowBackend(const glio_opts& opts, int device = 0) : opts_(opts), W_(opts.window) {
@@ -385,6 +414,52 @@ public:
         map_points_ = pts;
         return pts;
     }
+    // buildLocalMapWithLandMark's rebuild branch (Estimator.cpp:3545-3579) + downSampleCloud + setInputCloud: the ring becomes the keyframes frame_idx (oldest
+    // first) of the clouds resident in a batch association (BatchAssociationBackend::handle()), at poses [n][7] = t, q (q_po * q_bl, q_po * t_bl + t_po)
+    int rebuildLocalMapFromFrames(glio_bassoc* frames, const std::vector<int32_t>& frame_idx, const double* poses) {
+        int pts = 0;
+        check(glio_localmap_rebuild_from_frames(ctx_, frames, (int)frame_idx.size(), frame_idx.data(), poses, &pts), "glio_localmap_rebuild_from_frames");
+        map_points_ = pts;
+        return pts;
+    }
+    // ---- the reference's map schedule (opt-in; without it the caller pushes each keyframe once, pushScanAndBuildLocalMap, and never re-poses it): every keyframe
+    // call asks localMapPlan and either rebuilds the ring from the resident keyframes at the poses pose_info_keyframe holds NOW or pushes the newest keyframe's
+    // resident scan.  loopClosed() is correctPoses' recent_surf_keyframes.clear() (:4660).  The Python twin is sliding.ReferenceMapSchedule.
+    void enableReferenceMapSchedule(int local_map_width, const double q_bl[4], const double t_bl[3]) {
+        ref_map_ = true; ref_width_ = local_map_width; ref_recent_ = 0; ref_latest_ = -1;
+        for (int k = 0; k < 4; ++k) ref_qbl_[k] = q_bl[k];
+        for (int k = 0; k < 3; ++k) ref_tbl_[k] = t_bl[k];
+    }
+    bool referenceMapSchedule() const { return ref_map_; }
+    void loopClosed() { ref_recent_ = 0; }
+    // a call whose plan says "rebuild" does not use a map built ahead: ask before pushScanAheadAndBuildLocalMap
+    bool nextLocalMapCallRebuilds(int n_keyframes) const { return ref_map_ && localMapPlan(ref_recent_, n_keyframes, ref_width_, ref_latest_).action == MAP_REBUILD; }
+    // pose_info [>= n_keyframes][7] = t_po, q_po of every keyframe; the newest keyframe's scan is resident in window slot scan_slot and its own-frame cloud in
+    // `frames` (setFrameFromScan).  Returns the plan's action; the map size is mapPoints().
+    int updateLocalMapByReferenceSchedule(glio_bassoc* frames, int n_keyframes, const double* pose_info, int scan_slot, const float lidar_offset[3]) {
+        if (!ref_map_) throw std::runtime_error("updateLocalMapByReferenceSchedule: enableReferenceMapSchedule first");
+        const LocalMapPlan p = localMapPlan(ref_recent_, n_keyframes, ref_width_, ref_latest_);
+        ref_recent_ = p.recent_size; ref_latest_ = p.latest_frame_idx;
+        if (p.action == MAP_NOTHING) return p.action;
+        std::vector<double> poses(7 * p.frames.size());
+        for (size_t f = 0; f < p.frames.size(); ++f) {
+            const double* in = pose_info + 7 * (size_t)p.frames[f];
+            const double* q = in + 3; const double* b = ref_qbl_; const double* v = ref_tbl_;
+            double* out = &poses[7 * f];
+            out[3] = q[0] * b[0] - q[1] * b[1] - q[2] * b[2] - q[3] * b[3];
+            out[4] = q[0] * b[1] + q[1] * b[0] + q[2] * b[3] - q[3] * b[2];
+            out[5] = q[0] * b[2] + q[2] * b[0] + q[3] * b[1] - q[1] * b[3];
+            out[6] = q[0] * b[3] + q[3] * b[0] + q[1] * b[2] - q[2] * b[1];
+            double uv[3] = {q[2] * v[2] - q[3] * v[1], q[3] * v[0] - q[1] * v[2], q[1] * v[1] - q[2] * v[0]};
+            uv[0] = uv[0] + uv[0]; uv[1] = uv[1] + uv[1]; uv[2] = uv[2] + uv[2];
+            const double uuv[3] = {q[2] * uv[2] - q[3] * uv[1], q[3] * uv[0] - q[1] * uv[2], q[1] * uv[1] - q[2] * uv[0]};
+            for (int k = 0; k < 3; ++k) out[k] = (v[k] + q[0] * uv[k] + uuv[k]) + in[k];
+        }
+        if (p.action == MAP_REBUILD) rebuildLocalMapFromFrames(frames, p.frames, poses.data());
+        else pushScanAndBuildLocalMap(scan_slot, lidar_offset, &poses[3], &poses[0]);
+        return p.action;
+    }
+    int mapPoints() const { return map_points_; }
     // shift the host-side state like the reference's slideWindow(): the newest slot is initialised by the caller
     void slideState(const double new_t[3], const double new_q[4], const double new_sb[9]) {
         for (int i = 0; i + 1 < W_; ++i) {
@@ -427,6 +502,7 @@ private:
     int W_;
     std::vector<int32_t> sel_;
     int map_points_ = 0;
+    bool ref_map_ = false; int ref_width_ = 0, ref_recent_ = 0, ref_latest_ = -1; double ref_qbl_[4] = {1, 0, 0, 0}, ref_tbl_[3] = {0, 0, 0};      // enableReferenceMapSchedule
     glio_ctx* ctx_ = nullptr;
 };
 

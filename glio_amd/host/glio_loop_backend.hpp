@@ -171,5 +171,56 @@ inline bool loopConstraint(const glio_loop_result& res, const double pose_latest
     return true;
 }
 
+// The sliding window's share of correctPoses (Estimator.cpp:4664-4686, :4702-4773).  abs_poses [N][7] = q (w first), t, in/out -- the estimator's abs_poses, where
+// row i + 1 belongs to keyframe i; W = slide_window_width; corrected [N - W][7], same layout: the pose-graph poses of keyframes 0 .. N - 1 - W
+// (pose_each_frame[keyframe_id_in_frame[i]], :4702-4713).  (1) the W - 1 relative poses between rows N - W .. N - 1 are taken BEFORE anything is corrected,
+// q_rel = q_from.inverse() * q_to, t_rel = q_from.inverse() * (t_to - t_from), Eigen's inverse() = conjugate / squaredNorm; (2) rows 1 .. N - W take the
+// corrected poses; (3) rows N - W + 1 .. N - 1 are chained back on: t = t_prev + q_prev * t_rel, q = q_prev * q_rel.  Rs [N][9] (row-major toRotationMatrix(),
+// not normalised) and Ps [N][3] receive every rewritten row (row 0 is not written; either may be null).  pose_keyframe / pose_info_keyframe[i] are row i + 1.
+// What stays with the caller: GTSAM / iSAM2, pose_each_frame, recent_surf_keyframes.clear() (SlidingWindowBackend::loopClosed), marg = false
+// (glio_set_prior(NULL)).  The Python twin is loop.correct_window_poses (tests/test_map_schedule_host_cpu.py: bit for bit).  false: bad sizes.
+inline bool correctWindowPoses(double* abs_poses, int N, const double* corrected, int n_corrected, int W, double* Rs, double* Ps) {
+    if (W < 1 || W > N || n_corrected != N - W) return false;
+    auto q2R = [](const double q[4], double R[9]) {
+        const double w = q[0], x = q[1], y = q[2], z = q[3];
+        const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
+        const double twx = tx * w, twy = ty * w, twz = tz * w;
+        const double txx = tx * x, txy = ty * x, txz = tz * x;
+        const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+        R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+        R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
+        R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
+    };
+    auto book = [&](int row) {
+        if (Rs) q2R(abs_poses + 7 * row, Rs + 9 * row);
+        if (Ps) for (int c = 0; c < 3; ++c) Ps[3 * row + c] = abs_poses[7 * row + 4 + c];
+    };
+    std::vector<double> rel((size_t)(W > 1 ? W - 1 : 0) * 7);
+    for (int i = N - W, k = 0; i < N - 1; ++i, ++k) {
+        const double* from = abs_poses + 7 * i; const double* to = abs_poses + 7 * (i + 1);
+        const double n2 = from[0] * from[0] + from[1] * from[1] + from[2] * from[2] + from[3] * from[3];
+        double qi[4] = {0.0, 0.0, 0.0, 0.0};
+        if (n2 > 0.0) { qi[0] = from[0] / n2; qi[1] = -from[1] / n2; qi[2] = -from[2] / n2; qi[3] = -from[3] / n2; }
+        const double d[3] = {to[4] - from[4], to[5] - from[5], to[6] - from[6]};
+        loop_detail::qmul(qi, to, &rel[7 * (size_t)k]);
+        loop_detail::qrot(qi, d, &rel[7 * (size_t)k + 4]);
+    }
+    for (int i = 0; i < N - W; ++i) {
+        for (int c = 0; c < 7; ++c) abs_poses[7 * (i + 1) + c] = corrected[7 * i + c];
+        book(i + 1);
+    }
+    for (int i = N - W, k = 0; i < N - 1; ++i, ++k) {
+        const double* prev = abs_poses + 7 * i;
+        double r[3], q[4];
+        loop_detail::qrot(prev, &rel[7 * (size_t)k + 4], r);
+        loop_detail::qmul(prev, &rel[7 * (size_t)k], q);
+        double* out = abs_poses + 7 * (i + 1);
+        for (int c = 0; c < 3; ++c) out[4 + c] = prev[4 + c] + r[c];
+        for (int c = 0; c < 4; ++c) out[c] = q[c];
+        book(i + 1);
+    }
+    return true;
+}
+
 }  // namespace glio
 #endif  // GLIO_LOOP_BACKEND_HPP_

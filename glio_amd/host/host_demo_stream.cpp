@@ -23,7 +23,7 @@ static double now_s() { return std::chrono::duration<double>(std::chrono::steady
 
 extern "C" int glio_debug_arrow_stamps(glio_ctx* c, long long* out320);      // debug export of the library (scripts/chain_step_time.py reads the same)
 int main(int argc, char** argv) {
-    if (argc < 2) { fprintf(stderr, "usage: host_demo_stream stream.bin [device] [search_range] [defer] [res=N] [draws=FILE] [timed=N]\n"); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: host_demo_stream stream.bin [device] [search_range] [defer] [res=N] [draws=FILE] [timed=N] [map_rebuild=1] ...\n"); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror("open"); return 2; }
     const int device = argc > 2 ? atoi(argv[2]) : 0;
@@ -90,6 +90,11 @@ int main(int argc, char** argv) {
         // any stage time).  sleep_at: 0 = between the batch association's preparation and the solve, 1 = before the call's first entry point, 2 = between the solve and
         // the batch association's enqueue
         int sleep_ms = 0, sleep_at = 0;
+        // map_rebuild=1: every call rebuilds the local map from local_map_width - 1 resident keyframes at their current poses (glio_localmap_rebuild_from_frames)
+        // instead of pushing the newest scan -- what a keyframe costs in the reference after its first loop closure, where buildLocalMapWithLandMark takes the
+        // rebuild branch on every call (Estimator.cpp:3545-3579).  The last local_map_width - 1 keyframes of the stream so far; a stream shorter than
+        // that repeats its keyframes (same point count, the timing's concern).  Not with defer=1 (the newest keyframe's cloud must be resident).
+        bool map_rebuild = false;
         std::vector<uint64_t> table;
         size_t table_k = 0;
         for (int a = 5; a < argc; ++a) {
@@ -100,6 +105,7 @@ int main(int argc, char** argv) {
             else if (!strncmp(argv[a], "prepare_early=", 14)) prepare_early = atoi(argv[a] + 14) != 0;
             else if (!strncmp(argv[a], "ahead=", 6)) ahead = atoi(argv[a] + 6) != 0;
             else if (!strncmp(argv[a], "map_ahead=", 10)) map_ahead = atoi(argv[a] + 10) != 0;
+            else if (!strncmp(argv[a], "map_rebuild=", 12)) map_rebuild = atoi(argv[a] + 12) != 0;
             else if (!strncmp(argv[a], "sleep_ms=", 9)) sleep_ms = atoi(argv[a] + 9);
             else if (!strncmp(argv[a], "sleep_at=", 9)) sleep_at = atoi(argv[a] + 9);
             else if (!strncmp(argv[a], "draws=", 6)) {
@@ -110,6 +116,7 @@ int main(int argc, char** argv) {
             } else { fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
         }
         if (timed_last < 1 || timed_last > NK) timed_last = NK;
+        if (map_rebuild && (defer || map_ahead)) { fprintf(stderr, "map_rebuild=1 goes with neither defer=1 nor map_ahead=1\n"); return 2; }
         std::mt19937_64 rng(20260925);
         auto rand_u64 = [&]() -> uint64_t { return table.empty() ? (uint64_t)rng() : table[table_k++ % table.size()]; };
         auto rand_below = [&](uint64_t n) -> uint64_t {
@@ -144,6 +151,17 @@ int main(int argc, char** argv) {
             // deferred variant the previous keyframe's searches are still in flight on that store's stream, and the copy is made once they were collected
             if (!defer) ba.setFrameFromScan(nw, be.ctx(), W - 1, tlb);
             const double t1 = now_s();
+            if (map_rebuild) {
+                const int nf = hdr[2] > 1 ? hdr[2] - 1 : 1;
+                std::vector<int32_t> fr((size_t)nf);
+                std::vector<double> fp((size_t)nf * 7);
+                for (int i = 0; i < nf; ++i) {
+                    const int g = ((nw - (nf - 1 - i)) % (nw + 1) + (nw + 1)) % (nw + 1);
+                    fr[i] = g;
+                    for (int c = 0; c < 7; ++c) fp[7 * (size_t)i + c] = kf_poses[7 * (size_t)g + c];
+                }
+                map_pts = be.rebuildLocalMapFromFrames(ba.handle(), fr, fp.data());
+            } else
             if (!have_map_ahead) map_pts = be.pushScanAndBuildLocalMap(W - 1, tlb, &gtq[4 * nw], &gtt[3 * nw]);
             have_map_ahead = false;
             const double t2 = now_s();

@@ -163,7 +163,7 @@ def write_stream(path, long, wins, W, n_keyframes, pts, lm_width=50, leaf=0.4, b
                 f.write(bytes(d))
 
 
-def run_demo_stream(path, device=0, env=None, search_range=6, defer=False, feature_res_num=0, draws=None, timed=None, per_slot=False, sleep_ms=0, sleep_at=0, stream_draws=True, prepare_early=True, ahead=False, map_ahead=False):
+def run_demo_stream(path, device=0, env=None, search_range=6, defer=False, feature_res_num=0, draws=None, timed=None, per_slot=False, sleep_ms=0, sleep_at=0, stream_draws=True, prepare_early=True, ahead=False, map_ahead=False, map_rebuild=False):
     """feature_res_num > 0: featureSelection behind every slot's search (Estimator.cpp:2223); draws: file of uint64 both hosts draw from (sliding.TableRng);
     timed: only the last `timed` keyframes enter the time averages"""
     import json
@@ -185,6 +185,8 @@ def run_demo_stream(path, device=0, env=None, search_range=6, defer=False, featu
         cmd.append("ahead=1")
     if map_ahead:
         cmd.append("map_ahead=1")
+    if map_rebuild:
+        cmd.append("map_rebuild=1")
     r = subprocess.run(cmd, capture_output=True, text=True, env=env)
     if r.returncode != 0:
         raise RuntimeError("host_demo_stream failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
@@ -326,4 +328,46 @@ def run_demo_loop(path, device=0, env=None):
             out["constraint"] = None if w[1] == "none" else (np.array([float.fromhex(x) for x in w[1:8]]), float.fromhex(w[8]))
         elif ln.startswith("{"):
             out.update(json.loads(ln))
+    return out
+
+
+DEMO_MAP_SCHEDULE = os.path.join(HERE, "host_demo_map_schedule")
+
+
+def build_demo_map_schedule(force=False):
+    """The C++ reference map schedule (host_demo_map_schedule.cpp over glio::SlidingWindowBackend); built on demand by its test."""
+    src = [os.path.join(HERE, "host_demo_map_schedule.cpp"), os.path.join(HERE, "glio_backend.hpp"), os.path.join(HERE, "glio_batch_backend.hpp")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_MAP_SCHEDULE) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_MAP_SCHEDULE) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_MAP_SCHEDULE])
+    return DEMO_MAP_SCHEDULE
+
+
+def write_map_schedule(path, opts, cap, width, leaf, scans, pose_info, loop_after=-1, accumulation=0, q_bl=(1.0, 0.0, 0.0, 0.0), t_bl=(0.0, 0.0, 0.0)):
+    """opts | n_keyframes cap width loop_after accumulation 0 0 0 | leaf tlb[3] | q_bl[4] t_bl[3] | per keyframe: n, scan | pose_info [call][keyframe][7] = t_po, q_po
+    (pose_info_keyframe as call j finds it; rows of keyframes that do not exist yet are ignored)"""
+    nk = len(scans)
+    pose_info = np.ascontiguousarray(pose_info, np.float64)
+    assert pose_info.shape == (nk, nk, 7)
+    with open(path, "wb") as f:
+        f.write(bytes(opts))
+        f.write(np.array([nk, cap, width, loop_after, accumulation, 0, 0, 0], np.int32).tobytes())
+        f.write(np.array([leaf] + list(opts.t_lb), np.float32).tobytes())
+        f.write(np.ascontiguousarray(q_bl, np.float64).tobytes()); f.write(np.ascontiguousarray(t_bl, np.float64).tobytes())
+        for sc in scans:
+            sc = np.ascontiguousarray(sc, np.float32)
+            f.write(np.array([len(sc)], np.int32).tobytes()); f.write(sc.tobytes())
+        f.write(pose_info.tobytes())
+
+
+def run_demo_map_schedule(path, out_path, device=0, env=None):
+    """-> per keyframe call (action, map size reported, map [n][4])"""
+    r = subprocess.run([build_demo_map_schedule(), path, out_path, str(device)], capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError("host_demo_map_schedule failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
+    raw = open(out_path, "rb").read()
+    out, o = [], 0
+    while o < len(raw):
+        action, reported, n, _ = np.frombuffer(raw, np.int32, 4, o); o += 16
+        out.append((int(action), int(reported), np.frombuffer(raw, np.float32, 4 * int(n), o).reshape(-1, 4).copy())); o += 16 * int(n)
     return out

@@ -3,8 +3,11 @@ batch association and performLoopClosure's ICP, Estimator.cpp:5101-5273) and the
 loop (:5113-5128), which keyframes make the two submaps (:5133-5175), their poses (:5147-5148), and the relative pose handed to the pose graph
 (:5210-5247).  `glio::LoopClosure`, `glio::detectLoopCandidate`, `glio::loopSubmapFrames`, `glio::loopFramePoses` and `glio::loopConstraint`
 (host/glio_loop_backend.hpp) are the C++ twins: the same scalar arithmetic in the same order, so the two hosts agree bit for bit
-(tests/test_loop_host_cpu.py).  GTSAM, correctPoses and the prior reset (:5249-5269) stay with the caller.  There is no CPU fallback for the
-submaps or the registration."""
+(tests/test_loop_host_cpu.py).  Of correctPoses (:4658-4787) the window's share is here too -- correct_window_poses / glio::correctWindowPoses: the
+relative poses inside the sliding window taken before the correction, the older keyframes set to the caller's corrected poses, the window chained back on,
+Rs / Ps -- and its recent_surf_keyframes.clear() is sliding.ReferenceMapSchedule.loop_closed() (the next call rebuilds the local map from the resident
+keyframes at the corrected poses, glio_localmap_rebuild_from_frames).  GTSAM / iSAM2 (the corrected poses themselves), pose_each_frame and the prior reset
+(:5249-5269, :4785 marg = false: glio_set_prior(NULL)) stay with the caller.  There is no CPU fallback for the submaps or the registration."""
 import ctypes as C
 import math
 
@@ -253,3 +256,57 @@ def loop_constraint(result, pose_latest, pose_closest, icp_thres):
     q_rel = _qmul(qfi, qt)
     t_rel = _qrot(qfi, [pc[0] - tf[0], pc[1] - tf[1], pc[2] - tf[2]])
     return np.array(t_rel + q_rel), np.full(6, float(result.fitness))
+
+
+def _qinv(q):
+    """Eigen's Quaterniond::inverse(): conjugate / squaredNorm (zeros for the zero quaternion)"""
+    n2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]
+    if not n2 > 0.0:
+        return [0.0, 0.0, 0.0, 0.0]
+    return [q[0] / n2, -q[1] / n2, -q[2] / n2, -q[3] / n2]
+
+
+def _q2R(q):
+    """Eigen's toRotationMatrix() (no normalisation), row-major [9]"""
+    w, x, y, z = q
+    tx, ty, tz = 2.0 * x, 2.0 * y, 2.0 * z
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz = tx * x, ty * x, tz * x
+    tyy, tyz, tzz = ty * y, tz * y, tz * z
+    return [1.0 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1.0 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1.0 - (txx + tyy)]
+
+
+def correct_window_poses(abs_poses, corrected, W):
+    """The sliding window's share of correctPoses (Estimator.cpp:4664-4686, :4702-4773).  abs_poses [N][7] = q (w first), t -- the estimator's abs_poses, where
+    row i + 1 belongs to keyframe i (row 0 is the start pose); W = slide_window_width; corrected [N - W][7], same layout: the pose-graph poses of the keyframes
+    0 .. N - 1 - W (pose_each_frame[keyframe_id_in_frame[i]], :4702-4713: the keyframes up to the window's oldest).
+      1. the W - 1 relative poses between rows N - W .. N - 1 are taken BEFORE anything is corrected: q_rel = q_from.inverse() * q_to,
+         t_rel = q_from.inverse() * (t_to - t_from) (Eigen's inverse(): conjugate / squaredNorm);
+      2. rows 1 .. N - W take the corrected poses;
+      3. rows N - W + 1 .. N - 1 are chained back on: t = t_prev + q_prev * t_rel, q = q_prev * q_rel.
+    Returns (abs_poses', Rs [N][9] row-major toRotationMatrix() of each rewritten row, Ps [N][3]); row 0 of Rs / Ps is left zero (the reference does not write
+    it).  pose_keyframe / pose_info_keyframe[i] are row i + 1 of abs_poses'.  glio::correctWindowPoses is the C++ twin, bit for bit.
+    (Eigen's q * v assumes a unit quaternion: with |q| = 1 + e the chained translations are off by ~2 e |t_rel|, in the reference as here.)"""
+    a = np.array(abs_poses, np.float64).reshape(-1, 7)
+    N, W = len(a), int(W)
+    c = np.asarray(corrected, np.float64).reshape(-1, 7)
+    if not (1 <= W <= N) or len(c) != N - W:
+        raise ValueError(f"correct_window_poses: {N} poses, window {W}, {len(c)} corrected poses (want {N - W})")
+    out = [[float(x) for x in row] for row in a]
+    rel = []
+    for i in range(N - W, N - 1):
+        qf, tf, qt, tt = out[i][:4], out[i][4:], out[i + 1][:4], out[i + 1][4:]
+        qi = _qinv(qf)
+        rel.append((_qmul(qi, qt), _qrot(qi, [tt[0] - tf[0], tt[1] - tf[1], tt[2] - tf[2]])))
+    Rs, Ps = np.zeros((N, 9)), np.zeros((N, 3))
+    for i in range(N - W):
+        out[i + 1] = [float(x) for x in c[i]]
+        Rs[i + 1], Ps[i + 1] = _q2R(out[i + 1][:4]), out[i + 1][4:]
+    for k, i in enumerate(range(N - W, N - 1)):
+        q, t = out[i][:4], out[i][4:]
+        r = _qrot(q, rel[k][1])
+        t = [t[0] + r[0], t[1] + r[1], t[2] + r[2]]
+        q = _qmul(q, rel[k][0])
+        out[i + 1] = q + t
+        Rs[i + 1], Ps[i + 1] = _q2R(q), t
+    return np.array(out), Rs, Ps

@@ -138,6 +138,74 @@ class SlidingWindowDriver:
         self.first += 1
 
 
+# ------------------------------------------------------------------ the local map's schedule (scalar bookkeeping, mirrored by glio::localMapPlan)
+MAP_NOTHING, MAP_PUSH, MAP_REBUILD = 0, 1, 2
+
+
+def local_map_plan(recent_size, n_keyframes, width, latest_frame_idx):
+    """buildLocalMapWithLandMark's bookkeeping (Estimator.cpp:3545-3610) without the clouds: what the call does to recent_surf_keyframes when the deque holds
+    `recent_size` clouds, pose_keyframe `n_keyframes` poses, local_map_width = `width`.  Returns (action, frames, recent_size', latest_frame_idx'):
+      MAP_REBUILD  the deque is thrown away and refilled with the keyframes `frames` (oldest first) at their CURRENT poses (:3545-3579) -- taken whenever
+                   recent_size < width.  With n_keyframes > width the loop's guard `i <= size - local_map_width` (:3550) ends it after width - 1 frames, so
+                   the deque never reaches `width` again and EVERY later call rebuilds (quirk Q17: the permanent state after the first loop closure, whose
+                   correctPoses clears the deque, :4660); with n_keyframes <= width it takes them all.  latest_frame_idx is not touched here.
+      MAP_PUSH     the deque is full: the oldest cloud leaves, keyframe n_keyframes - 1 (= frames[0]) enters at the pose it has now (:3582-3609)
+      MAP_NOTHING  full and no new keyframe since the last push (:3582), or no keyframe yet (:3531-3543: the initial map is the caller's).
+    (Keyframes whose pose_keyframe intensity is negative, :3549, do not occur: every keyframe of this port has a cloud.)"""
+    recent_size, n, width, latest = int(recent_size), int(n_keyframes), int(width), int(latest_frame_idx)
+    if n < 1:
+        return MAP_NOTHING, [], recent_size, latest
+    if recent_size < width:
+        frames = []
+        i = n - 1
+        while i >= 0:
+            if n > width and i <= n - width:
+                break
+            frames.insert(0, i)
+            if len(frames) >= width:
+                break
+            i -= 1
+        return MAP_REBUILD, frames, len(frames), latest
+    if latest != n - 1:
+        return MAP_PUSH, [n - 1], recent_size, n - 1
+    return MAP_NOTHING, [], recent_size, latest
+
+
+class ReferenceMapSchedule:
+    """The local map kept the way the reference keeps it (opt-in; the drivers above push each keyframe once and never re-pose it): every keyframe call asks
+    local_map_plan and either rebuilds the ring from the keyframe clouds resident in a batch.BatchAssociation at the poses pose_info_keyframe holds NOW
+    (glio_localmap_rebuild_from_frames) or pushes the newest keyframe's resident scan (glio_localmap_push_scan + glio_localmap_build).  loop_closed() is
+    correctPoses' recent_surf_keyframes.clear() (Estimator.cpp:4660).  glio::ReferenceMapSchedule (glio_backend.hpp) is the C++ twin."""
+
+    def __init__(self, ctx, assoc, width, q_bl=(1.0, 0.0, 0.0, 0.0), t_bl=(0.0, 0.0, 0.0)):
+        self.ctx, self.assoc, self.width = ctx, assoc, int(width)
+        self.q_bl, self.t_bl = q_bl, t_bl
+        self.recent_size, self.latest_frame_idx = 0, -1
+        self.last_action, self.last_frames = MAP_NOTHING, []
+
+    def loop_closed(self):
+        self.recent_size = 0
+
+    def will_rebuild(self, n_keyframes):
+        """a call whose plan says "rebuild" does not use a map built ahead: ask before glio_localmap_push_scan_ahead_and_build"""
+        return local_map_plan(self.recent_size, n_keyframes, self.width, self.latest_frame_idx)[0] == MAP_REBUILD
+
+    def update(self, n_keyframes, pose_info, scan_slot, lidar_offset):
+        """pose_info [>= n_keyframes][7] = t_po, q_po of every keyframe; the newest keyframe's scan is resident in window slot `scan_slot` and its own-frame
+        cloud in the association (set_frame_from_scan).  Returns the map size (None when the plan says nothing)."""
+        from . import loop
+        action, frames, self.recent_size, self.latest_frame_idx = local_map_plan(self.recent_size, n_keyframes, self.width, self.latest_frame_idx)
+        self.last_action, self.last_frames = action, frames
+        if action == MAP_NOTHING:
+            return None
+        pose_info = np.asarray(pose_info, np.float64).reshape(-1, 7)
+        poses = loop.frame_poses(pose_info[frames], self.q_bl, self.t_bl)
+        if action == MAP_REBUILD:
+            return self.ctx.localmap_rebuild_from_frames(self.assoc, frames, poses)
+        self.ctx.localmap_push_scan(scan_slot, lidar_offset, poses[0, 3:], poses[0, :3])
+        return self.ctx.localmap_build()
+
+
 class ResidentSlidingWindow:
     """The same per-keyframe sequence with everything kept on the device between keyframes (capi.Context only):
     scans slide with `glio_slide_window`, only the NEW keyframe's scan is uploaded, all slots are associated in one call,

@@ -63,7 +63,9 @@ int glio_set_map_strided(glio_ctx* ctx, const void* map_points, int n, int strid
  * (Estimator.cpp:3529-3631, 2056) by a ring of the last `width` keyframe clouds kept on the device in the map frame:
  * per keyframe ONE scan crosses PCIe (glio_localmap_push), the concatenation is voxel-averaged (pcl::VoxelGrid
  * semantics, leaf = surf_ds_size) and hashed on the device (glio_localmap_build does what glio_set_map does).
- *   width = local_map_width (yaml: 50); q,t = q_po * q_bl, q_po * t_bl + t_po (:3569-3570). */
+ *   width = local_map_width (yaml: 50); q,t = q_po * q_bl, q_po * t_bl + t_po (:3569-3570).
+ * A push is the reference's steady-state branch (:3580-3610: pop the oldest, append the newest at the pose it has now); the branch that re-poses the whole
+ * deque (:3545-3579) is glio_localmap_rebuild_from_frames below. */
 int glio_localmap_config(glio_ctx* ctx, int width, float leaf, int max_points_per_keyframe);
 int glio_localmap_push(glio_ctx* ctx, const float* cloud_xyzi, int n, const double q[4], const double t[3]);
 int glio_localmap_push_strided(glio_ctx* ctx, const void* cloud_points, int n, int stride_bytes, int intensity_offset, const double q[4], const double t[3]);
@@ -100,8 +102,9 @@ int glio_set_scan_strided(glio_ctx* ctx, int slot, const void* scan_points, int 
 int glio_set_scan_ahead(glio_ctx* ctx, const float* scan_xyzi, int n);
 int glio_set_scan_ahead_strided(glio_ctx* ctx, const void* scan_points, int n, int stride_bytes, int intensity_offset);
 /* ... and, behind it, the next call's local map: glio_localmap_push_scan of the cloud just sent ahead at the new keyframe's pose + glio_localmap_build, on the same
- * stream beside the call's tail (the new keyframe's initial pose follows from this call's solve and the odometry: buildLocalMapWithLandMark pushes each keyframe
- * once, at the pose it has when it arrives, Estimator.cpp:3585-3616).  The next call then makes neither call; its glio_slide_window waits for the event. */
+ * stream beside the call's tail (the new keyframe's initial pose follows from this call's solve and the odometry: in its steady state -- the deque full,
+ * Estimator.cpp:3580-3610 -- buildLocalMapWithLandMark pushes each keyframe once, at the pose it has when it arrives; the rebuild branch, :3545-3579, is
+ * glio_localmap_rebuild_from_frames).  The next call then makes neither call; its glio_slide_window waits for the event. */
 int glio_localmap_push_scan_ahead_and_build(glio_ctx* ctx, const float lidar_offset[3], const double q[4], const double t[3], int* out_points);
 int glio_associate_resident(glio_ctx* ctx, int slot, const double q[4], const double t[3], int* out_count);
 /* Slide the window by one keyframe: the resident scan of slot s+1 becomes that of slot s (the scans are a ring on the device: nothing is
@@ -371,6 +374,24 @@ int glio_bassoc_prepare_async(glio_bassoc* b, int n_pairs, const int32_t* pair_c
  * the keyframe that just entered the window is not uploaded a second time).  The copy runs on the association's stream; the context's next
  * glio_set_scan and glio_destroy are ordered behind it on the device (no host wait). */
 int glio_bassoc_set_frame_from_scan(glio_bassoc* b, int k, glio_ctx* ctx, int slot, const float lidar_offset[3]);
+/* ---- the local map rebuilt from resident keyframes.  buildLocalMapWithLandMark's rebuild branch (Estimator.cpp:3545-3579) + downSampleCloud + setInputCloud
+ * (:3618-3631, :2056): whenever recent_surf_keyframes holds fewer than local_map_width clouds -- during the first local_map_width keyframes of every run, and on
+ * EVERY keyframe call after the first loop closure (correctPoses clears the deque, :4660, and the loop's guard at :3550 then refills it with local_map_width - 1
+ * clouds only) -- the reference throws the deque away and re-transforms surf_frames[idx] of the last keyframes at their current pose_info_keyframe poses.
+ * The ring becomes exactly the n_frames keyframes frame_idx[0..n) (oldest first = concatenation order) of `frames`' resident own-frame clouds
+ * (glio_bassoc_set_frame*: scan - lidar_offset, the floats glio_localmap_push_scan forms), each moved by transformCloud at poses[f] = t[3], q[4] (w first; the
+ * layout of glio_loop_build_submap; q, t = q_po * q_bl, q_po * t_bl + t_po as for glio_localmap_push), then voxel grid + K1 as glio_localmap_build does.
+ * *out_points = the map's size.  Bit for bit what a fresh ring gives that got glio_localmap_push(cloud frame_idx[f], pose f) for f = 0..n-1 and then
+ * glio_localmap_build, in both accumulation modes, and later pushes / evictions / builds go on as if those pushes had happened -- in two launches plus the
+ * build's chain instead of three to four launches and one upload per frame.  Runs on the context's stream behind the association's pending frame copies (an
+ * event, no host wait; the association's next write to a cloud is ordered behind the rebuild the same way) and behind a scan / map sent ahead, whose map it
+ * supersedes (the scan sent ahead stays for the next glio_slide_window).  One host wait in its middle, as glio_localmap_build.
+ * GLIO_E_STATE without glio_localmap_config; GLIO_E_ARG (ring untouched): n_frames outside [1, width], a frame index outside [0, K), a frame that was never
+ * set (or holds no point), a frame with more points than the ring's max_points_per_keyframe, a non-finite pose, an association on another device. */
+int glio_localmap_rebuild_from_frames(glio_ctx* ctx, glio_bassoc* frames, int n_frames, const int32_t* frame_idx, const double* poses /* [n_frames][7] */, int* out_points);
+/* device time of the last rebuild's own two launches (table clear + the multi-frame kernel), ms; only in a process started with GLIO_LM_REBUILD_TIMING=1
+ * (GLIO_E_STATE otherwise: the timing events are not recorded by default) */
+int glio_localmap_last_rebuild_device_ms(glio_ctx* ctx, float* ms);
 int glio_bassoc_results_dev(glio_bassoc* b, const float** cp_dev, const double** norm_cent_dev, const double** score_dev);
 /* globalFeatureSelectionAdd_Batch / globalFeatureSelection_Batch (Estimator.cpp:4057-4116, 3994-4055; batch_feature_res_num: 25):
  * keep records src_index[0..n_keep) of the current n_current records, in that order (pair after pair; the caller updates its
