@@ -19,6 +19,7 @@ sys.path.insert(0, os.path.join(HERE, "..", ".."))
 
 N = 64
 SEED = 20260926
+DD_SIZES = (10, 2, 3, 7, 19, 20, 5)
 
 
 def rand_q(rng, unit=True):
@@ -138,11 +139,26 @@ def generate():
     anc0 = np.array(win.frame.anc_ecef)
     fs, Pis, Pjs, yaws, ancs, rs, J0s, J1s = [], [], [], [], [], [], [], []
     for k in range(N):
-        f = copy.copy(win.dd[k % len(win.dd)])
-        ns = f.n_sat
+        # n_sat through DD_SIZES (2 and GLIO_DD_MAX_SAT = 20 included: more than one constellation's ten are the two factors of an epoch merged),
+        # the master at the first, a middle and the last position, the weight dense / lower-triangular / symmetric
+        ns = DD_SIZES[k % len(DD_SIZES)]
+        e = (k % (len(win.dd) // 2)) * 2
+        f = copy.copy(win.dd[e])
+        for i in range(10, ns):
+            f.user_sat_pos[i][:], f.ref_sat_pos[i][:] = list(win.dd[e + 1].user_sat_pos[i - 10]), list(win.dd[e + 1].ref_sat_pos[i - 10])
+            f.user_psr[i], f.ref_psr[i] = win.dd[e + 1].user_psr[i - 10], win.dd[e + 1].ref_psr[i - 10]
+        f.n_sat = ns
+        f.master = (0, ns // 2, ns - 1)[(k // 2) % 3]
         if k % 3 == 0:
             Wm = np.eye(ns - 1) + rng.normal(0, 0.2, (ns - 1, ns - 1))
-            f.weight[:(ns - 1) ** 2] = list(Wm.ravel())
+        else:
+            D = np.zeros((ns - 1, ns))
+            D[:, f.master] = 1
+            D[np.arange(ns - 1), [i for i in range(ns) if i != f.master]] = -1
+            Rm = D @ np.diag(1.0 / (rng.uniform(30, 50, ns) / 50.0) ** 2) @ D.T
+            Wm = np.linalg.inv(np.linalg.cholesky(Rm)) if k % 3 == 1 else np.linalg.inv(np.sqrt(Rm))
+        f.weight[:] = [0.0] * len(f.weight)
+        f.weight[:(ns - 1) ** 2] = list(Wm.ravel())
         f.threshold = [1e9, 5.0, 0.5, 0.0][k % 4]
         f.ratio = rng.uniform(0, 1)
         Pi, Pj = win.init.trans[f.slot_i] + rng.normal(0, 3, 3), win.init.trans[f.slot_j] + rng.normal(0, 3, 3)
@@ -157,6 +173,11 @@ def generate():
     for k in range(N):
         f = copy.copy(win.dop[k % len(win.dop)])
         f.epoch = int(rng.integers(0, nslot)); f.ratio = rng.uniform(0, 1)
+        if k % 2:                                            # a lever arm on every second row, and on half of those a matrix of the row's own yaw
+            f.lever_arm[:] = list(rng.normal(0, 0.5, 3))
+        if k % 4 == 3:
+            yr = rng.uniform(-3, 3)
+            f.R_ecef_local[:] = list((synth.ecef2rotation(anc0) @ np.array([[np.cos(yr), -np.sin(yr), 0], [np.sin(yr), np.cos(yr), 0], [0, 0, 1]])).ravel())
         args = [st.trans[f.slot_i] + rng.normal(0, 2, 3), st.speed_bias[f.slot_i] + rng.normal(0, 1, 9), st.trans[f.slot_j] + rng.normal(0, 2, 3),
                 st.speed_bias[f.slot_j] + rng.normal(0, 1, 9), rng.normal(0, 3, nslot)]
         yaw, anc = rng.uniform(-3, 3), anc0 + rng.normal(0, 30, 3)

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 from glio_amd import synth
+from parity_checks import check_root as _check_root
+from parity_checks import rel_err
 
 pytestmark = pytest.mark.gpu
 
@@ -23,21 +25,6 @@ def hip():
 def po():
     from oracle import pyoracle
     return pyoracle
-
-
-def rel_err(a, b):
-    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
-
-
-def _check_root(out_h, out_o):
-    Jh, rh, Jo, ro = out_h["lin_jac"], out_h["lin_res"], out_o["lin_jac"], out_o["lin_res"]
-    assert rel_err(Jh.T @ Jh, Jo.T @ Jo) <= 1e-8
-    assert rel_err(Jh.T @ rh, Jo.T @ ro) <= 1e-8
-    assert abs(rh @ rh - ro @ ro) <= 1e-7 * max(ro @ ro, 1e-30)
-    assert np.allclose(Jh, np.triu(Jh)), "Cholesky root is upper triangular"
-    for k in ("blk_slot", "blk_kind", "blk_idx"):
-        assert np.array_equal(out_h[k], out_o[k])
-    assert np.array_equal(out_h["blk_x0"], out_o["blk_x0"])
 
 
 @pytest.mark.parametrize("use_prior", [False, True], ids=["first_window", "with_prior"])

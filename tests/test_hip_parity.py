@@ -6,6 +6,7 @@ import pytest
 
 from glio_amd import ctypes_types as T
 from glio_amd import synth
+from parity_checks import assert_pose_parity, rel_err, rot_angle  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,23 +22,6 @@ def hip():
 def po():
     from oracle import pyoracle
     return pyoracle
-
-
-def rel_err(a, b):
-    return np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300)
-
-
-def rot_angle(qa, qb):
-    d = synth.qmul(synth.qconj(qa), qb)
-    return 2 * np.arctan2(np.linalg.norm(d[1:]), abs(d[0]))
-
-
-def assert_pose_parity(sa, sb, tol_t=1e-4, tol_r=1e-5):
-    dt = np.linalg.norm(sa.trans - sb.trans, axis=1).max()
-    dr = max(rot_angle(sa.quat[i], sb.quat[i]) for i in range(sa.W))
-    assert dt <= tol_t, f"translation parity {dt:.3e} m"
-    assert dr <= tol_r, f"rotation parity {dr:.3e} rad"
-    return dt, dr
 
 
 CASES = [

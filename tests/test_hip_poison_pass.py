@@ -11,7 +11,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILES = ["tests/test_hip_parity.py", "tests/test_hip_marg.py", "tests/test_hip_batch_tr.py", "tests/test_hip_streaming.py", "tests/test_golden_ref.py"]
+FILES = ["tests/test_hip_parity.py", "tests/test_hip_marg.py", "tests/test_hip_batch_tr.py", "tests/test_hip_streaming.py", "tests/test_golden_ref.py",
+         "tests/test_hip_factor_branches.py"]
 
 
 def test_parity_suites_pass_with_lds_and_allocations_poisoned():

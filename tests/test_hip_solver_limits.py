@@ -209,7 +209,7 @@ def test_solve_at_the_limit(hip, po, key, form):
 def test_marginalize_at_the_limit(hip, po):
     """W = 61: the device's square root of the Schur complement against the oracle's, by test_hip_marg's _check_root (J0^T J0, J0^T r0,
     |r0|^2, an upper triangular root, the same parameter blocks)."""
-    from test_hip_marg import _check_root
+    from parity_checks import check_root as _check_root
     win, corr, _ = _window("W61")
     so, _ = _oracle_solve(po, "W61")
     ctx = hip.Context(win.opts)
