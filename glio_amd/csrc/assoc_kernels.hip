@@ -43,17 +43,6 @@
 // operations; a fused product changes the last bit and with it the ranking of exact-tie neighbours).
 #pragma clang fp contract(off)
 
-// q * v through Eigen's _transformVector, compiled here so that it obeys the pragma above
-__device__ __forceinline__ void a_qrot(const double q[4], const double v[3], double o[3]) {
-    double uv[3], uuv[3];
-    uv[0] = q[2] * v[2] - q[3] * v[1]; uv[1] = q[3] * v[0] - q[1] * v[2]; uv[2] = q[1] * v[1] - q[2] * v[0];
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    uuv[0] = q[2] * uv[2] - q[3] * uv[1]; uuv[1] = q[3] * uv[0] - q[1] * uv[2]; uuv[2] = q[1] * uv[1] - q[2] * uv[0];
-    o[0] = v[0] + q[0] * uv[0] + uuv[0];
-    o[1] = v[1] + q[0] * uv[1] + uuv[1];
-    o[2] = v[2] + q[0] * uv[2] + uuv[2];
-}
-
 struct AssocWork {
     float cell;                   // cell edge
     float inv_cell;
@@ -552,7 +541,7 @@ __device__ __forceinline__ void knn5_group_body(const AssocArgs& a, const float4
         // transformPoint: double math, float store
         const double pin[3] = {(double)pl.x, (double)pl.y, (double)pl.z};
         double po[3];
-        a_qrot(sl.q, pin, po);
+        d_qrot_nc(sl.q, pin, po);
         px = (float)(po[0] + sl.t[0]); py = (float)(po[1] + sl.t[1]); pz = (float)(po[2] + sl.t[2]);
     }
     const int cx = cell_of(px, a.inv_cell), cy = cell_of(py, a.inv_cell), cz = cell_of(pz, a.inv_cell);
@@ -706,7 +695,7 @@ __global__ __launch_bounds__(QC_THREADS) void k_qbin_count(const AssocArgs a, co
         const float4 pl = scan[sl.qoff + i];
         const double pin[3] = {(double)pl.x, (double)pl.y, (double)pl.z};
         double po[3];
-        a_qrot(sl.q, pin, po);
+        d_qrot_nc(sl.q, pin, po);
         px = (float)(po[0] + sl.t[0]); py = (float)(po[1] + sl.t[1]); pz = (float)(po[2] + sl.t[2]);
         const unsigned long long key = pack_key(cell_of(px, a.inv_cell), cell_of(py, a.inv_cell), cell_of(pz, a.inv_cell));
         unsigned q = hash_key(key) & (QC_SLOTS - 1);
@@ -863,7 +852,7 @@ __global__ __launch_bounds__(QT_THREADS) void k_qbin_tile(const AssocArgs a, con
         const float4 pl = ps[sl.qoff + i];
         const double pin[3] = {(double)pl.x, (double)pl.y, (double)pl.z};
         double po[3];
-        a_qrot(sl.q, pin, po);
+        d_qrot_nc(sl.q, pin, po);
         px = (float)(po[0] + sl.t[0]); py = (float)(po[1] + sl.t[1]); pz = (float)(po[2] + sl.t[2]); pw = pl.w;
         float kx = px, ky = py, kz = pz;            // the position the query is grouped by
         if (sl.local) {
@@ -872,7 +861,7 @@ __global__ __launch_bounds__(QT_THREADS) void k_qbin_tile(const AssocArgs a, con
             const double dw[3] = {(po[0] + sl.t[0]) - sl.lt[0], (po[1] + sl.t[1]) - sl.lt[1], (po[2] + sl.t[2]) - sl.lt[2]};
             const double qc[4] = {sl.lq[0], -sl.lq[1], -sl.lq[2], -sl.lq[3]};
             double pl2[3];
-            a_qrot(qc, dw, pl2);
+            d_qrot_nc(qc, dw, pl2);
             kx = (float)pl2[0]; ky = (float)pl2[1]; kz = (float)pl2[2];
         }
         const unsigned long long key = pack_key(cell_of(kx, a.inv_cell), cell_of(ky, a.inv_cell), cell_of(kz, a.inv_cell));
@@ -1557,7 +1546,7 @@ __global__ __launch_bounds__(PF_BLOCK) void k_plane_fit(const AssocArgs a, const
     const float4 pl = scan[qlive ? i : 0];
     const double pin[3] = {(double)pl.x, (double)pl.y, (double)pl.z};
     double po[3];
-    a_qrot(sl.q, pin, po);
+    d_qrot_nc(sl.q, pin, po);
     const float px = (float)(po[0] + sl.t[0]), py = (float)(po[1] + sl.t[1]), pz = (float)(po[2] + sl.t[2]);
     int mp5[5], mi[5];
     float md4 = FLT_MAX;
@@ -1702,7 +1691,6 @@ __global__ __launch_bounds__(PF_BLOCK) void k_compact(const int* __restrict__ fl
 }
 
 // ------------------------------------------------------------------------------------------------
-static int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 struct KnnBinHost { KnnBin d; int rows, cap, capq_max; };
 static unsigned long long* g_knn_dbg = nullptr;      // statistics of the near-block search (glio_debug_knn_stats)
@@ -2249,7 +2237,7 @@ __global__ void k_transform_cloud(const float4* __restrict__ in, int n, const do
     const float4 p = in[i];
     const double pin[3] = {(double)p.x, (double)p.y, (double)p.z};
     double po[3];
-    a_qrot(q, pin, po);
+    d_qrot_nc(q, pin, po);
     out[i] = make_float4((float)(po[0] + t[0]), (float)(po[1] + t[1]), (float)(po[2] + t[2]), p.w);
 }
 
@@ -2273,7 +2261,7 @@ __global__ void k_transform_cloud_multi(const FrameBuild* __restrict__ fb) {
     const float4 p = f.local[i];                                  // (the PRESORTED copy of the keyframe cloud: w = index in the cloud; consecutive points are neighbours,
     const double pin[3] = {(double)p.x, (double)p.y, (double)p.z};    //  which is what lets the tile insert below aggregate its atomics)
     double po[3];
-    a_qrot(q, pin, po);
+    d_qrot_nc(q, pin, po);
     f.global[i] = make_float4((float)(po[0] + t[0]), (float)(po[1] + t[1]), (float)(po[2] + t[2]), p.w);
 }
 __global__ __launch_bounds__(HI_THREADS) void k_hash_insert_multi(const FrameBuild* __restrict__ fb, const float inv_cell) {

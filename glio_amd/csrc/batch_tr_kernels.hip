@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "batch_device.h"
+#include "factor_math.h"
 
 #define SREC 124           // Haa 36 | Hbb 36 | Hab 36 | ga 6 | gb 6 | cost 1 | pad
 #define TRV_THREADS 256
@@ -59,27 +60,6 @@ struct BtStatus {
 };
 
 // ------------------------------------------------------------------------------------------------ small factors
-__device__ __forceinline__ void bt_plus_jac(const double q[4], double P[12]) {
-    P[0] = -q[1]; P[1] = -q[2]; P[2] = -q[3];
-    P[3] = q[0];  P[4] = q[3];  P[5] = -q[2];
-    P[6] = -q[3]; P[7] = q[0];  P[8] = q[1];
-    P[9] = q[2];  P[10] = -q[1]; P[11] = q[0];
-}
-__device__ __forceinline__ void bt_qleft(const double q[4], double M[16]) {
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    M[0] = w; M[1] = -x; M[2] = -y; M[3] = -z;
-    M[4] = x; M[5] = w; M[6] = -z; M[7] = y;
-    M[8] = y; M[9] = z; M[10] = w; M[11] = -x;
-    M[12] = z; M[13] = -y; M[14] = x; M[15] = w;
-}
-__device__ __forceinline__ void bt_qright(const double p[4], double M[16]) {
-    const double w = p[0], x = p[1], y = p[2], z = p[3];
-    M[0] = w; M[1] = -x; M[2] = -y; M[3] = -z;
-    M[4] = x; M[5] = w; M[6] = z; M[7] = -y;
-    M[8] = y; M[9] = -z; M[10] = w; M[11] = x;
-    M[12] = z; M[13] = y; M[14] = -x; M[15] = w;
-}
-
 // one wavefront per factor: nr residuals with local Jacobians Ja, Jb (nr x 6, LDS) -> the record
 __global__ __launch_bounds__(64) void k_small_eval(const BtSel sel, const int n_fac, const int* __restrict__ fa, const int* __restrict__ fb, const int* __restrict__ ftype,
                                                    const int* __restrict__ fidx, const double* __restrict__ poses0, const double* __restrict__ poses1,
@@ -106,14 +86,12 @@ __global__ __launch_bounds__(64) void k_small_eval(const BtSel sel, const int n_
             const double* qi = pa + 3;
             const double* qj = pb + 3;
             double A[4], u[4], Au[4], p[4];
-            d_qinv(dq, A); d_qinv(qi, u);
-            d_qmul(A, u, Au); d_qmul(Au, qj, p);
-            double LA[16], Rv[16], M[16], LAu[16], Pa[12], Pb[12];
-            bt_qleft(A, LA); bt_qright(qj, Rv); bt_qleft(Au, LAu);
+            fm_qdiff_products(dq, qi, qj, A, u, Au, p);
+            // d p / d u = Qleft(A) Qright(qj) in full, then the lane's row (the factor below picks the row first: the same sums; written that way here,
+            // the kernel needs a quarter more registers and loses a wave per SIMD)
+            double LA[16], Rv[16], M[16], LAu[16];
+            d_qleft(A, LA); d_qright(qj, Rv); d_qleft(Au, LAu);
             for (int x = 0; x < 4; ++x) for (int y = 0; y < 4; ++y) { double s = 0; for (int k = 0; k < 4; ++k) s += LA[x * 4 + k] * Rv[k * 4 + y]; M[x * 4 + y] = s; }
-            const double n2 = qi[0] * qi[0] + qi[1] * qi[1] + qi[2] * qi[2] + qi[3] * qi[3];
-            const double Cq[4] = {qi[0], -qi[1], -qi[2], -qi[3]};
-            bt_plus_jac(qi, Pa); bt_plus_jac(qj, Pb);
             {
                 const int k = lane;
                 // row 1 + k of M and of LAu by selects (a run-time index into a register array would put the arrays into scratch memory)
@@ -122,16 +100,10 @@ __global__ __launch_bounds__(64) void k_small_eval(const BtSel sel, const int n_
                 for (int m = 0; m < 4; ++m) { Mk[m] = k == 0 ? M[4 + m] : (k == 1 ? M[8 + m] : M[12 + m]); Lk[m] = k == 0 ? LAu[4 + m] : (k == 1 ? LAu[8 + m] : LAu[12 + m]); }
                 rr[k] = 10000.0 * (k == 0 ? p[1] : (k == 1 ? p[2] : p[3]));
                 double Jgi[4], Jgj[4];
-                for (int c = 0; c < 4; ++c) {
-                    double s = 0;
-                    for (int m = 0; m < 4; ++m) s += Mk[m] * (((m == c ? (m == 0 ? 1.0 : -1.0) : 0.0) - 2.0 * Cq[m] * qi[c] / n2) / n2);
-                    Jgi[c] = 10000.0 * s;
-                    Jgj[c] = 10000.0 * Lk[c];
-                }
-                for (int c = 0; c < 3; ++c) {
-                    Ja[k * 6 + 3 + c] = Jgi[0] * Pa[c] + Jgi[1] * Pa[3 + c] + Jgi[2] * Pa[6 + c] + Jgi[3] * Pa[9 + c];
-                    Jb[k * 6 + 3 + c] = Jgj[0] * Pb[c] + Jgj[1] * Pb[3 + c] + Jgj[2] * Pb[6 + c] + Jgj[3] * Pb[9 + c];
-                }
+                fm_qinv_chain(Mk, qi, Jgi);
+                for (int c = 0; c < 4; ++c) { Jgi[c] = 10000.0 * Jgi[c]; Jgj[c] = 10000.0 * Lk[c]; }
+                fm_quat_local(Jgi, qi, Ja + k * 6 + 3);
+                fm_quat_local(Jgj, qj, Jb + k * 6 + 3);
             }
         }
     } else if (ftype[f] == 2) {
@@ -144,20 +116,15 @@ __global__ __launch_bounds__(64) void k_small_eval(const BtSel sel, const int n_
             const double* q1 = pa + 3;
             const double* q2 = pb + 3;
             double A[4], u[4], Au[4], p[4], v[3];
-            d_qinv(cst, A); d_qinv(q1, u);
-            d_qmul(A, u, Au); d_qmul(Au, q2, p);
+            fm_qdiff_products(cst, q1, q2, A, u, Au, p);
             for (int k = 0; k < 3; ++k) v[k] = pb[k] - pa[k];
-            double Pa[12], Pb[12];
-            bt_plus_jac(q1, Pa); bt_plus_jac(q2, Pb);
-            const double n2 = q1[0] * q1[0] + q1[1] * q1[1] + q1[2] * q1[2] + q1[3] * q1[3];
-            const double Cq[4] = {q1[0], -q1[1], -q1[2], -q1[3]};
             const int k = lane < 3 ? lane : lane - 3;
             double Jg1[4], Jg2[4] = {0, 0, 0, 0}, Jp[3] = {0, 0, 0};        // this row's global Jacobians wrt q1, q2 and wrt p2 (= - wrt p1)
             double G[4];                                                       // the row of d r / d u (u = q1^-1), before d u / d q1
             double res;
             if (lane < 3) {
                 double LA[16], Rv[16], LAu[16];
-                bt_qleft(A, LA); bt_qright(q2, Rv); bt_qleft(Au, LAu);
+                d_qleft(A, LA); d_qright(q2, Rv); d_qleft(Au, LAu);
 #pragma unroll
                 for (int m = 0; m < 4; ++m) {
                     double sM = 0;
@@ -189,21 +156,14 @@ __global__ __launch_bounds__(64) void k_small_eval(const BtSel sel, const int n_
                     Jp[c] = 20.0 * ((k == c ? 1.0 : 0.0) + 2.0 * w * sq[c] + 2.0 * (qk * qq[c] - (k == c ? q2n : 0.0)));
                 }
             }
+            fm_qinv_chain(G, q1, Jg1);
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                double sacc = 0;
-#pragma unroll
-                for (int m = 0; m < 4; ++m) sacc += G[m] * (((m == c ? (m == 0 ? 1.0 : -1.0) : 0.0) - 2.0 * Cq[m] * q1[c] / n2) / n2);
-                Jg1[c] = 20.0 * sacc;
-            }
+            for (int c = 0; c < 4; ++c) Jg1[c] = 20.0 * Jg1[c];
             rr[lane] = res;
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                Ja[lane * 6 + c] = -Jp[c];
-                Jb[lane * 6 + c] = Jp[c];
-                Ja[lane * 6 + 3 + c] = Jg1[0] * Pa[c] + Jg1[1] * Pa[3 + c] + Jg1[2] * Pa[6 + c] + Jg1[3] * Pa[9 + c];
-                Jb[lane * 6 + 3 + c] = Jg2[0] * Pb[c] + Jg2[1] * Pb[3 + c] + Jg2[2] * Pb[6 + c] + Jg2[3] * Pb[9 + c];
-            }
+            for (int c = 0; c < 3; ++c) { Ja[lane * 6 + c] = -Jp[c]; Jb[lane * 6 + c] = Jp[c]; }
+            fm_quat_local(Jg1, q1, Ja + lane * 6 + 3);
+            fm_quat_local(Jg2, q2, Jb + lane * 6 + 3);
         }
     } else {
 #pragma clang fp contract(off)
@@ -212,37 +172,18 @@ __global__ __launch_bounds__(64) void k_small_eval(const BtSel sel, const int n_
         nr = 19;
         const glio_dd_psr& F = dd[fidx[f]];
         const int ns = F.n_sat, m = F.master, nw = ns - 1, i = lane;
-        const double* R = Rel;
-        if (i < ns && i != m) {
-            double lp[3], Pe[3];
-            for (int k = 0; k < 3; ++k) lp[k] = F.ratio * pa[k] + (1.0 - F.ratio) * pb[k];
-            for (int k = 0; k < 3; ++k) Pe[k] = R[3 * k] * lp[0] + R[3 * k + 1] * lp[1] + R[3 * k + 2] * lp[2] + Rel[9 + k];
+        if (i < ns && i != m) {           // its satellite and the master, back to back
+            double Pe[3], ru_i, rr_i, obs_i, e_i[3], ru_m, rr_m, obs_m, e_m[3];
+            fm_dd_position(F.ratio, pa, pb, Rel, Rel + 9, Pe);
+            fm_dd_satellite(F, i, Pe, Rel, ru_i, rr_i, obs_i, e_i);
+            fm_dd_satellite(F, m, Pe, Rel, ru_m, rr_m, obs_m, e_m);
             const int ri = i < m ? i : i - 1;
-            double d_ui[3], d_um[3], d_ri[3], d_rm[3];
-            for (int k = 0; k < 3; ++k) {
-                d_ui[k] = F.user_sat_pos[i][k] - Pe[k]; d_um[k] = F.user_sat_pos[m][k] - Pe[k];
-                d_ri[k] = F.ref_sat_pos[i][k] - F.station[k]; d_rm[k] = F.ref_sat_pos[m][k] - F.station[k];
-            }
-            const double r_ui = sqrt(d_dot3_nc(d_ui, d_ui)), r_um = sqrt(d_dot3_nc(d_um, d_um)), r_ri = sqrt(d_dot3_nc(d_ri, d_ri)), r_rm = sqrt(d_dot3_nc(d_rm, d_rm));
-            const double est = (r_ui - r_ri) - (r_um - r_rm);
-            const double obs = (F.user_psr[i] - F.ref_psr[i]) - (F.user_psr[m] - F.ref_psr[m]);
-            const double wgt = fabs(est - obs) > F.threshold ? 0.05 : 1.0;
-            raw[ri] = wgt * (est - obs);
-            for (int c = 0; c < 3; ++c) {
-                const double ei = (d_ui[0] * R[c] + d_ui[1] * R[3 + c] + d_ui[2] * R[6 + c]) / r_ui;
-                const double em = (d_um[0] * R[c] + d_um[1] * R[3 + c] + d_um[2] * R[6 + c]) / r_um;
-                Jri[ri * 3 + c] = (-ei * wgt * F.ratio) - (-em * wgt * F.ratio);
-                Jrj[ri * 3 + c] = (-ei * wgt * (1.0 - F.ratio)) - (-em * wgt * (1.0 - F.ratio));
-            }
+            fm_dd_row(F.ratio, F.threshold, ru_i, rr_i, obs_i, e_i, ru_m, rr_m, obs_m, e_m, raw[ri], Jri + ri * 3, Jrj + ri * 3);
         }
         GLIO_WAVE_LDS_SYNC();
         if (i < nw) {
-            double sr = 0, si[3] = {0, 0, 0}, sj[3] = {0, 0, 0};
-            for (int q = 0; q < nw; ++q) {
-                const double wv = F.weight[i * nw + q];
-                sr += wv * raw[q];
-                for (int k = 0; k < 3; ++k) { si[k] += wv * Jri[q * 3 + k]; sj[k] += wv * Jrj[q * 3 + k]; }
-            }
+            double sr, si[3], sj[3];
+            fm_dd_whiten(F.weight, i, nw, raw, Jri, Jrj, sr, si, sj);
             rr[i] = sr;
             for (int k = 0; k < 3; ++k) { Ja[i * 6 + k] = si[k]; Jb[i * 6 + k] = sj[k]; }
         }

@@ -11,7 +11,7 @@
 #include <cstring>
 #include <vector>
 
-#include "glio_device.h"
+#include "factor_math.h"
 
 #define EV_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { glio_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); return GLIO_E_HIP; } } while (0)
 
@@ -24,37 +24,18 @@ __global__ __launch_bounds__(64) void k_eval_dd(const glio_dd_psr* __restrict__ 
     const double* Pi = prm; const double* Pj = prm + 3; const double* R = prm + 6; const double* anc = prm + 15;
     if (i < 19) { raw[i] = 0; for (int k = 0; k < 3; ++k) { Ji[i * 3 + k] = 0; Jj[i * 3 + k] = 0; } }
     __syncthreads();
-    if (i < ns && i != m) {
-        double lp[3], Pe[3];
-        for (int k = 0; k < 3; ++k) lp[k] = F.ratio * Pi[k] + (1.0 - F.ratio) * Pj[k];
-        for (int k = 0; k < 3; ++k) Pe[k] = R[3 * k] * lp[0] + R[3 * k + 1] * lp[1] + R[3 * k + 2] * lp[2] + anc[k];
+    if (i < ns && i != m) {           // one lane per row: its satellite and the master, back to back
+        double Pe[3], ru_i, rr_i, obs_i, e_i[3], ru_m, rr_m, obs_m, e_m[3];
+        fm_dd_position(F.ratio, Pi, Pj, R, anc, Pe);
+        fm_dd_satellite(F, i, Pe, R, ru_i, rr_i, obs_i, e_i);
+        fm_dd_satellite(F, m, Pe, R, ru_m, rr_m, obs_m, e_m);
         const int ri = i < m ? i : i - 1;
-        double d_ui[3], d_um[3], d_ri[3], d_rm[3];
-        for (int k = 0; k < 3; ++k) {
-            d_ui[k] = F.user_sat_pos[i][k] - Pe[k]; d_um[k] = F.user_sat_pos[m][k] - Pe[k];
-            d_ri[k] = F.ref_sat_pos[i][k] - F.station[k]; d_rm[k] = F.ref_sat_pos[m][k] - F.station[k];
-        }
-        const double r_ui = sqrt(d_dot3_nc(d_ui, d_ui)), r_um = sqrt(d_dot3_nc(d_um, d_um)), r_ri = sqrt(d_dot3_nc(d_ri, d_ri)), r_rm = sqrt(d_dot3_nc(d_rm, d_rm));
-        const double est = (r_ui - r_ri) - (r_um - r_rm);
-        const double obs = (F.user_psr[i] - F.ref_psr[i]) - (F.user_psr[m] - F.ref_psr[m]);
-        const double wgt = fabs(est - obs) > F.threshold ? 0.05 : 1.0;
-        raw[ri] = wgt * (est - obs);
-        for (int c = 0; c < 3; ++c) {
-            const double ei = (d_ui[0] * R[c] + d_ui[1] * R[3 + c] + d_ui[2] * R[6 + c]) / r_ui;
-            const double em = (d_um[0] * R[c] + d_um[1] * R[3 + c] + d_um[2] * R[6 + c]) / r_um;
-            Ji[ri * 3 + c] = (-ei * wgt * F.ratio) - (-em * wgt * F.ratio);
-            Jj[ri * 3 + c] = (-ei * wgt * (1.0 - F.ratio)) - (-em * wgt * (1.0 - F.ratio));
-        }
+        fm_dd_row(F.ratio, F.threshold, ru_i, rr_i, obs_i, e_i, ru_m, rr_m, obs_m, e_m, raw[ri], Ji + ri * 3, Jj + ri * 3);
     }
     __syncthreads();
     if (i < 19) {                     // W embedded top-left, rows >= nw are zero (dd_psr_factor.hpp:126-167)
         double sr = 0, si[3] = {0, 0, 0}, sj[3] = {0, 0, 0};
-        if (i < nw)
-            for (int b = 0; b < nw; ++b) {
-                const double wv = F.weight[i * nw + b];
-                sr += wv * raw[b];
-                for (int k = 0; k < 3; ++k) { si[k] += wv * Ji[b * 3 + k]; sj[k] += wv * Jj[b * 3 + k]; }
-            }
+        if (i < nw) fm_dd_whiten(F.weight, i, nw, raw, Ji, Jj, sr, si, sj);
         out[i] = sr;
         for (int k = 0; k < 3; ++k) { out[19 + i * 3 + k] = si[k]; out[19 + 57 + i * 3 + k] = sj[k]; }
     }
@@ -65,34 +46,15 @@ __global__ void k_eval_doppler(const glio_doppler* __restrict__ Fp, const double
 #pragma clang fp contract(off)
     if (threadIdx.x != 0) return;
     const glio_doppler& F = *Fp;
-    const double OMG = 7.2921151467e-5, CLIGHT = 2.99792458e8;
     const double* Pi = prm; const double* Vi = prm + 3; const double* Pj = prm + 6; const double* Vj = prm + 9;
     const double ddt = prm[12];
     const double* anc = prm + 13;
-    const double* Rf = F.R_ecef_local;
-    double lp[3], lv[3], Pe[3], Ve[3];
-    for (int k = 0; k < 3; ++k) { lp[k] = F.ratio * Pi[k] + (1.0 - F.ratio) * Pj[k] + F.lever_arm[k]; lv[k] = F.ratio * Vi[k] + (1.0 - F.ratio) * Vj[k]; }
-    for (int k = 0; k < 3; ++k) {
-        Pe[k] = Rf[3 * k] * lp[0] + Rf[3 * k + 1] * lp[1] + Rf[3 * k + 2] * lp[2] + anc[k];
-        Ve[k] = Rf[3 * k] * lv[0] + Rf[3 * k + 1] * lv[1] + Rf[3 * k + 2] * lv[2];
-    }
-    const double d[3] = {F.sat_pos[0] - Pe[0], F.sat_pos[1] - Pe[1], F.sat_pos[2] - Pe[2]};
-    const double rho = sqrt(d_dot3_nc(d, d));
-    const double eh[3] = {d[0] / rho, d[1] / rho, d[2] / rho};
-    const double sag = OMG / CLIGHT * (F.sat_vel[0] * Pe[1] + F.sat_pos[0] * Ve[1] - F.sat_vel[1] * Pe[0] - F.sat_pos[1] * Ve[0]);
-    const double av[3] = {F.sat_vel[0] - Ve[0], F.sat_vel[1] - Ve[1], F.sat_vel[2] - Ve[2]};
-    const double ae = d_dot3_nc(av, eh);
-    out[0] = (ae + sag + ddt - F.sv_ddt + F.doppler * F.lamda) / F.var;
-    double gP[3], gV[3];
-    for (int k = 0; k < 3; ++k) { gP[k] = -(av[k] - ae * eh[k]) / rho; gV[k] = -eh[k]; }
-    gP[0] += OMG / CLIGHT * (-F.sat_vel[1]); gP[1] += OMG / CLIGHT * F.sat_vel[0];
-    gV[0] += OMG / CLIGHT * (-F.sat_pos[1]); gV[1] += OMG / CLIGHT * F.sat_pos[0];
-    const double iv = 1.0 / F.var;
+    double res, iv, gPl[3], gVl[3];
+    fm_doppler_row(F.ratio, F.var, F.sat_pos, F.sat_vel, F.lever_arm, F.sv_ddt, F.doppler, F.lamda, F.R_ecef_local, Pi, Vi, Pj, Vj, anc, ddt, res, iv, gPl, gVl);
+    out[0] = res;
     for (int c = 0; c < 3; ++c) {
-        const double gPl = gP[0] * Rf[c] + gP[1] * Rf[3 + c] + gP[2] * Rf[6 + c];
-        const double gVl = gV[0] * Rf[c] + gV[1] * Rf[3 + c] + gV[2] * Rf[6 + c];
-        out[1 + c] = F.ratio * gPl * iv; out[4 + c] = F.ratio * gVl * iv;
-        out[7 + c] = (1.0 - F.ratio) * gPl * iv; out[10 + c] = (1.0 - F.ratio) * gVl * iv;
+        out[1 + c] = F.ratio * gPl[c] * iv; out[4 + c] = F.ratio * gVl[c] * iv;
+        out[7 + c] = (1.0 - F.ratio) * gPl[c] * iv; out[10 + c] = (1.0 - F.ratio) * gVl[c] * iv;
     }
     out[13] = iv;
 }
@@ -107,20 +69,9 @@ __global__ __launch_bounds__(256) void k_eval_marg(const double* __restrict__ J0
     for (int b = tid; b < nb; b += blockDim.x) {
         const double* x = prm + 9 * b; const double* xb0 = x0 + 9 * b;
         if (kind[b] == GLIO_BLK_QUAT) {
-            double q0inv[4], dq[4], L[16];
-            d_qinv(xb0, q0inv);
-            d_qmul(q0inv, x, dq);
-            const double s = dq[0] >= 0 ? 2.0 : -2.0;                 // MarginalizationFactor.cpp:246-252, 276-281
-            d_qnormalize(dq);
-            for (int k = 0; k < 3; ++k) dx[idx[b] + k] = s * dq[1 + k];
-            sg[b] = s;
-            // Qleft(q0inv) rows 1..3
-            const double w = q0inv[0], a = q0inv[1], bb = q0inv[2], c = q0inv[3];
-            L[0] = w; L[1] = -a; L[2] = -bb; L[3] = -c;
-            L[4] = a; L[5] = w; L[6] = -c; L[7] = bb;
-            L[8] = bb; L[9] = c; L[10] = w; L[11] = -a;
-            L[12] = c; L[13] = -bb; L[14] = a; L[15] = w;
-            for (int k = 0; k < 12; ++k) Lq[12 * b + k] = L[4 + k];
+            double L[16];
+            sg[b] = fm_prior_quat(xb0, x, dx + idx[b], L);
+            for (int k = 0; k < 12; ++k) Lq[12 * b + k] = L[4 + k];           // Qleft(q0inv) rows 1..3
         } else {
             const int size = kind[b] == GLIO_BLK_TRANS ? 3 : 9;
             for (int k = 0; k < size; ++k) dx[idx[b] + k] = x[k] - xb0[k];

@@ -18,6 +18,7 @@
 // is that a whole trust-region solve runs without a host round trip.
 #include "k3_device.h"
 #include "batch_device.h"
+#include "factor_math.h"
 
 #define SF_THREADS 256
 
@@ -47,21 +48,6 @@ __device__ __forceinline__ double* chain_slice(const SmallArgs& a, const int whi
 // ------------------------------------------------------------------------------------------------
 // IMU
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void qleft16(const double q[4], double M[16]) {
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    M[0] = w; M[1] = -x; M[2] = -y; M[3] = -z;
-    M[4] = x; M[5] = w; M[6] = -z; M[7] = y;
-    M[8] = y; M[9] = z; M[10] = w; M[11] = -x;
-    M[12] = z; M[13] = -y; M[14] = x; M[15] = w;
-}
-__device__ __forceinline__ void qright16(const double p[4], double M[16]) {
-    const double w = p[0], x = p[1], y = p[2], z = p[3];
-    M[0] = w; M[1] = -x; M[2] = -y; M[3] = -z;
-    M[4] = x; M[5] = w; M[6] = z; M[7] = -y;
-    M[8] = y; M[9] = -z; M[10] = w; M[11] = x;
-    M[12] = z; M[13] = y; M[14] = -x; M[15] = w;
-}
-
 // global column offsets of the six parameter blocks Pi3 Qi4 SBi9 Pj3 Qj4 SBj9
 #define IMU_GC 32
 struct ImuLds { double Jg[15 * IMU_GC], Jl[15 * 30], WJ[15 * 30], S[225], r[15], wr[15]; };
@@ -164,7 +150,7 @@ __device__ __forceinline__ void imu_block(const double gravity, const double* __
             }
         }
         double L[16], Rm[16];
-        qleft16(Qj_inv, L); qright16(cdq, Rm);
+        d_qleft(Qj_inv, L); d_qright(cdq, Rm);
         for (int p = 0; p < 3; ++p)
             for (int c = 0; c < 4; ++c) {
                 double s = 0;
@@ -197,7 +183,7 @@ __device__ __forceinline__ void imu_block(const double gravity, const double* __
     if (role_lane && role_wave == 3) {     // Qj
         double qa[4], L[16];
         d_qmul(cdq_inv, Qi_inv, qa);
-        qleft16(qa, L);
+        d_qleft(qa, L);
         for (int p = 0; p < 3; ++p) for (int c = 0; c < 4; ++c) Jg[(O_R + p) * IMU_GC + 19 + c] = 2 * L[(1 + p) * 4 + c];
     }
     if (role_lane && role_wave == 0) {     // SBj
@@ -367,18 +353,9 @@ __device__ void gnss_block(const SmallArgs& a, const double* __restrict__ x, con
             for (int k = i; k < 19 * 19; k += 32) sWt[fl][k] = F.weight[k];
             if (i == 0) { s_nw[fl] = F.n_sat - 1; s_m[fl] = F.master; }
             if (i < GLIO_DD_MAX_SAT) {
-                double Pe[3], lp[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) lp[k] = f_ratio * Pi[k] + (1.0 - f_ratio) * Pj[k];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) Pe[k] = R[3 * k] * lp[0] + R[3 * k + 1] * lp[1] + R[3 * k + 2] * lp[2] + a.anc[k];
-                double d_u[3], d_r[3];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { d_u[k] = F.user_sat_pos[i][k] - Pe[k]; d_r[k] = F.ref_sat_pos[i][k] - F.station[k]; }
-                const double r_u = sqrt(d_dot3_nc(d_u, d_u)), r_r = sqrt(d_dot3_nc(d_r, d_r));
-                sRu[fl][i] = r_u; sRr[fl][i] = r_r; sObs[fl][i] = F.user_psr[i] - F.ref_psr[i];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) sE[fl][i][c] = (d_u[0] * R[c] + d_u[1] * R[3 + c] + d_u[2] * R[6 + c]) / r_u;
+                double Pe[3];
+                fm_dd_position(f_ratio, Pi, Pj, R, a.anc, Pe);
+                fm_dd_satellite(F, i, Pe, R, sRu[fl][i], sRr[fl][i], sObs[fl][i], sE[fl][i]);
             }
         }
         GN_STAMP(1);
@@ -391,28 +368,15 @@ __device__ void gnss_block(const SmallArgs& a, const double* __restrict__ x, con
             const int ns = s_nw[fl] + 1, m = s_m[fl];
             if (i < ns && i != m) {
                 const int ri = i < m ? i : i - 1;
-                const double est = (sRu[fl][i] - sRr[fl][i]) - (sRu[fl][m] - sRr[fl][m]);
-                const double obs = sObs[fl][i] - sObs[fl][m];
-                const double wgt = fabs(est - obs) > f_thr ? 0.05 : 1.0;     // :99-102
-                raw[fl][ri] = wgt * (est - obs);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const double ei = sE[fl][i][c], em = sE[fl][m][c];
-                    Jri[fl][ri * 3 + c] = (-ei * wgt * f_ratio) - (-em * wgt * f_ratio);
-                    Jrj[fl][ri * 3 + c] = (-ei * wgt * (1.0 - f_ratio)) - (-em * wgt * (1.0 - f_ratio));
-                }
+                fm_dd_row(f_ratio, f_thr, sRu[fl][i], sRr[fl][i], sObs[fl][i], sE[fl][i], sRu[fl][m], sRr[fl][m], sObs[fl][m], sE[fl][m],
+                          raw[fl][ri], Jri[fl] + ri * 3, Jrj[fl] + ri * 3);
             }
         }
         GLIO_WAVE_LDS_SYNC();
         if (fl < nf && i < s_nw[fl]) {        // residual = W r, J = W J  (:151-167)
             const int nw = s_nw[fl];
-            double sr = 0, s6[6] = {0, 0, 0, 0, 0, 0};
-            for (int b = 0; b < nw; ++b) {
-                const double wv = sWt[fl][i * nw + b];
-                sr += wv * raw[fl][b];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) { s6[k] += wv * Jri[fl][b * 3 + k]; s6[3 + k] += wv * Jrj[fl][b * 3 + k]; }
-            }
+            double sr, s6[6];
+            fm_dd_whiten(sWt[fl], i, nw, raw[fl], Jri[fl], Jrj[fl], sr, s6, s6 + 3);
             wE[fl][i * 8 + 6] = sr;
 #pragma unroll
             for (int k = 0; k < 6; ++k) wE[fl][i * 8 + k] = s6[k];
@@ -450,7 +414,6 @@ __device__ void gnss_block(const SmallArgs& a, const double* __restrict__ x, con
     GN_STAMP(3);
     // ---- Doppler rows (dopp_factor.hpp:24-75 + HuberLoss(1.0), Estimator.cpp:2335): all epochs of the pair side by
     //      side, one lane per row; sums are taken epoch by epoch (run = the rows of one epoch, contiguous)
-    const double OMG = 7.2921151467e-5, CLIGHT = 2.99792458e8;
     double carry = 0.0;          // tid 192..247: partial c / h / g of an epoch that straddles a chunk boundary
     int carry_run = -1;
     for (int c0 = gr.dop_begin; c0 < gr.dop_end; c0 += DOP_CHUNK) {
@@ -458,34 +421,11 @@ __device__ void gnss_block(const SmallArgs& a, const double* __restrict__ x, con
         if (tid < cnt) {
             const bool first = c0 == gr.dop_begin;
             const DopRow rw = first ? rowp : load_row(a.dop[c0 + tid]);
-            const struct { double ratio, var, sv_ddt, doppler, lamda; double sat_pos[3], sat_vel[3], lever_arm[3]; int epoch; } F =
-                {rw.ratio, rw.var, rw.sv_ddt, rw.doppler, rw.lamda, {rw.p0, rw.p1, rw.p2}, {rw.v0, rw.v1, rw.v2}, {rw.l0, rw.l1, rw.l2}, rw.epoch};
+            const double sat_pos[3] = {rw.p0, rw.p1, rw.p2}, sat_vel[3] = {rw.v0, rw.v1, rw.v2}, lever_arm[3] = {rw.l0, rw.l1, rw.l2};
             const double Rf[9] = {rw.R0, rw.R1, rw.R2, rw.R3, rw.R4, rw.R5, rw.R6, rw.R7, rw.R8};
-            double lp[3], lv[3], Pe[3], Ve[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                lp[k] = F.ratio * Pi[k] + (1.0 - F.ratio) * Pj[k] + F.lever_arm[k];
-                lv[k] = F.ratio * Vi[k] + (1.0 - F.ratio) * Vj[k];
-            }
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                Pe[k] = Rf[3 * k] * lp[0] + Rf[3 * k + 1] * lp[1] + Rf[3 * k + 2] * lp[2] + a.anc[k];
-                Ve[k] = Rf[3 * k] * lv[0] + Rf[3 * k + 1] * lv[1] + Rf[3 * k + 2] * lv[2];
-            }
-            const double d[3] = {F.sat_pos[0] - Pe[0], F.sat_pos[1] - Pe[1], F.sat_pos[2] - Pe[2]};
-            const double rho = sqrt(d_dot3_nc(d, d));
-            const double eh[3] = {d[0] / rho, d[1] / rho, d[2] / rho};
-            const double sag = OMG / CLIGHT * (F.sat_vel[0] * Pe[1] + F.sat_pos[0] * Ve[1] - F.sat_vel[1] * Pe[0] - F.sat_pos[1] * Ve[0]);
-            const double av[3] = {F.sat_vel[0] - Ve[0], F.sat_vel[1] - Ve[1], F.sat_vel[2] - Ve[2]};
-            const double ae = d_dot3_nc(av, eh);
-            const double ddt = (first && ddt_have) ? ddt_p : x[16 * W + F.epoch];
-            const double res = (ae + sag + ddt - F.sv_ddt + F.doppler * F.lamda) / F.var;
-            double gP[3], gV[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { gP[k] = -(av[k] - ae * eh[k]) / rho; gV[k] = -eh[k]; }
-            gP[0] += OMG / CLIGHT * (-F.sat_vel[1]); gP[1] += OMG / CLIGHT * F.sat_vel[0];
-            gV[0] += OMG / CLIGHT * (-F.sat_pos[1]); gV[1] += OMG / CLIGHT * F.sat_pos[0];
-            const double iv = 1.0 / F.var;
+            const double ddt = (first && ddt_have) ? ddt_p : x[16 * W + rw.epoch];
+            double res, iv, gPl[3], gVl[3];
+            fm_doppler_row(rw.ratio, rw.var, sat_pos, sat_vel, lever_arm, rw.sv_ddt, rw.doppler, rw.lamda, Rf, Pi, Vi, Pj, Vj, a.anc, ddt, res, iv, gPl, gVl);
             // Huber corrector for a scalar residual: sqrt(rho') on J and r, cost rho/2
             const double ar = fabs(res), ah = a.dop_huber;
             const bool inl = ar <= ah;
@@ -496,12 +436,10 @@ __device__ void gnss_block(const SmallArgs& a, const double* __restrict__ x, con
             J[15] = 1.0;
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const double gPl = gP[0] * Rf[c] + gP[1] * Rf[3 + c] + gP[2] * Rf[6 + c];
-                const double gVl = gV[0] * Rf[c] + gV[1] * Rf[3 + c] + gV[2] * Rf[6 + c];
-                J[0 + c] = sw * F.ratio * gPl * iv;
-                J[3 + c] = sw * F.ratio * gVl * iv;
-                J[6 + c] = sw * (1.0 - F.ratio) * gPl * iv;
-                J[9 + c] = sw * (1.0 - F.ratio) * gVl * iv;
+                J[0 + c] = sw * rw.ratio * gPl[c] * iv;
+                J[3 + c] = sw * rw.ratio * gVl[c] * iv;
+                J[6 + c] = sw * (1.0 - rw.ratio) * gPl[c] * iv;
+                J[9 + c] = sw * (1.0 - rw.ratio) * gVl[c] * iv;
             }
             J[12] = sw * iv;
         }
@@ -630,15 +568,9 @@ __device__ __forceinline__ void prior_dx_M(const SmallArgs& a, const double* __r
         } else if (kind == GLIO_BLK_SPEEDBIAS) {
             for (int k = 0; k < 9; ++k) dx[idx + k] = x[7 * W + 9 * s + k] - x0[k];
         } else {
-            double q[4], q0inv[4], dq[4];
+            double q[4], L[16], P[12];
             for (int k = 0; k < 4; ++k) q[k] = x[3 * W + 4 * s + k];
-            d_qinv(x0, q0inv);
-            d_qmul(q0inv, q, dq);
-            const double sg = dq[0] >= 0 ? 2.0 : -2.0;           // :246-252, :276-281
-            d_qnormalize(dq);
-            for (int k = 0; k < 3; ++k) dx[idx + k] = sg * dq[1 + k];
-            double L[16], P[12];
-            qleft16(q0inv, L);
+            const double sg = fm_prior_quat(x0, q, dx + idx, L);
             d_plus_jac(q, P);
             for (int p = 0; p < 3; ++p)
                 for (int c = 0; c < 3; ++c) {
@@ -868,15 +800,6 @@ struct AsmArgs {
     const double* pH; const double* pg; const double* pcost; const int* prior_index;
     double* H0; double* H1; double* g0; double* g1; double* c0; double* c1;
 };
-
-__device__ __forceinline__ int lidar_sym_index(int i, int j) {   // upper-triangle packed index, i<=j<6
-    return i * 6 - (i * (i - 1)) / 2 + (j - i);
-}
-__device__ __forceinline__ int dop_local12(int slot_is_j, int lc) {  // pose-local column -> 12-vector index or -1
-    int k;
-    if (lc < 3) k = lc; else if (lc >= 6 && lc < 9) k = 3 + (lc - 6); else return -1;
-    return slot_is_j ? 6 + k : k;
-}
 
 // Every entry of H sums up to six block entries that live in different arrays.  All addresses come from LDS lookup tables
 // (built once per workgroup from one round of coalesced global reads) and every candidate is loaded UNCONDITIONALLY from a

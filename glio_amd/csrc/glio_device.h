@@ -304,6 +304,44 @@ __device__ __forceinline__ void d_q2R(const double q[4], double R[9]) {
     R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
     R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
 }
+// d_qrot / d_q2R with every product rounded before it is added, whatever the including file's contraction setting: Eigen's q * v
+// (_transformVector) and toRotationMatrix() as the reference's scalar build evaluates them, for the files held to it bit for bit
+__device__ __forceinline__ void d_qrot_nc(const double q[4], const double v[3], double o[3]) {
+#pragma clang fp contract(off)
+    double uv[3], uuv[3];
+    uv[0] = q[2] * v[2] - q[3] * v[1]; uv[1] = q[3] * v[0] - q[1] * v[2]; uv[2] = q[1] * v[1] - q[2] * v[0];
+    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
+    uuv[0] = q[2] * uv[2] - q[3] * uv[1]; uuv[1] = q[3] * uv[0] - q[1] * uv[2]; uuv[2] = q[1] * uv[1] - q[2] * uv[0];
+    o[0] = v[0] + q[0] * uv[0] + uuv[0];
+    o[1] = v[1] + q[0] * uv[1] + uuv[1];
+    o[2] = v[2] + q[0] * uv[2] + uuv[2];
+}
+__device__ __forceinline__ void d_q2R_nc(const double q[4], double R[9]) {
+#pragma clang fp contract(off)
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    const double tx = 2 * x, ty = 2 * y, tz = 2 * z;
+    const double twx = tx * w, twy = ty * w, twz = tz * w;
+    const double txx = tx * x, txy = ty * x, txz = tz * x;
+    const double tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
+}
+// left / right multiplication matrices, 4x4 row-major: q (x) p = Qleft(q) p = Qright(p) q
+__device__ __forceinline__ void d_qleft(const double q[4], double M[16]) {
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    M[0] = w; M[1] = -x; M[2] = -y; M[3] = -z;
+    M[4] = x; M[5] = w; M[6] = -z; M[7] = y;
+    M[8] = y; M[9] = z; M[10] = w; M[11] = -x;
+    M[12] = z; M[13] = -y; M[14] = x; M[15] = w;
+}
+__device__ __forceinline__ void d_qright(const double p[4], double M[16]) {
+    const double w = p[0], x = p[1], y = p[2], z = p[3];
+    M[0] = w; M[1] = -x; M[2] = -y; M[3] = -z;
+    M[4] = x; M[5] = w; M[6] = z; M[7] = -y;
+    M[8] = y; M[9] = -z; M[10] = w; M[11] = x;
+    M[12] = z; M[13] = y; M[14] = -x; M[15] = w;
+}
 // Ceres QuaternionParameterization::Plus
 __device__ __forceinline__ void d_quat_plus(const double q[4], const double d[3], double o[4]) {
     const double nrm = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
@@ -324,6 +362,20 @@ __device__ __forceinline__ void d_plus_jac(const double q[4], double P[12]) {
     P[6] = -q[3]; P[7] = q[0];  P[8] = q[1];
     P[9] = q[2];  P[10] = -q[1]; P[11] = q[0];
 }
+
+// index and integer helpers
+__device__ __forceinline__ int lidar_sym_index(int i, int j) {   // upper-triangle packed index, i<=j<6
+    return i * 6 - (i * (i - 1)) / 2 + (j - i);
+}
+__device__ __forceinline__ int dop_local12(int slot_is_j, int lc) {  // pose-local column -> 12-vector index or -1
+    int k;
+    if (lc < 3) k = lc; else if (lc >= 6 && lc < 9) k = 3 + (lc - 6); else return -1;
+    return slot_is_j ? 6 + k : k;
+}
+// floats as integers of the same order (for atomicMin / atomicMax on coordinates) and back
+__device__ __forceinline__ int f2ord(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
+__device__ __forceinline__ float ord2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
+static inline int next_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 // broadcast lane `l` (compile-time constant) of a double through v_readlane_b32 (SALU path, no LDS)
 // Ordering point for LDS traffic between the lanes of ONE wavefront: earlier ds_writes are complete and visible, later

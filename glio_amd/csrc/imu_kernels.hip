@@ -30,24 +30,6 @@ namespace {
 
 struct ImuNoise2 { double an2, gn2, aw2, gw2; };
 
-__device__ __forceinline__ void q_rotate(const double q[4], const double v[3], double out[3]) {
-    // Eigen's `q * v` (_transformVector): uv = 2 (q.vec x v); v + w uv + q.vec x uv -- no normalisation of q
-    double uv0 = q[2] * v[2] - q[3] * v[1], uv1 = q[3] * v[0] - q[1] * v[2], uv2 = q[1] * v[1] - q[2] * v[0];
-    uv0 += uv0; uv1 += uv1; uv2 += uv2;
-    out[0] = v[0] + q[0] * uv0 + (q[2] * uv2 - q[3] * uv1);
-    out[1] = v[1] + q[0] * uv1 + (q[3] * uv0 - q[1] * uv2);
-    out[2] = v[2] + q[0] * uv2 + (q[1] * uv1 - q[2] * uv0);
-}
-__device__ __forceinline__ void q_to_R(const double q[4], double R[9]) {
-    // Eigen's toRotationMatrix() as it evaluates it, also for a non-unit q (Preintegration.h:134-160; synth.q2R_eigen)
-    const double tx = 2 * q[1], ty = 2 * q[2], tz = 2 * q[3];
-    const double twx = tx * q[0], twy = ty * q[0], twz = tz * q[0];
-    const double txx = tx * q[1], txy = ty * q[1], txz = tz * q[1];
-    const double tyy = ty * q[2], tyz = tz * q[2], tzz = tz * q[3];
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
 __device__ __forceinline__ double sel3(double a, double b, double c, int idx) { return idx == 0 ? a : (idx == 1 ? b : c); }
 // element (i, j) of (s A) * B from row i of A and column j of B, summed as the dense product sums it
 __device__ __forceinline__ double row_col(double s, const double a[3], const double b[3]) { return ((s * a[0]) * b[0] + (s * a[1]) * b[1]) + (s * a[2]) * b[2]; }
@@ -125,7 +107,7 @@ __global__ __launch_bounds__(64) void k_imu_integrate(const int* __restrict__ of
             double a0[3], a1[3], w[3], un0[3], un1[3], rq[4], rp[3], rv[3];
 #pragma unroll
             for (int k = 0; k < 3; ++k) { a0[k] = acc0[k] - ba[k]; a1[k] = acc1[k] - ba[k]; w[k] = 0.5 * (gyr0[k] + gyr1[k]) - bg[k]; }
-            q_rotate(dq, a0, un0);
+            d_qrot_nc(dq, a0, un0);
             {
                 const double bx = w[0] * dt / 2, by = w[1] * dt / 2, bz = w[2] * dt / 2;      // Quaterniond(1, ...): not normalised here (:108)
                 rq[0] = dq[0] * 1.0 - dq[1] * bx - dq[2] * by - dq[3] * bz;
@@ -133,7 +115,7 @@ __global__ __launch_bounds__(64) void k_imu_integrate(const int* __restrict__ of
                 rq[2] = dq[0] * by + dq[2] * 1.0 + dq[3] * bx - dq[1] * bz;
                 rq[3] = dq[0] * bz + dq[3] * 1.0 + dq[1] * by - dq[2] * bx;
             }
-            q_rotate(rq, a1, un1);
+            d_qrot_nc(rq, a1, un1);
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 const double un = 0.5 * (un0[k] + un1[k]);
@@ -142,7 +124,7 @@ __global__ __launch_bounds__(64) void k_imu_integrate(const int* __restrict__ of
             }
             // ---- F and V (Preintegration.h:117-163): lane 3 i + j forms element (i, j) of every 3x3 block (the lanes above 8 repeat lanes 0-8 and write nothing)
             double Rq[9], Rr[9];
-            q_to_R(dq, Rq); q_to_R(rq, Rr);
+            d_q2R_nc(dq, Rq); d_q2R_nc(rq, Rr);
             const double wd0 = w[0] * dt, wd1 = w[1] * dt, wd2 = w[2] * dt;
             const double hdt = 0.5 * dt;
             {

@@ -68,8 +68,6 @@ struct LmFrame { const float4* src; int n, pad_; double q[4], t[3]; };
 #define LM_EMPTY (~0ull)
 #define LM_FIX 1048576.0            /* 2^20: fixed-point scale of the voxel sums */
 
-__device__ __forceinline__ int f2ord(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
-__device__ __forceinline__ float ord2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
 static inline float h_ord2f(int i) { const int u = i >= 0 ? i : i ^ 0x7fffffff; float f; memcpy(&f, &u, 4); return f; }     // the same on the host
 
 __global__ void k_lm_transform(const float4* __restrict__ in, int n, const double q0, const double q1, const double q2, const double q3,
@@ -528,7 +526,6 @@ __global__ __launch_bounds__(LM_RB_THREADS) void k_lm_rebuild_frames(const LmFra
 }
 
 #define LM_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { glio_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); return GLIO_E_HIP; } } while (0)
-static int lm_pow2(int v) { int p = 1; while (p < v) p <<= 1; return p; }
 
 static void lm_free(LocalMap* m) {
     if (!m) return;
@@ -553,7 +550,7 @@ void glio_localmap_destroy(glio_ctx* c) {
 // the buffers of a ring of m->width x m->cap points and of a voxel table for m->max_vox voxels (width, cap, leaf, max_vox set by the caller), cleared on `stream`
 static int lm_alloc(LocalMap* m, hipStream_t stream) {
     const int width = m->width;
-    m->table_cap = lm_pow2(2 * m->max_vox);
+    m->table_cap = next_pow2(2 * m->max_vox);
     m->h_n = new int[width]();
     LM_CHECK(hipMalloc((void**)&m->d_n, (size_t)width * 4));
     LM_CHECK(hipMalloc((void**)&m->d_ring, (size_t)width * m->cap * 16));

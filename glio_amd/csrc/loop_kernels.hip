@@ -69,9 +69,6 @@ struct glio_loop {
     unsigned seq;
 };
 
-__device__ __forceinline__ int lp_f2ord(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
-__device__ __forceinline__ float lp_ord2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
-
 // ---- the target's grid
 __global__ void k_lp_bbox_init(int* bbox) { const int i = threadIdx.x; if (i < 3) bbox[i] = 0x7fffffff; else if (i < 6) bbox[i] = (int)0x80000000; }
 __global__ __launch_bounds__(256) void k_lp_bbox(const float4* __restrict__ pts, const int n, int* bbox) {
@@ -80,7 +77,7 @@ __global__ __launch_bounds__(256) void k_lp_bbox(const float4* __restrict__ pts,
         const float4 p = pts[i];
         const float c[3] = {p.x, p.y, p.z};
 #pragma unroll
-        for (int a = 0; a < 3; ++a) if (c[a] == c[a] && fabsf(c[a]) <= FLT_MAX) { const int o = lp_f2ord(c[a]); mn[a] = min(mn[a], o); mx[a] = max(mx[a], o); }
+        for (int a = 0; a < 3; ++a) if (c[a] == c[a] && fabsf(c[a]) <= FLT_MAX) { const int o = f2ord(c[a]); mn[a] = min(mn[a], o); mx[a] = max(mx[a], o); }
     }
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -96,8 +93,8 @@ __global__ void k_lp_grid_params(const int* __restrict__ bbox, const float cell0
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float lo[3], hi[3];
     for (int a = 0; a < 3; ++a) {
-        lo[a] = bbox[a] == 0x7fffffff ? 0.f : lp_ord2f(bbox[a]);          // (no finite coordinate on this axis: one cell)
-        hi[a] = bbox[3 + a] == (int)0x80000000 ? 0.f : lp_ord2f(bbox[3 + a]);
+        lo[a] = bbox[a] == 0x7fffffff ? 0.f : ord2f(bbox[a]);          // (no finite coordinate on this axis: one cell)
+        hi[a] = bbox[3 + a] == (int)0x80000000 ? 0.f : ord2f(bbox[3 + a]);
     }
     LoopGrid g;
     g.ox = lo[0]; g.oy = lo[1]; g.oz = lo[2];

@@ -2537,12 +2537,6 @@ struct GatherTabs {
     const short* pidx;                // [15 W] prior row of a pose parameter or -1
     double* lid;                      // [W][28] K3 partials of one buffer summed in index order
 };
-__device__ __forceinline__ int kc_lidar_sym_index(int i, int j) { return i * 6 - (i * (i - 1)) / 2 + (j - i); }
-__device__ __forceinline__ int kc_dop_local12(int slot_is_j, int lc) {
-    int k;
-    if (lc < 3) k = lc; else if (lc >= 6 && lc < 9) k = 3 + (lc - 6); else return -1;
-    return slot_is_j ? 6 + k : k;
-}
 // chain-layout index of an entry: r30 < 15 -> D_i[r30][j] (j <= r30), r30 >= 15 -> B_i[r30 - 15][j]
 __device__ __forceinline__ int kc_w(const int r30, const int j) { return r30 < 15 ? r30 * (r30 + 1) / 2 + j : 120 + (r30 - 15) * 15 + j; }
 // One entry of the block-tridiagonal H as the sum of the LiDAR block and the five chain-layout slices of keyframe i, added in
@@ -2553,7 +2547,7 @@ __device__ __forceinline__ double kc_gather_entry(const GatherArgs& G, const Gat
     const double v0 = p[0], v1 = p[GLIO_CS_STRIDE], v2 = p[2 * GLIO_CS_STRIDE], v3 = p[3 * GLIO_CS_STRIDE], v4 = p[4 * GLIO_CS_STRIDE];
     const bool lid = (r30 < 6) & (j < 6);
     double s = 0;
-    s += lid ? T.lid[i * GLIO_LIDAR_ACC + kc_lidar_sym_index(j < r30 ? j : r30, j < r30 ? r30 : j)] : 0.0;
+    s += lid ? T.lid[i * GLIO_LIDAR_ACC + lidar_sym_index(j < r30 ? j : r30, j < r30 ? r30 : j)] : 0.0;
     s += v0; s += v1; s += v2; s += v3; s += v4;
     return s;
 }
@@ -2647,7 +2641,7 @@ struct ChainBuilder {
             if (r == 30) { a.L[(size_t)e * n + e] = scale[ie] * dd[e].h * scale[ie] + mu * diag[ie] * diag[ie]; continue; }
             if (!dd[e].used) continue;
             const int sa = G->gnss_blocks[(size_t)cur * G->gnss_stride + dd[e].group].slot_a;
-            const int k12 = kc_dop_local12(r >= 15, r < 15 ? r : r - 15);
+            const int k12 = dop_local12(r >= 15, r < 15 ? r : r - 15);
             if (k12 < 0) continue;
             const int irow = 15 * sa + r;
             a.L[(size_t)(nd + irow) * n + e] = scale[irow] * dd[e].c[k12] * scale[ie];
@@ -2695,7 +2689,7 @@ __device__ __forceinline__ void chain_step_helper(const ChainArgs& a, const TrAr
             int r30, j;
             if (w < 120) { int r = 0; while ((r + 1) * (r + 2) / 2 <= w) ++r; r30 = r; j = w - r * (r + 1) / 2; }
             else { r30 = 15 + (w - 120) / 15; j = (w - 120) % 15; }
-            lix = (r30 < 6 && j < 6) ? kc_lidar_sym_index(j, r30) : -1;
+            lix = (r30 < 6 && j < 6) ? lidar_sym_index(j, r30) : -1;
             const double* p = G.chain_src + (((size_t)cand * W + i) * GLIO_CS_SOURCES) * GLIO_CS_STRIDE + w;
 #pragma unroll
             for (int sidx = 0; sidx < 5; ++sidx) v[sidx] = p[sidx * GLIO_CS_STRIDE];
@@ -2805,7 +2799,7 @@ __device__ __forceinline__ void chain_step_fat_helper(const ChainArgs& a, const 
             int r30, j;
             if (w < 120) { int r = 0; while ((r + 1) * (r + 2) / 2 <= w) ++r; r30 = r; j = w - r * (r + 1) / 2; }
             else { r30 = 15 + (w - 120) / 15; j = (w - 120) % 15; }
-            lix = (r30 < 6 && j < 6) ? kc_lidar_sym_index(j, r30) : -1;
+            lix = (r30 < 6 && j < 6) ? lidar_sym_index(j, r30) : -1;
             const double* p = G.chain_src + (((size_t)cand * W + i) * GLIO_CS_SOURCES) * GLIO_CS_STRIDE + w;
             const double* pp = G.chain_src + (((size_t)cand * W + (i > 0 ? i - 1 : 0)) * GLIO_CS_SOURCES) * GLIO_CS_STRIDE + w;
 #pragma unroll
@@ -2869,7 +2863,7 @@ __device__ __forceinline__ void chain_step_fat_helper(const ChainArgs& a, const 
                     const bool lidp = rlc < 6;
                     if (rk == 2) {
                         double sacc = 0;
-                        sacc += lidp ? f_lid[2 * GLIO_LIDAR_ACC + kc_lidar_sym_index(lidp ? rlc : 0, lidp ? rlc : 0)] : 0.0;
+                        sacc += lidp ? f_lid[2 * GLIO_LIDAR_ACC + lidar_sym_index(lidp ? rlc : 0, lidp ? rlc : 0)] : 0.0;
                         sacc += dn[0]; sacc += dn[1]; sacc += dn[2]; sacc += dn[3]; sacc += dn[4];
                         hv = sacc;
                     } else hv = (rk == 1 ? f_h : f_hp)[kc_w(rlc, rlc)];
@@ -2921,7 +2915,7 @@ __device__ __forceinline__ void chain_step_fat_helper(const ChainArgs& a, const 
             for (int it = tid; it < (t1e - t0e) * 30; it += KC_THREADS) {
                 const int e = f_elist[t0e + it / 30], q = it % 30;
                 const int lc = q < 15 ? q : q - 15;
-                const int k12 = kc_dop_local12(q >= 15, lc);
+                const int k12 = dop_local12(q >= 15, lc);
                 const int2 sl = f_eps[e];
                 const int used = reinterpret_cast<const int*>(f_dds + e * 15 + 14)[1];
                 const int s1 = q >= 15 ? sl.y : sl.x;
@@ -2951,7 +2945,7 @@ __device__ __forceinline__ void chain_step_fat_helper(const ChainArgs& a, const 
                 }
             }
             if (tid >= 448 && tid < 448 + 15) { const int j = tid - 448; f_blk[30 * KC_RS + j] = f_S[16 + j] * f_G[16 + j]; }
-            // the rows that can carry an epoch coupling are the position and velocity rows (kc_dop_local12): the corrections run over that fixed set -- a row
+            // the rows that can carry an epoch coupling are the position and velocity rows (dop_local12): the corrections run over that fixed set -- a row
             // whose V is zero for every epoch of this keyframe receives a sum of zeros, as in workgroup 0's data-derived set
             if (tid == 0) { const int rows6[6] = {0, 1, 2, 6, 7, 8}; for (int q = 0; q < 6; ++q) f_misc[2 + q] = rows6[q]; f_misc[1] = 6; }
             __syncthreads();
@@ -3095,7 +3089,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
         if (w < 120) { int r = 0; while ((r + 1) * (r + 2) / 2 <= w) ++r; r30 = r; j = w - r * (r + 1) / 2; }
         else { r30 = 15 + (w - 120) / 15; j = (w - 120) % 15; }
         wr30[w] = (short)r30; wj[w] = (short)j;
-        wlx[w] = (short)((r30 < 6 && j < 6) ? kc_lidar_sym_index(j, r30) : -1);      // j <= r30 in the lower triangle
+        wlx[w] = (short)((r30 < 6 && j < 6) ? lidar_sym_index(j, r30) : -1);      // j <= r30 in the lower triangle
     }
     for (int e = tid; e < nd; e += KC_THREADS) eps[e] = a.ep_slots[e];
     for (int i = tid; i <= W; i += KC_THREADS) eoff[i] = a.ep_off[i];
@@ -3192,7 +3186,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
             if (pose) {
                 const bool lidp = lc < 6;
                 double sacc = 0;        // kc_gather_entry's order: LiDAR, the five slices
-                sacc += lidp ? T.lid[sc * GLIO_LIDAR_ACC + kc_lidar_sym_index(lidp ? lc : 0, lidp ? lc : 0)] : 0.0;
+                sacc += lidp ? T.lid[sc * GLIO_LIDAR_ACC + lidar_sym_index(lidp ? lc : 0, lidp ? lc : 0)] : 0.0;
                 sacc += e5[0]; sacc += e5[1]; sacc += e5[2]; sacc += e5[3]; sacc += e5[4];
                 hv = sacc;
                 const double vl = T.lid[sc * GLIO_LIDAR_ACC + 21 + (lidp ? lc : 0)];
@@ -3427,7 +3421,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
             const int itc = in[u] ? it : tid;
             const int e = itc / 30, q = itc - 30 * e;
             ee[u] = e; lc[u] = q < 15 ? q : q - 15;
-            k12[u] = kc_dop_local12(q >= 15, lc[u]);
+            k12[u] = dop_local12(q >= 15, lc[u]);
             sl[u] = eps[e];
             used[u] = reinterpret_cast<const int*>(dds + e * 15 + 14)[1];
             cv[u] = dds[e * 15 + (k12[u] >= 0 ? k12[u] : 0)]; se[u] = sS[np15 + e]; re[u] = rd[e];
