@@ -165,6 +165,13 @@ class Context:
         """0: exact fixed-point voxel sums (default); 1: pcl::VoxelGrid's float sums in concatenation order (bit-identical to the oracle's map)"""
         _check(load().glio_localmap_set_accumulation(self._h, int(mode)))
 
+    def localmap_stats(self):
+        """test hook (glio_debug_localmap_stats): [table_cap, nkeys_seen, table rebuilds from the ring, ordered-output path of the last build (0 empty, 1 bitmap
+        rank, 2 radix sort), its radix passes, its voxels, builds that wiped the whole bitmap, 0] -- host fields, no synchronisation"""
+        out = np.zeros(8, np.int32)
+        _check(load().glio_debug_localmap_stats(self._h, T.iptr(out)))
+        return [int(x) for x in out]
+
     def localmap_build(self):
         n = C.c_int()
         _check(load().glio_localmap_build(self._h, C.byref(n)))

@@ -1969,10 +1969,20 @@ static int enqueue_assoc_window(glio_ctx* c, const double* quats, const double* 
 }
 
 int glio_assoc_finish_pending(glio_ctx* c);
+// A map that was built but holds no point (a local map whose ring holds only empty keyframes: enqueue_build's n == 0) is not "no map": nothing can be
+// associated against it, so slots [slot0, slot0 + ns) keep 0 correspondences and no search is launched.  (w->last_src: set by every build.)
+static bool assoc_map_is_empty(const glio_ctx* c) { return c->map_n == 0 && c->assoc->last_src != nullptr; }
+static int assoc_keep_nothing(glio_ctx* c, int slot0, int ns, int32_t* out_counts) {
+    GLIO_HIP_CHECK(hipMemsetAsync(c->d_count + slot0, 0, (size_t)ns * 4, c->stream));
+    GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (int s = 0; s < ns; ++s) { c->h_count[slot0 + s] = 0; if (out_counts) out_counts[s] = 0; }
+    return GLIO_OK;
+}
 int glio_assoc_run(glio_ctx* c, int slot, const double q[4], const double t[3], int* out_count) {
     AssocWork* w = c->assoc;
     if (!w) return GLIO_E_STATE;
     { const int rp = glio_assoc_finish_pending(c); if (rp != GLIO_OK) return rp; }
+    if (assoc_map_is_empty(c)) return assoc_keep_nothing(c, slot, 1, out_count);
     if (c->map_n <= 0) { glio_set_error("no map set"); return GLIO_E_STATE; }
     const int n = c->h_scan_count[slot];
     if (slot == 0) { for (int k = 0; k < 4; ++k) w->last_pose0[k] = q[k]; for (int k = 0; k < 3; ++k) w->last_pose0[4 + k] = t[k]; w->have_pose0 = 1; }
@@ -2088,6 +2098,7 @@ int glio_assoc_run_window(glio_ctx* c, const double* quats, const double* trans,
     AssocWork* w = c->assoc;
     if (!w) return GLIO_E_STATE;
     { const int rp = glio_assoc_finish_pending(c); if (rp != GLIO_OK) return rp; }      // (counts of an earlier asynchronous call must not overwrite this call's later)
+    if (assoc_map_is_empty(c)) return assoc_keep_nothing(c, 0, c->W, out_counts);
     if (c->map_n <= 0) { glio_set_error("no map set"); return GLIO_E_STATE; }
     for (int k = 0; k < 4; ++k) w->last_pose0[k] = quats[k];
     for (int k = 0; k < 3; ++k) w->last_pose0[4 + k] = trans[k];
@@ -2106,6 +2117,7 @@ int glio_assoc_run_window(glio_ctx* c, const double* quats, const double* trans,
 int glio_assoc_run_window_async(glio_ctx* c, const double* quats, const double* trans) {
     AssocWork* w = c->assoc;
     if (!w) return GLIO_E_STATE;
+    if (assoc_map_is_empty(c)) { const int rp = glio_assoc_finish_pending(c); return rp != GLIO_OK ? rp : assoc_keep_nothing(c, 0, c->W, nullptr); }
     if (c->map_n <= 0) { glio_set_error("no map set"); return GLIO_E_STATE; }
     // an earlier asynchronous call may still be reading the pinned staging block (poses, scan counts) this one rewrites: take it over first
     { const int rp = glio_assoc_finish_pending(c); if (rp != GLIO_OK) return rp; }

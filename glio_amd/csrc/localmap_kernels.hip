@@ -56,6 +56,8 @@ struct LocalMap {
     // concatenated cloud (keyframes oldest first, points in scan order: the order a stable sort by voxel index leaves, and what the oracle's restatement
     // does) -- instead of the exact fixed-point sums.  Same voxels, same output order; the centroids then equal the oracle's bit for bit.
     int accumulation;
+    // what glio_debug_localmap_stats reports (host counters since glio_localmap_config; nothing reads them on the way)
+    int n_table_rebuilds, n_bm_wipes, last_path, last_passes, last_nv;
     int* d_fill; int* d_slot_start; int* d_plist;      // [table_cap], [table_cap], [width * cap]: per-voxel fill counters, list starts, point lists
     // glio_localmap_rebuild_from_frames: the frame table [width] (pinned, its device mirror, the event of its last upload) and the event that orders the context's
     // stream behind the frame copies of the batch association
@@ -157,7 +159,10 @@ __device__ __forceinline__ unsigned lm_hash(unsigned long long k) {
 __device__ __forceinline__ unsigned long long lm_key(int ix, int iy, int iz) {        // absolute voxel coordinates, 21 bits each, biased
     return ((unsigned long long)(unsigned)(ix + (1 << 20)) << 42) | ((unsigned long long)(unsigned)(iy + (1 << 20)) << 21) | (unsigned long long)(unsigned)(iz + (1 << 20));
 }
-// add (sign = +1) or remove (sign = -1) the points of one keyframe
+// add (sign = +1) or remove (sign = -1) the points of one keyframe.
+// A removal may assume that its key is in the table only while every insertion since the last k_lm_clear found a place.  After an overflow (bit 30 of
+// *nkeys) some points of a keyframe were never inserted: their removal meets an empty slot, or walks a table without one, and then leaves every slot
+// as it is -- the table is no longer what the ring holds anyway, and the host reconstructs it from the ring at the next build (lm_voxelize).
 __global__ void k_lm_accumulate(const float4* __restrict__ pts, int n, float inv_leaf, int sign, unsigned long long* keys, long long* sum, int* cnt,
                                 int cap, int* nkeys) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -168,10 +173,10 @@ __global__ void k_lm_accumulate(const float4* __restrict__ pts, int n, float inv
     int probes = 0;
     for (;;) {
         const unsigned long long k = sign > 0 ? atomicCAS(keys + s, LM_EMPTY, key) : keys[s];
-        if (k == LM_EMPTY) { if (sign > 0) atomicAdd(nkeys, 1); break; }       // (a removal always finds its key)
+        if (k == LM_EMPTY) { if (sign < 0) return; atomicAdd(nkeys, 1); break; }      // (a removal that does not find its key touches nothing)
         if (k == key) break;
         s = (s + 1) & (cap - 1);
-        if (++probes >= cap) { atomicOr(nkeys, 0x40000000); return; }          // table full: reported by glio_localmap_build
+        if (++probes >= cap) { if (sign > 0) atomicOr(nkeys, 0x40000000); return; }          // table full: reported by glio_localmap_build
     }
     const long long f[4] = {llrint((double)p.x * LM_FIX), llrint((double)p.y * LM_FIX), llrint((double)p.z * LM_FIX), llrint((double)p.w * LM_FIX)};
 #pragma unroll
@@ -414,8 +419,23 @@ __global__ void k_lm_scatter_idx(const float4* __restrict__ ring, const int* __r
     const int pos = atomicAdd(fill + s, 1);
     plist[slot_start[s] + pos] = age * cap + j;
 }
-// one thread per voxel: its list sorted by concatenated index (insertion sort in the thread's own segment: a voxel holds tens of points), then the
-// float sums in that order and the centroid = sum / (float) count, as pcl::VoxelGrid
+// one thread per voxel: its list sorted by concatenated index in the thread's own segment, then the float sums in that order and the centroid =
+// sum / (float) count, as pcl::VoxelGrid.  A voxel holds tens of points: insertion sort.  One that holds thousands (a wall next to a standing vehicle, seen by
+// every keyframe of the ring) would cost n^2 / 4 dependent round trips in one thread -- seconds -- so long lists take an in-place heapsort; the entries
+// are distinct, so both leave the same list.
+#define LM_LIST_INSERTION_MAX 64
+__device__ __forceinline__ void lm_sift_down(int* __restrict__ L, int root, const int end) {       // max-heap over L[0, end)
+    const int x = L[root];
+    for (;;) {
+        int ch = 2 * root + 1;
+        if (ch >= end) break;
+        if (ch + 1 < end && L[ch + 1] > L[ch]) ++ch;
+        if (L[ch] <= x) break;
+        L[root] = L[ch];
+        root = ch;
+    }
+    L[root] = x;
+}
 __global__ void k_lm_emit_float(const int* __restrict__ vslot_sorted, const int nv, const int* __restrict__ cnt, const int* __restrict__ slot_start,
                                 int* __restrict__ plist, const float4* __restrict__ ring, const int cap, const int width, const int head, float4* __restrict__ out,
                                 unsigned* __restrict__ bm, const unsigned long long* __restrict__ vkey, const unsigned long long bm_bits) {
@@ -424,11 +444,16 @@ __global__ void k_lm_emit_float(const int* __restrict__ vslot_sorted, const int 
     bm_clear_word(bm, vkey, v, bm_bits);
     const int s = vslot_sorted[v], n = cnt[s];
     int* L = plist + slot_start[s];
-    for (int a = 1; a < n; ++a) {
-        const int x = L[a];
-        int b = a - 1;
-        while (b >= 0 && L[b] > x) { L[b + 1] = L[b]; --b; }
-        L[b + 1] = x;
+    if (n <= LM_LIST_INSERTION_MAX) {
+        for (int a = 1; a < n; ++a) {
+            const int x = L[a];
+            int b = a - 1;
+            while (b >= 0 && L[b] > x) { L[b + 1] = L[b]; --b; }
+            L[b + 1] = x;
+        }
+    } else {
+        for (int r = n / 2 - 1; r >= 0; --r) lm_sift_down(L, r, n);
+        for (int e = n - 1; e > 0; --e) { const int top = L[0]; L[0] = L[e]; L[e] = top; lm_sift_down(L, 0, e); }
     }
     float ax = 0.f, ay = 0.f, az = 0.f, aw = 0.f;
     for (int a = 0; a < n; ++a) {
@@ -716,7 +741,9 @@ static bool lm_wait_published(LocalMap* m, int* out8) {
 static int lm_voxelize(LocalMap* m, hipStream_t stream, int* nv_out) {
     const float inv_leaf = 1.0f / m->leaf;
     // (the slots' point counts are on the device already: every push records its own, k_lm_bbox_init)
-    if (m->nkeys_seen > m->table_cap / 2) {               // too many tombstones: rebuild the table from the ring once
+    m->last_path = 0; m->last_passes = 0; m->last_nv = 0;
+    if (m->nkeys_seen > m->table_cap / 2) {               // too many tombstones (or a refused build, below): rebuild the table from the ring once
+        ++m->n_table_rebuilds;
         hipLaunchKernelGGL(k_lm_clear, dim3((m->table_cap + 255) / 256), dim3(256), 0, stream, m->d_keys, m->d_sum, m->d_cnt, m->table_cap, m->d_nkeys);
         for (int k = 0; k < m->count; ++k) {
             const int slot = (m->head + k) % m->width, n = m->h_n[slot];
@@ -727,6 +754,7 @@ static int lm_voxelize(LocalMap* m, hipStream_t stream, int* nv_out) {
     if (m->d_bm && m->bm_dirty) {          // a build that ended between k_lm_list and its emit kernel (an error return) left bits behind
         LM_CHECK(hipMemsetAsync(m->d_bm, 0, (size_t)(BM_MAX_BITS / 32) * 4, stream));
         m->bm_dirty = 0;
+        ++m->n_bm_wipes;
     }
     hipLaunchKernelGGL(k_lm_bbox_union, dim3(1), dim3(64), 0, stream, m->d_slot_bbox, m->d_n, m->width, m->d_bbox, m->d_bm_over, m->d_nvox);
     hipLaunchKernelGGL(k_lm_list, dim3((m->table_cap + 1023) / 1024), dim3(1024), 0, stream, m->d_keys, m->d_cnt, m->table_cap, inv_leaf, m->d_bbox,
@@ -747,9 +775,13 @@ static int lm_voxelize(LocalMap* m, hipStream_t stream, int* nv_out) {
     const bool bm_over = (m->h_pin[1] & 0x20000000) != 0;
     m->h_pin[1] &= ~0x20000000;
     const int nv = m->h_pin[0];
-    if (m->h_pin[1] & 0x40000000) { glio_set_error("local map voxel table overflow (raise max_map_points)"); return GLIO_E_ARG; }
+    // A refused build leaves the ring (clouds, counts, slot boxes) as the pushes made it, and the table to be reconstructed from it: nkeys_seen = table_cap
+    // sends the next build through the rebuild above, which clears the overflow bit with the table.  After an overflow the table holds only part of the
+    // ring, so nothing less will do; it succeeds as soon as the ring fits again and is refused again while it does not.
+    if (m->h_pin[1] & 0x40000000) { m->nkeys_seen = m->table_cap; glio_set_error("local map voxel table overflow (raise max_map_points)"); return GLIO_E_ARG; }
     m->nkeys_seen = m->h_pin[1];
-    if (nv > m->max_vox) { glio_set_error("local map has %d voxels, max_map_points is %d", nv, m->max_vox); return GLIO_E_ARG; }
+    m->last_nv = nv;
+    if (nv > m->max_vox) { m->nkeys_seen = m->table_cap; glio_set_error("local map has %d voxels, max_map_points is %d", nv, m->max_vox); return GLIO_E_ARG; }
     if (nv > 0) {
         // number of key bits from the bounding box, exactly as k_lm_list forms the linear index
         double span = 1.0;
@@ -766,6 +798,7 @@ static int lm_voxelize(LocalMap* m, hipStream_t stream, int* nv_out) {
             hipLaunchKernelGGL(k_bm_scan2, dim3(1), dim3(1024), 0, stream, m->d_bm_blk, nblk);
             hipLaunchKernelGGL(k_bm_rank, dim3((nv + 255) / 256), dim3(256), 0, stream, m->d_vkey, m->d_vslot, nv, m->d_bm, m->d_bm_pre, m->d_bm_blk, m->d_vslot_sorted);
             va = m->d_vslot_sorted;
+            m->last_path = 1;
         } else {
             int bits = 1;
             while (bits < 63 && (double)(1ull << bits) < span) ++bits;
@@ -780,6 +813,7 @@ static int lm_voxelize(LocalMap* m, hipStream_t stream, int* nv_out) {
                 std::swap(ka, kb); std::swap(va, vb);
             }
             keys_final = ka;
+            m->last_path = 2; m->last_passes = passes;
         }
         LM_CHECK(hipGetLastError());
         if (m->accumulation == 1) {
@@ -893,6 +927,17 @@ int glio_localmap_set_accumulation(glio_ctx* c, int mode) {
     LocalMap* m = c->localmap;
     LM_CHECK(hipSetDevice(c->device));
     return lm_set_accumulation(m, mode);
+}
+
+// test hook (undeclared): which branches the local map has taken -- host fields only, no launch, no synchronisation.
+// out[0] table_cap, [1] nkeys_seen, [2] table rebuilds from the ring since glio_localmap_config, [3] ordered-output path of the last build (0 empty,
+// 1 bitmap rank, 2 radix sort), [4] its radix passes, [5] its voxels, [6] builds that wiped the whole bitmap after an interrupted one, [7] 0
+int glio_debug_localmap_stats(glio_ctx* c, int32_t out[8]) {
+    if (!c || !c->localmap || !out) return GLIO_E_ARG;
+    const LocalMap* m = c->localmap;
+    out[0] = m->table_cap; out[1] = m->nkeys_seen; out[2] = m->n_table_rebuilds; out[3] = m->last_path; out[4] = m->last_passes; out[5] = m->last_nv;
+    out[6] = m->n_bm_wipes; out[7] = 0;
+    return GLIO_OK;
 }
 
 int glio_localmap_read(glio_ctx* c, float* out_xyzi, int capacity, int* out_n) {

@@ -73,7 +73,10 @@ int glio_localmap_push_strided(glio_ctx* ctx, const void* cloud_points, int n, i
  * the newest keyframe's cloud crosses PCIe once for both the association and the map */
 int glio_localmap_push_scan(glio_ctx* ctx, int scan_slot, const float lidar_offset[3], const double q[4], const double t[3]);
 /* Voxel grid + hash of the ring's content; *out_points = the map's size.  The call waits ONCE in its middle (the voxel count sizes the rest) and returns with
- * the ordered output and the hash build still running on the context's stream: the searches are ordered behind them, glio_localmap_read waits. */
+ * the ordered output and the hash build still running on the context's stream: the searches are ordered behind them, glio_localmap_read waits.
+ * GLIO_E_ARG when the ring holds more voxels than opts.max_map_points or its voxel table overflows: the ring stays as the pushes made it and the previous map
+ * stays installed; the next build reconstructs the table from the ring and succeeds as soon as the ring fits (the offending keyframe evicted).  A ring that
+ * holds no point gives a map of 0 points: no error, and an association against it keeps 0 correspondences. */
 int glio_localmap_build(glio_ctx* ctx, int* out_points);
 /* centroid arithmetic of the voxel grid: 0 (default) exact fixed-point sums; 1 = float sums in the order of the concatenated cloud, as the oracle's
  * restatement of pcl::VoxelGrid forms them (Estimator.cpp:3618-3631 through PCL): bit-identical to the ORACLE's map (stable order inside a voxel).  PCL itself

@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILES = ["tests/test_hip_parity.py", "tests/test_hip_marg.py", "tests/test_hip_batch_tr.py", "tests/test_hip_streaming.py", "tests/test_golden_ref.py",
-         "tests/test_hip_factor_branches.py"]
+         "tests/test_hip_factor_branches.py", "tests/test_hip_localmap_limits.py"]
 
 
 def test_parity_suites_pass_with_lds_and_allocations_poisoned():
