@@ -314,6 +314,17 @@ class Context:
         self._keep = [prior]          # glio_set_prior copies synchronously; only the latest is held (for the caller's convenience)
         _check(load().glio_set_prior(self._h, C.byref(ps)))
 
+    def set_speed_bias_priors(self, targets):
+        """The speed-bias priors of the window after a loop closure on slots 0 .. len(targets) - 1 (at most W - 1); None or an empty list removes them."""
+        t = np.ascontiguousarray(np.zeros((0, 9)) if targets is None else targets, np.float64).reshape(-1, 9)
+        _check(load().glio_set_speed_bias_priors(self._h, len(t), T.dptr(t) if len(t) else None))
+
+    def marginalize_size(self):
+        """(n, n_blocks) the next marginalize() will return"""
+        n, nb = C.c_int32(), C.c_int32()
+        _check(load().glio_marginalize_size(self._h, C.byref(n), C.byref(nb)))
+        return n.value, nb.value
+
     def set_gnss(self, frame, dd, dop):
         self.set_gnss_marshalled(self.marshal_gnss(frame, dd, dop))
 
@@ -348,9 +359,7 @@ class Context:
 
     def marginalize(self, state):
         """Marginalize slot 0 at `state` (Estimator.cpp:2462-2607): returns the glio_prior fields of the next window."""
-        W = self.W
-        n = 6 * (W - 1) + 9
-        nb = 2 * (W - 1) + 1
+        n, nb = self.marginalize_size()
         out = dict(n=n, lin_jac=np.zeros((n, n)), lin_res=np.zeros(n), blk_slot=np.zeros(nb, np.int32),
                    blk_kind=np.zeros(nb, np.int32), blk_idx=np.zeros(nb, np.int32), blk_x0=np.zeros((nb, 9)))
         cs = state.c()

@@ -169,13 +169,14 @@ static int create_body(int device, const glio_opts* opts, glio_ctx* c) {
     ALLOC(c->d_ddt_blocks, 2 * (size_t)ne * sizeof(DdtBlock));
     GLIO_HIP_CHECK(hipMemsetAsync(c->d_ddt_blocks, 0, 2 * (size_t)ne * sizeof(DdtBlock), c->stream));
     GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
-    const int npmax = 6 * W + 9;
+    const int npmax = glio_prior_np_limit(W), nbmax = glio_prior_nb_limit(W);      // (the layouts after a loop closure included: glio_marg_layout)
     ALLOC(c->d_prior_J0, (size_t)npmax * npmax * 8); ALLOC(c->d_prior_A0, (size_t)npmax * npmax * 8);
-    ALLOC(c->d_prior_r0, npmax * 8); ALLOC(c->d_prior_x0, (size_t)(2 * W + 1) * 9 * 8);
-    ALLOC(c->d_prior_slot, (2 * W + 1) * 4); ALLOC(c->d_prior_kind, (2 * W + 1) * 4); ALLOC(c->d_prior_idx, (2 * W + 1) * 4);
+    ALLOC(c->d_prior_r0, npmax * 8); ALLOC(c->d_prior_x0, (size_t)nbmax * 9 * 8);
+    ALLOC(c->d_prior_slot, nbmax * 4); ALLOC(c->d_prior_kind, nbmax * 4); ALLOC(c->d_prior_idx, nbmax * 4);
+    ALLOC(c->d_sbp_target, (size_t)W * 9 * 8); ALLOC(c->d_marg_T, (size_t)15 * 15 * W * 8);
     ALLOC(c->d_prior_index, 15 * W * 4);
     ALLOC(c->d_prior_H, 2 * (size_t)npmax * npmax * 8); ALLOC(c->d_prior_g, 2 * npmax * 8); ALLOC(c->d_prior_cost, 2 * 8);
-    ALLOC(c->d_prior_work, (size_t)(3 * npmax + 9 * (2 * W + 1)) * 8);
+    ALLOC(c->d_prior_work, (size_t)(3 * npmax + 9 * nbmax) * 8);
     const int nx = glio_x_size(W, c->n_ddt_max);
     {   // [SolverStatus | pad to 512 B | x buffer 0] in one allocation (and one pinned mirror): a solve starts with ONE upload
         unsigned char* up = nullptr;
@@ -269,7 +270,8 @@ void glio_destroy(glio_ctx* c) {
                     c->d_prior_kind, c->d_prior_idx, c->d_prior_index, c->d_prior_H, c->d_prior_g, c->d_prior_cost, c->d_prior_work,
                     /* d_x[0] lives inside d_status' allocation */ c->d_x[1], c->d_H[0], c->d_H[1], c->d_g[0], c->d_g[1], c->d_cost[0], c->d_cost[1], c->d_xout,
                     c->d_lidar_partials, c->d_hdiag[0], c->d_hdiag[1], c->d_chain_tabs, c->d_chain_src, c->d_lidar_blocks, c->d_L, c->d_vec, c->d_status,
-                    c->arrow.d_ep_slots, c->arrow.d_ep_off, c->arrow.d_ep_list, c->arrow.d_Y, c->arrow.d_blk, c->arrow.d_Lblk, c->arrow.d_Sp, c->arrow.d_z, c->arrow.d_flag, c->arrow.d_dbg, c->arrow.d_chain_sum, c->arrow.d_chain_done, c->arrow.d_fat_ep};
+                    c->arrow.d_ep_slots, c->arrow.d_ep_off, c->arrow.d_ep_list, c->arrow.d_Y, c->arrow.d_blk, c->arrow.d_Lblk, c->arrow.d_Sp, c->arrow.d_z, c->arrow.d_flag, c->arrow.d_dbg, c->arrow.d_chain_sum, c->arrow.d_chain_done, c->arrow.d_fat_ep,
+                    c->d_sbp_target, c->d_marg_T};
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->h_status) hipHostFree(c->h_status); /* h_xbuf lives inside it */
     if (c->h_progress) hipHostFree((void*)c->h_progress);
@@ -834,13 +836,17 @@ int glio_set_prior(glio_ctx* c, const glio_prior* p) {
     { const int rp = marg_pending_done(c); if (rp) return rp; }
     GLIO_HIP_CHECK(hipSetDevice(c->device));
     if (!p || p->n <= 0) {
-        c->prior_n = 0; c->prior_nb = 0; c->arrow.prior_ok = 1; c->arrow.prior_chain = 1;
+        c->prior_n = 0; c->prior_nb = 0; c->arrow.prior_ok = 1; c->arrow.prior_chain = 1; c->prior_ext_coupled = 0;
         for (int k = 0; k < 15 * c->W; ++k) c->h_prior_index[k] = -1;
         c->chain_tabs_dirty = 1; c->h_band_clean = 0;
         return GLIO_OK;
     }
     const int np = p->n, nb = p->n_blocks, W = c->W;
-    if (np > 6 * W + 9 || nb > 2 * W + 1) { glio_set_error("prior too large for window"); return GLIO_E_ARG; }
+    if (nb <= 0 || !p->lin_jac || !p->lin_res || !p->blk_slot || !p->blk_kind || !p->blk_idx || !p->blk_x0) { glio_set_error("prior: null table"); return GLIO_E_ARG; }
+    if (np > glio_prior_np_limit(W) || nb > glio_prior_nb_limit(W)) {
+        glio_set_error("prior too large for window: n = %d in %d blocks, a window of %d takes n <= %d in <= %d blocks", np, nb, W, glio_prior_np_limit(W), glio_prior_nb_limit(W));
+        return GLIO_E_ARG;
+    }
     std::vector<int> index(15 * W, -1), colblk(np, -1);
     for (int b = 0; b < nb; ++b) {
         const int s = p->blk_slot[b], k = p->blk_kind[b], idx = p->blk_idx[b];
@@ -871,6 +877,8 @@ int glio_set_prior(glio_ctx* c, const glio_prior* p) {
             }
         c->arrow.prior_chain = chain ? 1 : 0;
         c->prior_device_made = 0;
+        c->prior_ext_coupled = 0;
+        for (int b = 0; b < nb; ++b) if (p->blk_kind[b] == GLIO_BLK_SPEEDBIAS && p->blk_slot[b] >= 2) c->prior_ext_coupled = 1;
     }
     GnssDevExtra* ex = glio_extra(c);
     GLIO_HIP_CHECK(hipMemcpy(c->d_prior_J0, p->lin_jac, (size_t)np * np * 8, hipMemcpyHostToDevice));
@@ -888,6 +896,78 @@ int glio_set_prior(glio_ctx* c, const glio_prior* p) {
     GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
     c->have_factors = 1;
     return GLIO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- speed-bias priors
+// The window after a loop closure (correctPoses ends with marg = false, Estimator.cpp:4785): SpeedBiasPriorFactorAutoDiff on the speed/bias of slots
+// 0 .. W-2 (Estimator.cpp:2164-2176).  Each is evaluated by the workgroup of the IMU edge that leaves its slot (imu_block) and lands in that edge's block:
+// the keyframe's own diagonal, gradient and cost -- the structure of the problem, and with it the solver's path, stays what it is without them.
+static int marg_layout_fits(glio_ctx* c, int sbp_n) {
+    const int keep = c->sbp_n;
+    c->sbp_n = sbp_n;
+    const int ne = glio_marg_layout(c, nullptr), n = 6 * (c->W - 1) + 9 + 9 * ne, nb = 2 * (c->W - 1) + 1 + ne;
+    c->sbp_n = keep;
+    if (n <= glio_prior_np_limit(c->W) && nb <= glio_prior_nb_limit(c->W)) return 1;
+    glio_set_error("the marginalization of this window would keep n = %d columns in %d blocks (%d speed-bias blocks beyond slot 1): a window of %d holds n <= %d "
+                   "in <= %d blocks (PRIOR_MAX_NP = %d bounds the prior's LDS; windows of up to 27 keyframes hold every such layout)", n, nb, ne, c->W,
+                   glio_prior_np_limit(c->W), glio_prior_nb_limit(c->W), PRIOR_MAX_NP);
+    return 0;
+}
+static int sbp_edges_ok(glio_ctx* c) {
+    for (int s = 0; s < c->sbp_n; ++s) {
+        bool have = false;
+        for (int k = 0; k < c->n_imu; ++k) have = have || c->h_imu_slot[k] == s;
+        if (!have) { glio_set_error("the speed-bias prior of slot %d needs the IMU edge (%d, %d): it is evaluated with that edge", s, s, s + 1); return 0; }
+    }
+    return 1;
+}
+int glio_set_speed_bias_priors(glio_ctx* c, int n_slots, const double* target) {
+    if (!c) return GLIO_E_ARG;
+    if (n_slots < 0 || n_slots > c->W - 1) { glio_set_error("speed-bias priors on %d slots: a window of %d takes 0 .. %d (slots 0 .. W-2)", n_slots, c->W, c->W - 1); return GLIO_E_ARG; }
+    if (n_slots > 0 && !target) { glio_set_error("speed-bias priors: null target"); return GLIO_E_ARG; }
+    for (int k = 0; k < 9 * n_slots; ++k) if (!std::isfinite(target[k])) { glio_set_error("speed-bias prior of slot %d: target[%d] is not finite", k / 9, k % 9); return GLIO_E_ARG; }
+    { const int rp = marg_pending_done(c); if (rp) return rp; }
+    if (n_slots > 0 && !marg_layout_fits(c, n_slots)) return GLIO_E_ARG;
+    GLIO_HIP_CHECK(hipSetDevice(c->device));
+    if (n_slots > 0) {
+        memcpy(c->h_sbp_target, target, (size_t)9 * n_slots * 8);
+        GLIO_HIP_CHECK(hipMemcpyAsync(c->d_sbp_target, c->h_sbp_target, (size_t)9 * n_slots * 8, hipMemcpyHostToDevice, c->stream));
+        GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
+    c->sbp_n = n_slots;
+    return GLIO_OK;
+}
+int glio_marginalize_size(glio_ctx* c, int32_t* out_n, int32_t* out_n_blocks) {
+    if (!c) return GLIO_E_ARG;
+    if (c->W < 2) { glio_set_error("marginalization needs a window of at least 2 keyframes"); return GLIO_E_ARG; }
+    { const int rp = marg_pending_done(c); if (rp) return rp; }
+    const int ne = glio_marg_layout(c, nullptr);
+    if (out_n) *out_n = 6 * (c->W - 1) + 9 + 9 * ne;
+    if (out_n_blocks) *out_n_blocks = 2 * (c->W - 1) + 1 + ne;
+    return GLIO_OK;
+}
+// the block tables of the next prior (GetParameterBlocks with addr_shift slot s -> s-1, Estimator.cpp:2584-2600) in the layout of glio_marg_layout
+static void marg_block_tables(const glio_ctx* c, const glio_state* s, int32_t* blk_slot, int32_t* blk_kind, int32_t* blk_idx, double* blk_x0, int* n_out, int* nb_out) {
+    const int W = c->W, ns = 6 * (W - 1) + 9;
+    short extra[GLIO_MAX_WINDOW];
+    const int ne = glio_marg_layout(c, extra);
+    int nb = 0;
+    for (int k = 1; k < W; ++k) {
+        const int kinds = k == 1 ? 3 : 2;
+        for (int kind = 0; kind < kinds; ++kind) {
+            blk_slot[nb] = k - 1; blk_kind[nb] = kind;
+            blk_idx[nb] = k == 1 ? (kind == 0 ? 0 : (kind == 1 ? 3 : 6)) : 15 + 6 * (k - 2) + 3 * kind;
+            const double* src = kind == 0 ? s->trans + 3 * k : (kind == 1 ? s->quat + 4 * k : s->speed_bias + 9 * k);
+            const int gs = kind == 0 ? 3 : (kind == 1 ? 4 : 9);
+            for (int j = 0; j < 9; ++j) blk_x0[9 * nb + j] = j < gs ? src[j] : 0.0;
+            ++nb;
+        }
+    }
+    for (int j = 0; j < ne; ++j, ++nb) {
+        blk_slot[nb] = extra[j] - 1; blk_kind[nb] = GLIO_BLK_SPEEDBIAS; blk_idx[nb] = ns + 9 * j;
+        for (int q = 0; q < 9; ++q) blk_x0[9 * nb + q] = s->speed_bias[9 * extra[j] + q];
+    }
+    *n_out = ns + 9 * ne; *nb_out = nb;
 }
 
 // ---------------------------------------------------------------------------------------------- GNSS
@@ -1038,6 +1118,7 @@ static int check_state(glio_ctx* c, const glio_state* s) {
     if (!c || !s || !s->trans || !s->quat || !s->speed_bias) { glio_set_error("null state"); return GLIO_E_ARG; }
     if (s->n_ddt < 0 || s->n_ddt > c->n_ddt_max || (s->n_ddt > 0 && !s->rcv_ddt)) { glio_set_error("n_ddt %d exceeds max_ddt_epochs %d", s->n_ddt, c->n_ddt_max); return GLIO_E_ARG; }
     if (!c->have_factors) { glio_set_error("no factors set"); return GLIO_E_STATE; }
+    if (c->sbp_n > 0 && !sbp_edges_ok(c)) return GLIO_E_ARG;
     // every Doppler epoch is an unknown of the problem: a state that carries fewer clock-drift slots than the factors
     // reference would leave x[16 W + epoch] unset and drop that epoch's column from H (silently wrong)
     if (c->n_dop > 0 && c->arrow.max_epoch >= s->n_ddt) {
@@ -1260,7 +1341,10 @@ int glio_marginalize(glio_ctx* c, const glio_state* s, double* lin_jac, double* 
     const int W = c->W;
     if (W < 2) { glio_set_error("marginalization needs a window of at least 2 keyframes"); return GLIO_E_ARG; }
     GLIO_HIP_CHECK(hipSetDevice(c->device));
-    const int n_ddt = s->n_ddt, nx = glio_x_size(W, n_ddt), n = 6 * (W - 1) + 9;
+    if (!marg_layout_fits(c, c->sbp_n)) return GLIO_E_ARG;
+    int n = 0, nb = 0;
+    marg_block_tables(c, s, blk_slot, blk_kind, blk_idx, blk_x0, &n, &nb);
+    const int n_ddt = s->n_ddt, nx = glio_x_size(W, n_ddt);
     pack_state(c, s, c->h_xbuf);
     GLIO_HIP_CHECK(hipMemcpyAsync(c->d_x[0], c->h_xbuf, (size_t)nx * 8, hipMemcpyHostToDevice, c->stream));
     lds_poison(c);
@@ -1277,19 +1361,6 @@ int glio_marginalize(glio_ctx* c, const glio_state* s, double* lin_jac, double* 
     GLIO_HIP_CHECK(hipMemcpyAsync(&ok, dok, 4, hipMemcpyDeviceToHost, c->stream));
     GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
     if (!ok) { glio_set_error("marginalization: Schur complement is not positive definite (rank-deficient kept block)"); return GLIO_E_NUMERIC; }
-    // GetParameterBlocks with addr_shift slot s -> s-1 (Estimator.cpp:2584-2600)
-    int nb = 0;
-    for (int k = 1; k < W; ++k) {
-        const int kinds = k == 1 ? 3 : 2;
-        for (int kind = 0; kind < kinds; ++kind) {
-            blk_slot[nb] = k - 1; blk_kind[nb] = kind;
-            blk_idx[nb] = k == 1 ? (kind == 0 ? 0 : (kind == 1 ? 3 : 6)) : 15 + 6 * (k - 2) + 3 * kind;
-            const double* src = kind == 0 ? s->trans + 3 * k : (kind == 1 ? s->quat + 4 * k : s->speed_bias + 9 * k);
-            const int gs = kind == 0 ? 3 : (kind == 1 ? 4 : 9);
-            for (int j = 0; j < 9; ++j) blk_x0[9 * nb + j] = j < gs ? src[j] : 0.0;
-            ++nb;
-        }
-    }
     if (out_n) *out_n = n;
     if (out_n_blocks) *out_n_blocks = nb;
     return GLIO_OK;
@@ -1322,7 +1393,13 @@ int glio_marginalize_keep_async(glio_ctx* c, const glio_state* s) {
     const int W = c->W;
     if (W < 2) { glio_set_error("marginalization needs a window of at least 2 keyframes"); return GLIO_E_ARG; }
     GLIO_HIP_CHECK(hipSetDevice(c->device));
-    const int n_ddt = s->n_ddt, nx = glio_x_size(W, n_ddt), n = 6 * (W - 1) + 9, nb = 2 * (W - 1) + 1;
+    if (!marg_layout_fits(c, c->sbp_n)) return GLIO_E_ARG;
+    const int n_ddt = s->n_ddt, nx = glio_x_size(W, n_ddt), nbmax = glio_prior_nb_limit(W);
+    std::vector<int> slot(nbmax), kind(nbmax), idx(nbmax);
+    std::vector<double> x0((size_t)nbmax * 9, 0.0);
+    int n = 0, nb = 0;
+    marg_block_tables(c, s, slot.data(), kind.data(), idx.data(), x0.data(), &n, &nb);
+    const int n_extra = nb - (2 * (W - 1) + 1);
     pack_state(c, s, c->h_xbuf);
     GLIO_HIP_CHECK(hipMemcpyAsync(c->d_x[0], c->h_xbuf, (size_t)nx * 8, hipMemcpyHostToDevice, c->stream));
     lds_poison(c);
@@ -1336,20 +1413,11 @@ int glio_marginalize_keep_async(glio_ctx* c, const glio_state* s) {
     // the new prior's block tables (slots already shifted s -> s-1, Estimator.cpp:2584-2600).  Everything below is enqueued behind the
     // marginalization kernels without waiting for them: the tables go through the pinned arena, the "positive definite" flag is
     // read back last, ONE synchronisation ends the call (two synchronisations and eight pageable copies cost ~0.1 ms of the 0.33 ms)
-    std::vector<int> slot(nb), kind(nb), idx(nb), index(15 * W, -1), colblk(n, -1);
-    std::vector<double> x0((size_t)nb * 9, 0.0);
-    int b = 0;
-    for (int k = 1; k < W; ++k) {
-        const int kinds = k == 1 ? 3 : 2;
-        for (int kd = 0; kd < kinds; ++kd, ++b) {
-            slot[b] = k - 1; kind[b] = kd;
-            idx[b] = k == 1 ? (kd == 0 ? 0 : (kd == 1 ? 3 : 6)) : 15 + 6 * (k - 2) + 3 * kd;
-            const double* src = kd == 0 ? s->trans + 3 * k : (kd == 1 ? s->quat + 4 * k : s->speed_bias + 9 * k);
-            const int gs = kd == 0 ? 3 : (kd == 1 ? 4 : 9), ls = kd == 2 ? 9 : 3;
-            for (int j = 0; j < gs; ++j) x0[9 * b + j] = src[j];
-            const int off = 15 * (k - 1) + (kd == 0 ? 0 : (kd == 1 ? 3 : 6));
-            for (int j = 0; j < ls; ++j) { index[off + j] = idx[b] + j; colblk[idx[b] + j] = b; }
-        }
+    std::vector<int> index(15 * W, -1), colblk(n, -1);
+    for (int b = 0; b < nb; ++b) {
+        const int kd = kind[b], ls = kd == GLIO_BLK_SPEEDBIAS ? 9 : 3;
+        const int off = 15 * slot[b] + (kd == GLIO_BLK_TRANS ? 0 : (kd == GLIO_BLK_QUAT ? 3 : 6));
+        for (int j = 0; j < ls; ++j) { index[off + j] = idx[b] + j; colblk[idx[b] + j] = b; }
     }
     GnssDevExtra* ex = glio_extra(c);
     { const int rs = stage_reserve(c, (size_t)nb * 9 * 8 + 3 * (size_t)nb * 4 + 15 * (size_t)W * 4 + (size_t)n * 4 + 8 * 64 + 64); if (rs != GLIO_OK) return rs; }
@@ -1367,8 +1435,12 @@ int glio_marginalize_keep_async(glio_ctx* c, const glio_state* s) {
     c->prior_n = n; c->prior_nb = nb;
     for (int k = 0; k < 15 * W; ++k) c->h_prior_index[k] = index[k];
     c->chain_tabs_dirty = 1; c->h_band_clean = 0;
-    c->arrow.prior_ok = 1; c->arrow.prior_chain = chain;
+    // (several speed-bias blocks: block diagonal by keyframe like the rest, so the keyframe chain takes them as they are -- its slices and its prior index
+    //  are per (keyframe, local column); the arrow factorisation, which keeps one speed-bias chain, does not)
+    c->arrow.prior_ok = n_extra == 0; c->arrow.prior_chain = chain;
     c->prior_device_made = 1;
+    if (n_extra == 0) c->prior_ext_coupled = 0;
+    c->sbp_n = 0;          // the reference's marg = true (Estimator.cpp:2517): the next window carries them in its prior
     glio_launch_gram(c, n);
     int* h_ok = reinterpret_cast<int*>(c->h_stage + ((c->h_stage_used + 63) & ~(size_t)63));      // (pinned; reserved above)
     GLIO_HIP_CHECK(hipMemcpyAsync(h_ok, dok, 4, hipMemcpyDeviceToHost, c->stream));
@@ -1381,7 +1453,7 @@ static int marginalize_keep_wait(glio_ctx* c) {
     extra_of(c)->marg_h_ok = nullptr;
     GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
     if (!*h_ok) {          // the installed tables describe a factor that does not exist: the context is left WITHOUT a prior
-        c->prior_n = 0; c->prior_nb = 0; c->arrow.prior_ok = 1; c->arrow.prior_chain = 1;
+        c->prior_n = 0; c->prior_nb = 0; c->arrow.prior_ok = 1; c->arrow.prior_chain = 1; c->prior_ext_coupled = 0;
         for (int k = 0; k < 15 * W; ++k) c->h_prior_index[k] = -1;
         c->chain_tabs_dirty = 1; c->h_band_clean = 0;
         glio_set_error("marginalization: Schur complement is not positive definite (the context now has no prior)");
@@ -1516,7 +1588,7 @@ int glio_time_kernel(glio_ctx* c, int which, int reps, float* ms_out) {
                 GLIO_HIP_CHECK(hipMemcpyAsync(c->d_status, c->h_status, sizeof st, hipMemcpyHostToDevice, c->stream));
                 glio_launch_tr_step(c, n_ddt);
             } else if (which == GLIO_KERNEL_MARGINALIZE) {
-                if (c->W < 2) return GLIO_E_ARG;
+                if (c->W < 2 || !marg_layout_fits(c, c->sbp_n)) return GLIO_E_ARG;
                 double *dJ, *dr; int* dok;
                 glio_launch_lidar_linearize(c, 0, 0, 1); glio_launch_lidar_reduce(c, 0);
                 glio_launch_small_factors(c, 0, 0, n_ddt, 1);

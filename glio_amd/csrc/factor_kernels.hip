@@ -40,6 +40,8 @@ struct SmallArgs {
     double* pH; double* pg; double* pcost; double* pwork;
     // chain-layout contributions (glio_device.h, GLIO_CS_*): written beside the pair blocks, consumed by k_chain_step
     double* chain_src; const short* chain_tabs; int pair_H;
+    // speed-bias priors of the window after a loop closure (glio_set_speed_bias_priors): slots 0 .. sbp_n - 1, targets [sbp_n][9]
+    int sbp_n; const double* sbp_target;
 };
 __device__ __forceinline__ double* chain_slice(const SmallArgs& a, const int which, const int slot, const int source) {
     return a.chain_src + (((size_t)which * a.W + slot) * GLIO_CS_SOURCES + source) * GLIO_CS_STRIDE;
@@ -56,7 +58,8 @@ struct ImuLds { double Jg[15 * IMU_GC], Jl[15 * 30], WJ[15 * 30], S[225], r[15],
 __device__ __forceinline__ void imu_block(const double gravity, const double* __restrict__ pPi, const double* __restrict__ pQi,
                           const double* __restrict__ pSBi, const double* __restrict__ pPj, const double* __restrict__ pQj,
                           const double* __restrict__ pSBj, const ImuEdgeDev& e, PairBlock* out, double* eval_out, const int marg, unsigned char* pool,
-                          double* cs_a = nullptr, double* cs_b = nullptr, long long* stamp_dbg = nullptr, const bool pair_H = true) {
+                          double* cs_a = nullptr, double* cs_b = nullptr, long long* stamp_dbg = nullptr, const bool pair_H = true,
+                          const double* __restrict__ sbp = nullptr) {
 #ifdef GLIO_DEV_STAMPS
 #define IMU_STAMP(k) do { if (stamp_dbg && threadIdx.x == 0) stamp_dbg[k] = wall_clock64(); } while (0)
 #else
@@ -244,6 +247,8 @@ __device__ __forceinline__ void imu_block(const double gravity, const double* __
         double s = 0;
 #pragma unroll
         for (int k = 0; k < 15; ++k) s += WJ[k * 30 + p] * WJ[k * 30 + c];
+        // the speed-bias prior of slot_i (sbp: its target) rides on this edge's block: it touches SBi's own diagonal, gradient and the cost only
+        if (sbp && p == c && p >= 6 && p < 15) { double rk; const double w = fm_speed_bias_prior(p - 6, pSBi[p - 6], sbp[p - 6], rk); s += w * w; }
         if (pair_H) out->H[idx] = s;
         if (cs_a) {          // the same entry in chain layout: aa -> D of slot_i, ba -> B of slot_i, bb -> D of slot_j
             if (p < 15) { if (c <= p) cs_a[p * (p + 1) / 2 + c] = s; }
@@ -254,12 +259,19 @@ __device__ __forceinline__ void imu_block(const double gravity, const double* __
     if (tid < 30) {
         double s = 0;
         for (int k = 0; k < 15; ++k) s += WJ[k * 30 + tid] * wr[k];
+        if (sbp && tid >= 6 && tid < 15) { double rk; const double w = fm_speed_bias_prior(tid - 6, pSBi[tid - 6], sbp[tid - 6], rk); s += w * rk; }
         out->g[tid] = s;
     }
     if (tid == 32) {
         double s = 0;
         for (int k = 0; k < 15; ++k) s += wr[k] * wr[k];
-        out->cost = 0.5 * s;
+        double cst = 0.5 * s;
+        if (sbp) {
+            double s2 = 0;
+            for (int k = 0; k < 9; ++k) { double rk; fm_speed_bias_prior(k, pSBi[k], sbp[k], rk); s2 += rk * rk; }
+            cst += 0.5 * s2;
+        }
+        out->cost = cst;
         out->slot_a = i; out->slot_b = j;
     }
     IMU_STAMP(5);
@@ -583,8 +595,7 @@ __device__ __forceinline__ void prior_dx_M(const SmallArgs& a, const double* __r
     __syncthreads();
 }
 
-#define PRIOR_MAX_NP (6 * GLIO_MAX_WINDOW + 9)
-#define PRIOR_MAX_NB (2 * GLIO_MAX_WINDOW + 1)
+// (PRIOR_MAX_NP, PRIOR_MAX_NB: glio_device.h -- glio_set_prior and the marginalization hold every layout to them)
 
 // workgroup 0 of the prior: r = r0 + J0 dx (one wavefront per row, coalesced), v = J0^T r, g = M^T v, cost
 struct PriorLds { double dx[PRIOR_MAX_NP], r[PRIOR_MAX_NP], v[PRIOR_MAX_NP], Mb[9 * PRIOR_MAX_NB]; };
@@ -702,7 +713,9 @@ __device__ void small_factors_body(const SmallArgs& a, const int role) {
         const int si = a.imu[b].slot_i, sj = si + 1, W = a.W;
         imu_block(a.gravity, x + 3 * si, x + 3 * W + 4 * si, x + 7 * W + 9 * si, x + 3 * sj, x + 3 * W + 4 * sj, x + 7 * W + 9 * sj,
                   a.imu[b], a.imu_blocks + (size_t)which * a.W + b, nullptr, a.marg, pool,
-                  a.marg ? nullptr : chain_slice(a, which, si, 0), a.marg ? nullptr : chain_slice(a, which, sj, 1), (b == 0 && a.dbg) ? a.dbg + 190 : nullptr, a.pair_H != 0);
+                  a.marg ? nullptr : chain_slice(a, which, si, 0), a.marg ? nullptr : chain_slice(a, which, sj, 1), (b == 0 && a.dbg) ? a.dbg + 190 : nullptr, a.pair_H != 0,
+                  // (the marginalization re-creates the priors at the state it is taken at, Estimator.cpp:2483-2518: zero residual, the diagonal is k_marg_assemble's)
+                  (!a.marg && si < a.sbp_n) ? a.sbp_target + 9 * si : nullptr);
         return;
     }
     b -= a.n_imu;
@@ -1110,6 +1123,7 @@ static int fill_small_args(glio_ctx* c, int use_status_cand, int which, int n_dd
     a.pslot = c->d_prior_slot; a.pkind = c->d_prior_kind; a.pidx = c->d_prior_idx; a.pcolblk = ex->d_prior_colblk;
     a.pH = c->d_prior_H; a.pg = c->d_prior_g; a.pcost = c->d_prior_cost; a.pwork = c->d_prior_work;
     a.chain_src = c->d_chain_src; a.chain_tabs = c->d_chain_tabs; a.pair_H = (marg || !c->d_chain_src) ? 1 : c->want_pair_H;
+    a.sbp_n = c->sbp_n; a.sbp_target = c->d_sbp_target;
     return c->n_imu + c->n_groups + (a.has_prior ? 1 + PRIOR_H_BLOCKS : 0);
 }
 void glio_launch_small_factors(glio_ctx* c, int use_status_cand, int which, int n_ddt, int marg) {

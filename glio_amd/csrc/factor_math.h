@@ -115,6 +115,16 @@ __device__ __forceinline__ double fm_prior_quat(const double q0[4], const double
 }
 
 // ------------------------------------------------------------------------------------------------
+// SpeedBiasPriorFactorAutoDiff (PriorFactor.h:10-40), entry k of the 9: r = w (x - target) with w = 8 for the two horizontal velocities and 1 for the
+// rest, no loss; returns w (the factor's only Jacobian entry in row k).  H_kk += w w, g_k += w r, cost += r r / 2.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double fm_speed_bias_prior(const int k, const double x, const double target, double& r) {
+    const double w = k < 2 ? 8.0 : 1.0;
+    r = w * (x - target);
+    return w;
+}
+
+// ------------------------------------------------------------------------------------------------
 // The quaternion part shared by delta_q_factor_auto (LidarKeyframeFactor.h:283-303) and LidarPoseFactorBatchRelativeAutoDiff (LidarPoseFactor.h:55-97):
 // p = dq^-1 (x) qi^-1 (x) qj with Eigen's inverse() = conjugate / |q|^2, as the reference's Jets differentiate it
 // ------------------------------------------------------------------------------------------------

@@ -250,7 +250,30 @@ struct glio_ctx {
     int prior_device_made;                    // the installed prior is glio_marginalize_keep's own product: block diagonal with EXACT zeros (a caller's prior is only held to a tolerance)
     int n_cu;                                 // compute units of THIS context's device (the helper workgroups of k_chain_step need 2 (1 + W) of them)
     struct FeatWork* features;                // raw-scan feature extraction (feature_kernels.hip), created by glio_features_config
+    // ---- speed-bias priors of the windows after a loop closure (glio_set_speed_bias_priors, Estimator.cpp:2164-2176)
+    int sbp_n;                                // slots 0 .. sbp_n - 1 carry one (0: none)
+    double* d_sbp_target;                     // [W][9] their targets
+    double h_sbp_target[9 * GLIO_MAX_WINDOW];
+    int prior_ext_coupled;                    // the installed prior descends from a CALLER's prior with speed-bias blocks beyond slot 1: those may couple to the
+                                              // poses of their keyframe, so the marginalization takes the general root (the per-block root wants them alone)
+    double* d_marg_T;                         // [15 (W - 1)][15] T = Arm Amm^+ of the marginalization (the kept part has up to 15 (W - 1) columns)
 };
+
+// Limits of a prior: the LDS arrays of the prior's workgroups (factor_kernels.hip, PriorLds) are sized by them.  A standard prior has 6 W + 9 columns in
+// 2 W + 1 blocks; the layouts of the windows after a loop closure (speed-bias blocks of several keyframes) up to 15 (W - 1) in 3 (W - 1): W <= 27.
+#define PRIOR_MAX_NP (6 * GLIO_MAX_WINDOW + 9)
+#define PRIOR_MAX_NB (2 * GLIO_MAX_WINDOW + 1)
+static inline int glio_prior_np_limit(int W) { const int a = 6 * W + 9, b = 15 * (W - 1), m = a > b ? a : b; return m < PRIOR_MAX_NP ? m : PRIOR_MAX_NP; }
+static inline int glio_prior_nb_limit(int W) { const int a = 2 * W + 1, b = 3 * (W - 1), m = a > b ? a : b; return m < PRIOR_MAX_NB ? m : PRIOR_MAX_NB; }
+// Kept layout of the next marginalization: the poses of slots 1 .. W-1 and the speed/bias of slot 1 as ever ([T1 Q1 SB1 | T2 Q2 | ...], 6 (W - 1) + 9
+// columns), then the speed/bias of every slot s >= 2 that carries a speed-bias prior or has a speed-bias block in the installed prior, ascending, 9
+// columns each.  Returns their number; extra_slot[j] = s.
+static inline int glio_marg_layout(const glio_ctx* c, short* extra_slot) {
+    int ne = 0;
+    for (int s = 2; s < c->W; ++s)
+        if (s < c->sbp_n || (c->prior_n > 0 && c->h_prior_index[15 * s + 6] >= 0)) { if (extra_slot) extra_slot[ne] = (short)s; ++ne; }
+    return ne;
+}
 
 static inline int glio_x_size(int W, int n_ddt) { return 16 * W + n_ddt; }
 static inline size_t glio_partials_stride(const glio_ctx* c) { return (size_t)c->W * GLIO_K3_MAX_BLOCKS_PER_KF * GLIO_LIDAR_ACC; }

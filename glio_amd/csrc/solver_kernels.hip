@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "glio_device.h"
+#include "factor_math.h"
 
 #define TR_THREADS 512
 #define TR_WAVES (TR_THREADS / 64)
@@ -4130,8 +4131,21 @@ __device__ __forceinline__ int jacobi16_wave(double* buf, const int lane) {
     return cur;
 }
 
+// Kept order of the marginalization: [T1 Q1 SB1 (15) | T2 Q2 (6) | T3 Q3 (6) | ... up to ns = 6 (W - 1) + 9 | speed/bias of later keyframes (9 each)
+// up to n].  The tail exists only in the windows after a loop closure (glio_marg_layout); n == ns otherwise, and every expression below is then the
+// one the standard layout always had.
+__device__ __forceinline__ bool marg_kept_layout_ok(const int n, const int ns) { return ns >= 15 && (ns - 15) % 6 == 0 && n >= ns && (n - ns) % 9 == 0; }
+__device__ __forceinline__ int marg_kept_block(const int i, const int ns) { return i < 15 ? 0 : (i < ns ? 1 + (i - 15) / 6 : 1 + (ns - 15) / 6 + (i - ns) / 9); }
+__device__ __forceinline__ int marg_kept_blocks(const int n, const int ns) { return 1 + (ns - 15) / 6 + (n - ns) / 9; }
+__device__ __forceinline__ void marg_kept_span(const int bI, const int ns, int& o, int& bs) {
+    const int n6 = (ns - 15) / 6;
+    if (bI == 0) { o = 0; bs = 15; }
+    else if (bI <= n6) { o = 15 + 6 * (bI - 1); bs = 6; }
+    else { o = ns + 9 * (bI - 1 - n6); bs = 9; }
+}
+
 // A: pos x pos row-major (pos = 15 + n), b: pos.  Out: J0 (n x n row-major), r0 (n), *ok.
-__global__ __launch_bounds__(TR_THREADS) void k_marg_schur(const double* A, const double* b, const int n, double* Lwork, double* Twork,
+__global__ __launch_bounds__(TR_THREADS) void k_marg_schur(const double* A, const double* b, const int n, const int ns, double* Lwork, double* Twork,
                                                            double* J0, double* r0, int* ok) {
     __builtin_amdgcn_s_setprio(3);
     const int tid = threadIdx.x, m = 15, pos = m + n;
@@ -4245,14 +4259,14 @@ __global__ __launch_bounds__(TR_THREADS) void k_marg_schur(const double* A, cons
     // roots of the blocks: one wavefront per block, the same register steps and the same null-pivot rule as the dense routine,
     // instead of eight 16-column panels over the whole 123 x 123 matrix.  Any non-zero outside the blocks: dense routine.
     int& bdiag = flag[3];
-    if (tid == 0) bdiag = (n >= 15 && (n - 15) % 6 == 0) ? 1 : 0;
+    if (tid == 0) bdiag = marg_kept_layout_ok(n, ns) ? 1 : 0;
     __syncthreads();
     {
         int viol = 0;
         for (int e = tid; e < n * n; e += TR_THREADS) {
             const int i = e / n, j = e - n * i;
             if (j >= i) continue;
-            const int bi = i < 15 ? 0 : 1 + (i - 15) / 6, bj = j < 15 ? 0 : 1 + (j - 15) / 6;
+            const int bi = marg_kept_block(i, ns), bj = marg_kept_block(j, ns);
             if (bi != bj && Lwork[e] != 0.0) viol = 1;
         }
         if (viol) bdiag = 0;
@@ -4260,11 +4274,12 @@ __global__ __launch_bounds__(TR_THREADS) void k_marg_schur(const double* A, cons
     __syncthreads();
     bool good;
     if (bdiag) {
-        const int lane = tid & 63, wv = tid >> 6, nblk = 1 + (n - 15) / 6;
+        const int lane = tid & 63, wv = tid >> 6, nblk = marg_kept_blocks(n, ns);
         if (tid == 0) *flag = 0;
         __syncthreads();
         for (int bI = wv; bI < nblk; bI += TR_WAVES) {
-            const int o = bI == 0 ? 0 : 15 + 6 * (bI - 1), bs = bI == 0 ? 15 : 6;
+            int o, bs;
+            marg_kept_span(bI, ns, o, bs);
             const bool isrow = lane < bs, isrhs = lane == TR_NB;
             double a[TR_NB];
 #pragma unroll
@@ -4391,7 +4406,7 @@ __global__ __launch_bounds__(64) void k_marg_inv(const double* A, const int n, d
     for (int t = lane; t < 225; t += 64) Ainv_out[t] = sAinv[t];
 }
 // blockIdx.x = i < n: row i of S (lower part) ; blockIdx.x = n: the carried right-hand side.  128 threads.
-__global__ __launch_bounds__(128) void k_marg_rows(const double* __restrict__ A, const double* __restrict__ b, const int n, const double* __restrict__ Ainv,
+__global__ __launch_bounds__(128) void k_marg_rows(const double* __restrict__ A, const double* __restrict__ b, const int n, const int ns, const double* __restrict__ Ainv,
                                                    double* __restrict__ Twork, double* __restrict__ Lwork, double* __restrict__ tol, int* __restrict__ viol) {
     __builtin_amdgcn_s_setprio(3);
     __shared__ double sA[225], sT[15], sArow[15];
@@ -4414,7 +4429,7 @@ __global__ __launch_bounds__(128) void k_marg_rows(const double* __restrict__ A,
             Lwork[(size_t)i * n + j] = sacc;
             if (j == i) tol[i] = fmax(1e-8, 1e-9 * sacc);
             else {
-                const int bi = i < 15 ? 0 : 1 + (i - 15) / 6, bj = j < 15 ? 0 : 1 + (j - 15) / 6;
+                const int bi = marg_kept_block(i, ns), bj = marg_kept_block(j, ns);
                 if (bi != bj && sacc != 0.0) bad = 1;
             }
         }
@@ -4437,10 +4452,10 @@ __global__ __launch_bounds__(128) void k_marg_rows(const double* __restrict__ A,
 // panels (~100 KB: a request that, beside the batch association's searches, waits for a compute unit to EMPTY).  Should the pattern check of k_marg_rows
 // have found a non-zero after all, it reports failure (ok = 0: the caller is left without a prior, as for a rank-deficient complement).
 template <bool SMALL>
-__global__ __launch_bounds__(TR_THREADS) void k_marg_root(const int n, double* Lwork, const double* __restrict__ tol, const int* __restrict__ viol, double* J0, double* r0, int* ok) {
+__global__ __launch_bounds__(TR_THREADS) void k_marg_root(const int n, const int ns, double* Lwork, const double* __restrict__ tol, const int* __restrict__ viol, double* J0, double* r0, int* ok) {
     __builtin_amdgcn_s_setprio(3);      // (a short latency-bound kernel that shares its compute unit with the batch association's wide launches: its wavefronts issue first)
     const int tid = threadIdx.x;
-    __shared__ double s_tol[SMALL ? 6 * GLIO_MAX_WINDOW + 16 : 2];
+    __shared__ double s_tol[SMALL ? 6 * GLIO_MAX_WINDOW + 16 : 2];      // (n <= PRIOR_MAX_NP = 6 GLIO_MAX_WINDOW + 9 for every layout: glio_launch_marginalize)
     __shared__ int s_flag[8];
     double* Bp = SMALL ? nullptr : reinterpret_cast<double*>(tr_lds);
     double* part = SMALL ? nullptr : Bp + TR_NB * bp_stride(n);
@@ -4449,15 +4464,16 @@ __global__ __launch_bounds__(TR_THREADS) void k_marg_root(const int n, double* L
     double* red = SMALL ? nullptr : ylds + n + (n & 1);
     int* flag = SMALL ? s_flag : reinterpret_cast<int*>(red + 32);
     for (int j = tid; j < n; j += TR_THREADS) ylds[j] = tol[j];
-    const bool bdiag = (n >= 15 && (n - 15) % 6 == 0) && *viol == 0;
+    const bool bdiag = marg_kept_layout_ok(n, ns) && *viol == 0;
     if (tid == 0) *flag = 0;
     __syncthreads();
     if (SMALL && !bdiag) { if (tid == 0) *ok = 0; return; }
     bool good;
     if (bdiag) {
-        const int lane = tid & 63, wv = tid >> 6, nblk = 1 + (n - 15) / 6;
+        const int lane = tid & 63, wv = tid >> 6, nblk = marg_kept_blocks(n, ns);
         for (int bI = wv; bI < nblk; bI += TR_WAVES) {
-            const int o = bI == 0 ? 0 : 15 + 6 * (bI - 1), bs = bI == 0 ? 15 : 6;
+            int o, bs;
+            marg_kept_span(bI, ns, o, bs);
             const bool isrow = lane < bs, isrhs = lane == TR_NB;
             double a[TR_NB];
 #pragma unroll
@@ -4505,20 +4521,26 @@ __global__ __launch_bounds__(TR_THREADS) void k_marg_root(const int n, double* L
     if (tid == 0) *ok = good ? 1 : 0;
 }
 
-// marginalization ordering: [T0 Q0 SB0 | T1 Q1 SB1 | T2 Q2 | ... ] -> index in the window state vector (15 per slot)
-__device__ __forceinline__ int marg_state_index(int mi) { return mi < 30 ? mi : 15 * (2 + (mi - 30) / 6) + (mi - 30) % 6; }
-
+// marginalization ordering: [T0 Q0 SB0 | T1 Q1 SB1 | T2 Q2 | ... | SB of extra_slot[0] | SB of extra_slot[1] | ...] -> index in the window state
+// vector (15 per slot); the standard part ends at pos_std = 15 + 6 (W - 1) + 9
 struct MargAsmArgs {
     int W, pos, np, has_prior, imu_edge0;
+    int pos_std, sbp_n;                      // sbp_n: slots 0 .. sbp_n - 1 carry a speed-bias prior (diag(w^2) on their block, nothing in b: they are re-created at this state)
+    short extra_slot[GLIO_MAX_WINDOW];
     const double* lidar_blocks; const PairBlock* imu_blocks; const double* pH; const double* pg; const int* prior_index;
     double* A; double* b;
 };
+__device__ __forceinline__ int marg_state_index(const MargAsmArgs& a, const int mi) {
+    if (mi < 30) return mi;
+    if (mi < a.pos_std) return 15 * (2 + (mi - 30) / 6) + (mi - 30) % 6;
+    return 15 * a.extra_slot[(mi - a.pos_std) / 9] + 6 + (mi - a.pos_std) % 9;
+}
 __global__ __launch_bounds__(256) void k_marg_assemble(const MargAsmArgs a) {
     __builtin_amdgcn_s_setprio(3);      // (a short latency-bound kernel that shares its compute unit with the batch association's wide launches: its wavefronts issue first)
     const int pos = a.pos;
     for (int r = blockIdx.x; r <= pos; r += gridDim.x) {
         for (int c = threadIdx.x; c < pos; c += blockDim.x) {
-            const int sc_i = marg_state_index(c), sc = sc_i / 15, lc = sc_i % 15;
+            const int sc_i = marg_state_index(a, c), sc = sc_i / 15, lc = sc_i % 15;
             double sacc = 0;
             if (r == pos) {          // b
                 if (lc < 6) sacc += a.lidar_blocks[sc * GLIO_LIDAR_ACC + 21 + lc];
@@ -4527,21 +4549,25 @@ __global__ __launch_bounds__(256) void k_marg_assemble(const MargAsmArgs a) {
                 a.b[c] = sacc;
                 continue;
             }
-            const int sr_i = marg_state_index(r), sr = sr_i / 15, lr = sr_i % 15;
+            const int sr_i = marg_state_index(a, r), sr = sr_i / 15, lr = sr_i % 15;
             if (sr == sc && lr < 6 && lc < 6) {
                 const int i = lr <= lc ? lr : lc, j = lr <= lc ? lc : lr;
                 sacc += a.lidar_blocks[sr * GLIO_LIDAR_ACC + i * 6 - (i * (i - 1)) / 2 + (j - i)];
             }
             if (a.imu_edge0 >= 0 && sr <= 1 && sc <= 1) sacc += a.imu_blocks[a.imu_edge0].H[(15 * sr + lr) * GLIO_PAIR_DIM + 15 * sc + lc];
             if (a.has_prior) { const int pi = a.prior_index[sr_i], pj = a.prior_index[sc_i]; if (pi >= 0 && pj >= 0) sacc += a.pH[(size_t)pi * a.np + pj]; }
+            if (sr_i == sc_i && sc < a.sbp_n && lc >= 6) { double r0_; const double w = fm_speed_bias_prior(lc - 6, 0.0, 0.0, r0_); sacc += w * w; }
             a.A[(size_t)r * pos + c] = sacc;
         }
     }
 }
 
 int glio_launch_marginalize(glio_ctx* c, int imu_edge0, double** J0_dev, double** r0_dev, int** ok_dev) {
-    const int W = c->W, n = 6 * (W - 1) + 9, pos = 15 + n;
+    const int W = c->W, ns = 6 * (W - 1) + 9;
     MargAsmArgs a;
+    const int ne = glio_marg_layout(c, a.extra_slot);          // (n <= glio_prior_np_limit(W): checked by the callers)
+    const int n = ns + 9 * ne, pos = 15 + n;
+    a.pos_std = 15 + ns; a.sbp_n = c->sbp_n;
     a.W = W; a.pos = pos; a.np = c->prior_n; a.has_prior = c->prior_n > 0; a.imu_edge0 = imu_edge0;
     a.lidar_blocks = c->d_lidar_blocks; a.imu_blocks = c->d_imu_blocks; a.pH = c->d_prior_H; a.pg = c->d_prior_g; a.prior_index = c->d_prior_index;
     a.A = c->d_H[0]; a.b = c->d_g[0];
@@ -4550,7 +4576,7 @@ int glio_launch_marginalize(glio_ctx* c, int imu_edge0, double** J0_dev, double*
     c->h_band_clean = 0;
     hipLaunchKernelGGL(k_marg_assemble, dim3(pos + 1), dim3(256), 0, c->stream, a);
     int* d_ok = reinterpret_cast<int*>(c->d_vec + 9 * (size_t)c->n_max);
-    double* Twork = c->d_vec;                    // n x 15 <= 10 n_max doubles? n*15 <= 15W*... checked by the caller
+    double* Twork = c->d_marg_T;                 // n x 15, n <= 15 (W - 1)
     static const bool split = !(getenv("GLIO_MARG_SPLIT") && atoi(getenv("GLIO_MARG_SPLIT")) == 0);      // (0: the one-workgroup form, for A/B and tests)
     // scratch of the split form: Ainv (225), the tolerances (n), the pattern flag -- behind the (n + 1) x n work matrix in d_L, when it fits there
     const size_t lwork = (size_t)(n + 1) * n + 2, need = 226 + (size_t)n + 2 + 1100, have = (size_t)(c->n_max + 1) * c->n_max;
@@ -4561,13 +4587,14 @@ int glio_launch_marginalize(glio_ctx* c, int imu_edge0, double** J0_dev, double*
         double* jbuf = tol + n + 2;                  // the Jacobi fallback's working matrices (global memory: k_marg_inv)
         // the complement is block diagonal by construction when the old prior is (or there is none): the root then needs no panels
         // (a prior the CALLER handed over is block diagonal only to glio_set_prior's tolerance: its complement takes the general root)
-        const bool bd = (c->prior_n == 0 || (c->arrow.prior_chain && c->prior_device_made)) && n >= 15 && (n - 15) % 6 == 0;
+        // (a speed-bias block beyond slot 1 that a CALLER's prior brought in may couple to its keyframe's pose: the per-block root wants it alone)
+        const bool bd = (c->prior_n == 0 || (c->arrow.prior_chain && c->prior_device_made && !c->prior_ext_coupled)) && n >= 15 && (ns - 15) % 6 == 0;
         hipLaunchKernelGGL(k_marg_inv, dim3(1), dim3(64), 0, c->stream, c->d_H[0], n, Ainv, viol, jbuf);
-        hipLaunchKernelGGL(k_marg_rows, dim3(n + 1), dim3(128), 0, c->stream, c->d_H[0], c->d_g[0], n, Ainv, Twork, c->d_L, tol, viol);
-        if (bd) hipLaunchKernelGGL(k_marg_root<true>, dim3(1), dim3(TR_THREADS), 0, c->stream, n, c->d_L, tol, viol, c->d_H[1], c->d_g[1], d_ok);
-        else hipLaunchKernelGGL(k_marg_root<false>, dim3(1), dim3(TR_THREADS), glio_tr_step_lds_bytes(n), c->stream, n, c->d_L, tol, viol, c->d_H[1], c->d_g[1], d_ok);
+        hipLaunchKernelGGL(k_marg_rows, dim3(n + 1), dim3(128), 0, c->stream, c->d_H[0], c->d_g[0], n, ns, Ainv, Twork, c->d_L, tol, viol);
+        if (bd) hipLaunchKernelGGL(k_marg_root<true>, dim3(1), dim3(TR_THREADS), 0, c->stream, n, ns, c->d_L, tol, viol, c->d_H[1], c->d_g[1], d_ok);
+        else hipLaunchKernelGGL(k_marg_root<false>, dim3(1), dim3(TR_THREADS), glio_tr_step_lds_bytes(n), c->stream, n, ns, c->d_L, tol, viol, c->d_H[1], c->d_g[1], d_ok);
     } else
-    hipLaunchKernelGGL(k_marg_schur, dim3(1), dim3(TR_THREADS), glio_tr_step_lds_bytes(n), c->stream, c->d_H[0], c->d_g[0], n, c->d_L, Twork,
+    hipLaunchKernelGGL(k_marg_schur, dim3(1), dim3(TR_THREADS), glio_tr_step_lds_bytes(n), c->stream, c->d_H[0], c->d_g[0], n, ns, c->d_L, Twork,
                        c->d_H[1], c->d_g[1], d_ok);
     *J0_dev = c->d_H[1]; *r0_dev = c->d_g[1]; *ok_dev = d_ok;
     return 0;

@@ -295,8 +295,16 @@ public:
         check(glio_set_gnss(ctx_, frame, (int)dd.size(), dd.data(), (int)dop.size(), dop.data()), "glio_set_gnss");
     }
 
+    // correctPoses' `marg = false` (Estimator.cpp:4785; the loop thread then deletes last_marginalization_info, :5264-5267 -- that half is the caller's
+    // setMarginalizationPrior(nullptr)).  Armed, the next solve() installs SpeedBiasPriorFactorAutoDiff on tmpSpeedBias[0 .. W-2] as they stand when it is
+    // called (:2164-2176), and the marginalization after it re-creates them at the solved state, keeps the blocks of slots 1 .. W-2 in the new prior and
+    // disarms (`marg = true`, :2517).  Opt-in: loopClosed() alone does not arm.
+    void armSpeedBiasPriors() { sbp_armed_ = true; }
+    bool speedBiasPriorsArmed() const { return sbp_armed_; }
+
     // Estimator.cpp:2424-2433 ceres::Solve + :2439-2457 quaternion sign unification
     glio_summary solve(std::vector<double>* rcv_ddt = nullptr) {
+        if (sbp_armed_) check(glio_set_speed_bias_priors(ctx_, W_ - 1, tmpSpeedBias.data()), "glio_set_speed_bias_priors");
         glio_state st;
         st.trans = tmpTrans.data(); st.quat = tmpQuat.data(); st.speed_bias = tmpSpeedBias.data();
         st.rcv_ddt = rcv_ddt && !rcv_ddt->empty() ? rcv_ddt->data() : nullptr;
@@ -311,7 +319,8 @@ public:
     // Estimator.cpp:2462-2607: marginalize the oldest keyframe at the solved state (call after solve()); the
     // result is what setMarginalizationPrior() takes for the next window.
     MarginalizationPrior marginalize() {
-        const int n = 6 * (W_ - 1) + 9, nb = 2 * (W_ - 1) + 1;
+        int32_t n = 0, nb = 0;          // (6 (W-1) + 9 and 2 (W-1) + 1 but in the windows after a loop closure)
+        check(glio_marginalize_size(ctx_, &n, &nb), "glio_marginalize_size");
         MarginalizationPrior m;
         m.linearized_jacobians.assign((size_t)n * n, 0.0); m.linearized_residuals.assign(n, 0.0); m.keep_block_data.assign((size_t)nb * 9, 0.0);
         m.keep_block_slot.assign(nb, 0); m.keep_block_kind.assign(nb, 0); m.keep_block_idx.assign(nb, 0);
@@ -321,6 +330,7 @@ public:
         check(glio_marginalize(ctx_, &st, m.linearized_jacobians.data(), m.linearized_residuals.data(), m.keep_block_slot.data(),
                                m.keep_block_kind.data(), m.keep_block_idx.data(), m.keep_block_data.data(), &on, &onb), "glio_marginalize");
         m.n = on;
+        disarmSpeedBiasPriors(true);        // (glio_marginalize leaves the context as it found it)
         return m;
     }
 
@@ -375,6 +385,7 @@ public:
         st.trans = tmpTrans.data(); st.quat = tmpQuat.data(); st.speed_bias = tmpSpeedBias.data();
         st.rcv_ddt = rcv_ddt && !rcv_ddt->empty() ? rcv_ddt->data() : nullptr; st.n_ddt = rcv_ddt ? (int)rcv_ddt->size() : 0;
         check(glio_marginalize_keep(ctx_, &st), "glio_marginalize_keep");
+        disarmSpeedBiasPriors(false);       // (glio_marginalize_keep removed them from the context)
     }
     // the same in two halves: the marginalization enqueued (the host is free: setScanAhead() of the next keyframe's cloud, say), then waited for
     void marginalizeAndKeepAsync(std::vector<double>* rcv_ddt = nullptr) {
@@ -382,6 +393,7 @@ public:
         st.trans = tmpTrans.data(); st.quat = tmpQuat.data(); st.speed_bias = tmpSpeedBias.data();
         st.rcv_ddt = rcv_ddt && !rcv_ddt->empty() ? rcv_ddt->data() : nullptr; st.n_ddt = rcv_ddt ? (int)rcv_ddt->size() : 0;
         check(glio_marginalize_keep_async(ctx_, &st), "glio_marginalize_keep_async");
+        disarmSpeedBiasPriors(false);
     }
     void marginalizeFinish() { check(glio_marginalize_keep_finish(ctx_), "glio_marginalize_keep_finish"); }
     // the NEXT keyframe's cloud, sent during this keyframe's call (after the solve): the next call's slideWindow() finds it in slot W - 1 and makes no setScan()
@@ -502,6 +514,12 @@ private:
     int W_;
     std::vector<int32_t> sel_;
     int map_points_ = 0;
+    bool sbp_armed_ = false;      // armSpeedBiasPriors
+    void disarmSpeedBiasPriors(bool clear_context) {
+        if (!sbp_armed_) return;
+        if (clear_context) check(glio_set_speed_bias_priors(ctx_, 0, nullptr), "glio_set_speed_bias_priors");
+        sbp_armed_ = false;
+    }
     bool ref_map_ = false; int ref_width_ = 0, ref_recent_ = 0, ref_latest_ = -1; double ref_qbl_[4] = {1, 0, 0, 0}, ref_tbl_[3] = {0, 0, 0};      // enableReferenceMapSchedule
     glio_ctx* ctx_ = nullptr;
 };

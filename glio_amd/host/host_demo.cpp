@@ -1,5 +1,7 @@
 // host_demo.cpp -- the C++ call sequence of optimizeSlidingWindowWithLandMark() on the HIP backend, fed from
 // a flat binary window file written by tests (glio_amd/host/window_io.py).  Prints the solved state as text.
+// `host_demo window.bin arm`: the window is the first after a loop closure (armSpeedBiasPriors before the solve; the marginalization carries the
+// speed-bias blocks), and the resident half arms again, so that marginalizeAndKeep installs the wider prior and the last solve runs on it.
 // Build: g++ -std=c++14 -O2 host_demo.cpp -I../../include -L../lib -lglio_hip -Wl,-rpath,'$ORIGIN/../lib'
 #include <cstdio>
 #include <cstdlib>
@@ -10,7 +12,8 @@
 template <typename T> static void rd(FILE* f, T* p, size_t n) { if (fread(p, sizeof(T), n, f) != n) { fprintf(stderr, "short read\n"); exit(2); } }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { fprintf(stderr, "usage: host_demo window.bin\n"); return 2; }
+    if (argc < 2) { fprintf(stderr, "usage: host_demo window.bin [arm]\n"); return 2; }
+    const bool arm = argc > 2 && strcmp(argv[2], "arm") == 0;
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror("open"); return 2; }
     glio_opts opts;
@@ -38,6 +41,7 @@ int main(int argc, char** argv) {
         fclose(f);
         std::vector<double> Ps = be.tmpTrans, Qs = be.tmpQuat, Vs(3 * W), psb = be.tmpSpeedBias;
         for (int i = 0; i < W; ++i) for (int k = 0; k < 3; ++k) Vs[3 * i + k] = be.tmpSpeedBias[9 * i + k];
+        if (arm) be.armSpeedBiasPriors();
         const glio_summary sum = be.solve();
         be.writeBack(Ps.data(), Qs.data(), Vs.data(), psb.data());
         printf("kept %ld iterations %d termination %d cost %.17g -> %.17g\n", kept, sum.iterations, sum.termination, sum.initial_cost, sum.final_cost);
@@ -54,9 +58,19 @@ int main(int argc, char** argv) {
         const std::vector<int32_t> counts = be.findCorrespondingSurfFeaturesWindow();
         long kept_window = 0;
         for (int32_t c : counts) kept_window += c;
+        if (arm) {
+            be.armSpeedBiasPriors();
+            const glio_summary again = be.solve();
+            printf("rearmed %d %.17g\n", again.iterations, again.final_cost);
+        }
         be.marginalizeAndKeep();
         const glio_summary sum2 = be.solve();
         printf("resident %ld %d %.17g\n", kept_window, sum2.iterations, sum2.final_cost);
+        if (arm) {
+            int32_t n = 0, nb = 0;
+            glio::check(glio_marginalize_size(be.ctx(), &n, &nb), "glio_marginalize_size");
+            printf("next %d %d %d\n", (int)n, (int)nb, be.speedBiasPriorsArmed() ? 1 : 0);
+        }
     } catch (const std::exception& e) {
         fprintf(stderr, "error: %s\n", e.what());
         return 1;

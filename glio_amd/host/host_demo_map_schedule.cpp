@@ -3,9 +3,12 @@
 // backend asks glio::localMapPlan and either rebuilds the ring from the resident keyframes at the poses pose_info_keyframe holds in THAT call
 // (glio_localmap_rebuild_from_frames) or pushes the newest scan.  Input: a flat file written by window_io.write_map_schedule; output: a flat file of the map
 // after every call (action, frame list, points) -- tests/test_hip_localmap_rebuild.py holds it against the Python driver and the oracle.
+// A fifth argument `arm` makes the loop closure also arm the speed-bias priors of the next window (armSpeedBiasPriors, correctPoses' marg = false); the
+// fourth word of every call's record then says whether they are armed (this program solves nothing: host_demo's `arm` runs such a window).
 // Build: g++ -std=c++14 -O2 host_demo_map_schedule.cpp -I../../include -L../lib -lglio_hip -Wl,-rpath,'$ORIGIN/../lib'
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "glio_backend.hpp"
@@ -15,10 +18,11 @@ template <typename T> static void rd(FILE* f, T* p, size_t n) { if (n && fread(p
 template <typename T> static void wr(FILE* f, const T* p, size_t n) { if (n && fwrite(p, sizeof(T), n, f) != n) { fprintf(stderr, "short write\n"); exit(2); } }
 
 int main(int argc, char** argv) {
-    if (argc < 3) { fprintf(stderr, "usage: host_demo_map_schedule schedule.bin maps.bin [device]\n"); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: host_demo_map_schedule schedule.bin maps.bin [device [arm]]\n"); return 2; }
     FILE* f = fopen(argv[1], "rb");
     if (!f) { perror("open"); return 2; }
     const int device = argc > 3 ? atoi(argv[3]) : 0;
+    const bool arm = argc > 4 && std::string(argv[4]) == "arm";
     glio_opts opts;
     rd(f, &opts, 1);
     int32_t hdr[8];            // n_keyframes, points per scan (capacity), local-map width, keyframe after whose call the loop closes (-1: never), accumulation, 0 0 0
@@ -52,9 +56,9 @@ int main(int argc, char** argv) {
             glio::check(glio_localmap_read(be.ctx(), nullptr, 0, &n), "glio_localmap_read");
             map.assign((size_t)(n > 0 ? n : 1) * 4, 0.f);
             glio::check(glio_localmap_read(be.ctx(), map.data(), n, &n), "glio_localmap_read");
-            const int32_t rec[4] = {action, be.mapPoints(), n, 0};
+            if (j == loop_after) { be.loopClosed(); if (arm) be.armSpeedBiasPriors(); }
+            const int32_t rec[4] = {action, be.mapPoints(), n, be.speedBiasPriorsArmed() ? 1 : 0};
             wr(out, rec, 4); wr(out, map.data(), (size_t)n * 4);
-            if (j == loop_after) be.loopClosed();
         }
     } catch (const std::exception& e) {
         fprintf(stderr, "error: %s\n", e.what());

@@ -38,8 +38,9 @@ def write_window(path, win):
             f.write(np.ascontiguousarray(win.scans[s], np.float32).tobytes())
 
 
-def run_demo(path):
-    out = subprocess.run([build_demo(), path], capture_output=True, text=True, check=True).stdout.splitlines()
+def run_demo(path, arm=False):
+    """arm: the window is the first after a loop closure (host_demo's `arm`): info gains "rearmed" and "next" """
+    out = subprocess.run([build_demo(), path] + (["arm"] if arm else []), capture_output=True, text=True, check=True).stdout.splitlines()
     head = out[0].split()
     info = dict(kept=int(head[1]), iterations=int(head[3]), termination=int(head[5]), initial_cost=float(head[7]), final_cost=float(head[9]))
     rows = np.array([[float(x) for x in ln.split()[2:]] for ln in out[1:] if ln.startswith("kf ")])
@@ -50,6 +51,12 @@ def run_demo(path):
         if ln.startswith("resident "):
             p = ln.split()
             info["resident"] = dict(kept=int(p[1]), iterations=int(p[2]), final_cost=float(p[3]))
+        if ln.startswith("rearmed "):
+            p = ln.split()
+            info["rearmed"] = dict(iterations=int(p[1]), final_cost=float(p[2]))
+        if ln.startswith("next "):
+            p = ln.split()
+            info["next"] = dict(n=int(p[1]), n_blocks=int(p[2]), armed=int(p[3]))
     return info, rows[:, :3], rows[:, 3:]
 
 
@@ -360,14 +367,14 @@ def write_map_schedule(path, opts, cap, width, leaf, scans, pose_info, loop_afte
         f.write(pose_info.tobytes())
 
 
-def run_demo_map_schedule(path, out_path, device=0, env=None):
-    """-> per keyframe call (action, map size reported, map [n][4])"""
-    r = subprocess.run([build_demo_map_schedule(), path, out_path, str(device)], capture_output=True, text=True, env=env)
+def run_demo_map_schedule(path, out_path, device=0, env=None, arm=False):
+    """-> per keyframe call (action, map size reported, map [n][4]); arm: the loop closure arms the speed-bias priors, and every row gains whether they are armed"""
+    r = subprocess.run([build_demo_map_schedule(), path, out_path, str(device)] + (["arm"] if arm else []), capture_output=True, text=True, env=env)
     if r.returncode != 0:
         raise RuntimeError("host_demo_map_schedule failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
     raw = open(out_path, "rb").read()
     out, o = [], 0
     while o < len(raw):
-        action, reported, n, _ = np.frombuffer(raw, np.int32, 4, o); o += 16
-        out.append((int(action), int(reported), np.frombuffer(raw, np.float32, 4 * int(n), o).reshape(-1, 4).copy())); o += 16 * int(n)
+        action, reported, n, armed = np.frombuffer(raw, np.int32, 4, o); o += 16
+        out.append((int(action), int(reported), np.frombuffer(raw, np.float32, 4 * int(n), o).reshape(-1, 4).copy()) + ((int(armed),) if arm else ())); o += 16 * int(n)
     return out

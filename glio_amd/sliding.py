@@ -99,6 +99,14 @@ class SlidingWindowDriver:
         self.state = None
         self.first = 0                   # index (into the keyframe stream) of slot 0
         self.history = []
+        self.speed_bias_priors_armed = False
+
+    def arm_speed_bias_priors(self):
+        """correctPoses' `marg = false` (Estimator.cpp:4785; dropping the prior as the loop thread does, :5264-5267, is the caller's `self.prior = None`): the
+        next step() installs SpeedBiasPriorFactorAutoDiff on the speed/bias of slots 0 .. W-2 as they stand before its solve (:2164-2176); its marginalization
+        re-creates them at the solved state, keeps the blocks of slots 1 .. W-2 in the new prior and disarms (`marg = true`, :2517).  Opt-in.
+        glio::SlidingWindowBackend::armSpeedBiasPriors is the C++ twin."""
+        self.speed_bias_priors_armed = True
 
     def start(self, init_states):
         """init_states: WindowState of the first full window."""
@@ -123,9 +131,14 @@ class SlidingWindowDriver:
         set_imu_edges(be, preints)
         be.set_prior(self.prior)
         be.set_gnss(None, [], [])
+        if self.speed_bias_priors_armed:
+            be.set_speed_bias_priors(self.state.speed_bias[:W - 1])
         sol, summ = be.solve(self.state)
         unify_quaternions(sol)
         self.prior = be.marginalize(sol)
+        if self.speed_bias_priors_armed:             # (marginalize leaves the backend as it found it)
+            be.set_speed_bias_priors(None)
+            self.speed_bias_priors_armed = False
         self.state = sol
         self.history.append((self.first, sol.copy(), summ, counts))
         return sol, summ, counts
@@ -217,6 +230,12 @@ class ResidentSlidingWindow:
         self.state = None
         self.first = 0
         self._have_scans = False
+        self.speed_bias_priors_armed = False
+
+    def arm_speed_bias_priors(self):
+        """As SlidingWindowDriver.arm_speed_bias_priors; here marginalize_keep removes the factors from the context itself.  (The loop thread's deletion of the
+        prior is the caller's ctx.set_prior(None).)"""
+        self.speed_bias_priors_armed = True
 
     def start(self, init_states):
         self.state = init_states.copy()
@@ -242,9 +261,12 @@ class ResidentSlidingWindow:
         else:
             counts = ctx.associate_window(np.array([p[0] for p in poses]), np.array([p[1] for p in poses]))
         set_imu_edges(ctx, preints)
+        if self.speed_bias_priors_armed:
+            ctx.set_speed_bias_priors(self.state.speed_bias[:W - 1])
         sol, summ = ctx.solve(self.state)
         unify_quaternions(sol)
         ctx.marginalize_keep(sol)
+        self.speed_bias_priors_armed = False
         self.state = sol
         return sol, summ, [int(c) for c in counts]
 

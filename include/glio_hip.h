@@ -148,6 +148,15 @@ int glio_set_imu(glio_ctx* ctx, int n_edges, const glio_preint* edges, const int
 /* Replaces problem.AddResidualBlock(new MarginalizationFactor(last_marginalization_info), NULL,
  * last_marginalization_parameter_blocks) (Estimator.cpp:2153-2158).  prior->n == 0 removes it. */
 int glio_set_prior(glio_ctx* ctx, const glio_prior* prior);
+/* Limits of a prior in a window of W keyframes: n <= max(6 W + 9, 15 (W-1)) columns in n_blocks <= max(2 W + 1, 3 (W-1)) blocks, and n <= 393 whatever W
+ * (the prior's kernels keep three vectors of that length in LDS): windows of up to 27 keyframes hold every layout glio_marginalize can produce. */
+/* Replaces the SpeedBiasPriorFactorAutoDiff blocks of the window after a loop closure (correctPoses ends with marg = false, Estimator.cpp:4785; the
+ * factors: Estimator.cpp:2164-2176, PriorFactor.h:10-40): residual w o (x - target) on the speed/bias of slots 0 .. n_slots-1, w = (8, 8, 1, ..., 1), no
+ * loss.  target: [n_slots][9], copied.  n_slots <= W-1 (the reference uses W-1); 0 removes them.  They take part in glio_solve, glio_linearize,
+ * glio_time_solve and glio_marginalize*, with or without a marginalization prior beside them, and leave the solver on the path it takes without them.
+ * Each is evaluated together with the IMU edge that leaves its slot, so that edge has to be set when the problem is evaluated (GLIO_E_ARG otherwise).
+ * glio_marginalize_keep(_async) removes them (the reference's marg = true, Estimator.cpp:2517): the prior it installs carries them on. */
+int glio_set_speed_bias_priors(glio_ctx* ctx, int n_slots, const double* target);
 /* Replaces addDDPsrResFactor (Estimator.cpp:1893-1897) and the tcdopplerFactor blocks
  * (Estimator.cpp:2329-2337); para_yaw_enu_local / para_anc_ecef are the constant blocks. */
 int glio_set_gnss(glio_ctx* ctx, const glio_gnss_frame* frame, int n_dd, const glio_dd_psr* dd,
@@ -165,7 +174,7 @@ int glio_linearize(glio_ctx* ctx, const glio_state* state, double* H, double* g,
  * Estimator.cpp:2462-2607 (addResidualBlockInfo x {prior, IMU(0,1), every LidarPlaneNormFactor with Huber},
  * preMarginalize, marginalize, getParameterBlocks(addr_shift)) on the factors currently set in the context,
  * evaluated at `state` (the solution of glio_solve).  Outputs, caller-allocated for n = 6 (W-1) + 9 and
- * nb = 2 (W-1) + 1: lin_jac [n][n] row-major, lin_res [n], blocks (slot already shifted s -> s-1, kind, first
+ * nb = 2 (W-1) + 1 (glio_marginalize_size in the windows after a loop closure): lin_jac [n][n] row-major, lin_res [n], blocks (slot already shifted s -> s-1, kind, first
  * column, x0[9]) -- exactly the fields of glio_prior for the NEXT window.  lin_jac^T lin_jac and
  * lin_jac^T lin_res equal the reference's (it factors the Schur complement by eigen-decomposition, this
  * library by Cholesky: a different square root of the same matrix).  GLIO_E_NUMERIC if the Schur
@@ -173,6 +182,12 @@ int glio_linearize(glio_ctx* ctx, const glio_state* state, double* H, double* g,
 int glio_marginalize(glio_ctx* ctx, const glio_state* state, double* lin_jac, double* lin_res,
                      int32_t* blk_slot, int32_t* blk_kind, int32_t* blk_idx, double* blk_x0,
                      int32_t* out_n, int32_t* out_n_blocks);
+/* What the next glio_marginalize will write: n and n_blocks.  6 (W-1) + 9 and 2 (W-1) + 1 unless speed-bias priors are set or the installed prior
+ * already carries speed-bias blocks of several keyframes (the windows after a loop closure): the reference re-creates the speed-bias priors at the state
+ * being marginalized (Estimator.cpp:2483-2518) and KEEPS the blocks of slots 1 .. W-2.  Kept layout: the standard columns at their usual offsets, then the
+ * speed/bias of every slot s >= 2 that has such a prior or a speed-bias block in the installed prior, in ascending slot order at 6 (W-1) + 9 + 9 j, named
+ * s-1.  The following windows shrink it by one block per keyframe. */
+int glio_marginalize_size(glio_ctx* ctx, int32_t* out_n, int32_t* out_n_blocks);
 
 /* The same, but the result is installed as THIS context's prior for the next window without leaving the device
  * (= glio_marginalize + glio_set_prior of its output, minus the two PCIe trips of the n x n matrix).  The caller then
