@@ -152,6 +152,28 @@ extern __shared__ __attribute__((aligned(16))) unsigned char tr_lds[];
 // LDS carve of the factor kernel
 __device__ __host__ __forceinline__ constexpr int bp_stride(int n) { return ((n + 15) & ~15) + 2; }   // even -> 16-B aligned rows
 
+// One wavefront's pass over a panel, in both factorisations below: the wavefront carries the diagonal block in lanes 0-15 (factored redundantly,
+// identical arithmetic) and 48 of the rows below in lanes 16-63; the 16 right-looking register steps -- pivot and multipliers broadcast with
+// v_readlane -- factor the block AND solve X L_kk^T = A_panel for those rows: no separate triangular-solve phase, no LDS.  The rows below go back to
+// memory at once; the factored diagonal block is only kept in registers (`adg`, wavefront 0, first pass) and goes back with chol_store_diag AFTER the
+// caller's barrier: the other wavefronts, and every wavefront that comes round a second time, load the diagonal block at the start of their pass -- it
+// must still be the unfactored one, and nothing orders that read before a store here.  (Until the end of round 3 wavefront 0 stored it at the end of
+// its first pass: every system with n >= 400 was factored wrongly, rel. error 3e-2; found with scripts/dense_probe_414.py, pinned by
+// tests/test_hip_parity.py::test_blocked_cholesky_sizes.)
+// The pass itself stays written out in chol_left_looking and chol_packed_lds, and so do the two back substitutions (back_substitute,
+// backsub_packed_lds) and the per-block panels of the marginalization kernels.  Tried and measured on the MI355X against the same source without it
+// (profiles/solver_dedup_ab.txt): the 16 register steps as one routine chol_panel16<SEMI> plus one back substitution templated on the factor's
+// addressing left registers and occupancy alone, but the compiler scheduled the inlined body differently -- n = 414 factorisation 423.4 -> 434.2 us,
+// arrow step at W = 20 153.2 -> 154.6 us, both several times the run-to-run spread; with only the 16 steps written out again still 428.6 us.  The
+// load / steps / store as one routine (tried with `adg` filled inside and with the register array owned by the caller) cost k_chain_step
+// 209 -> 210 VGPRs.
+__device__ __forceinline__ void chol_store_diag(double* prow, const int nb, const int lane, const double (&adg)[TR_NB]) {
+#pragma unroll
+    for (int j = 0; j < TR_NB; ++j) if (j < nb && j <= lane) prow[j] = adg[j];
+}
+
+__device__ __forceinline__ int pk_off(const int i) { return (i * (i + 1)) >> 1; }      // packed lower triangle: row i starts at i (i + 1) / 2
+
 // ------------------------------------------------------------------------------------------------
 // Blocked left-looking Cholesky of the leading n x n block of the (n+1) x n row-major matrix A (lower
 // triangle), row n carried along (= forward substitution of the right-hand side).
@@ -240,20 +262,14 @@ __device__ __forceinline__ bool chol_left_looking(double* A, const int n, double
                 __syncthreads();
             }
         }
-        // (2+3) fused panel factorisation: every wavefront carries the diagonal block in lanes 0-15 (factored
-        //       redundantly, identical arithmetic) and 48 of the rows below (incl. the carried row n) in lanes 16-63.
-        //       The 16 right-looking register steps -- pivot and multipliers broadcast with v_readlane -- factor the
-        //       block AND solve X L_kk^T = A_panel for those rows: no separate triangular-solve phase, no LDS.
+        // (2+3) fused panel factorisation (see chol_store_diag), the carried row n among the rows below
         const int r0 = k0 + nb;
         const int mb = n + 1 - r0;
-        // The factored diagonal block goes back to memory only AFTER the barrier below: with more than TR_WAVES * 48 = 384 rows under the panel
-        // the wavefronts come round a second time and load the diagonal block again -- it must still be the unfactored one.  (Until the end of
-        // round 3 wavefront 0 stored it at the end of its first round: every system with n >= 400 was factored wrongly, rel. error 3e-2; found
-        // with scripts/dense_probe_414.py, pinned by tests/test_hip_parity.py::test_blocked_cholesky_sizes.)
         double adg[TR_NB];
 #pragma unroll
         for (int j = 0; j < TR_NB; ++j) adg[j] = 0.0;
         if (!(skip & 2)) {
+            // more than TR_WAVES * 48 = 384 rows under the panel: the wavefronts come round again (and load the diagonal block again)
             for (int base = wv * 48; base < mb; base += TR_WAVES * 48) {       // mb >= 1: wavefront 0 always runs
                 const bool isdiag = lane < TR_NB;
                 const int bi = base + lane - TR_NB;
@@ -290,11 +306,7 @@ __device__ __forceinline__ bool chol_left_looking(double* A, const int n, double
         }
         __syncthreads();
         if (*flag) return false;
-        if (!(skip & 2) && wv == 0 && lane < nb) {
-            double* prow = A + (size_t)(k0 + lane) * ld + k0;
-#pragma unroll
-            for (int j = 0; j < TR_NB; ++j) if (j < nb && j <= lane) prow[j] = adg[j];
-        }
+        if (!(skip & 2) && wv == 0 && lane < nb) chol_store_diag(A + (size_t)(k0 + lane) * ld + k0, nb, lane, adg);
         // Inside the loop nothing reads this diagonal block again (later panels touch rows >= k0 + 16 only), but after the LAST panel
         // the caller does (the marginalization kernel copies L out with all eight wavefronts straight after the call): the store
         // above must be ordered before the return by a barrier, not by timing.
@@ -344,7 +356,6 @@ __device__ __forceinline__ void back_substitute(const double* A, const int n, do
 // trailing triangle takes its rank-16 update on the matrix cores (one 16x16 tile per wavefront, operands read from
 // LDS).  No global-memory round trip between the phases.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int pk_off(const int i) { return (i * (i + 1)) >> 1; }
 __host__ __device__ __forceinline__ size_t pk_doubles(const int n) { const size_t d = (size_t)(n + 1) * (n + 2) / 2; return d + (d & 1); }
 
 __device__ __forceinline__ bool chol_packed_lds(double* P, const int n, double* sD, int* flag) {
@@ -354,13 +365,11 @@ __device__ __forceinline__ bool chol_packed_lds(double* P, const int n, double* 
     __syncthreads();
     for (int k0 = 0; k0 < n; k0 += TR_NB) {
         const int nb = min(TR_NB, n - k0);
-        // (a+b) fused: every participating wavefront carries the diagonal block in lanes 0-15 (factored redundantly)
-        //       and 48 of the rows below in lanes 16-63; the 16 right-looking register steps then factor the block
-        //       AND solve those rows with the same v_readlane broadcasts -- no separate triangular-solve phase.
+        // (a+b) fused panel factorisation (see chol_store_diag): one pass, every wavefront that has rows below the panel takes part
         const int r0 = k0 + nb;
         const int mb = n + 1 - r0;
-        double adg[TR_NB];                        // wavefront 0: the factored diagonal block, stored after the barrier (the other wavefronts
-#pragma unroll                                    // read the unfactored one at the start of their step; nothing orders that read before a store here)
+        double adg[TR_NB];
+#pragma unroll
         for (int j = 0; j < TR_NB; ++j) adg[j] = 0.0;
         if (wv == 0 || wv * 48 < mb) {
             const bool isdiag = lane < TR_NB;
@@ -393,11 +402,7 @@ __device__ __forceinline__ bool chol_packed_lds(double* P, const int n, double* 
         }
         __syncthreads();
         if (*flag) return false;
-        if (wv == 0 && lane < nb) {
-            double* prow = P + pk_off(k0 + lane) + k0;
-#pragma unroll
-            for (int j = 0; j < TR_NB; ++j) if (j < nb && j <= lane) prow[j] = adg[j];
-        }
+        if (wv == 0 && lane < nb) chol_store_diag(P + pk_off(k0 + lane) + k0, nb, lane, adg);
         if (nb == TR_NB && r0 < n) {
             const int T = (n + 1 - r0 + 15) >> 4;
             const int ntiles = (T * (T + 1)) >> 1;
@@ -851,6 +856,23 @@ __device__ __forceinline__ void tr_factor_body(const TrArgs& a, const Builder& b
 // ------------------------------------------------------------------------------------------------
 // K7d  k_tr_dogleg
 // ------------------------------------------------------------------------------------------------
+// Step selection: step (D-space) = ca * grad + cb * gn, from gg = |grad|^2, nn = |gn|^2, gd = grad . gn (gnorm, gnn: their roots) and the Cauchy
+// step length alpha.  snorm: the step's norm where it is known in closed form, -1 where the caller takes it from the step itself.
+__device__ __forceinline__ void dogleg_coeffs(const bool lm, const double gg, const double nn, const double gd, const double gnorm, const double gnn,
+                                              const double radius, const double alpha, double& ca, double& cb, double& snorm) {
+    if (lm) { ca = 0.0; cb = 1.0; snorm = gnn; }        // Levenberg-Marquardt: the damped step itself
+    else if (gnn <= radius) { ca = 0.0; cb = 1.0; snorm = gnn; }
+    else if (gnorm * alpha >= radius) { ca = -(radius / gnorm); cb = 0.0; snorm = radius; }
+    else {
+        const double b_dot_a = -alpha * gd;
+        const double a_sq = alpha * alpha * gg;
+        const double b_minus_a_sq = nn - 2 * b_dot_a + a_sq;
+        const double c = b_dot_a - a_sq;
+        const double d = sqrt(c * c + b_minus_a_sq * (radius * radius - a_sq));
+        const double beta = (c <= 0) ? (d - c) / b_minus_a_sq : (radius * radius - a_sq) / (d + c);
+        ca = -alpha * (1.0 - beta); cb = beta; snorm = -1.0;
+    }
+}
 __device__ __forceinline__ void tr_dogleg_body(const TrArgs& a) {
     double* red = reinterpret_cast<double*>(tr_lds);                       // the factorisation's panel buffer is free again
     SolverStatus& s = *reinterpret_cast<SolverStatus*>(red + 32);
@@ -867,19 +889,8 @@ __device__ __forceinline__ void tr_dogleg_body(const TrArgs& a) {
     for (int i = tid; i < n; i += TR_THREADS) { gg += grad[i] * grad[i]; nn += gn[i] * gn[i]; gd += grad[i] * gn[i]; }
     { double v3[3] = {gg, nn, gd}; block_sum_n<3>(v3, red); gg = v3[0]; nn = v3[1]; gd = v3[2]; }
     const double gnorm = sqrt(gg), gnn = sqrt(nn), radius = s.radius, alpha = s.alpha;
-    double ca, cb, snorm;       // step (D-space) = ca * grad + cb * gn
-    if (a.lm) { ca = 0.0; cb = 1.0; snorm = gnn; }        // Levenberg-Marquardt: the damped step itself
-    else if (gnn <= radius) { ca = 0.0; cb = 1.0; snorm = gnn; }
-    else if (gnorm * alpha >= radius) { ca = -(radius / gnorm); cb = 0.0; snorm = radius; }
-    else {
-        const double b_dot_a = -alpha * gd;
-        const double a_sq = alpha * alpha * gg;
-        const double b_minus_a_sq = nn - 2 * b_dot_a + a_sq;
-        const double c = b_dot_a - a_sq;
-        const double d = sqrt(c * c + b_minus_a_sq * (radius * radius - a_sq));
-        const double beta = (c <= 0) ? (d - c) / b_minus_a_sq : (radius * radius - a_sq) / (d + c);
-        ca = -alpha * (1.0 - beta); cb = beta; snorm = -1.0;
-    }
+    double ca, cb, snorm;
+    dogleg_coeffs(a.lm, gg, nn, gd, gnorm, gnn, radius, alpha, ca, cb, snorm);
     // step_s = step / D = ca * (g~/D) + cb * (-y); w = S step_s.
     // Hs step_s = ca * Hs (g~/D) - cb * Hs y, with Hs (g~/D) = S H u = S t and Hs y = S g - mu D^2 y
     // -> model cost change = -(gs.step_s + step_s^T Hs step_s / 2) without another matrix pass.
@@ -1440,6 +1451,47 @@ __device__ __forceinline__ void chain_wave_sync() {
     else GLIO_WAVE_LDS_SYNC();
 }
 
+// ---- pieces of one chain step, shared by the outer fronts (chain_step15) and the inner fronts (chain_step15e)
+// Loads of a step: nx = this lane's row of the next block Bn (rows 0..14: its diagonal block, lane 30: its right-hand side), ld = this lane's coupling
+// row (lanes 15..29) of block Bi -- stored transposed in Bn when the front runs DOWN, or handed over in Nrows (meeting block).  Unconditional reads at
+// clamped (always valid) addresses, selected afterwards by the caller: the 30 ds_reads go out back to back.
+template <bool DOWN>
+__device__ __forceinline__ void chain_load_panel(const double* Bn, const double* Bi, const double* Nrows, const int r, double (&nx)[KC_NB], double (&ld)[KC_NB]) {
+    const int row = r < KC_NB ? r : 30;
+    const int rb = (r >= KC_NB && r < 30) ? r : KC_NB;
+#pragma unroll
+    for (int j = 0; j < KC_NB; ++j) nx[j] = Bn[row * KC_RS + j];
+#pragma unroll
+    for (int j = 0; j < KC_NB; ++j) ld[j] = DOWN ? Bn[(KC_NB + j) * KC_RS + (rb - KC_NB)] : (Nrows ? Nrows[(rb - KC_NB) * KC_RS + j] : Bi[rb * KC_RS + j]);
+}
+// The 15 right-looking register steps over a panel held one row per lane; rpv: lane j keeps 1 / sqrt(d_j).
+// The pivots form a scalar recurrence d_{j+1} = a_{j+1,j+1} - (a_{j+1,j} / sqrt(d_j))^2 that is carried in the uniform
+// domain one step ahead of the vector update: the next 1/sqrt starts three dependent operations after the previous
+// one instead of waiting for the column scaling, the rank-1 update and a v_readlane round trip.  A non-positive or
+// non-finite pivot only raises `bad` (the dense fallback redoes the solve); it is not patched on the critical path.
+__device__ __forceinline__ void chain_pivots15(double (&av)[KC_NB], const int lane, bool& bad, double& rpv) {
+    double djj = readlane_d(av[0], 0);
+#pragma unroll
+    for (int j = 0; j < KC_NB; ++j) {
+        bad |= !((djj > 0.0) & (djj < 1e300));                       // also true for NaN
+        const double rdj = pivot_rsqrt(djj);
+        if (j + 1 < KC_NB) {
+            const double lnx = readlane_d(av[j], j + 1) * rdj;        // L[j+1][j]
+            djj = fma(-lnx, lnx, readlane_d(av[j + 1], j + 1));       // next pivot (both operands were final before this step)
+        }
+        const double lij = av[j] * rdj;                              // lane j: d / sqrt(d) = sqrt(d)
+        rpv = lane == j ? rdj : rpv;
+        av[j] = lij;
+#pragma unroll
+        for (int c = j + 1; c < KC_NB; ++c) av[c] -= lij * readlane_d(lij, c);
+    }
+}
+// rows 0..30 of the factored panel back into block Bi (zeros above the diagonal), the reciprocal pivots into its row 31; lanes r < 31 only
+__device__ __forceinline__ void chain_store_panel(double* Bi, const double (&av)[KC_NB], const double rpv, const int r, const int tri) {
+#pragma unroll
+    for (int j = 0; j < KC_NB; ++j) Bi[r * KC_RS + j] = j < tri ? av[j] : 0.0;
+    if (r < KC_NB) Bi[31 * KC_RS + r] = rpv;
+}
 template <bool DOWN, bool G = false>
 __device__ __forceinline__ void chain_step15(const int i, const int nb, const bool has_nb, double (&av)[KC_NB], double* Blk, double* Cs, const int lane, bool& bad,
                                              long long* ph = nullptr, const double* Nrows = nullptr) {
@@ -1459,14 +1511,8 @@ __device__ __forceinline__ void chain_step15(const int i, const int nb, const bo
     double nx[KC_NB];
     {
         const double* Bn = Blk + (size_t)(has_nb ? nb : i) * KC_BLK;
-        // unconditional reads at clamped (always valid) addresses, selected afterwards: the 30 ds_reads go out back to back
-        const int row = r < KC_NB ? r : 30;
-        const int rb = (r >= KC_NB && r < 30) ? r : KC_NB;
         double ld[KC_NB];
-#pragma unroll
-        for (int j = 0; j < KC_NB; ++j) nx[j] = Bn[row * KC_RS + j];
-#pragma unroll
-        for (int j = 0; j < KC_NB; ++j) ld[j] = DOWN ? Bn[(KC_NB + j) * KC_RS + (rb - KC_NB)] : (Nrows ? Nrows[(rb - KC_NB) * KC_RS + j] : Bi[rb * KC_RS + j]);
+        chain_load_panel<DOWN>(Bn, Bi, Nrows, r, nx, ld);
         const bool keep_nx = has_nb & (lim > 0);
         const bool is_b = (r >= KC_NB) & (r < 30);
 #pragma unroll
@@ -1476,31 +1522,9 @@ __device__ __forceinline__ void chain_step15(const int i, const int nb, const bo
     }
     CS_PH(0);
     double rpv = 0.0;
-    // The pivots form a scalar recurrence d_{j+1} = a_{j+1,j+1} - (a_{j+1,j} / sqrt(d_j))^2 that is carried in the uniform
-    // domain one step ahead of the vector update: the next 1/sqrt starts three dependent operations after the previous
-    // one instead of waiting for the column scaling, the rank-1 update and a v_readlane round trip.  A non-positive or
-    // non-finite pivot only raises `bad` (the dense fallback redoes the solve); it is not patched on the critical path.
-    double djj = readlane_d(av[0], 0);
-#pragma unroll
-    for (int j = 0; j < KC_NB; ++j) {
-        bad |= !((djj > 0.0) & (djj < 1e300));                       // also true for NaN
-        const double rdj = pivot_rsqrt(djj);
-        if (j + 1 < KC_NB) {
-            const double lnx = readlane_d(av[j], j + 1) * rdj;        // L[j+1][j]
-            djj = fma(-lnx, lnx, readlane_d(av[j + 1], j + 1));       // next pivot (both operands were final before this step)
-        }
-        const double lij = av[j] * rdj;                              // lane j: d / sqrt(d) = sqrt(d)
-        rpv = lane == j ? rdj : rpv;
-        av[j] = lij;
-#pragma unroll
-        for (int c = j + 1; c < KC_NB; ++c) av[c] -= lij * readlane_d(lij, c);
-    }
+    chain_pivots15(av, lane, bad, rpv);
     CS_PH(1);
-    if (r < 31) {
-#pragma unroll
-        for (int j = 0; j < KC_NB; ++j) Bi[r * KC_RS + j] = j < tri ? av[j] : 0.0;
-        if (r < KC_NB) Bi[31 * KC_RS + r] = rpv;
-    }
+    if (r < 31) chain_store_panel(Bi, av, rpv, r, tri);
     chain_wave_sync<G>();
     CS_PH(2);
     if (has_nb) {
@@ -1545,6 +1569,8 @@ __device__ __forceinline__ void chain_step15(const int i, const int nb, const bo
 // each, L broadcast from LDS); rows 15..29 then hold M = L^-T X^T (row = OWN unknown) and row 30 holds w = L^-T y, so that
 // the back substitution of this keyframe is one matrix-vector product, z = w - M z_neighbour, instead of a 15-step
 // triangular solve on the critical path.
+// (The L^T m = x loop is written out here and in chain_prepare_back_e: as one routine -- tried with Bi const, non-const, and with the load of m
+// inside -- it cost k_chain_solve<true> 224 -> 226 VGPRs.)
 template <bool G = false>
 __device__ __forceinline__ void chain_prepare_back(double* Bi, const int lane) {
     const int c = lane < 16 ? lane : 0;
@@ -1609,13 +1635,8 @@ __device__ __forceinline__ void chain_step15e(const int i, const int nb, double 
     double nx[KC_NB];
     {
         const double* Bn = Blk + (size_t)nb * KC_BLK;
-        const int row = r < KC_NB ? r : 30;
-        const int rb = (r >= KC_NB && r < 30) ? r : KC_NB;
         double ld[KC_NB];
-#pragma unroll
-        for (int j = 0; j < KC_NB; ++j) nx[j] = Bn[row * KC_RS + j];
-#pragma unroll
-        for (int j = 0; j < KC_NB; ++j) ld[j] = DOWN ? Bn[(KC_NB + j) * KC_RS + (rb - KC_NB)] : Bi[rb * KC_RS + j];
+        chain_load_panel<DOWN>(Bn, Bi, nullptr, r, nx, ld);
         const bool keep_nx = lim > 0;
         const bool is_b = (r >= KC_NB) & (r < 30);
 #pragma unroll
@@ -1624,26 +1645,9 @@ __device__ __forceinline__ void chain_step15e(const int i, const int nb, double 
         for (int j = 0; j < KC_NB; ++j) av[j] = is_b ? ld[j] : av[j];
     }
     double rpv = 0.0;
-    double djj = readlane_d(av[0], 0);
-#pragma unroll
-    for (int j = 0; j < KC_NB; ++j) {
-        bad |= !((djj > 0.0) & (djj < 1e300));
-        const double rdj = pivot_rsqrt(djj);
-        if (j + 1 < KC_NB) {
-            const double lnx = readlane_d(av[j], j + 1) * rdj;
-            djj = fma(-lnx, lnx, readlane_d(av[j + 1], j + 1));
-        }
-        const double lij = av[j] * rdj;
-        rpv = lane == j ? rdj : rpv;
-        av[j] = lij;
-#pragma unroll
-        for (int c = j + 1; c < KC_NB; ++c) av[c] -= lij * readlane_d(lij, c);
-    }
-    if (r < 31) {
-#pragma unroll
-        for (int j = 0; j < KC_NB; ++j) Bi[r * KC_RS + j] = j < tri ? av[j] : 0.0;
-        if (r < KC_NB) Bi[31 * KC_RS + r] = rpv;
-    } else if (is_e) {
+    chain_pivots15(av, lane, bad, rpv);
+    if (r < 31) chain_store_panel(Bi, av, rpv, r, tri);
+    else if (is_e) {
 #pragma unroll
         for (int j = 0; j < KC_NB; ++j) Ei[(r - 32) * KC_ERS + j] = av[j];
     }
@@ -2105,6 +2109,205 @@ __host__ __device__ __forceinline__ size_t chain_fat_helper_lds_bytes(int W, int
     return (size_t)(352 * 2 + 84 + 48 * 6 + 2 * KC_BLK + 16 * KC_RS + (size_t)nd * 30 + 4 * (nd + 2) + (size_t)nd * 15 + (nd & 1) + 3 * (nd + 2) + 16) * 8 +
            (size_t)(nd + 2) * 8 + (size_t)(((W + 2) & ~1) + 2 + 2 * nd + 2 + 24) * 4 + 80 * 2 + 64;
 }
+// ------------------------------------------------------------------------------------------------
+// Phases that k_chain_solve<G> and k_chain_step (workgroup 0) share.  None of them contains a workgroup barrier: the kernels cut them at their own
+// (k_chain_step: GLIO_BLOCK_LDS_SYNC, everything it hands over is in LDS; k_chain_solve: __syncthreads, its G = true blocks are in global memory).
+// ------------------------------------------------------------------------------------------------
+// The carve at the front of the dynamic LDS.  G: the staged blocks live in global memory (gblk) and the two Schur tiles move up.
+struct ChainLds {
+    double* rd;          // [nd] 1 / sqrt(m) of the epochs
+    double* yd;          // [nd] forward-substituted right-hand side of the epochs
+    double* Vs;          // [nd][30]: epoch column restricted to its two keyframes, scaled
+    double* Blk;         // [W][KC_BLK]
+    double* CsT; double* CsB;      // the two fronts' Schur tiles
+    double* zb;          // [15 W]
+    int2* eps; int* eoff; int* elist;
+    int* esd;            // [2 nd] per list entry: offset into Vs of this keyframe's rows
+    int* eoth;           // [2 nd] ... of the next keyframe's rows, or -1
+    int* misc;           // [0] bad, [1] number of active local rows, [2..17] their indices
+    double* wd;          // [nd] u / s of the epochs (for t = H u)
+    double* wdr;         // [nd] (u / s) sqrt(m): lives where the index lists (esd) go AFTER t = H u
+};
+template <bool G>
+__device__ __forceinline__ ChainLds chain_lds_carve(const int W, const int nd, double* gblk) {
+    ChainLds m;
+    m.rd = reinterpret_cast<double*>(tr_lds);
+    m.yd = m.rd + nd + (nd & 1);
+    m.Vs = m.yd + nd + (nd & 1);
+    m.Blk = G ? gblk : m.Vs + (size_t)nd * 30;
+    m.CsT = G ? m.Vs + (size_t)nd * 30 : m.Blk + (size_t)W * KC_BLK;
+    m.CsB = m.CsT + 288;
+    m.zb = m.CsB + 288;
+    m.eps = reinterpret_cast<int2*>(m.zb + 15 * W + (W & 1));
+    m.eoff = reinterpret_cast<int*>(m.eps + nd + 2);
+    m.elist = m.eoff + ((W + 2) & ~1) + 2;
+    m.esd = m.elist + 2 * nd + 2;
+    m.eoth = m.esd + 2 * nd + 2;
+    m.misc = m.eoth + 2 * nd + 2;
+    m.wd = reinterpret_cast<double*>(m.misc + 24);
+    m.wdr = reinterpret_cast<double*>(m.esd);
+    return m;
+}
+// t = H u from the staged (scaled) blocks, row r of keyframe i before the division by its scale: sum_j (S H S)_ij w_j with w = u / s in zb (keyframes)
+// and wdr (epochs, times sqrt(m): the stored columns V = S c S r are un-scaled with it).
+__device__ __forceinline__ double chain_t_row_kf(const int i, const int r, const int W, const double mu, const double d_row, const double* Blk, const double* zb,
+                                                 const int* eoff, const int* elist, const int2* eps, const double* Vs, const double* wdr) {
+    double acc = 0.0;
+    const double* Bi = Blk + (size_t)i * KC_BLK;
+#pragma unroll
+    for (int j = 0; j < KC_NB; ++j) {
+        double v = j <= r ? Bi[r * KC_RS + j] : Bi[j * KC_RS + r];
+        if (j == r) v -= mu * d_row * d_row;
+        acc += v * zb[15 * i + j];
+    }
+    if (i + 1 < W) {
+#pragma unroll
+        for (int j = 0; j < KC_NB; ++j) acc += Bi[(KC_NB + j) * KC_RS + r] * zb[15 * (i + 1) + j];
+    }
+    if (i > 0) {
+        const double* Bp = Blk + (size_t)(i - 1) * KC_BLK;
+#pragma unroll
+        for (int j = 0; j < KC_NB; ++j) acc += Bp[(KC_NB + r) * KC_RS + j] * zb[15 * (i - 1) + j];
+    }
+    // the epochs of this keyframe, eight at a time: the list entries, then their slot pairs, then the operands go out as three
+    // batches of independent LDS reads (one after the other they are three dependent round trips PER EPOCH); added in list order
+    const int t0e = eoff[i], t1e = eoff[i + 1];
+    for (int tb = t0e; tb < t1e; tb += 8) {
+        int ee[8], sd[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) ee[q] = elist[tb + q < t1e ? tb + q : t1e - 1];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) sd[q] = eps[ee[q]].x == i ? 0 : 15;
+        double xv[8], xw[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) { xv[q] = Vs[ee[q] * 30 + sd[q] + r]; xw[q] = wdr[ee[q]]; }
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc = tb + q < t1e ? acc + xv[q] * xw[q] : acc;
+    }
+    return acc;
+}
+// ... and the row of epoch e (se: its scale, he: its diagonal entry of H)
+__device__ __forceinline__ double chain_t_row_epoch(const int e, const double se, const double he, const int2* eps, const double* rd, const double* Vs,
+                                                    const double* zb, const double* wd) {
+    const int2 sl = eps[e];
+    double acc = se * he * se * wd[e];
+    if (sl.x >= 0) {
+        const double ire = 1.0 / rd[e];             // one division per epoch, not one per entry
+#pragma unroll
+        for (int q = 0; q < 30; ++q) acc += (Vs[e * 30 + q] * ire) * zb[15 * (q < 15 ? sl.x : sl.y) + (q < 15 ? q : q - 15)];
+    }
+    return acc;
+}
+// per list entry (keyframe i, epoch e): offset of the epoch's rows of keyframe i in Vs, and of keyframe i+1 (or -1)
+__device__ __forceinline__ void chain_epoch_tables(const int W, const int* eoff, const int* elist, const int2* eps, int* esd, int* eoth, const int lane, const int wv) {
+    for (int i = wv; i < W; i += KC_THREADS / 64)
+        for (int t = eoff[i] + lane; t < eoff[i + 1]; t += 64) {
+            const int e = elist[t];
+            const int2 sl = eps[e];
+            const int side = sl.x == i ? 0 : 15;
+            esd[t] = e * 30 + side;
+            eoth[t] = (sl.x == i ? sl.y : sl.x) == i + 1 ? e * 30 + (15 - side) : -1;
+        }
+}
+// Minus the epoch contribution, flat form (row sets that do not fit chain_epoch_corrections_mfma's 16-row tile): one item per touched entry,
+// accumulated over the epochs of its keyframe in list order.  NA: int, or an integral_constant for the usual row set.
+template <class NA>
+__device__ __forceinline__ void chain_epoch_corrections_items(const NA na_c, const int W, const int* misc, const int* eoff, const int* elist, const int* esd, const int* eoth,
+                                                              const double* Vs, const double* yd, double* Blk, const int tid) {
+    const int na = na_c;
+    const int per = 2 * na * na + na;            // D entries, B entries, rhs entries per keyframe
+    for (int item = tid; item < W * per; item += KC_THREADS) {
+        const int i = item / per, w = item - i * per;
+        int r, j, kindI;                          // kindI 0: D_i[r][j], 1: B_i[r][j] (rows of keyframe i+1), 2: rhs_i[j]
+        if (w < na * na) { kindI = 0; r = misc[2 + w / na]; j = misc[2 + w % na]; if (j > r) continue; }
+        else if (w < 2 * na * na) { kindI = 1; const int u = w - na * na; r = misc[2 + u / na]; j = misc[2 + u % na]; if (i + 1 >= W) continue; }
+        else { kindI = 2; r = 0; j = misc[2 + w - 2 * na * na]; }
+        double* dst = Blk + (size_t)i * KC_BLK + (kindI == 0 ? r : (kindI == 1 ? KC_NB + r : 30)) * KC_RS + j;
+        double v = *dst;
+        // four epochs per round: the index reads, then the operand reads, go out as independent batches (the
+        // subtractions stay in list order, so the result does not depend on the batching)
+        const int t1 = eoff[i + 1];
+        for (int t = eoff[i]; t < t1; t += 4) {
+            int base[4], ob[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int tt = t + q < t1 ? t + q : t1 - 1;
+                base[q] = esd[tt];
+                ob[q] = kindI == 1 ? eoth[tt] : (kindI == 2 ? elist[tt] : 0);
+            }
+            double xa[4], xb[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                xb[q] = Vs[base[q] + j];
+                xa[q] = kindI == 0 ? Vs[base[q] + r] : (kindI == 1 ? Vs[(ob[q] >= 0 ? ob[q] : base[q]) + r] : yd[ob[q]]);
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const bool live = (t + q < t1) & !(kindI == 1 && ob[q] < 0);
+                v -= live ? xa[q] * xb[q] : 0.0;
+            }
+        }
+        *dst = v;
+    }
+}
+// (the usual row set -- position and velocity, six rows -- as a compile-time constant: the index arithmetic of an item is five divisions
+// by na and per, ~150 instructions with run-time divisors)
+__device__ __forceinline__ void chain_epoch_corrections_flat(const int W, const int* misc, const int* eoff, const int* elist, const int* esd, const int* eoth,
+                                                             const double* Vs, const double* yd, double* Blk, const int tid) {
+    if (misc[1] == 6) chain_epoch_corrections_items(std::integral_constant<int, 6>{}, W, misc, eoff, elist, esd, eoth, Vs, yd, Blk, tid);
+    else chain_epoch_corrections_items(misc[1], W, misc, eoff, elist, esd, eoth, Vs, yd, Blk, tid);
+}
+// two fronts: wavefront 0 starts at keyframe 0, wavefront 2 at keyframe W - 1 (lanes 0..14: the diagonal block's rows, lane 30: the right-hand side)
+__device__ __forceinline__ void chain_two_front_start(double (&av)[KC_NB], const double* Blk, const int W, const int nT, const int nB, const int lane, const int wv) {
+#pragma unroll
+    for (int j = 0; j < KC_NB; ++j) av[j] = 0.0;
+    if (lane < KC_NB || lane == 30) {
+        const int row = lane < KC_NB ? lane : 30;
+        if (wv == 0 && nT > 0) { for (int j = 0; j < KC_NB; ++j) av[j] = Blk[row * KC_RS + j]; }
+        if (wv == 2 && nB > 0) { for (int j = 0; j < KC_NB; ++j) av[j] = Blk[(size_t)(W - 1) * KC_BLK + row * KC_RS + j]; }
+    }
+}
+// the middle keyframe, where the two fronts meet: its block minus the last update of either front (CsT, CsB)
+__device__ __forceinline__ void chain_join_middle(double (&av)[KC_NB], const double* Blk, const double* CsT, const double* CsB, const int mid, const int nT, const int nB,
+                                                  const int lane) {
+    const int row = lane < KC_NB ? lane : 30, crow = lane < KC_NB ? lane : 15;
+    const int lim = lane == 30 ? KC_NB : (lane < KC_NB ? lane + 1 : 0);
+    double b0[KC_NB], c0[KC_NB], c1[KC_NB];
+#pragma unroll
+    for (int j = 0; j < KC_NB; ++j) { b0[j] = Blk[(size_t)mid * KC_BLK + row * KC_RS + j]; c0[j] = CsT[crow * KC_RS + j]; c1[j] = CsB[crow * KC_RS + j]; }
+#pragma unroll
+    for (int j = 0; j < KC_NB; ++j) {
+        double v = b0[j];
+        if (nT > 0) v -= c0[j];
+        if (nB > 0) v -= c1[j];
+        av[j] = j < lim ? v : 0.0;
+    }
+}
+// z_i = w_i - M_i z_neighbour on a block that chain_prepare_back transformed
+__device__ __forceinline__ void chain_back_mv(const double* Blk, double* zb, const int i, const int nbr, const int lane) {
+    const double* Bi = Blk + (size_t)i * KC_BLK;
+    if (lane < KC_NB) {
+        double mrow[KC_NB], zn[KC_NB];
+#pragma unroll
+        for (int k = 0; k < KC_NB; ++k) { mrow[k] = Bi[(KC_NB + lane) * KC_RS + k]; zn[k] = zb[15 * nbr + k]; }
+        double s0 = Bi[30 * KC_RS + lane], s1 = 0, s2 = 0;
+#pragma unroll
+        for (int k = 0; k < KC_NB; k += 3) { s0 -= mrow[k] * zn[k]; s1 -= mrow[k + 1] * zn[k + 1]; s2 -= mrow[k + 2] * zn[k + 2]; }
+        zb[15 * i + lane] = (s0 + s1) + s2;
+    }
+    GLIO_WAVE_LDS_SYNC();
+}
+// back substitution of epoch e from the keyframes' z
+__device__ __forceinline__ double chain_epoch_back(const int e, const int2* eps, const double* yd, const double* Vs, const double* zb, const double* rd) {
+    const int2 sl = eps[e];
+    double v = yd[e];
+    if (sl.x >= 0) {
+#pragma unroll
+        for (int q = 0; q < 15; ++q) { v -= Vs[e * 30 + q] * zb[15 * sl.x + q]; v -= Vs[e * 30 + 15 + q] * zb[15 * sl.y + q]; }
+    }
+    return v * rd[e];
+}
+
 struct ChainArgs {
     int W, n, nd;
     const int2* ep_slots; const int* ep_off; const int* ep_list;
@@ -2156,21 +2359,10 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_solve(const ChainArgs a, c
     // entries of S H S + mu D^2 as k_tr_scale forms them (same operations in the same order); everything is loaded
     // unconditionally and selected afterwards, so that a thread's loads go out as one batch
     auto Rld = [&](const int p) { const int i = nat(p); return scv[i] * gn[i]; };
-    double* rd = reinterpret_cast<double*>(tr_lds);
-    double* yd = rd + nd + (nd & 1);                       // forward-substituted right-hand side of the epochs
-    double* Vs = yd + nd + (nd & 1);                       // [nd][30]: epoch column restricted to its two keyframes, scaled
-    double* Blk = G ? a.blk : Vs + (size_t)nd * 30;        // [W][KC_BLK]
-    double* CsT = G ? Vs + (size_t)nd * 30 : Blk + (size_t)W * KC_BLK;
-    double* CsB = CsT + 288;
-    double* zb = CsB + 288;                                // [15 W]
-    int2* eps = reinterpret_cast<int2*>(zb + 15 * W + (W & 1));
-    int* eoff = reinterpret_cast<int*>(eps + nd + 2);
-    int* elist = eoff + ((W + 2) & ~1) + 2;
-    int* esd = elist + 2 * nd + 2;                         // [2 nd] per list entry: offset into Vs of this keyframe's rows
-    int* eoth = esd + 2 * nd + 2;                          // [2 nd] ... of the next keyframe's rows, or -1
-    int* misc = eoth + 2 * nd + 2;                         // [0] bad, [1] number of active local rows, [2..17] their indices
-    double* wd = reinterpret_cast<double*>(misc + 24);     // [nd] u / s of the epochs (for t = H u)
-    double* wdr = reinterpret_cast<double*>(esd);          // [nd] (u / s) sqrt(m): lives where the index lists go AFTER t = H u
+    const ChainLds cl = chain_lds_carve<G>(W, nd, a.blk);
+    double *rd = cl.rd, *yd = cl.yd, *Vs = cl.Vs, *Blk = cl.Blk, *CsT = cl.CsT, *CsB = cl.CsB, *zb = cl.zb, *wd = cl.wd, *wdr = cl.wdr;
+    int2* eps = cl.eps;
+    int *eoff = cl.eoff, *elist = cl.elist, *esd = cl.esd, *eoth = cl.eoth, *misc = cl.misc;
     __shared__ int rowmask;                            // cleared here, two barriers before the first atomicOr into it
     __shared__ int s_prog[4];
     const bool f4 = G && a.fronts4 != 0;
@@ -2251,44 +2443,14 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_solve(const ChainArgs a, c
     // t = H u from the staged (scaled) blocks: t_i = (sum_j (S H S)_ij w_j) / s_i, one row per thread (its scalars were
     // fetched with the blocks, so this phase touches LDS only)
     for (int row = tid; row < np15 + nd; row += KC_THREADS) {
-        double acc = 0.0;
         const bool first = row == tid;
         const double s_row = first ? pre_s : scv[row], d_row = first ? pre_d : dgv[row];
         if (row < np15) {
             const int i = row / 15, r = row - 15 * i;
-            const double* Bi = Blk + (size_t)i * KC_BLK;
-#pragma unroll
-            for (int j = 0; j < KC_NB; ++j) {
-                double v = j <= r ? Bi[r * KC_RS + j] : Bi[j * KC_RS + r];
-                if (j == r) v -= mu * d_row * d_row;
-                acc += v * zb[15 * i + j];
-            }
-            if (i + 1 < W) {
-#pragma unroll
-                for (int j = 0; j < KC_NB; ++j) acc += Bi[(KC_NB + j) * KC_RS + r] * zb[15 * (i + 1) + j];
-            }
-            if (i > 0) {
-                const double* Bp = Blk + (size_t)(i - 1) * KC_BLK;
-#pragma unroll
-                for (int j = 0; j < KC_NB; ++j) acc += Bp[(KC_NB + r) * KC_RS + j] * zb[15 * (i - 1) + j];
-            }
-            for (int tt = eoff[i]; tt < eoff[i + 1]; ++tt) {
-                const int e = elist[tt];
-                const int side = eps[e].x == i ? 0 : 15;
-                acc += Vs[e * 30 + side + r] * wdr[e];
-            }
-            V_T(tr)[row] = acc / s_row;
+            V_T(tr)[row] = chain_t_row_kf(i, r, W, mu, d_row, Blk, zb, eoff, elist, eps, Vs, wdr) / s_row;
         } else {
-            const int e = row - np15;
-            const int2 sl = eps[e];
-            const double se = s_row;
-            acc = se * (first ? pre_h : Hn[(size_t)row * n + row]) * se * wd[e];
-            if (sl.x >= 0) {
-                const double ire = 1.0 / rd[e];             // one division per epoch, not one per entry
-#pragma unroll
-                for (int q = 0; q < 30; ++q) acc += (Vs[e * 30 + q] * ire) * zb[15 * (q < 15 ? sl.x : sl.y) + (q < 15 ? q : q - 15)];
-            }
-            V_T(tr)[row] = acc / se;
+            const double he = first ? pre_h : Hn[(size_t)row * n + row];
+            V_T(tr)[row] = chain_t_row_epoch(row - np15, s_row, he, eps, rd, Vs, zb, wd) / s_row;
         }
     }
     __syncthreads();
@@ -2297,67 +2459,16 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_solve(const ChainArgs a, c
     __syncthreads();
     if (2 * misc[1] + 1 <= 16) chain_epoch_corrections_mfma(W, misc[1], misc + 2, eoff, elist, eps, Vs, yd, Blk, lane, wv, KC_THREADS / 64);
     else {
-    // per list entry (keyframe i, epoch e): offset of the epoch's rows of keyframe i in Vs, and of keyframe i+1 (or -1)
-    for (int i = wv; i < W; i += KC_THREADS / 64)
-        for (int t = eoff[i] + lane; t < eoff[i + 1]; t += 64) {
-            const int e = elist[t];
-            const int2 sl = eps[e];
-            const int side = sl.x == i ? 0 : 15;
-            esd[t] = e * 30 + side;
-            eoth[t] = (sl.x == i ? sl.y : sl.x) == i + 1 ? e * 30 + (15 - side) : -1;
-        }
+    chain_epoch_tables(W, eoff, elist, eps, esd, eoth, lane, wv);
     __syncthreads();
-    // minus the epoch contribution: one item per touched entry, accumulated over the epochs of its keyframe in list order
-    {
-        const int na = misc[1];
-        const int per = 2 * na * na + na;            // D entries, B entries, rhs entries per keyframe
-        for (int item = tid; item < W * per; item += KC_THREADS) {
-            const int i = item / per, w = item - i * per;
-            int r, j, kindI;                          // kindI 0: D_i[r][j], 1: B_i[r][j] (rows of keyframe i+1), 2: rhs_i[j]
-            if (w < na * na) { kindI = 0; r = misc[2 + w / na]; j = misc[2 + w % na]; if (j > r) continue; }
-            else if (w < 2 * na * na) { kindI = 1; const int u = w - na * na; r = misc[2 + u / na]; j = misc[2 + u % na]; if (i + 1 >= W) continue; }
-            else { kindI = 2; r = 0; j = misc[2 + w - 2 * na * na]; }
-            double* dst = Blk + (size_t)i * KC_BLK + (kindI == 0 ? r : (kindI == 1 ? KC_NB + r : 30)) * KC_RS + j;
-            double v = *dst;
-            // four epochs per round: the index reads, then the operand reads, go out as independent batches (the
-            // subtractions stay in list order, so the result does not depend on the batching)
-            const int t1 = eoff[i + 1];
-            for (int t = eoff[i]; t < t1; t += 4) {
-                int base[4], ob[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int tt = t + q < t1 ? t + q : t1 - 1;
-                    base[q] = esd[tt];
-                    ob[q] = kindI == 1 ? eoth[tt] : (kindI == 2 ? elist[tt] : 0);
-                }
-                double xa[4], xb[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    xb[q] = Vs[base[q] + j];
-                    xa[q] = kindI == 0 ? Vs[base[q] + r] : (kindI == 1 ? Vs[(ob[q] >= 0 ? ob[q] : base[q]) + r] : yd[ob[q]]);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const bool live = (t + q < t1) & !(kindI == 1 && ob[q] < 0);
-                    v -= live ? xa[q] * xb[q] : 0.0;
-                }
-            }
-            *dst = v;
-        }
-    }
+    chain_epoch_corrections_flat(W, misc, eoff, elist, esd, eoth, Vs, yd, Blk, tid);
     }
     __syncthreads();
     AR_STAMP(43);
     // the chain from both ends
     const int mid = W / 2, nT = mid, nB = W - 1 - mid, T = nT > nB ? nT : nB;
     double av[KC_NB];
-#pragma unroll
-    for (int j = 0; j < KC_NB; ++j) av[j] = 0.0;
-    if (lane < KC_NB || lane == 30) {
-        const int row = lane < KC_NB ? lane : 30;
-        if (wv == 0 && nT > 0) { for (int j = 0; j < KC_NB; ++j) av[j] = Blk[row * KC_RS + j]; }
-        if (wv == 2 && nB > 0) { for (int j = 0; j < KC_NB; ++j) av[j] = Blk[(size_t)(W - 1) * KC_BLK + row * KC_RS + j]; }
-    }
+    chain_two_front_start(av, Blk, W, nT, nB, lane, wv);
     bool bad = false;
     long long ph[5] = {0, 0, 0, 0, 0};
     if (f4) chain_f4_factor<G>(W, cs, Blk, CsT, CsB, f4m, zb, s_prog, lane, wv, bad, ph, a.dbg);
@@ -2366,20 +2477,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_solve(const ChainArgs a, c
         if (wv == 0) {
             if (it < nT) chain_step15<false, G>(it, it + 1, true, av, Blk, CsT, lane, bad, ph);
             else if (it == T) {
-                {
-                    const int row = lane < KC_NB ? lane : 30, crow = lane < KC_NB ? lane : 15;
-                    const int lim = lane == 30 ? KC_NB : (lane < KC_NB ? lane + 1 : 0);
-                    double b0[KC_NB], c0[KC_NB], c1[KC_NB];
-#pragma unroll
-                    for (int j = 0; j < KC_NB; ++j) { b0[j] = Blk[(size_t)mid * KC_BLK + row * KC_RS + j]; c0[j] = CsT[crow * KC_RS + j]; c1[j] = CsB[crow * KC_RS + j]; }
-#pragma unroll
-                    for (int j = 0; j < KC_NB; ++j) {
-                        double v = b0[j];
-                        if (nT > 0) v -= c0[j];
-                        if (nB > 0) v -= c1[j];
-                        av[j] = j < lim ? v : 0.0;
-                    }
-                }
+                chain_join_middle(av, Blk, CsT, CsB, mid, nT, nB, lane);
                 chain_step15<false, G>(mid, mid, false, av, Blk, CsT, lane, bad);
             }
         } else if (wv == 2) {
@@ -2399,62 +2497,20 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_solve(const ChainArgs a, c
     __syncthreads();
     if (misc[0]) { if (tid == 0) { atomicOr(a.flag, 1); if (a.dbg) a.dbg[301] += 1; } return; }     // (slot 301: breakdowns handed to the dense fallback)
     // back substitution: meeting keyframe, then the two halves in parallel:  L_ii^T z_i = y_i - L_{nbr,i}^T z_nbr
-    auto back = [&](const int i, const int nbr) {
-        const double* Bi = Blk + (size_t)i * KC_BLK;
-        const int ln = lane < KC_NB ? lane : 0;
-        double lcol[KC_NB], bcol[KC_NB];             // column `lane` of L_ii and of L_{nbr,i}: fetched before the dependent chain starts
-#pragma unroll
-        for (int k = 0; k < KC_NB; ++k) { lcol[k] = Bi[k * KC_RS + ln]; bcol[k] = Bi[(KC_NB + k) * KC_RS + ln]; }
-        const double rp = lane < KC_NB ? Bi[31 * KC_RS + lane] : 1.0;
-        double v = lane < KC_NB ? Bi[30 * KC_RS + lane] : 0.0;
-        if (nbr >= 0) {
-            double s0 = 0, s1 = 0, s2 = 0;
-#pragma unroll
-            for (int k = 0; k < KC_NB; k += 3) { s0 += bcol[k] * zb[15 * nbr + k]; s1 += bcol[k + 1] * zb[15 * nbr + k + 1]; s2 += bcol[k + 2] * zb[15 * nbr + k + 2]; }
-            v -= (s0 + s1) + s2;
-        }
-#pragma unroll
-        for (int k = KC_NB - 1; k >= 0; --k) {
-            const double zk = readlane_d(v, k) * readlane_d(rp, k);
-            if (lane == k) v = zk;
-            else if (lane < k) v -= lcol[k] * zk;
-        }
-        if (lane < KC_NB) zb[15 * i + lane] = v;
-        GLIO_WAVE_LDS_SYNC();
-    };
-    auto back_mv = [&](const int i, const int nbr) {          // z_i = w_i - M_i z_neighbour (blocks transformed by chain_prepare_back)
-        const double* Bi = Blk + (size_t)i * KC_BLK;
-        if (lane < KC_NB) {
-            double mrow[KC_NB], zn[KC_NB];
-#pragma unroll
-            for (int k = 0; k < KC_NB; ++k) { mrow[k] = Bi[(KC_NB + lane) * KC_RS + k]; zn[k] = zb[15 * nbr + k]; }
-            double s0 = Bi[30 * KC_RS + lane], s1 = 0, s2 = 0;
-#pragma unroll
-            for (int k = 0; k < KC_NB; k += 3) { s0 -= mrow[k] * zn[k]; s1 -= mrow[k + 1] * zn[k + 1]; s2 -= mrow[k + 2] * zn[k + 2]; }
-            zb[15 * i + lane] = (s0 + s1) + s2;
-        }
-        GLIO_WAVE_LDS_SYNC();
-    };
     if (f4) {
         __syncthreads();
         chain_f4_backsub<G>(W, cs, Blk, f4m, zb, lane, wv);
     } else {
-    if (wv == 0) back(mid, -1);
+    if (wv == 0) chain_back_solve<G>(Blk, mid, -1, zb, nullptr, lane);
     __syncthreads();
-    if (wv == 0) { for (int i = mid - 1; i >= 0; --i) back_mv(i, i + 1); }
-    else if (wv == 1) { for (int i = mid + 1; i < W; ++i) back_mv(i, i - 1); }
+    if (wv == 0) { for (int i = mid - 1; i >= 0; --i) chain_back_mv(Blk, zb, i, i + 1, lane); }
+    else if (wv == 1) { for (int i = mid + 1; i < W; ++i) chain_back_mv(Blk, zb, i, i - 1, lane); }
     }
     __syncthreads();
     AR_STAMP(45);
     double bd2 = 0.0;
     for (int e = tid; e < nd; e += KC_THREADS) {
-        const int2 sl = eps[e];
-        double v = yd[e];
-        if (sl.x >= 0) {
-#pragma unroll
-            for (int q = 0; q < 15; ++q) { v -= Vs[e * 30 + q] * zb[15 * sl.x + q]; v -= Vs[e * 30 + 15 + q] * zb[15 * sl.y + q]; }
-        }
-        v *= rd[e];
+        const double v = chain_epoch_back(e, eps, yd, Vs, zb, rd);
         a.z[e] = v;
         if (!isfinite(v)) bd2 = 1.0;
     }
@@ -3030,21 +3086,10 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
     const int np15 = 15 * W;
     // ---- carve (dynamic LDS).  The gather tables sit BEHIND the region tr_factor_body / tr_dogleg_body overlay at the
     // front of tr_lds: they are still needed by the dense fallback.
-    double* rd = reinterpret_cast<double*>(tr_lds);
-    double* yd = rd + nd + (nd & 1);
-    double* Vs = yd + nd + (nd & 1);
-    double* Blk = Vs + (size_t)nd * 30;
-    double* CsT = Blk + (size_t)W * KC_BLK;
-    double* CsB = CsT + 288;
-    double* zb = CsB + 288;
-    int2* eps = reinterpret_cast<int2*>(zb + 15 * W + (W & 1));
-    int* eoff = reinterpret_cast<int*>(eps + nd + 2);
-    int* elist = eoff + ((W + 2) & ~1) + 2;
-    int* esd = elist + 2 * nd + 2;
-    int* eoth = esd + 2 * nd + 2;
-    int* misc = eoth + 2 * nd + 2;
-    double* wd = reinterpret_cast<double*>(misc + 24);
-    double* wdr = reinterpret_cast<double*>(esd);        // [nd] (u / s) sqrt(m) for t = H u: lives where the index lists go afterwards
+    const ChainLds cl = chain_lds_carve<false>(W, nd, nullptr);
+    double *rd = cl.rd, *yd = cl.yd, *Vs = cl.Vs, *Blk = cl.Blk, *CsT = cl.CsT, *CsB = cl.CsB, *zb = cl.zb, *wd = cl.wd, *wdr = cl.wdr;
+    int2* eps = cl.eps;
+    int *eoff = cl.eoff, *elist = cl.elist, *esd = cl.esd, *eoth = cl.eoth, *misc = cl.misc;
     double* gt_base = reinterpret_cast<double*>(tr_lds + chain_step_tabs_offset(W, nd, n));
     double* lid = gt_base;                               // [W][28]
     const int n2 = n + (n & 1), nx = n + W, nx2 = nx + (nx & 1);
@@ -3513,54 +3558,16 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
     // (the list of rows with an epoch coupling, for the corrections below: by the last thread, which has no row of t when n < 512)
     if (tid == KC_THREADS - 1) { int na = 0; for (int q = 0; q < 15; ++q) if (rowmask >> q & 1) misc[2 + na++] = q; misc[1] = na; }
     for (int row = tid; row < np15 + nd; row += KC_THREADS) {
-        double acc = 0.0;
         const double s_row = sS[row], d_row = sDg[row];
+        double tv;
         if (row < np15) {
             const int i = row / 15, r = row - 15 * i;
-            const double* Bi = Blk + (size_t)i * KC_BLK;
-#pragma unroll
-            for (int j = 0; j < KC_NB; ++j) {
-                double v = j <= r ? Bi[r * KC_RS + j] : Bi[j * KC_RS + r];
-                if (j == r) v -= mu * d_row * d_row;
-                acc += v * zb[15 * i + j];
-            }
-            if (i + 1 < W) {
-#pragma unroll
-                for (int j = 0; j < KC_NB; ++j) acc += Bi[(KC_NB + j) * KC_RS + r] * zb[15 * (i + 1) + j];
-            }
-            if (i > 0) {
-                const double* Bp = Blk + (size_t)(i - 1) * KC_BLK;
-#pragma unroll
-                for (int j = 0; j < KC_NB; ++j) acc += Bp[(KC_NB + r) * KC_RS + j] * zb[15 * (i - 1) + j];
-            }
-            // the epochs of this keyframe, eight at a time: the list entries, then their slot pairs, then the operands go out as three
-            // batches of independent LDS reads (one after the other they are three dependent round trips PER EPOCH); added in list order
-            const int t0e = eoff[i], t1e = eoff[i + 1];
-            for (int tb = t0e; tb < t1e; tb += 8) {
-                int ee[8], sd[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) ee[q] = elist[tb + q < t1e ? tb + q : t1e - 1];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) sd[q] = eps[ee[q]].x == i ? 0 : 15;
-                double xv[8], xw[8];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) { xv[q] = Vs[ee[q] * 30 + sd[q] + r]; xw[q] = wdr[ee[q]]; }
-#pragma unroll
-                for (int q = 0; q < 8; ++q) acc = tb + q < t1e ? acc + xv[q] * xw[q] : acc;
-            }
-            { const double tv = acc / s_row; V_T(tr)[row] = tv; if (mir) sT[row] = tv; }
+            tv = chain_t_row_kf(i, r, W, mu, d_row, Blk, zb, eoff, elist, eps, Vs, wdr) / s_row;
         } else {
             const int e = row - np15;
-            const int2 sl = eps[e];
-            const double se = s_row;
-            acc = se * dds[e * 15 + 12] * se * wd[e];
-            if (sl.x >= 0) {
-                const double ire = 1.0 / rd[e];             // one division per epoch, not one per entry
-#pragma unroll
-                for (int q = 0; q < 30; ++q) acc += (Vs[e * 30 + q] * ire) * zb[15 * (q < 15 ? sl.x : sl.y) + (q < 15 ? q : q - 15)];
-            }
-            { const double tv = acc / se; V_T(tr)[row] = tv; if (mir) sT[row] = tv; }
+            tv = chain_t_row_epoch(e, s_row, dds[e * 15 + 12], eps, rd, Vs, zb, wd) / s_row;
         }
+        V_T(tr)[row] = tv; if (mir) sT[row] = tv;
     }
     AR_STAMP(94);
     GLIO_BLOCK_LDS_SYNC();
@@ -3575,54 +3582,10 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
         chain_epoch_corrections_mfma(W, misc[1], misc + 2, eoff, elist, eps, Vs, yd, Blk, lane, wv, KC_THREADS / 64, a.dbg);
         AR_STAMP(110);
     } else {
-    for (int i = wv; i < W; i += KC_THREADS / 64)
-        for (int t = eoff[i] + lane; t < eoff[i + 1]; t += 64) {
-            const int e = elist[t];
-            const int2 sl = eps[e];
-            const int side = sl.x == i ? 0 : 15;
-            esd[t] = e * 30 + side;
-            eoth[t] = (sl.x == i ? sl.y : sl.x) == i + 1 ? e * 30 + (15 - side) : -1;
-        }
+    chain_epoch_tables(W, eoff, elist, eps, esd, eoth, lane, wv);
     GLIO_BLOCK_LDS_SYNC();
     AR_STAMP(96);
-    // (the usual row set -- position and velocity, six rows -- as a compile-time constant: the index arithmetic of an item is five divisions
-    // by na and per, ~150 instructions with run-time divisors)
-    auto corrections = [&](const auto na_c) {
-        const int na = na_c;
-        const int per = 2 * na * na + na;
-        for (int item = tid; item < W * per; item += KC_THREADS) {
-            const int i = item / per, w = item - i * per;
-            int r, j, kindI;
-            if (w < na * na) { kindI = 0; r = misc[2 + w / na]; j = misc[2 + w % na]; if (j > r) continue; }
-            else if (w < 2 * na * na) { kindI = 1; const int u = w - na * na; r = misc[2 + u / na]; j = misc[2 + u % na]; if (i + 1 >= W) continue; }
-            else { kindI = 2; r = 0; j = misc[2 + w - 2 * na * na]; }
-            double* dst = Blk + (size_t)i * KC_BLK + (kindI == 0 ? r : (kindI == 1 ? KC_NB + r : 30)) * KC_RS + j;
-            double v = *dst;
-            const int t1 = eoff[i + 1];
-            for (int t = eoff[i]; t < t1; t += 4) {
-                int base[4], ob[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int tt = t + q < t1 ? t + q : t1 - 1;
-                    base[q] = esd[tt];
-                    ob[q] = kindI == 1 ? eoth[tt] : (kindI == 2 ? elist[tt] : 0);
-                }
-                double xa[4], xb[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    xb[q] = Vs[base[q] + j];
-                    xa[q] = kindI == 0 ? Vs[base[q] + r] : (kindI == 1 ? Vs[(ob[q] >= 0 ? ob[q] : base[q]) + r] : yd[ob[q]]);
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const bool live = (t + q < t1) & !(kindI == 1 && ob[q] < 0);
-                    v -= live ? xa[q] * xb[q] : 0.0;
-                }
-            }
-            *dst = v;
-        }
-    };
-    if (misc[1] == 6) corrections(std::integral_constant<int, 6>{}); else corrections(misc[1]);
+    chain_epoch_corrections_flat(W, misc, eoff, elist, esd, eoth, Vs, yd, Blk, tid);
     }
     }   // !fat_path
     if (tid < 4) s_prog[tid] = 0;
@@ -3641,13 +3604,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
     // the chain from both ends
     const int mid = W / 2, nT = mid, nB = W - 1 - mid, Tn = nT > nB ? nT : nB;
     double av[KC_NB];
-#pragma unroll
-    for (int j = 0; j < KC_NB; ++j) av[j] = 0.0;
-    if (lane < KC_NB || lane == 30) {
-        const int row = lane < KC_NB ? lane : 30;
-        if (wv == 0 && nT > 0) { for (int j = 0; j < KC_NB; ++j) av[j] = Blk[row * KC_RS + j]; }
-        if (wv == 2 && nB > 0) { for (int j = 0; j < KC_NB; ++j) av[j] = Blk[(size_t)(W - 1) * KC_BLK + row * KC_RS + j]; }
-    }
+    chain_two_front_start(av, Blk, W, nT, nB, lane, wv);
     bool bad = false;
     long long ph[5] = {0, 0, 0, 0, 0};
     // back substitution of the middle keyframe (the one block whose triangular solve is on the critical path)
@@ -3671,20 +3628,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
         while (__hip_atomic_load(&s_prog[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < nB) __builtin_amdgcn_s_sleep(1);
         AR_STAMP(101);
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-        {
-            const int row = lane < KC_NB ? lane : 30, crow = lane < KC_NB ? lane : 15;
-            const int lim = lane == 30 ? KC_NB : (lane < KC_NB ? lane + 1 : 0);
-            double b0[KC_NB], c0[KC_NB], c1[KC_NB];
-#pragma unroll
-            for (int j = 0; j < KC_NB; ++j) { b0[j] = Blk[(size_t)mid * KC_BLK + row * KC_RS + j]; c0[j] = CsT[crow * KC_RS + j]; c1[j] = CsB[crow * KC_RS + j]; }
-#pragma unroll
-            for (int j = 0; j < KC_NB; ++j) {
-                double v = b0[j];
-                if (nT > 0) v -= c0[j];
-                if (nB > 0) v -= c1[j];
-                av[j] = j < lim ? v : 0.0;
-            }
-        }
+        chain_join_middle(av, Blk, CsT, CsB, mid, nT, nB, lane);
         chain_step15<false>(mid, mid, false, av, Blk, CsT, lane, bad);
         AR_STAMP(102);
         back(mid, -1);          // (garbage in, garbage out when a pivot broke down: nobody reads zb then)
@@ -3718,35 +3662,15 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
     GLIO_BLOCK_LDS_SYNC();
     AR_STAMP(97);
     if (!misc[0]) {
-        // z_i = w_i - M_i z_neighbour on the blocks chain_prepare_back transformed
-        auto back_mv = [&](const int i, const int nbr) {
-            const double* Bi = Blk + (size_t)i * KC_BLK;
-            if (lane < KC_NB) {
-                double mrow[KC_NB], zn[KC_NB];
-#pragma unroll
-                for (int k = 0; k < KC_NB; ++k) { mrow[k] = Bi[(KC_NB + lane) * KC_RS + k]; zn[k] = zb[15 * nbr + k]; }
-                double s0 = Bi[30 * KC_RS + lane], s1 = 0, s2 = 0;
-#pragma unroll
-                for (int k = 0; k < KC_NB; k += 3) { s0 -= mrow[k] * zn[k]; s1 -= mrow[k + 1] * zn[k + 1]; s2 -= mrow[k + 2] * zn[k + 2]; }
-                zb[15 * i + lane] = (s0 + s1) + s2;
-            }
-            GLIO_WAVE_LDS_SYNC();
-        };
         if (f4) chain_f4_backsub<false>(W, cs, Blk, f4m, zb, lane, wv);
-        else if (wv == 0) { for (int i = mid - 1; i >= 0; --i) back_mv(i, i + 1); }
-        else if (wv == 1) { for (int i = mid + 1; i < W; ++i) back_mv(i, i - 1); }
+        else if (wv == 0) { for (int i = mid - 1; i >= 0; --i) chain_back_mv(Blk, zb, i, i + 1, lane); }
+        else if (wv == 1) { for (int i = mid + 1; i < W; ++i) chain_back_mv(Blk, zb, i, i - 1, lane); }
         AR_STAMP(98);
         GLIO_BLOCK_LDS_SYNC();
         AR_STAMP(99);
         double bd2 = 0.0;
         for (int e = tid; e < nd; e += KC_THREADS) {
-            const int2 sl = eps[e];
-            double v = yd[e];
-            if (sl.x >= 0) {
-#pragma unroll
-                for (int q = 0; q < 15; ++q) { v -= Vs[e * 30 + q] * zb[15 * sl.x + q]; v -= Vs[e * 30 + 15 + q] * zb[15 * sl.y + q]; }
-            }
-            v *= rd[e];
+            const double v = chain_epoch_back(e, eps, yd, Vs, zb, rd);
             a.z[e] = v;
             wd[e] = v;                  // (the fast tail reads the solution from LDS)
             if (!isfinite(v)) bd2 = 1.0;
@@ -3782,19 +3706,8 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
         AR_STAMP(70);
         const double alpha = q2 / p;
         const double gnorm = sqrt(gg), gnn = sqrt(nn), radius = s0.radius;
-        double ca, cb, snorm;       // step (D-space) = ca * grad + cb * gn
-        if (tr.lm) { ca = 0.0; cb = 1.0; snorm = gnn; }
-        else if (gnn <= radius) { ca = 0.0; cb = 1.0; snorm = gnn; }
-        else if (gnorm * alpha >= radius) { ca = -(radius / gnorm); cb = 0.0; snorm = radius; }
-        else {
-            const double b_dot_a = -alpha * gd;
-            const double a_sq = alpha * alpha * gg;
-            const double b_minus_a_sq = nn - 2 * b_dot_a + a_sq;
-            const double c = b_dot_a - a_sq;
-            const double d = sqrt(c * c + b_minus_a_sq * (radius * radius - a_sq));
-            const double beta = (c <= 0) ? (d - c) / b_minus_a_sq : (radius * radius - a_sq) / (d + c);
-            ca = -alpha * (1.0 - beta); cb = beta; snorm = -1.0;
-        }
+        double ca, cb, snorm;
+        dogleg_coeffs(tr.lm, gg, nn, gd, gnorm, gnn, radius, alpha, ca, cb, snorm);
         const double mu_u = s0.mu;                             // the factorisation succeeded with the record's mu: mu_used = mu
         double sn2 = 0, lin = 0, quad = 0;
         for (int i = tid; i < n; i += TR_THREADS) {
@@ -3911,17 +3824,22 @@ void glio_chain_tabs_upload(glio_ctx* c) {
     c->chain_tabs_dirty = 0;
 }
 
+// dynamic LDS of the arrow path's k_arrow_forward and k_arrow_solve; lds_chol: the pose block's packed factor fits the LDS (chol_packed_lds)
+static void arrow_lds_sizes(const int W, const int n_ddt, size_t& lds_fwd, size_t& lds_slv, bool& lds_chol) {
+    const int np = 6 * W, K = 15 * W + n_ddt - np;
+    lds_fwd = arrow_forward_lds_doubles(W, n_ddt) * 8;
+    const size_t slv_tail = ((size_t)(TR_NB + 1) * TR_PS + np + (np & 1) + 48 + arrow_solve_extra_doubles(W, K)) * 8;
+    const size_t lds_pk = pk_doubles(np) * 8 + slv_tail;
+    lds_chol = lds_pk <= 160 * 1024;
+    lds_slv = lds_chol ? lds_pk : glio_tr_step_lds_bytes(np) + arrow_solve_extra_doubles(W, K) * 8;
+}
 // which factorisation the trust-region step of this context takes for a state with n_ddt clock-drift unknowns:
 int glio_chain_kind(const glio_ctx* c, int n_ddt);
 // 2 = keyframe chain (k_chain_step, no dense H), 1 = arrow, 0 = dense
 int glio_solver_path(const glio_ctx* c, int n_ddt) {
-    const int n = 15 * c->W + n_ddt;
-    const int np = 6 * c->W, K = n - np;
-    const size_t lds_fwd = arrow_forward_lds_doubles(c->W, n_ddt) * 8;
-    const size_t slv_tail = ((size_t)(TR_NB + 1) * TR_PS + np + (np & 1) + 48 + arrow_solve_extra_doubles(c->W, K)) * 8;
-    const size_t lds_pk = pk_doubles(np) * 8 + slv_tail;
-    const bool lds_chol = lds_pk <= 160 * 1024;
-    const size_t lds_slv = lds_chol ? lds_pk : glio_tr_step_lds_bytes(np) + arrow_solve_extra_doubles(c->W, K) * 8;
+    size_t lds_fwd, lds_slv;
+    bool lds_chol;
+    arrow_lds_sizes(c->W, n_ddt, lds_fwd, lds_slv, lds_chol);
     const bool arrow = c->arrow.mode >= 1 && c->arrow.gnss_ok && c->arrow.prior_ok && c->arrow.max_epoch < n_ddt && lds_fwd <= 160 * 1024 && lds_slv <= 160 * 1024;
     return glio_chain_kind(c, n_ddt) ? 2 : (arrow ? 1 : 0);
 }
@@ -3994,11 +3912,9 @@ void glio_launch_tr_step(glio_ctx* c, int n_ddt) {
     // structured factorisation when the factor graph is a chain (IMU / Doppler edges between neighbours only, at most
     // one speed-bias block in the prior) and its workspaces fit the LDS; the dense kernel stays as the fallback
     const int np = 6 * c->W, K = a.n - np;
-    const size_t lds_fwd = arrow_forward_lds_doubles(c->W, n_ddt) * 8;
-    const size_t slv_tail = ((size_t)(TR_NB + 1) * TR_PS + np + (np & 1) + 48 + arrow_solve_extra_doubles(c->W, K)) * 8;
-    const size_t lds_pk = pk_doubles(np) * 8 + slv_tail;
-    const bool lds_chol = lds_pk <= 160 * 1024;
-    const size_t lds_slv = lds_chol ? lds_pk : glio_tr_step_lds_bytes(np) + arrow_solve_extra_doubles(c->W, K) * 8;
+    size_t lds_fwd, lds_slv;
+    bool lds_chol;
+    arrow_lds_sizes(c->W, n_ddt, lds_fwd, lds_slv, lds_chol);
     const int path = glio_solver_path(c, n_ddt);
     const bool chain = path == 2, arrow = path >= 1;       // (arrow is only consulted when !chain)
     const int ckind = glio_chain_kind(c, n_ddt);
@@ -4144,6 +4060,11 @@ __device__ __forceinline__ void marg_kept_span(const int bI, const int ns, int& 
     else { o = ns + 9 * (bI - 1 - n6); bs = 9; }
 }
 
+// The Amm inverse, Ainv, the per-block roots and the J0 / r0 write-out are written out in k_marg_schur and again in k_marg_inv / k_marg_root on
+// purpose.  As shared routines (marg_linv_wave, marg_ainv_from_linv / _eig, marg_block_roots, marg_emit_root) they gave the same bits, registers
+// and occupancy, but the marginalization measured slower on the MI355X than the same source without them, five alternating rounds, medians:
+// one-workgroup form 96.38 -> 97.05 us (spread of the written-out build 0.45 us), three-launch form 74.41 -> 74.32 and 74.03 -> 74.6 us in two
+// sessions (profiles/solver_dedup_ab.txt).  tests/test_hip_marg.py holds the two forms together bit for bit.
 // A: pos x pos row-major (pos = 15 + n), b: pos.  Out: J0 (n x n row-major), r0 (n), *ok.
 __global__ __launch_bounds__(TR_THREADS) void k_marg_schur(const double* A, const double* b, const int n, const int ns, double* Lwork, double* Twork,
                                                            double* J0, double* r0, int* ok) {
