@@ -76,7 +76,7 @@ GlioTraceRange::~GlioTraceRange() { if (on) roctx().pop(); }
 
 extern "C" {
 
-int glio_abi_version(void) { return 4; }   // 3: glio_opts.lidar_precision, the batch pose problem (small factors, trust-region solve), 9 struct sizes
+int glio_abi_version(void) { return 5; }   // 5: the global map (glio_gmap_*); 3: glio_opts.lidar_precision, the batch pose problem (small factors, trust-region solve), 9 struct sizes
 const char* glio_last_error(void) { return g_err; }
 int glio_device_count(void) {
     int n = 0;

@@ -151,6 +151,16 @@ class GlioLoopStepResult(C.Structure):
                 ("rank_deficient", C.c_int32)]
 
 
+class GlioGmapOpts(C.Structure):
+    """glio_gmap_opts (include/glio_types.h): the global map's leaf (Estimator.cpp:856) and capacities"""
+    _fields_ = [("leaf", C.c_float), ("max_voxels", C.c_int32), ("max_points_per_add", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class GlioGmapInfo(C.Structure):
+    """glio_gmap_info: what glio_gmap_add_frames reports"""
+    _fields_ = [("n_points_total", C.c_int64), ("n_voxels", C.c_int32), ("radix_passes", C.c_int32), ("pcl_index_overflow", C.c_int32), ("reserved_", C.c_int32)]
+
+
 LOOP_SOURCE, LOOP_TARGET = 0, 1
 LOOP_NOT_CONVERGED, LOOP_ITERATIONS, LOOP_TRANSFORM, LOOP_ABS_MSE, LOOP_REL_MSE, LOOP_NO_CORRESPONDENCES = range(6)
 LOOP_STATE_NAMES = ("NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE", "NO_CORRESPONDENCES")

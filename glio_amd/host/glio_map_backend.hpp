@@ -1,0 +1,68 @@
+// glio_map_backend.hpp -- the global map of Estimator (GLIO/src/Estimator.cpp:5315-5350, mapVisualizationThread's save_pcd part; :5275-5313, publishCompleteMap)
+// on the C-ABI of include/glio_hip.h.  C-ABI only, C++14, no HIP headers.
+//
+//   glio::GlobalMap          the device object (glio_gmap_*): the listed resident keyframe clouds of a glio_bassoc moved to the world at their final poses, the
+//                            concatenation through one pcl::VoxelGrid (leaf 0.2, :856); added to call by call, bit for bit what one call would give
+//   glio::globalMapFrames    :5339   which keyframes enter the map
+// The poses are glio::loopFramePoses (glio_loop_backend.hpp, :5287-5288).  Writing the .pcd stays with the caller.
+// The Python twin is glio_amd/mapping.py.
+#ifndef GLIO_MAP_BACKEND_HPP_
+#define GLIO_MAP_BACKEND_HPP_
+#include <cstdint>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "glio_hip.h"
+
+namespace glio {
+
+// Estimator.cpp:5339: for (i = 0; i < n; i += mapping_interval)
+inline std::vector<int32_t> globalMapFrames(int n_keyframes, int mapping_interval) {
+    std::vector<int32_t> out;
+    if (mapping_interval < 1) throw std::invalid_argument("globalMapFrames: mapping_interval < 1");
+    for (int i = 0; i < n_keyframes; i += mapping_interval) out.push_back(i);
+    return out;
+}
+
+class GlobalMap {
+public:
+    // `assoc` owns the resident keyframe clouds and must outlive this object
+    explicit GlobalMap(glio_bassoc* assoc, const glio_gmap_opts* opts = nullptr) {
+        if (opts) o_ = *opts; else glio_gmap_opts_default(&o_);
+        check(glio_gmap_create(assoc, &o_, &h_), "glio_gmap_create");
+    }
+    ~GlobalMap() { glio_gmap_destroy(h_); }
+    GlobalMap(const GlobalMap&) = delete;
+    GlobalMap& operator=(const GlobalMap&) = delete;
+    glio_gmap* handle() const { return h_; }
+    const glio_gmap_opts& opts() const { return o_; }
+    // frames in list order (repeats allowed), poses [n][7] = t, q (loopFramePoses); behind everything added since the last clear.  Throws on a refusal, which
+    // leaves the map exactly as it was.
+    glio_gmap_info add(const std::vector<int32_t>& frames, const std::vector<double>& poses) {
+        glio_gmap_info info;
+        check(glio_gmap_add_frames(h_, (int)frames.size(), frames.data(), poses.data(), &info), "glio_gmap_add_frames");
+        return info;
+    }
+    void clear() { check(glio_gmap_clear(h_), "glio_gmap_clear"); }
+    int size() { int n = 0; check(glio_gmap_size(h_, &n), "glio_gmap_size"); return n; }
+    // voxels [first, first + n) as xyzi
+    std::vector<float> read(int first, int n) {
+        std::vector<float> out((size_t)(n > 0 ? n : 0) * 4);
+        check(glio_gmap_read(h_, first, n, out.data()), "glio_gmap_read");
+        return out;
+    }
+    std::vector<float> read() { return read(0, size()); }
+    // the map on the device ([size()] x 4 floats), valid until the next successful add
+    const void* pointsDev(int* n = nullptr) { const void* p = nullptr; check(glio_gmap_points_dev(h_, &p, n), "glio_gmap_points_dev"); return p; }
+    float lastDeviceMs() { float ms = 0; check(glio_gmap_last_device_ms(h_, &ms), "glio_gmap_last_device_ms"); return ms; }
+private:
+    static void check(int rc, const char* what) {
+        if (rc != GLIO_OK) throw std::runtime_error(std::string(what) + ": " + glio_last_error());
+    }
+    glio_gmap_opts o_;
+    glio_gmap* h_ = nullptr;
+};
+
+}  // namespace glio
+#endif  // GLIO_MAP_BACKEND_HPP_

@@ -378,3 +378,45 @@ def run_demo_map_schedule(path, out_path, device=0, env=None, arm=False):
         action, reported, n, armed = np.frombuffer(raw, np.int32, 4, o); o += 16
         out.append((int(action), int(reported), np.frombuffer(raw, np.float32, 4 * int(n), o).reshape(-1, 4).copy()) + ((int(armed),) if arm else ())); o += 16 * int(n)
     return out
+
+
+DEMO_MAP = os.path.join(HERE, "host_demo_map")
+
+
+def build_demo_map(force=False):
+    """The C++ global-map sequence (host_demo_map.cpp over glio::GlobalMap, glio_map_backend.hpp)."""
+    src = [os.path.join(HERE, "host_demo_map.cpp"), os.path.join(HERE, "glio_map_backend.hpp"), os.path.join(HERE, "glio_loop_backend.hpp")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_MAP) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_MAP) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_MAP])
+    return DEMO_MAP
+
+
+def write_map_case(path, opts, cap, clouds, pose_info, q_bl, t_bl, mapping_interval, chunk_frames):
+    """K cap mapping_interval chunk_frames 0 0 0 0 | glio_gmap_opts | K x (n, cloud) | pose_info [K][7] = t_po, q_po | q_bl t_bl"""
+    pose_info = np.ascontiguousarray(pose_info, np.float64)
+    assert pose_info.shape == (len(clouds), 7)
+    with open(path, "wb") as f:
+        f.write(np.array([len(clouds), cap, mapping_interval, chunk_frames, 0, 0, 0, 0], np.int32).tobytes())
+        f.write(bytes(opts))
+        for c in clouds:
+            c = np.ascontiguousarray(c, np.float32).reshape(-1, 4)
+            f.write(np.array([len(c)], np.int32).tobytes()); f.write(c.tobytes())
+        f.write(pose_info.tobytes())
+        f.write(np.ascontiguousarray(q_bl, np.float64).tobytes()); f.write(np.ascontiguousarray(t_bl, np.float64).tobytes())
+
+
+def run_demo_map(path, device=0, env=None):
+    """-> dict(n_voxels, checksum (loop_checksum of the map), n_points_total, radix_passes, pcl_index_overflow, n_frames, add_device_ms)"""
+    import json
+    r = subprocess.run([build_demo_map(), path, str(device)], capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError("host_demo_map failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
+    out = {}
+    for ln in r.stdout.splitlines():
+        w = ln.split()
+        if w and w[0] == "map":
+            out.update(n_voxels=int(w[1]), checksum=int(w[2], 16), n_points_total=int(w[3]), radix_passes=int(w[4]), pcl_index_overflow=bool(int(w[5])), n_frames=int(w[6]))
+        elif ln.startswith("{"):
+            out.update(json.loads(ln))
+    return out

@@ -534,6 +534,46 @@ int glio_loop_read_fallbacks(glio_loop* lp, int32_t* out, int capacity, int* n);
 /* device time of the last glio_loop_align (HIP events around its kernels), ms */
 int glio_loop_last_device_ms(glio_loop* lp, float* ms);
 
+/* ---- the global map on the device.  Replaces the live part of mapVisualizationThread (Estimator.cpp:5315-5350: every mapping_interval-th keyframe's surf cloud
+ * through transformCloud at its final pose, :5339-5341, the concatenation through ds_filter_global_map, :5342-5343) and the same computation of
+ * publishCompleteMap (:5275-5313, poses composed at :5287-5288; its full_clouds_ds is never filled, the push at :3626 is commented out).  Writing the .pcd stays
+ * with the caller.
+ * A glio_gmap is created on a glio_bassoc exactly like a glio_loop: same device, its own HIP stream, every call ordered behind the association's pending frame
+ * copies by an event; it changes nothing the association holds.  glio_gmap_add_frames returns when its kernels are done, so the association's next write to a cloud
+ * is behind the call.  Not thread-safe by itself.
+ *
+ * The map is, at any time, pcl::VoxelGrid(leaf) of the concatenation of every cloud added since the last clear, in the order they were added:
+ *   voxel coordinates floorf(p * (1.0f / leaf)) per axis, in float; per voxel the four channels summed IN FLOAT IN CONCATENATION ORDER and divided by the float
+ *   count; output by ascending PCL linear voxel index ix + iy dx + iz dx dy -- which is the order of (iz, iy, ix) whatever the bounding box.
+ * Adding in several calls gives the same bytes as one call, and as a clear followed by one call: a call's points continue each voxel's stored float sum one at a time.
+ * There is no removal (float sums cannot be undone): after a loop closure or a batch solve the caller clears and adds again.
+ * DEVIATIONS, both stated: (1) Estimator.cpp:5340 applies Tbl and then the pose -- two float roundings per point; here ONE composed pose (q_po * q_bl,
+ * q_po * t_bl + t_po, as publishCompleteMap :5287-5288 and the local map do) moves the resident scan - lidar_offset cloud.  (2) A bounding box of more than
+ * INT32_MAX cells: see glio_gmap_info.pcl_index_overflow. */
+typedef struct glio_gmap glio_gmap;
+void glio_gmap_opts_default(glio_gmap_opts* o);
+/* sizeof() of glio_gmap_opts, glio_gmap_info; returns how many there are (2) */
+int glio_gmap_struct_sizes(int32_t* out, int n);
+int glio_gmap_create(glio_bassoc* b, const glio_gmap_opts* opts, glio_gmap** out);
+void glio_gmap_destroy(glio_gmap* gm);
+/* global_map->clear() (:5348): the map is empty again */
+int glio_gmap_clear(glio_gmap* gm);
+/* cloud frame_idx[f] of the association moved by transformCloud (Estimator.cpp:1517-1546: double, products kept separate, stored as float) with
+ * poses[f] = t[3], q[4] (w first; the layout of glio_loop_build_submap), appended in list order behind everything added since the last clear (:5339-5341); the
+ * map afterwards is the VoxelGrid of the whole concatenation (:5342-5343).  Repeated frame indices are allowed.  info may be null.
+ * GLIO_E_ARG, and THE MAP STAYS EXACTLY AS IT WAS (size, bytes, device pointer): n_frames < 1 (or above 65535), a frame index outside [0, K), a frame that was
+ * never set or holds no point, a pose that is not finite, more points than max_points_per_add, more voxels than max_voxels, a voxel coordinate outside
+ * [-2^20, 2^20). */
+int glio_gmap_add_frames(glio_gmap* gm, int n_frames, const int32_t* frame_idx, const double* poses /* [n_frames][7] */, glio_gmap_info* info);
+int glio_gmap_size(glio_gmap* gm, int* n_voxels);
+/* voxels [first, first + n) of the map into out_xyzi [n][4] (ranges: a map can be gigabytes); GLIO_E_ARG for a range outside the map */
+int glio_gmap_read(glio_gmap* gm, int first, int n, float* out_xyzi);
+/* the map as a device pointer ([n_voxels] float4 on the association's device), valid until the next successful glio_gmap_add_frames; n_voxels may be null */
+int glio_gmap_points_dev(glio_gmap* gm, const void** points_dev, int* n_voxels);
+/* device time of the last glio_gmap_add_frames (HIP events around its kernels), ms; _stage_ms: the same by stage, ms4 = transform, sort, runs + sums, merge */
+int glio_gmap_last_device_ms(glio_gmap* gm, float* ms);
+int glio_gmap_last_stage_ms(glio_gmap* gm, float* ms4);
+
 #ifdef __cplusplus
 }
 #endif

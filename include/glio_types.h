@@ -294,6 +294,26 @@ typedef struct glio_loop_step_result {
     int32_t rank_deficient;
 } glio_loop_step_result;
 
+/* ---- the global map: mapVisualizationThread's save_pcd part and publishCompleteMap (Estimator.cpp:5315-5350, :5275-5313) on the device (glio_gmap_*).
+ * Default leaf (glio_gmap_opts_default): ds_filter_global_map.setLeafSize(0.2 ...), Estimator.cpp:856. */
+typedef struct glio_gmap_opts {
+    float leaf;                    /* 0.2 */
+    int32_t max_voxels;            /* capacity of the map (4194304); two voxel arrays of 44 B per voxel are held */
+    int32_t max_points_per_add;    /* points one glio_gmap_add_frames may bring (4194304); 44 B of workspace per point */
+    int32_t reserved_;
+} glio_gmap_opts;
+/* what glio_gmap_add_frames reports */
+typedef struct glio_gmap_info {
+    int64_t n_points_total;        /* points added since the last clear */
+    int32_t n_voxels;              /* the map's size */
+    int32_t radix_passes;          /* passes this call's sort ran: 8-bit digits of the call's voxel coordinates counted from the call's own minimum and packed
+                                    * without gaps, ceil((bits(extent x) + bits(extent y) + bits(extent z)) / 8); 0 when every point falls into one voxel */
+    int32_t pcl_index_overflow;    /* 1: the bounding box of everything added since the last clear holds more than INT32_MAX cells.  PCL 1.8.1's VoxelGrid then
+                                    * warns and passes the cloud through UNFILTERED (Estimator.cpp:5343 would save the raw concatenation); this library still filters,
+                                    * with a 64-bit index -- a stated deviation, reported here */
+    int32_t reserved_;
+} glio_gmap_info;
+
 #ifdef __cplusplus
 }
 #endif
