@@ -1,0 +1,1088 @@
+// posegraph_kernels.hip -- the pose graph on the device (glio_pgraph_*): the global graph (reference GLIO/src/Estimator.cpp:4586-4652, :5251-5256) and the
+// local graph (:4561-4581, addLIOFactor :1999-2043, addGNSSFactor :1915-1997) that the reference keeps in one gtsam::ISAM2.  The factor definitions, the
+// retraction and the termination are stated in include/glio_hip.h; everything here is fp64.
+//
+// One Gauss-Newton iteration:
+//   k_pg_lin_nodes    one thread per node i: the chain edge (i-1, i), the chain edge (i, i+1) and the node's unary factors (prior first, then GPS factors in
+//                     insertion order) are evaluated with analytic Jacobians and summed IN THAT ORDER into the node's diagonal block D_i, its coupling
+//                     C_i = H[i][i+1] and its gradient g_i; the node's share of the error is the edge (i, i+1) and its unary factors.  No atomics.
+//   k_pg_lin_loops    one thread per loop edge: its own 12x12 contribution (H_ii, H_ij, H_jj, g_i, g_j) and error
+//   k_pg_error        one workgroup: the total error in a fixed order (strided partial sums, an LDS tree, the loops one after the other), and the
+//                     termination test of the iteration that just ended (gtsam::checkConvergence on the error, never on the step)
+//   k_pg_segments     one wavefront per segment (the chain strictly between two separators): block elimination from the left, the spike E to the left
+//                     separator carried along.  Thirteen lanes each factor the 6x6 pivot block redundantly in registers and solve one of the columns of
+//                     [C_i | E_i | g_i]; 36 + 6 lanes then form the next pivot block, the next spike and the Schur sums.  What the back-substitution needs
+//                     (D^-1 C, D^-1 E, D^-1 g: 78 numbers per node) is kept.
+//   k_pg_sep_zero / k_pg_sep_assemble    the separator system: per separator its diagonal block, its coupling to the previous separator and its gradient
+//                     are gathered per destination (own block, left segment, right segment, the loops in insertion order)
+//   k_pg_sep_factor   ONE workgroup: right-looking Cholesky of the separator system in its own storage -- a band of two 6x6 blocks per row, and full rows
+//                     for the separators that are the later end of a loop (fill stays inside: eliminating column k touches the rest of its block, the
+//                     next block and the full rows that have begun) -- with the right-hand sides carried as extra rows (the forward substitution), then the
+//                     backward substitution, one wavefront per right-hand side
+//   k_pg_backsub      one wavefront per segment, right to left: x_i = -D^-1 g - D^-1 C x_{i+1} - D^-1 E x_left
+//   k_pg_update       x [+] delta per node; unit quaternions with w >= 0
+// Interior nodes first, separators last, each in index order: one exact Cholesky in one fixed order.  Every kernel returns at once when the device has
+// decided that the solve is over, so glio_pgraph_solve enqueues its iterations ahead (the first 12, then -- for a solve that needs them -- all the rest) and
+// waits once for each of the two batches.
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "glio_device.h"
+
+#define PG_MAX_LOOPS 1024
+#define PG_SEP_THREADS 1024
+#define PG_AHEAD 12               /* iterations enqueued before the first wait of a solve */
+#define PG_YS 78                /* per interior node: D^-1 C (36), D^-1 E (36), D^-1 g (6) */
+#define PG_SEGS 120             /* per segment: S_LL (36), S_LR (36), S_RR (36), g_L (6), g_R (6) */
+#define PG_LOOP_OUT 121         /* per loop: H_ii, H_ij, H_jj (36 each), g_i, g_j (6 each), error */
+#define PG_UNARY_PRIOR 0
+#define PG_UNARY_GPS 1
+
+struct PgCtl {
+    double err;                 // the last k_pg_error's sum
+    double err_cur, err0;
+    int done, reason, iterations, pivot_fail;
+    double cov[36];
+};
+
+// ------------------------------------------------------------------------------------------------------------------------------------ small algebra
+__host__ __device__ static inline void pg_qmul(const double* a, const double* b, double* o) {
+    const double w = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
+    const double x = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
+    const double y = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
+    const double z = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
+    o[0] = w; o[1] = x; o[2] = y; o[3] = z;
+}
+__host__ __device__ static inline void pg_qconj(const double* a, double* o) { o[0] = a[0]; o[1] = -a[1]; o[2] = -a[2]; o[3] = -a[3]; }
+// row major R of a unit quaternion
+__host__ __device__ static inline void pg_qmat(const double* q, double* R) {
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z);     R[2] = 2 * (x * z + w * y);
+    R[3] = 2 * (x * y + w * z);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
+    R[6] = 2 * (x * z - w * y);     R[7] = 2 * (y * z + w * x);     R[8] = 1 - 2 * (x * x + y * y);
+}
+__host__ __device__ static inline void pg_mtv(const double* R, const double* v, double* o) {      // R^T v
+    const double a = R[0] * v[0] + R[3] * v[1] + R[6] * v[2], b = R[1] * v[0] + R[4] * v[1] + R[7] * v[2], c = R[2] * v[0] + R[5] * v[1] + R[8] * v[2];
+    o[0] = a; o[1] = b; o[2] = c;
+}
+__host__ __device__ static inline void pg_mv(const double* R, const double* v, double* o) {
+    const double a = R[0] * v[0] + R[1] * v[1] + R[2] * v[2], b = R[3] * v[0] + R[4] * v[1] + R[5] * v[2], c = R[6] * v[0] + R[7] * v[1] + R[8] * v[2];
+    o[0] = a; o[1] = b; o[2] = c;
+}
+// Log of a unit quaternion (include/glio_hip.h)
+__host__ __device__ static inline void pg_log(const double* qin, double* phi) {
+    double w = qin[0], x = qin[1], y = qin[2], z = qin[3];
+    if (w < 0) { w = -w; x = -x; y = -y; z = -z; }
+    const double s = sqrt(x * x + y * y + z * z);
+    double k;
+    if (s < 1e-3) { const double u = s / w, u2 = u * u; k = 2.0 / w * (1.0 - u2 / 3.0 + u2 * u2 / 5.0); }
+    else k = 2.0 * atan2(s, w) / s;
+    phi[0] = k * x; phi[1] = k * y; phi[2] = k * z;
+}
+// the inverse right Jacobian of SO(3), row major
+__host__ __device__ static inline void pg_jrinv(const double* p, double* J) {
+    const double t2 = p[0] * p[0] + p[1] * p[1] + p[2] * p[2];
+    double c;
+    if (t2 < 1e-4) c = 1.0 / 12.0 + t2 / 720.0 + t2 * t2 / 30240.0;
+    else { const double t = sqrt(t2); c = 1.0 / t2 - (1.0 + cos(t)) / (2.0 * t * sin(t)); }
+    const double x = p[0], y = p[1], z = p[2];
+    // [p]x^2 = p p^T - |p|^2 I
+    J[0] = 1 + c * (x * x - t2);     J[1] = -0.5 * z + c * x * y;     J[2] = 0.5 * y + c * x * z;
+    J[3] = 0.5 * z + c * x * y;      J[4] = 1 + c * (y * y - t2);     J[5] = -0.5 * x + c * y * z;
+    J[6] = -0.5 * y + c * x * z;     J[7] = 0.5 * x + c * y * z;      J[8] = 1 + c * (z * z - t2);
+}
+// Exp as a unit quaternion
+__host__ __device__ static inline void pg_exp(const double* d, double* q) {
+    const double t2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    double k;
+    if (t2 < 1e-6) k = 0.5 - t2 / 48.0 + t2 * t2 / 3840.0;
+    else { const double t = sqrt(t2); k = sin(0.5 * t) / t; }
+    q[0] = cos(0.5 * sqrt(t2)); q[1] = k * d[0]; q[2] = k * d[1]; q[3] = k * d[2];
+}
+
+// between factor (xi, xj; meas; w = 1 / sqrt(var)): whitened residual and Jacobians (row major 6x6, tangent rotation first)
+__device__ static inline void pg_between(const double* xi, const double* xj, const double* m, const double* w, double* r, double* Ji, double* Jj) {
+    double qi_c[4], qm_c[4], qij[4], qe[4];
+    pg_qconj(xi + 3, qi_c); pg_qconj(m + 3, qm_c);
+    pg_qmul(qi_c, xj + 3, qij);
+    pg_qmul(qm_c, qij, qe);
+    double phi[3];
+    pg_log(qe, phi);
+    double Ri[9], Rm[9], Rij[9], E[9], Jr[9];
+    pg_qmat(xi + 3, Ri); pg_qmat(m + 3, Rm); pg_qmat(qij, Rij); pg_qmat(qe, E);
+    pg_jrinv(phi, Jr);
+    const double dt[3] = {xj[0] - xi[0], xj[1] - xi[1], xj[2] - xi[2]};
+    double u[3], e[3];
+    pg_mtv(Ri, dt, u);
+    const double um[3] = {u[0] - m[0], u[1] - m[1], u[2] - m[2]};
+    pg_mtv(Rm, um, e);
+    for (int k = 0; k < 3; ++k) { r[k] = w[k] * phi[k]; r[3 + k] = w[3 + k] * e[k]; }
+    for (int k = 0; k < 36; ++k) { Ji[k] = 0; Jj[k] = 0; }
+    // [u]x
+    const double ux[9] = {0, -u[2], u[1], u[2], 0, -u[0], -u[1], u[0], 0};
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) {
+            double s1 = 0, s2 = 0;
+            for (int k = 0; k < 3; ++k) { s1 += Jr[3 * a + k] * Rij[3 * b + k]; s2 += Rm[3 * k + a] * ux[3 * k + b]; }
+            Ji[6 * a + b] = -w[a] * s1;                         // -Jr^-1 Rij^T
+            Ji[6 * (3 + a) + b] = w[3 + a] * s2;                // Rm^T [u]x
+            Ji[6 * (3 + a) + 3 + b] = -w[3 + a] * Rm[3 * b + a];    // -Rm^T
+            Jj[6 * a + b] = w[a] * Jr[3 * a + b];
+            Jj[6 * (3 + a) + 3 + b] = w[3 + a] * E[3 * a + b];
+        }
+}
+// prior (x; meas; w)
+__device__ static inline void pg_prior(const double* x, const double* m, const double* w, double* r, double* J) {
+    double qm_c[4], qe[4], phi[3], Rm[9], E[9], Jr[9], e[3];
+    pg_qconj(m + 3, qm_c);
+    pg_qmul(qm_c, x + 3, qe);
+    pg_log(qe, phi);
+    pg_qmat(m + 3, Rm); pg_qmat(qe, E);
+    pg_jrinv(phi, Jr);
+    const double dt[3] = {x[0] - m[0], x[1] - m[1], x[2] - m[2]};
+    pg_mtv(Rm, dt, e);
+    for (int k = 0; k < 3; ++k) { r[k] = w[k] * phi[k]; r[3 + k] = w[3 + k] * e[k]; }
+    for (int k = 0; k < 36; ++k) J[k] = 0;
+    for (int a = 0; a < 3; ++a)
+        for (int b = 0; b < 3; ++b) { J[6 * a + b] = w[a] * Jr[3 * a + b]; J[6 * (3 + a) + 3 + b] = w[3 + a] * E[3 * a + b]; }
+}
+// H += J^T J (6x6), g += J^T r
+__device__ static inline void pg_acc_self(const double* J, const double* r, double* H, double* g) {
+    for (int a = 0; a < 6; ++a) {
+        for (int b = 0; b < 6; ++b) {
+            double s = 0;
+            for (int k = 0; k < 6; ++k) s += J[6 * k + a] * J[6 * k + b];
+            H[6 * a + b] += s;
+        }
+        double s = 0;
+        for (int k = 0; k < 6; ++k) s += J[6 * k + a] * r[k];
+        g[a] += s;
+    }
+}
+__device__ static inline void pg_cross(const double* Ja, const double* Jb, double* H) {        // H = Ja^T Jb
+    for (int a = 0; a < 6; ++a)
+        for (int b = 0; b < 6; ++b) {
+            double s = 0;
+            for (int k = 0; k < 6; ++k) s += Ja[6 * k + a] * Jb[6 * k + b];
+            H[6 * a + b] = s;
+        }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------ tables
+struct PgGraph {
+    int N, U, L;
+    const double* x;            // [N][7] t, q
+    const double* cm;           // [N][7] measurement of the chain edge INTO node i (i >= 1)
+    const double* cw;           // [N][6] its 1 / sqrt(var)
+    const int* un_node;         // [U] sorted by node, insertion order within a node (the prior of node 0 first)
+    const int* un_type;
+    const double* un_m;         // [U][7]
+    const double* un_w;         // [U][6]
+    const int* lp_i; const int* lp_j;
+    const double* lp_m;         // [L][7]
+    const double* lp_w;         // [L][6]
+};
+struct PgLin { double* D; double* C; double* g; double* nerr; double* lp_out; };
+// the elimination's plan (host) and storage
+struct PgPlan {
+    int S, nW, nrhs, n;         // separators, full-row separators, right-hand sides, n = 6 S
+    int cov_sep;                // the separator whose block of the inverse is asked (nrhs == 6), else -1
+    const int* sep_node;        // [S] ascending
+    const int* sep_w;           // [S] index among the full-row separators, or -1
+    const int* w_blk;           // [nW] ascending separator index
+    const int* w_lo;            // [nW] the earliest separator it is linked to
+    const int* lp_si; const int* lp_sj;     // [L] separator index of either end
+    const int* sl_off;          // [S + 1] the loops at a separator, insertion order ...
+    const int* sl_idx;          // ... 2 * loop + (0: the separator is the loop's i, 1: its j)
+    double* Y;                  // [N][PG_YS]
+    double* seg;                // [S - 1][PG_SEGS]
+    double* band;               // [n][12]
+    double* wide;               // [6 nW + nrhs][n]
+    double* ldiag;              // [n]
+    double* delta;              // [N][6]
+};
+
+__device__ static inline double* pg_A(const PgPlan& p, int r, int c) {
+    if (r >= p.n) return p.wide + (size_t)(6 * p.nW + (r - p.n)) * p.n + c;
+    const int b = r / 6, w = p.sep_w[b];
+    if (w >= 0) return p.wide + (size_t)(6 * w + (r - 6 * b)) * p.n + c;
+    return p.band + (size_t)r * 12 + (c - 6 * (b - 1));
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------ linearise
+__global__ void __launch_bounds__(64) k_pg_lin_nodes(PgGraph G, PgLin out, const PgCtl* ctl) {
+    if (ctl->done || ctl->pivot_fail) return;
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= G.N) return;
+    double D[36], g[6], r[6], Ji[36], Jj[36];
+    for (int k = 0; k < 36; ++k) D[k] = 0;
+    for (int k = 0; k < 6; ++k) g[k] = 0;
+    double err = 0;
+    double xi[7];
+    for (int k = 0; k < 7; ++k) xi[k] = G.x[(size_t)7 * i + k];
+    if (i > 0) {
+        pg_between(G.x + (size_t)7 * (i - 1), xi, G.cm + (size_t)7 * i, G.cw + (size_t)6 * i, r, Ji, Jj);
+        pg_acc_self(Jj, r, D, g);
+    }
+    double* C = out.C + (size_t)36 * i;
+    if (i + 1 < G.N) {
+        pg_between(xi, G.x + (size_t)7 * (i + 1), G.cm + (size_t)7 * (i + 1), G.cw + (size_t)6 * (i + 1), r, Ji, Jj);
+        pg_acc_self(Ji, r, D, g);
+        double Cc[36];
+        pg_cross(Ji, Jj, Cc);
+        for (int k = 0; k < 36; ++k) C[k] = Cc[k];
+        double s = 0;
+        for (int k = 0; k < 6; ++k) s += r[k] * r[k];
+        err += 0.5 * s;
+    } else {
+        for (int k = 0; k < 36; ++k) C[k] = 0;
+    }
+    // the node's unary factors: the first entry of the sorted table with un_node >= i
+    int lo = 0, hi = G.U;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (G.un_node[mid] < i) lo = mid + 1; else hi = mid; }
+    for (int u = lo; u < G.U && G.un_node[u] == i; ++u) {
+        const double* m = G.un_m + (size_t)7 * u;
+        const double* w = G.un_w + (size_t)6 * u;
+        if (G.un_type[u] == PG_UNARY_PRIOR) {
+            pg_prior(xi, m, w, r, Ji);
+            pg_acc_self(Ji, r, D, g);
+            double s = 0;
+            for (int k = 0; k < 6; ++k) s += r[k] * r[k];
+            err += 0.5 * s;
+        } else {
+            // GPS: r = t - p, J = [0 R]: J^T J = diag-weighted R^T W R in the translation block
+            double R[9];
+            pg_qmat(xi + 3, R);
+            double rr[3], s = 0;
+            for (int k = 0; k < 3; ++k) { rr[k] = w[k] * (xi[k] - m[k]); s += rr[k] * rr[k]; }
+            for (int a = 0; a < 3; ++a) {
+                for (int b = 0; b < 3; ++b) {
+                    double h = 0;
+                    for (int k = 0; k < 3; ++k) h += (w[k] * R[3 * k + a]) * (w[k] * R[3 * k + b]);
+                    D[6 * (3 + a) + 3 + b] += h;
+                }
+                double h = 0;
+                for (int k = 0; k < 3; ++k) h += (w[k] * R[3 * k + a]) * rr[k];
+                g[3 + a] += h;
+            }
+            err += 0.5 * s;
+        }
+    }
+    for (int k = 0; k < 36; ++k) out.D[(size_t)36 * i + k] = D[k];
+    for (int k = 0; k < 6; ++k) out.g[(size_t)6 * i + k] = g[k];
+    out.nerr[i] = err;
+}
+
+__global__ void __launch_bounds__(64) k_pg_lin_loops(PgGraph G, PgLin out, const PgCtl* ctl) {
+    if (ctl->done || ctl->pivot_fail) return;
+    const int l = blockIdx.x * 64 + threadIdx.x;
+    if (l >= G.L) return;
+    double r[6], Ji[36], Jj[36];
+    pg_between(G.x + (size_t)7 * G.lp_i[l], G.x + (size_t)7 * G.lp_j[l], G.lp_m + (size_t)7 * l, G.lp_w + (size_t)6 * l, r, Ji, Jj);
+    double* o = out.lp_out + (size_t)PG_LOOP_OUT * l;
+    double H[36], g[6];
+    for (int k = 0; k < 36; ++k) H[k] = 0;
+    for (int k = 0; k < 6; ++k) g[k] = 0;
+    pg_acc_self(Ji, r, H, g);
+    for (int k = 0; k < 36; ++k) o[k] = H[k];
+    for (int k = 0; k < 6; ++k) o[108 + k] = g[k];
+    pg_cross(Ji, Jj, H);
+    for (int k = 0; k < 36; ++k) o[36 + k] = H[k];
+    for (int k = 0; k < 36; ++k) H[k] = 0;
+    for (int k = 0; k < 6; ++k) g[k] = 0;
+    pg_acc_self(Jj, r, H, g);
+    for (int k = 0; k < 36; ++k) o[72 + k] = H[k];
+    for (int k = 0; k < 6; ++k) o[114 + k] = g[k];
+    double s = 0;
+    for (int k = 0; k < 6; ++k) s += r[k] * r[k];
+    o[120] = 0.5 * s;
+}
+
+// phase -1: the sum only; 0: the start of a solve; 1: the end of an iteration (gtsam::checkConvergence, unpinned)
+__global__ void __launch_bounds__(1024) k_pg_error(int N, int L, const double* nerr, const double* lp_out, PgCtl* ctl, int phase, int max_iter, double rel_tol, double abs_tol) {
+    if (ctl->done) return;
+    __shared__ double sh[1024];
+    const int t = threadIdx.x;
+    if (ctl->pivot_fail) {
+        if (t == 0) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_NONPOSITIVE_PIVOT; }
+        return;
+    }
+    double s = 0;
+    for (int i = t; i < N; i += 1024) s += nerr[i];
+    sh[t] = s;
+    __syncthreads();
+    for (int h = 512; h > 0; h >>= 1) {
+        if (t < h) sh[t] += sh[t + h];
+        __syncthreads();
+    }
+    if (t != 0) return;
+    double e = sh[0];
+    for (int l = 0; l < L; ++l) e += lp_out[(size_t)PG_LOOP_OUT * l + 120];
+    ctl->err = e;
+    if (phase < 0) return;
+    if (phase == 0) {
+        ctl->err0 = e; ctl->err_cur = e; ctl->iterations = 0;
+        if (max_iter <= 0) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_ITERATION_LIMIT; }
+        return;
+    }
+    const double cur = ctl->err_cur;
+    const int it = ctl->iterations + 1;
+    ctl->iterations = it;
+    ctl->err_cur = e;
+    const double dec = cur - e;
+    const bool conv = (e <= 0.0) || (rel_tol != 0.0 && dec / cur <= rel_tol) || (dec <= abs_tol);
+    if (conv) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_CONVERGED; }
+    else if (it >= max_iter) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_ITERATION_LIMIT; }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------ segments
+// in-register Cholesky of the symmetric 6x6 A (lower part read), then A^-1 b; returns false on a non-positive (or NaN) pivot
+__device__ static inline bool pg_chol6(const double* A, double* Lm) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double d = A[6 * j + j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) d -= Lm[6 * j + k] * Lm[6 * j + k];
+        if (!(d > 0.0)) { ok = false; d = 1.0; }
+        const double sd = sqrt(d), inv = 1.0 / sd;
+        Lm[6 * j + j] = sd;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double s = A[6 * i + j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s -= Lm[6 * i + k] * Lm[6 * j + k];
+            Lm[6 * i + j] = s * inv;
+        }
+    }
+    return ok;
+}
+__device__ static inline void pg_chol6_solve(const double* Lm, double* b) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double s = b[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) s -= Lm[6 * i + k] * b[k];
+        b[i] = s / Lm[6 * i + i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double s = b[i];
+#pragma unroll
+        for (int k = i + 1; k < 6; ++k) s -= Lm[6 * k + i] * b[k];
+        b[i] = s / Lm[6 * i + i];
+    }
+}
+
+__global__ void __launch_bounds__(64) k_pg_segments(PgPlan P, PgLin lin, PgCtl* ctl) {
+    if (ctl->done || ctl->pivot_fail) return;
+    const int k = blockIdx.x;                 // segment between separators k and k + 1
+    const int lane = threadIdx.x;
+    const int sL = P.sep_node[k], sR = P.sep_node[k + 1];
+    const int a = sL + 1, b = sR - 1;
+    double* so = P.seg + (size_t)PG_SEGS * k;
+    if (b < a) {                                // no interior node: the chain edge couples the two separators directly
+        if (lane < 36) { so[lane] = 0; so[36 + lane] = lin.C[(size_t)36 * sL + lane]; so[72 + lane] = 0; }
+        else if (lane < 48) so[108 + lane - 36] = 0;
+        return;
+    }
+    __shared__ double sD[36], sE[36], sg[6], sC[36], sY[PG_YS];
+    const int r6 = lane < 36 ? lane / 6 : (lane < 42 ? lane - 36 : 0), c6 = lane < 36 ? lane % 6 : 0;
+    if (lane < 36) { sD[lane] = lin.D[(size_t)36 * a + lane]; sE[lane] = lin.C[(size_t)36 * sL + 6 * c6 + r6]; }
+    else if (lane < 42) sg[lane - 36] = lin.g[(size_t)6 * a + lane - 36];
+    double acc = 0;                             // lanes < 36: S_LL entry; lanes 36 .. 41: g_L entry
+    for (int i = a; i <= b; ++i) {
+        if (lane < 36) sC[lane] = lin.C[(size_t)36 * i + lane];
+        __syncthreads();
+        // thirteen lanes: column `lane` of D^-1 [C | E | g]
+        {
+            double A[36], Lm[36], col[6];
+#pragma unroll
+            for (int q = 0; q < 36; ++q) A[q] = sD[q];
+            const bool ok = pg_chol6(A, Lm);
+            if (!ok) {                          // every lane sees the same block: the whole wavefront leaves
+                if (lane == 0) ctl->pivot_fail = 1;
+                return;
+            }
+            if (lane < 13) {
+#pragma unroll
+                for (int q = 0; q < 6; ++q) col[q] = lane < 6 ? sC[6 * q + lane] : (lane < 12 ? sE[6 * q + lane - 6] : sg[q]);
+                pg_chol6_solve(Lm, col);
+                double* Yg = P.Y + (size_t)PG_YS * i;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) {
+                    const int at = lane < 6 ? 6 * q + lane : (lane < 12 ? 36 + 6 * q + lane - 6 : 72 + q);
+                    sY[at] = col[q]; Yg[at] = col[q];
+                }
+            }
+        }
+        __syncthreads();
+        double nD = 0, nE = 0;
+        if (i < b) {
+            if (lane < 36) {
+                double s1 = 0, s2 = 0, s3 = 0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) { s1 += sC[6 * q + r6] * sY[6 * q + c6]; s2 += sC[6 * q + r6] * sY[36 + 6 * q + c6]; s3 += sE[6 * q + r6] * sY[36 + 6 * q + c6]; }
+                nD = lin.D[(size_t)36 * (i + 1) + lane] - s1; nE = -s2; acc -= s3;
+            } else if (lane < 42) {
+                double s1 = 0, s3 = 0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) { s1 += sC[6 * q + r6] * sY[72 + q]; s3 += sE[6 * q + r6] * sY[72 + q]; }
+                nD = lin.g[(size_t)6 * (i + 1) + r6] - s1; acc -= s3;
+            }
+        } else {
+            if (lane < 36) {
+                double s1 = 0, s2 = 0, s3 = 0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) { s1 += sC[6 * q + r6] * sY[6 * q + c6]; s2 += sE[6 * q + r6] * sY[6 * q + c6]; s3 += sE[6 * q + r6] * sY[36 + 6 * q + c6]; }
+                acc -= s3;
+                so[lane] = acc; so[36 + lane] = -s2; so[72 + lane] = -s1;
+            } else if (lane < 42) {
+                double s1 = 0, s3 = 0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) { s1 += sC[6 * q + r6] * sY[72 + q]; s3 += sE[6 * q + r6] * sY[72 + q]; }
+                acc -= s3;
+                so[108 + r6] = acc; so[114 + r6] = -s1;
+            }
+        }
+        __syncthreads();
+        if (i < b) {
+            if (lane < 36) { sD[lane] = nD; sE[lane] = nE; }
+            else if (lane < 42) sg[lane - 36] = nD;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(64) k_pg_backsub(PgPlan P, const PgCtl* ctl) {
+    if (ctl->done || ctl->pivot_fail) return;
+    const int k = blockIdx.x, lane = threadIdx.x, r = lane % 6;
+    const int sL = P.sep_node[k], sR = P.sep_node[k + 1];
+    const double xl = P.delta[(size_t)6 * sL + r];
+    double xn = P.delta[(size_t)6 * sR + r];
+    for (int i = sR - 1; i > sL; --i) {
+        const double* Y = P.Y + (size_t)PG_YS * i;
+        double s = -Y[72 + r];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) s -= Y[6 * r + c] * __shfl(xn, c);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) s -= Y[36 + 6 * r + c] * __shfl(xl, c);
+        xn = s;
+        if (lane < 6) P.delta[(size_t)6 * i + r] = s;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------ separator system
+__global__ void k_pg_sep_zero(PgPlan P, const PgCtl* ctl) {
+    if (ctl->done || ctl->pivot_fail) return;
+    const size_t nb = (size_t)P.n * 12, nw = (size_t)(6 * P.nW + P.nrhs) * P.n;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nb + nw; i += (size_t)gridDim.x * blockDim.x) {
+        if (i < nb) P.band[i] = 0; else P.wide[i - nb] = 0;
+    }
+}
+
+__global__ void __launch_bounds__(64) k_pg_sep_assemble(PgPlan P, PgLin lin, const PgCtl* ctl) {
+    if (ctl->done || ctl->pivot_fail) return;
+    const int k = blockIdx.x, e = threadIdx.x;
+    if (e >= 42) return;
+    const int s = P.sep_node[k];
+    const double* segl = k > 0 ? P.seg + (size_t)PG_SEGS * (k - 1) : nullptr;
+    const double* segr = k + 1 < P.S ? P.seg + (size_t)PG_SEGS * k : nullptr;
+    if (e < 36) {
+        const int r = e / 6, c = e % 6;
+        double v = lin.D[(size_t)36 * s + e];
+        if (segl) v += segl[72 + e];
+        if (segr) v += segr[e];
+        for (int q = P.sl_off[k]; q < P.sl_off[k + 1]; ++q) {
+            const int l = P.sl_idx[q] >> 1, end = P.sl_idx[q] & 1;
+            v += lin.lp_out[(size_t)PG_LOOP_OUT * l + (end ? 72 : 0) + e];
+        }
+        if (c <= r) *pg_A(P, 6 * k + r, 6 * k + c) = v;
+        if (segl) *pg_A(P, 6 * k + r, 6 * (k - 1) + c) = segl[36 + 6 * c + r];       // H[k][k-1] = S_LR^T
+        for (int q = P.sl_off[k]; q < P.sl_off[k + 1]; ++q) {
+            const int l = P.sl_idx[q] >> 1, end = P.sl_idx[q] & 1;
+            const int other = end ? P.lp_si[l] : P.lp_sj[l];
+            if (other > k) continue;            // stored in the later separator's rows
+            const double* Hij = lin.lp_out + (size_t)PG_LOOP_OUT * l + 36;
+            *pg_A(P, 6 * k + r, 6 * other + c) += end ? Hij[6 * c + r] : Hij[6 * r + c];
+        }
+    } else {
+        const int r = e - 36;
+        double v = lin.g[(size_t)6 * s + r];
+        if (segl) v += segl[114 + r];
+        if (segr) v += segr[108 + r];
+        for (int q = P.sl_off[k]; q < P.sl_off[k + 1]; ++q) {
+            const int l = P.sl_idx[q] >> 1, end = P.sl_idx[q] & 1;
+            v += lin.lp_out[(size_t)PG_LOOP_OUT * l + (end ? 114 : 108) + r];
+        }
+        if (P.cov_sep < 0) *pg_A(P, P.n, 6 * k + r) = -v;
+        else if (k == P.cov_sep) *pg_A(P, P.n + r, 6 * k + r) = 1.0;
+    }
+}
+
+// the rows that eliminating a column of block b touches: block b itself, block b + 1, the full-row separators from b + 2 on that have begun, the right-hand sides
+__device__ static inline int pg_rowset(const PgPlan& P, int b, int* rows, int* wtot) {
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int base = 6 + (b + 1 < P.S ? 6 : 0);
+    if (t < 6) rows[t] = 6 * b + t;
+    else if (t < base) rows[t] = 6 * (b + 1) + t - 6;
+    bool on = false;
+    if (t < P.nW) on = P.w_blk[t] >= b + 2 && P.w_lo[t] <= b;
+    const unsigned long long m = __ballot(on);
+    if (lane == 0) wtot[wave] = __popcll(m);
+    __syncthreads();
+    int off = 0, total = 0;
+    for (int w = 0; w < PG_SEP_THREADS / 64; ++w) { if (w < wave) off += wtot[w]; total += wtot[w]; }
+    if (on) {
+        const int at = base + 6 * (off + __popcll(m & ((1ull << lane) - 1ull)));
+        for (int q = 0; q < 6; ++q) rows[at + q] = 6 * P.w_blk[t] + q;
+    }
+    const int m0 = base + 6 * total;
+    if (t < P.nrhs) rows[m0 + t] = P.n + t;
+    __syncthreads();
+    return m0 + P.nrhs;
+}
+
+__global__ void __launch_bounds__(PG_SEP_THREADS) k_pg_sep_factor(PgPlan P, PgCtl* ctl) {
+    if (ctl->done || ctl->pivot_fail) return;
+    __shared__ int rows[12 + 6 * PG_MAX_LOOPS + 6];
+    __shared__ int wtot[PG_SEP_THREADS / 64];
+    const int t = threadIdx.x;
+    int m = 0;
+    for (int k = 0; k < P.n; ++k) {
+        const int b = k / 6;
+        if (k == 6 * b) m = pg_rowset(P, b, rows, wtot);
+        const double piv = *pg_A(P, k, k);
+        if (!(piv > 0.0)) {                     // uniform: every thread reads the same number
+            if (t == 0) ctl->pivot_fail = 1;
+            return;
+        }
+        const double d = sqrt(piv);
+        const int start = k - 6 * b + 1, mm = m - start;
+        if (t == 0) P.ldiag[k] = d;
+        for (int q = t; q < mm; q += PG_SEP_THREADS) { double* p = pg_A(P, rows[start + q], k); *p = *p / d; }
+        __syncthreads();
+        for (int q = t; q < mm * mm; q += PG_SEP_THREADS) {
+            const int ri = q / mm, ci = q - ri * mm;
+            if (ci > ri) continue;
+            const int r = rows[start + ri], c = rows[start + ci];
+            if (c >= P.n) continue;
+            *pg_A(P, r, c) -= *pg_A(P, r, k) * *pg_A(P, c, k);
+        }
+        __syncthreads();
+    }
+    // backward substitution, one wavefront per right-hand side, in place of the forward result in the right-hand side's row
+    const int wave = t >> 6, lane = t & 63;
+    for (int b = P.S - 1; b >= 0; --b) {
+        m = pg_rowset(P, b, rows, wtot);
+        const int mrows = m - P.nrhs;           // without the right-hand sides
+        if (wave < P.nrhs) {
+            double* x = P.wide + (size_t)(6 * P.nW + wave) * P.n;
+            for (int k = 6 * b + 5; k >= 6 * b; --k) {
+                const int start = k - 6 * b + 1;
+                double s = 0;
+                for (int q = start + lane; q < mrows; q += 64) { const int r = rows[q]; s += *pg_A(P, r, k) * x[r]; }
+                for (int h = 32; h > 0; h >>= 1) s += __shfl_xor(s, h);
+                if (lane == 0) x[k] = (x[k] - s) / P.ldiag[k];
+                __threadfence_block();
+            }
+        }
+        __syncthreads();
+    }
+    if (P.cov_sep < 0) {
+        const double* x = P.wide + (size_t)(6 * P.nW) * P.n;
+        for (int q = t; q < P.n; q += PG_SEP_THREADS) P.delta[(size_t)6 * P.sep_node[q / 6] + q % 6] = x[q];
+    } else if (t < 36) {
+        const int r = t / 6, c = t % 6, hi = r > c ? r : c, lo = r > c ? c : r;      // the lower triangle, mirrored: symmetric to the bit
+        ctl->cov[t] = P.wide[(size_t)(6 * P.nW + lo) * P.n + 6 * P.cov_sep + hi];
+    }
+}
+
+__global__ void __launch_bounds__(256) k_pg_update(int N, double* x, const double* delta, const PgCtl* ctl) {
+    if (ctl->done || ctl->pivot_fail) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    double* p = x + (size_t)7 * i;
+    const double* d = delta + (size_t)6 * i;
+    double R[9], dq[4], q[4], dt[3];
+    pg_qmat(p + 3, R);
+    pg_mv(R, d + 3, dt);
+    pg_exp(d, dq);
+    pg_qmul(p + 3, dq, q);
+    double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+    if (q[0] < 0) nrm = -nrm;
+    for (int k = 0; k < 3; ++k) p[k] += dt[k];
+    for (int k = 0; k < 4; ++k) p[3 + k] = q[k] / nrm;
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------ the object
+struct glio_pgraph {
+    int device;
+    glio_pgraph_opts o;
+    hipStream_t stream;
+    hipEvent_t ev_done, ev_t[6];
+    // the graph as the host holds it
+    int N, n_dev;                               // nodes; nodes whose rows are already on the device
+    std::vector<double> h_x, h_cm, h_cw;        // rows [n_dev, N) wait for their upload (rows below n_dev of h_x are stale: the device holds the estimate)
+    int have_prior; double prior_m[7], prior_w[6];
+    std::vector<int> gps_node; std::vector<double> gps_m, gps_w;
+    std::vector<int> lp_i, lp_j; std::vector<double> lp_m, lp_w;
+    int factors_dirty;
+    // device
+    double* d_x; double* d_x0; double* d_cm; double* d_cw;
+    int* d_un_node; int* d_un_type; double* d_un_m; double* d_un_w; int U;
+    int* d_lp_i; int* d_lp_j; double* d_lp_m; double* d_lp_w;
+    double* d_D; double* d_C; double* d_g; double* d_nerr; double* d_lp_out;
+    double* d_Y; double* d_seg; double* d_delta;
+    int* d_plan; size_t plan_cap;               // one int block: sep_node, sep_w, w_blk, w_lo, lp_si, lp_sj, sl_off, sl_idx
+    double* d_sys; size_t sys_cap;              // band, wide, ldiag
+    PgCtl* d_ctl; PgCtl* h_ctl;
+};
+
+#define PG_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { glio_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); return GLIO_E_HIP; } } while (0)
+
+static bool pg_finite(const double* v, int n) {
+    for (int k = 0; k < n; ++k) if (!(fabs(v[k]) <= DBL_MAX)) return false;
+    return true;
+}
+static bool pg_var_ok(const double* v, int n) {
+    for (int k = 0; k < n; ++k) if (!(v[k] > 0.0) || !(v[k] <= DBL_MAX)) return false;
+    return true;
+}
+// t, q with q normalised and w >= 0; false for a pose that is not finite or has no rotation
+static bool pg_pose_in(const double* in, double* out) {
+    if (!pg_finite(in, 7)) return false;
+    const double n = sqrt(in[3] * in[3] + in[4] * in[4] + in[5] * in[5] + in[6] * in[6]);
+    if (!(n > 0.0) || !(n <= DBL_MAX)) return false;
+    const double s = in[3] < 0 ? -n : n;
+    for (int k = 0; k < 3; ++k) out[k] = in[k];
+    for (int k = 0; k < 4; ++k) out[3 + k] = in[3 + k] / s;
+    return true;
+}
+// between(a, b): t = Ra^T (tb - ta), q = qa^-1 qb
+static void pg_between_meas(const double* a, const double* b, double* m) {
+    double R[9], qc[4];
+    pg_qmat(a + 3, R);
+    const double dt[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+    pg_mtv(R, dt, m);
+    pg_qconj(a + 3, qc);
+    pg_qmul(qc, b + 3, m + 3);
+}
+
+static int pg_flush_nodes(glio_pgraph* pg) {
+    if (pg->n_dev < pg->N) {
+        const size_t a = pg->n_dev, n = pg->N - pg->n_dev;
+        PG_CHECK(hipMemcpyAsync(pg->d_x + 7 * a, pg->h_x.data() + 7 * a, n * 7 * 8, hipMemcpyHostToDevice, pg->stream));
+        PG_CHECK(hipMemcpyAsync(pg->d_cm + 7 * a, pg->h_cm.data() + 7 * a, n * 7 * 8, hipMemcpyHostToDevice, pg->stream));
+        PG_CHECK(hipMemcpyAsync(pg->d_cw + 6 * a, pg->h_cw.data() + 6 * a, n * 6 * 8, hipMemcpyHostToDevice, pg->stream));
+        PG_CHECK(hipStreamSynchronize(pg->stream));     // pageable sources: nothing may change under the copy
+        pg->n_dev = pg->N;
+    }
+    return GLIO_OK;
+}
+static int pg_flush_factors(glio_pgraph* pg) {
+    if (!pg->factors_dirty) return GLIO_OK;
+    // the unary table sorted by node, insertion order within a node, the prior of node 0 first
+    const int ng = (int)pg->gps_node.size();
+    std::vector<int> order(ng);
+    for (int k = 0; k < ng; ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pg->gps_node[a] < pg->gps_node[b]; });
+    const int U = ng + (pg->have_prior ? 1 : 0);
+    std::vector<int> node(U), type(U); std::vector<double> m((size_t)7 * U, 0.0), w((size_t)6 * U, 0.0);
+    int at = 0;
+    if (pg->have_prior) { node[0] = 0; type[0] = PG_UNARY_PRIOR; memcpy(&m[0], pg->prior_m, 56); memcpy(&w[0], pg->prior_w, 48); at = 1; }
+    for (int k = 0; k < ng; ++k, ++at) {
+        const int s = order[k];
+        node[at] = pg->gps_node[s]; type[at] = PG_UNARY_GPS;
+        memcpy(&m[(size_t)7 * at], &pg->gps_m[(size_t)3 * s], 24); memcpy(&w[(size_t)6 * at], &pg->gps_w[(size_t)3 * s], 24);
+    }
+    if (U) {
+        PG_CHECK(hipMemcpy(pg->d_un_node, node.data(), (size_t)U * 4, hipMemcpyHostToDevice)); PG_CHECK(hipMemcpy(pg->d_un_type, type.data(), (size_t)U * 4, hipMemcpyHostToDevice));
+        PG_CHECK(hipMemcpy(pg->d_un_m, m.data(), (size_t)U * 56, hipMemcpyHostToDevice)); PG_CHECK(hipMemcpy(pg->d_un_w, w.data(), (size_t)U * 48, hipMemcpyHostToDevice));
+    }
+    pg->U = U;
+    const size_t L = pg->lp_i.size();
+    if (L) {
+        PG_CHECK(hipMemcpy(pg->d_lp_i, pg->lp_i.data(), L * 4, hipMemcpyHostToDevice)); PG_CHECK(hipMemcpy(pg->d_lp_j, pg->lp_j.data(), L * 4, hipMemcpyHostToDevice));
+        PG_CHECK(hipMemcpy(pg->d_lp_m, pg->lp_m.data(), L * 56, hipMemcpyHostToDevice)); PG_CHECK(hipMemcpy(pg->d_lp_w, pg->lp_w.data(), L * 48, hipMemcpyHostToDevice));
+    }
+    pg->factors_dirty = 0;
+    return GLIO_OK;
+}
+static PgGraph pg_graph(const glio_pgraph* pg) {
+    PgGraph G;
+    G.N = pg->N; G.U = pg->U; G.L = (int)pg->lp_i.size();
+    G.x = pg->d_x; G.cm = pg->d_cm; G.cw = pg->d_cw;
+    G.un_node = pg->d_un_node; G.un_type = pg->d_un_type; G.un_m = pg->d_un_m; G.un_w = pg->d_un_w;
+    G.lp_i = pg->d_lp_i; G.lp_j = pg->d_lp_j; G.lp_m = pg->d_lp_m; G.lp_w = pg->d_lp_w;
+    return G;
+}
+static PgLin pg_lin(const glio_pgraph* pg) { PgLin l; l.D = pg->d_D; l.C = pg->d_C; l.g = pg->d_g; l.nerr = pg->d_nerr; l.lp_out = pg->d_lp_out; return l; }
+
+static int pg_segment_nodes(const glio_pgraph* pg) {
+    if (pg->o.segment_nodes > 0) return pg->o.segment_nodes;
+    const int m = (int)lround(sqrt((double)pg->N));
+    return std::min(255, std::max(4, m));
+}
+// the separators (node 0, the last node, every loop endpoint, the node whose covariance is asked, and a node after every segment_nodes interior nodes), the
+// full-row separators, the loops per separator: computed on the host, one upload
+static int pg_make_plan(glio_pgraph* pg, int cov_node, PgPlan* P) {
+    const int N = pg->N, L = (int)pg->lp_i.size(), seg = pg_segment_nodes(pg);
+    std::vector<int> forced;
+    forced.push_back(0); forced.push_back(N - 1);
+    for (int l = 0; l < L; ++l) { forced.push_back(pg->lp_i[l]); forced.push_back(pg->lp_j[l]); }
+    if (cov_node >= 0) forced.push_back(cov_node);
+    std::sort(forced.begin(), forced.end());
+    forced.erase(std::unique(forced.begin(), forced.end()), forced.end());
+    std::vector<int> sep;
+    for (size_t f = 0; f < forced.size(); ++f) {
+        if (f > 0) for (long long s = (long long)forced[f - 1] + seg + 1; s < forced[f]; s += seg + 1) sep.push_back((int)s);
+        sep.push_back(forced[f]);
+    }
+    const int S = (int)sep.size();
+    auto sep_of = [&](int node) { return (int)(std::lower_bound(sep.begin(), sep.end(), node) - sep.begin()); };
+    std::vector<int> lp_si(L), lp_sj(L), lo(S);
+    for (int k = 0; k < S; ++k) lo[k] = k;
+    std::vector<std::vector<int>> at(S);
+    for (int l = 0; l < L; ++l) {
+        const int a = sep_of(pg->lp_i[l]), b = sep_of(pg->lp_j[l]);
+        lp_si[l] = a; lp_sj[l] = b;
+        at[a].push_back(2 * l); at[b].push_back(2 * l + 1);
+        const int hi = std::max(a, b), lw = std::min(a, b);
+        lo[hi] = std::min(lo[hi], lw);
+    }
+    std::vector<int> sep_w(S, -1), w_blk, w_lo;
+    for (int k = 0; k < S; ++k) if (lo[k] < k) { sep_w[k] = (int)w_blk.size(); w_blk.push_back(k); w_lo.push_back(lo[k]); }
+    const int nW = (int)w_blk.size();
+    std::vector<int> sl_off(S + 1, 0), sl_idx;
+    for (int k = 0; k < S; ++k) { for (int v : at[k]) sl_idx.push_back(v); sl_off[k + 1] = (int)sl_idx.size(); }
+    // one block of ints
+    std::vector<int> blk;
+    auto put = [&](const std::vector<int>& v) { const size_t o = blk.size(); blk.insert(blk.end(), v.begin(), v.end()); return o; };
+    const size_t o_sep = put(sep), o_sw = put(sep_w), o_wb = put(w_blk), o_wl = put(w_lo), o_si = put(lp_si), o_sj = put(lp_sj), o_off = put(sl_off), o_idx = put(sl_idx);
+    if (blk.size() > pg->plan_cap) {
+        if (pg->d_plan) { hipFree(pg->d_plan); pg->d_plan = nullptr; pg->plan_cap = 0; }
+        const size_t cap = blk.size() * 2;
+        PG_CHECK(hipMalloc((void**)&pg->d_plan, cap * 4));
+        pg->plan_cap = cap;
+    }
+    PG_CHECK(hipMemcpy(pg->d_plan, blk.data(), blk.size() * 4, hipMemcpyHostToDevice));
+    const int nrhs = cov_node >= 0 ? 6 : 1, n = 6 * S;
+    const size_t need = (size_t)n * 12 + (size_t)(6 * nW + nrhs) * n + n;
+    if (need > pg->sys_cap) {
+        if (pg->d_sys) { hipFree(pg->d_sys); pg->d_sys = nullptr; pg->sys_cap = 0; }
+        const size_t cap = need + need / 2;
+        PG_CHECK(hipMalloc((void**)&pg->d_sys, cap * 8));
+        pg->sys_cap = cap;
+    }
+    P->S = S; P->nW = nW; P->nrhs = nrhs; P->n = n;
+    P->cov_sep = cov_node >= 0 ? sep_of(cov_node) : -1;
+    P->sep_node = pg->d_plan + o_sep; P->sep_w = pg->d_plan + o_sw; P->w_blk = pg->d_plan + o_wb; P->w_lo = pg->d_plan + o_wl;
+    P->lp_si = pg->d_plan + o_si; P->lp_sj = pg->d_plan + o_sj; P->sl_off = pg->d_plan + o_off; P->sl_idx = pg->d_plan + o_idx;
+    P->Y = pg->d_Y; P->seg = pg->d_seg; P->delta = pg->d_delta;
+    P->band = pg->d_sys; P->wide = pg->d_sys + (size_t)n * 12; P->ldiag = P->wide + (size_t)(6 * nW + nrhs) * n;
+    return GLIO_OK;
+}
+
+static void pg_enqueue_linearise(glio_pgraph* pg, int phase) {
+    const PgGraph G = pg_graph(pg);
+    const PgLin lin = pg_lin(pg);
+    hipLaunchKernelGGL(k_pg_lin_nodes, dim3((G.N + 63) / 64), dim3(64), 0, pg->stream, G, lin, pg->d_ctl);
+    if (G.L) hipLaunchKernelGGL(k_pg_lin_loops, dim3((G.L + 63) / 64), dim3(64), 0, pg->stream, G, lin, pg->d_ctl);
+    hipLaunchKernelGGL(k_pg_error, dim3(1), dim3(1024), 0, pg->stream, G.N, G.L, pg->d_nerr, pg->d_lp_out, pg->d_ctl, phase, pg->o.max_iterations,
+                       pg->o.relative_error_tol, pg->o.absolute_error_tol);
+}
+// segments, separator system, back-substitution of one linear solve; ev (may be null): events after the segments and after the separator system
+static void pg_enqueue_linear_solve(glio_pgraph* pg, const PgPlan& P, hipEvent_t* ev) {
+    const PgLin lin = pg_lin(pg);
+    if (P.S > 1) hipLaunchKernelGGL(k_pg_segments, dim3(P.S - 1), dim3(64), 0, pg->stream, P, lin, pg->d_ctl);
+    if (ev) hipEventRecord(ev[0], pg->stream);
+    const size_t cells = (size_t)P.n * 12 + (size_t)(6 * P.nW + P.nrhs) * P.n;
+    hipLaunchKernelGGL(k_pg_sep_zero, dim3((unsigned)std::min<size_t>(1024, (cells + 255) / 256)), dim3(256), 0, pg->stream, P, pg->d_ctl);
+    hipLaunchKernelGGL(k_pg_sep_assemble, dim3(P.S), dim3(64), 0, pg->stream, P, lin, pg->d_ctl);
+    hipLaunchKernelGGL(k_pg_sep_factor, dim3(1), dim3(PG_SEP_THREADS), 0, pg->stream, P, pg->d_ctl);
+    if (ev) hipEventRecord(ev[1], pg->stream);
+}
+
+extern "C" {
+
+void glio_pgraph_opts_default(glio_pgraph_opts* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->relative_error_tol = 1e-5; o->absolute_error_tol = 1e-5; o->max_iterations = 100;     // gtsam::GaussNewtonParams (unpinned)
+    const double p[6] = {1e-2, 1e-2, M_PI * M_PI, 1e8, 1e8, 1e8}, od[6] = {1e-6, 1e-6, 1e-6, 1e-4, 1e-4, 1e-4};        // Estimator.cpp:864-865
+    for (int k = 0; k < 6; ++k) { o->prior_var[k] = p[k]; o->odom_var[k] = od[k]; }
+    o->gps_var_floor = 1.0;                 // max(noise, 1.0f), Estimator.cpp:1986
+    o->max_nodes = 65536; o->max_loops = 64; o->max_unary = 4096; o->segment_nodes = 0;
+}
+int glio_pgraph_struct_sizes(int32_t* out, int n) {
+    const int32_t v[2] = {(int32_t)sizeof(glio_pgraph_opts), (int32_t)sizeof(glio_pgraph_info)};
+    for (int i = 0; i < n && i < 2; ++i) out[i] = v[i];
+    return 2;
+}
+
+void glio_pgraph_destroy(glio_pgraph* pg) {
+    if (!pg) return;
+    (void)hipSetDevice(pg->device);
+    if (pg->stream) (void)hipStreamSynchronize(pg->stream);
+    void* p[] = {pg->d_x, pg->d_x0, pg->d_cm, pg->d_cw, pg->d_un_node, pg->d_un_type, pg->d_un_m, pg->d_un_w, pg->d_lp_i, pg->d_lp_j, pg->d_lp_m, pg->d_lp_w,
+                 pg->d_D, pg->d_C, pg->d_g, pg->d_nerr, pg->d_lp_out, pg->d_Y, pg->d_seg, pg->d_delta, pg->d_plan, pg->d_sys, pg->d_ctl};
+    for (void* q : p) if (q) (void)hipFree(q);
+    if (pg->h_ctl) (void)hipHostFree(pg->h_ctl);
+    if (pg->ev_done) (void)hipEventDestroy(pg->ev_done);
+    for (hipEvent_t e : pg->ev_t) if (e) (void)hipEventDestroy(e);
+    if (pg->stream) (void)hipStreamDestroy(pg->stream);
+    delete pg;
+}
+
+static int pg_create_body(glio_pgraph* pg) {
+    PG_CHECK(hipStreamCreateWithFlags(&pg->stream, hipStreamNonBlocking));
+    PG_CHECK(hipEventCreateWithFlags(&pg->ev_done, hipEventDisableTiming | hipEventBlockingSync));
+    for (int k = 0; k < 6; ++k) PG_CHECK(hipEventCreate(&pg->ev_t[k]));
+    const size_t N = (size_t)pg->o.max_nodes, U = (size_t)pg->o.max_unary + 1, L = (size_t)std::max(1, pg->o.max_loops);
+    PG_CHECK(hipMalloc((void**)&pg->d_x, N * 56)); PG_CHECK(hipMalloc((void**)&pg->d_x0, N * 56));
+    PG_CHECK(hipMalloc((void**)&pg->d_cm, N * 56)); PG_CHECK(hipMalloc((void**)&pg->d_cw, N * 48));
+    PG_CHECK(hipMalloc((void**)&pg->d_un_node, U * 4)); PG_CHECK(hipMalloc((void**)&pg->d_un_type, U * 4));
+    PG_CHECK(hipMalloc((void**)&pg->d_un_m, U * 56)); PG_CHECK(hipMalloc((void**)&pg->d_un_w, U * 48));
+    PG_CHECK(hipMalloc((void**)&pg->d_lp_i, L * 4)); PG_CHECK(hipMalloc((void**)&pg->d_lp_j, L * 4));
+    PG_CHECK(hipMalloc((void**)&pg->d_lp_m, L * 56)); PG_CHECK(hipMalloc((void**)&pg->d_lp_w, L * 48));
+    PG_CHECK(hipMalloc((void**)&pg->d_D, N * 288)); PG_CHECK(hipMalloc((void**)&pg->d_C, N * 288)); PG_CHECK(hipMalloc((void**)&pg->d_g, N * 48));
+    PG_CHECK(hipMalloc((void**)&pg->d_nerr, N * 8)); PG_CHECK(hipMalloc((void**)&pg->d_lp_out, L * PG_LOOP_OUT * 8));
+    PG_CHECK(hipMalloc((void**)&pg->d_Y, N * PG_YS * 8)); PG_CHECK(hipMalloc((void**)&pg->d_seg, N * PG_SEGS * 8)); PG_CHECK(hipMalloc((void**)&pg->d_delta, N * 48));
+    PG_CHECK(hipMalloc((void**)&pg->d_ctl, sizeof(PgCtl))); PG_CHECK(hipHostMalloc((void**)&pg->h_ctl, sizeof(PgCtl)));
+    return GLIO_OK;
+}
+static void pg_reset(glio_pgraph* pg) {
+    pg->N = 0; pg->n_dev = 0; pg->have_prior = 0; pg->U = 0; pg->factors_dirty = 1;
+    pg->h_x.clear(); pg->h_cm.clear(); pg->h_cw.clear();
+    pg->gps_node.clear(); pg->gps_m.clear(); pg->gps_w.clear();
+    pg->lp_i.clear(); pg->lp_j.clear(); pg->lp_m.clear(); pg->lp_w.clear();
+}
+
+int glio_pgraph_create(int device, const glio_pgraph_opts* opts, glio_pgraph** out) {
+    if (!opts || !out) { glio_set_error("glio_pgraph_create: null argument"); return GLIO_E_ARG; }
+    const glio_pgraph_opts& o = *opts;
+    if (o.max_nodes < 1 || o.max_nodes > (1 << 24) || o.max_loops < 0 || o.max_loops > PG_MAX_LOOPS || o.max_unary < 0 || o.max_unary > (1 << 24) || o.segment_nodes < 0 ||
+        !pg_finite(&o.relative_error_tol, 1) || !pg_finite(&o.absolute_error_tol, 1) || !pg_var_ok(o.prior_var, 6) || !pg_var_ok(o.odom_var, 6) ||
+        !(o.gps_var_floor >= 0.0) || !pg_finite(&o.gps_var_floor, 1)) {
+        glio_set_error("bad glio_pgraph_opts (max_nodes %d, max_loops %d of at most %d, max_unary %d, segment_nodes %d, or a tolerance / variance that is not finite and positive)",
+                       o.max_nodes, o.max_loops, PG_MAX_LOOPS, o.max_unary, o.segment_nodes);
+        return GLIO_E_ARG;
+    }
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) { glio_set_error("no HIP device visible: the pose graph has no CPU fallback"); return GLIO_E_HIP; }
+    if (device < 0 || device >= nd) { glio_set_error("glio_pgraph_create: device %d of %d", device, nd); return GLIO_E_ARG; }
+    PG_CHECK(hipSetDevice(device));
+    glio_pgraph* pg = new glio_pgraph();
+    pg->device = device; pg->o = o;
+    pg_reset(pg);
+    const int rc = pg_create_body(pg);
+    if (rc != GLIO_OK) { glio_pgraph_destroy(pg); return rc; }
+    *out = pg;
+    return GLIO_OK;
+}
+
+int glio_pgraph_clear(glio_pgraph* pg) {
+    if (!pg) return GLIO_E_ARG;
+    pg_reset(pg);
+    return GLIO_OK;
+}
+
+int glio_pgraph_set_prior(glio_pgraph* pg, const double pose[7], const double var[6]) {
+    if (!pg || !pose) { glio_set_error("glio_pgraph_set_prior: null argument"); return GLIO_E_ARG; }
+    const double* v = var ? var : pg->o.prior_var;
+    double m[7];
+    if (!pg_pose_in(pose, m)) { glio_set_error("glio_pgraph_set_prior: the pose is not finite (or its quaternion is zero)"); return GLIO_E_ARG; }
+    if (!pg_var_ok(v, 6)) { glio_set_error("glio_pgraph_set_prior: a variance is not positive and finite"); return GLIO_E_ARG; }
+    memcpy(pg->prior_m, m, 56);
+    for (int k = 0; k < 6; ++k) pg->prior_w[k] = 1.0 / sqrt(v[k]);
+    pg->have_prior = 1; pg->factors_dirty = 1;
+    return GLIO_OK;
+}
+
+int glio_pgraph_append(glio_pgraph* pg, int n, const double* poses, const double* prev_pose, const double* var) {
+    GLIO_TRACE("glio_pgraph_append");
+    if (!pg || n < 1 || !poses) { glio_set_error("glio_pgraph_append: null argument or n < 1"); return GLIO_E_ARG; }
+    if ((long long)pg->N + n > (long long)pg->o.max_nodes) { glio_set_error("glio_pgraph_append: %d + %d nodes, max_nodes = %d", pg->N, n, pg->o.max_nodes); return GLIO_E_ARG; }
+    const double* v = var ? var : pg->o.odom_var;
+    if (!pg_var_ok(v, 6)) { glio_set_error("glio_pgraph_append: a variance is not positive and finite"); return GLIO_E_ARG; }
+    std::vector<double> x((size_t)7 * n), cm((size_t)7 * n, 0.0);
+    for (int k = 0; k < n; ++k)
+        if (!pg_pose_in(poses + (size_t)7 * k, &x[(size_t)7 * k])) { glio_set_error("glio_pgraph_append: pose %d is not finite (or its quaternion is zero)", k); return GLIO_E_ARG; }
+    double prev[7];
+    if (pg->N > 0) {
+        if (prev_pose) {
+            if (!pg_pose_in(prev_pose, prev)) { glio_set_error("glio_pgraph_append: prev_pose is not finite (or its quaternion is zero)"); return GLIO_E_ARG; }
+        } else {
+            PG_CHECK(hipSetDevice(pg->device));
+            const int rf = pg_flush_nodes(pg);
+            if (rf != GLIO_OK) return rf;
+            PG_CHECK(hipMemcpy(prev, pg->d_x + (size_t)7 * (pg->N - 1), 56, hipMemcpyDeviceToHost));
+        }
+    }
+    for (int k = 0; k < n; ++k) {
+        const double* a = k > 0 ? &x[(size_t)7 * (k - 1)] : (pg->N > 0 ? prev : nullptr);
+        if (a) pg_between_meas(a, &x[(size_t)7 * k], &cm[(size_t)7 * k]);
+        else cm[(size_t)7 * k + 3] = 1.0;
+    }
+    pg->h_x.resize((size_t)7 * pg->N); pg->h_cm.resize((size_t)7 * pg->N); pg->h_cw.resize((size_t)6 * pg->N);
+    pg->h_x.insert(pg->h_x.end(), x.begin(), x.end());
+    pg->h_cm.insert(pg->h_cm.end(), cm.begin(), cm.end());
+    for (int k = 0; k < n; ++k) for (int c = 0; c < 6; ++c) pg->h_cw.push_back(1.0 / sqrt(v[c]));
+    pg->N += n;
+    return GLIO_OK;
+}
+
+int glio_pgraph_add_between(glio_pgraph* pg, int i, int j, const double rel[7], const double var[6]) {
+    if (!pg || !rel || !var) { glio_set_error("glio_pgraph_add_between: null argument"); return GLIO_E_ARG; }
+    if (i < 0 || j < 0 || i >= pg->N || j >= pg->N || i == j) { glio_set_error("glio_pgraph_add_between: nodes %d, %d of %d (they must differ)", i, j, pg->N); return GLIO_E_ARG; }
+    if ((int)pg->lp_i.size() >= pg->o.max_loops) { glio_set_error("glio_pgraph_add_between: max_loops = %d edges are held", pg->o.max_loops); return GLIO_E_ARG; }
+    double m[7];
+    if (!pg_pose_in(rel, m)) { glio_set_error("glio_pgraph_add_between: the measurement is not finite (or its quaternion is zero)"); return GLIO_E_ARG; }
+    if (!pg_var_ok(var, 6)) { glio_set_error("glio_pgraph_add_between: a variance is not positive and finite"); return GLIO_E_ARG; }
+    pg->lp_i.push_back(i); pg->lp_j.push_back(j);
+    pg->lp_m.insert(pg->lp_m.end(), m, m + 7);
+    for (int k = 0; k < 6; ++k) pg->lp_w.push_back(1.0 / sqrt(var[k]));
+    pg->factors_dirty = 1;
+    return GLIO_OK;
+}
+
+int glio_pgraph_add_gps(glio_pgraph* pg, int i, const double xyz[3], const double var[3]) {
+    if (!pg || !xyz || !var) { glio_set_error("glio_pgraph_add_gps: null argument"); return GLIO_E_ARG; }
+    if (i < 0 || i >= pg->N) { glio_set_error("glio_pgraph_add_gps: node %d of %d", i, pg->N); return GLIO_E_ARG; }
+    if ((int)pg->gps_node.size() >= pg->o.max_unary) { glio_set_error("glio_pgraph_add_gps: max_unary = %d factors are held", pg->o.max_unary); return GLIO_E_ARG; }
+    if (!pg_finite(xyz, 3)) { glio_set_error("glio_pgraph_add_gps: the position is not finite"); return GLIO_E_ARG; }
+    if (!pg_var_ok(var, 3)) { glio_set_error("glio_pgraph_add_gps: a variance is not positive and finite"); return GLIO_E_ARG; }
+    pg->gps_node.push_back(i);
+    pg->gps_m.insert(pg->gps_m.end(), xyz, xyz + 3);
+    for (int k = 0; k < 3; ++k) pg->gps_w.push_back(1.0 / sqrt(std::max(var[k], pg->o.gps_var_floor)));
+    pg->factors_dirty = 1;
+    return GLIO_OK;
+}
+
+static int pg_ready(glio_pgraph* pg, const char* who) {
+    if (pg->N < 1) { glio_set_error("%s: the graph has no node", who); return GLIO_E_ARG; }
+    if (!pg->have_prior && pg->gps_node.empty()) { glio_set_error("%s: neither a prior nor a GPS factor exists", who); return GLIO_E_ARG; }
+    PG_CHECK(hipSetDevice(pg->device));
+    int rc = pg_flush_nodes(pg);
+    if (rc == GLIO_OK) rc = pg_flush_factors(pg);
+    return rc;
+}
+
+int glio_pgraph_solve(glio_pgraph* pg, glio_pgraph_info* info) {
+    GLIO_TRACE("glio_pgraph_solve");
+    if (!pg) return GLIO_E_ARG;
+    { const int rc = pg_ready(pg, "glio_pgraph_solve"); if (rc != GLIO_OK) return rc; }
+    PgPlan P;
+    { const int rc = pg_make_plan(pg, -1, &P); if (rc != GLIO_OK) return rc; }
+    const int N = pg->N;
+    PG_CHECK(hipMemsetAsync(pg->d_ctl, 0, sizeof(PgCtl), pg->stream));
+    PG_CHECK(hipMemcpyAsync(pg->d_x0, pg->d_x, (size_t)N * 56, hipMemcpyDeviceToDevice, pg->stream));
+    PG_CHECK(hipEventRecord(pg->ev_t[0], pg->stream));
+    pg_enqueue_linearise(pg, 0);
+    PG_CHECK(hipEventRecord(pg->ev_t[1], pg->stream));
+    // The first PG_AHEAD iterations are enqueued ahead and waited for once; Gauss-Newton on these graphs ends within them.  A solve that does not gets the
+    // rest of its max_iterations enqueued ahead the same way, behind one more wait.
+    for (int it = 0; it < pg->o.max_iterations; ++it) {
+        pg_enqueue_linear_solve(pg, P, it == 0 ? &pg->ev_t[2] : nullptr);
+        if (P.S > 1) hipLaunchKernelGGL(k_pg_backsub, dim3(P.S - 1), dim3(64), 0, pg->stream, P, pg->d_ctl);
+        hipLaunchKernelGGL(k_pg_update, dim3((N + 255) / 256), dim3(256), 0, pg->stream, N, pg->d_x, pg->d_delta, pg->d_ctl);
+        if (it == 0) PG_CHECK(hipEventRecord(pg->ev_t[4], pg->stream));
+        pg_enqueue_linearise(pg, 1);
+        if (it + 1 == PG_AHEAD || it + 1 == pg->o.max_iterations) {
+            PG_CHECK(hipEventRecord(pg->ev_t[5], pg->stream));
+            PG_CHECK(hipMemcpyAsync(pg->h_ctl, pg->d_ctl, sizeof(PgCtl), hipMemcpyDeviceToHost, pg->stream));
+            PG_CHECK(hipEventRecord(pg->ev_done, pg->stream));
+            PG_CHECK(hipEventSynchronize(pg->ev_done));
+            if (pg->h_ctl->done || pg->h_ctl->pivot_fail) break;
+        }
+    }
+    if (pg->o.max_iterations <= 0) {
+        PG_CHECK(hipEventRecord(pg->ev_t[5], pg->stream));
+        PG_CHECK(hipMemcpyAsync(pg->h_ctl, pg->d_ctl, sizeof(PgCtl), hipMemcpyDeviceToHost, pg->stream));
+        PG_CHECK(hipEventRecord(pg->ev_done, pg->stream));
+        PG_CHECK(hipEventSynchronize(pg->ev_done));
+    }
+    PG_CHECK(hipGetLastError());
+    const PgCtl& c = *pg->h_ctl;
+    int reason = c.reason;
+    if (c.pivot_fail) reason = GLIO_PGRAPH_NONPOSITIVE_PIVOT;
+    if (reason == GLIO_PGRAPH_NONPOSITIVE_PIVOT) {
+        PG_CHECK(hipMemcpyAsync(pg->d_x, pg->d_x0, (size_t)N * 56, hipMemcpyDeviceToDevice, pg->stream));
+        PG_CHECK(hipStreamSynchronize(pg->stream));
+    }
+    if (info) {
+        memset(info, 0, sizeof *info);
+        info->initial_error = c.err0;
+        info->final_error = reason == GLIO_PGRAPH_NONPOSITIVE_PIVOT ? c.err0 : c.err_cur;
+        info->iterations = c.iterations; info->termination = reason;
+        info->separators = P.S; info->segments = P.S - 1;
+        (void)hipEventElapsedTime(&info->device_ms, pg->ev_t[0], pg->ev_t[5]);
+        if (pg->o.max_iterations > 0) {
+            (void)hipEventElapsedTime(&info->stage_ms[0], pg->ev_t[0], pg->ev_t[1]);
+            (void)hipEventElapsedTime(&info->stage_ms[1], pg->ev_t[1], pg->ev_t[2]);
+            (void)hipEventElapsedTime(&info->stage_ms[2], pg->ev_t[2], pg->ev_t[3]);
+            (void)hipEventElapsedTime(&info->stage_ms[3], pg->ev_t[3], pg->ev_t[4]);
+        }
+    }
+    return GLIO_OK;
+}
+
+int glio_pgraph_size(glio_pgraph* pg, int* n_nodes) {
+    if (!pg || !n_nodes) return GLIO_E_ARG;
+    *n_nodes = pg->N;
+    return GLIO_OK;
+}
+
+int glio_pgraph_read_poses(glio_pgraph* pg, int first, int n, double* out) {
+    if (!pg || first < 0 || n < 0 || (long long)first + n > (long long)pg->N || (n > 0 && !out)) { glio_set_error("glio_pgraph_read_poses: bad range"); return GLIO_E_ARG; }
+    if (n == 0) return GLIO_OK;
+    PG_CHECK(hipSetDevice(pg->device));
+    { const int rc = pg_flush_nodes(pg); if (rc != GLIO_OK) return rc; }
+    PG_CHECK(hipMemcpyAsync(out, pg->d_x + (size_t)7 * first, (size_t)n * 56, hipMemcpyDeviceToHost, pg->stream));
+    PG_CHECK(hipStreamSynchronize(pg->stream));
+    return GLIO_OK;
+}
+
+int glio_pgraph_error(glio_pgraph* pg, double* error) {
+    if (!pg || !error) return GLIO_E_ARG;
+    { const int rc = pg_ready(pg, "glio_pgraph_error"); if (rc != GLIO_OK) return rc; }
+    PG_CHECK(hipMemsetAsync(pg->d_ctl, 0, sizeof(PgCtl), pg->stream));
+    pg_enqueue_linearise(pg, -1);
+    PG_CHECK(hipMemcpyAsync(pg->h_ctl, pg->d_ctl, sizeof(PgCtl), hipMemcpyDeviceToHost, pg->stream));
+    PG_CHECK(hipStreamSynchronize(pg->stream));
+    PG_CHECK(hipGetLastError());
+    *error = pg->h_ctl->err;
+    return GLIO_OK;
+}
+
+int glio_pgraph_marginal_covariance(glio_pgraph* pg, int node, double* out) {
+    GLIO_TRACE("glio_pgraph_marginal_covariance");
+    if (!pg || !out) return GLIO_E_ARG;
+    if (node < 0 || node >= pg->N) { glio_set_error("glio_pgraph_marginal_covariance: node %d of %d", node, pg->N); return GLIO_E_ARG; }
+    { const int rc = pg_ready(pg, "glio_pgraph_marginal_covariance"); if (rc != GLIO_OK) return rc; }
+    PgPlan P;
+    { const int rc = pg_make_plan(pg, node, &P); if (rc != GLIO_OK) return rc; }
+    PG_CHECK(hipMemsetAsync(pg->d_ctl, 0, sizeof(PgCtl), pg->stream));
+    pg_enqueue_linearise(pg, -1);
+    pg_enqueue_linear_solve(pg, P, nullptr);
+    PG_CHECK(hipMemcpyAsync(pg->h_ctl, pg->d_ctl, sizeof(PgCtl), hipMemcpyDeviceToHost, pg->stream));
+    PG_CHECK(hipStreamSynchronize(pg->stream));
+    PG_CHECK(hipGetLastError());
+    if (pg->h_ctl->pivot_fail) { glio_set_error("glio_pgraph_marginal_covariance: a non-positive pivot"); return GLIO_E_NUMERIC; }
+    memcpy(out, pg->h_ctl->cov, 36 * 8);
+    return GLIO_OK;
+}
+
+int glio_pgraph_poses_dev(glio_pgraph* pg, const double** poses_dev, int* n_nodes) {
+    if (!pg || !poses_dev) return GLIO_E_ARG;
+    PG_CHECK(hipSetDevice(pg->device));
+    { const int rc = pg_flush_nodes(pg); if (rc != GLIO_OK) return rc; }
+    *poses_dev = pg->d_x;
+    if (n_nodes) *n_nodes = pg->N;
+    return GLIO_OK;
+}
+
+}  // extern "C"

@@ -161,6 +161,23 @@ class GlioGmapInfo(C.Structure):
     _fields_ = [("n_points_total", C.c_int64), ("n_voxels", C.c_int32), ("radix_passes", C.c_int32), ("pcl_index_overflow", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class GlioPgraphOpts(C.Structure):
+    """glio_pgraph_opts (include/glio_types.h): Gauss-Newton's termination, the reference's noise variances (Estimator.cpp:864-865, :1986), capacities"""
+    _fields_ = [("relative_error_tol", C.c_double), ("absolute_error_tol", C.c_double), ("prior_var", C.c_double * 6), ("odom_var", C.c_double * 6),
+                ("gps_var_floor", C.c_double), ("max_iterations", C.c_int32), ("max_nodes", C.c_int32), ("max_loops", C.c_int32), ("max_unary", C.c_int32),
+                ("segment_nodes", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class GlioPgraphInfo(C.Structure):
+    """glio_pgraph_info: what glio_pgraph_solve reports"""
+    _fields_ = [("initial_error", C.c_double), ("final_error", C.c_double), ("device_ms", C.c_float), ("stage_ms", C.c_float * 4), ("iterations", C.c_int32),
+                ("termination", C.c_int32), ("separators", C.c_int32), ("segments", C.c_int32), ("reserved_", C.c_int32)]
+
+
+PGRAPH_NOT_RUN, PGRAPH_CONVERGED, PGRAPH_ITERATION_LIMIT, PGRAPH_NONPOSITIVE_PIVOT = range(4)
+PGRAPH_TERMINATION_NAMES = ("NOT_RUN", "CONVERGED", "ITERATION_LIMIT", "NONPOSITIVE_PIVOT")
+
+
 LOOP_SOURCE, LOOP_TARGET = 0, 1
 LOOP_NOT_CONVERGED, LOOP_ITERATIONS, LOOP_TRANSFORM, LOOP_ABS_MSE, LOOP_REL_MSE, LOOP_NO_CORRESPONDENCES = range(6)
 LOOP_STATE_NAMES = ("NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE", "NO_CORRESPONDENCES")

@@ -6,7 +6,8 @@
 //   glio::loopSubmapFrames     :5133-5175   which keyframes make the two submaps
 //   glio::loopFramePoses       :5147-5148   their poses, as glio_loop_build_submap takes them
 //   glio::loopConstraint       :5210-5247   the gate on the ICP result and the relative pose for the BetweenFactor
-// GTSAM, correctPoses and the reset of the marginalization prior (:5249-5269) stay with the caller.
+// The pose graph that takes the constraint and returns the corrected poses (:5249-5262) is glio::GlobalGraph / glio::PoseGraph (glio_posegraph_backend.hpp,
+// glio_pgraph_*); a caller may keep GTSAM instead.  correctPoses' bookkeeping and the reset of the marginalization prior (:5264-5269) stay with the caller.
 // The Python twin is glio_amd/loop.py: the same scalar arithmetic in the same order (tests/test_loop_host_cpu.py holds the two to each other bit for bit).
 #ifndef GLIO_LOOP_BACKEND_HPP_
 #define GLIO_LOOP_BACKEND_HPP_
@@ -177,7 +178,8 @@ inline bool loopConstraint(const glio_loop_result& res, const double pose_latest
 // q_rel = q_from.inverse() * q_to, t_rel = q_from.inverse() * (t_to - t_from), Eigen's inverse() = conjugate / squaredNorm; (2) rows 1 .. N - W take the
 // corrected poses; (3) rows N - W + 1 .. N - 1 are chained back on: t = t_prev + q_prev * t_rel, q = q_prev * q_rel.  Rs [N][9] (row-major toRotationMatrix(),
 // not normalised) and Ps [N][3] receive every rewritten row (row 0 is not written; either may be null).  pose_keyframe / pose_info_keyframe[i] are row i + 1.
-// What stays with the caller: GTSAM / iSAM2, pose_each_frame, recent_surf_keyframes.clear() (SlidingWindowBackend::loopClosed), marg = false
+// The corrected poses come from glio::GlobalGraph::keyframePoses (glio_posegraph_backend.hpp; or from the caller's GTSAM / iSAM2).  What stays with the caller:
+// pose_each_frame, recent_surf_keyframes.clear() (SlidingWindowBackend::loopClosed), marg = false
 // (glio_set_prior(NULL)).  The Python twin is loop.correct_window_poses (tests/test_map_schedule_host_cpu.py: bit for bit).  false: bad sizes.
 inline bool correctWindowPoses(double* abs_poses, int N, const double* corrected, int n_corrected, int W, double* Rs, double* Ps) {
     if (W < 1 || W > N || n_corrected != N - W) return false;

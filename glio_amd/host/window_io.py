@@ -420,3 +420,52 @@ def run_demo_map(path, device=0, env=None):
         elif ln.startswith("{"):
             out.update(json.loads(ln))
     return out
+
+
+DEMO_POSE_GRAPH = os.path.join(HERE, "host_demo_pose_graph")
+
+
+def build_demo_pose_graph(force=False):
+    """The C++ pose-graph sequence (host_demo_pose_graph.cpp over glio::GlobalGraph / glio::PoseGraph, glio_posegraph_backend.hpp)."""
+    src = [os.path.join(HERE, "host_demo_pose_graph.cpp"), os.path.join(HERE, "glio_posegraph_backend.hpp")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_POSE_GRAPH) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_POSE_GRAPH) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_POSE_GRAPH])
+    return DEMO_POSE_GRAPH
+
+
+def write_pose_graph_case(path, pose_each_frame, keyframe_id_in_frame, W, latest_keyframe, closest_keyframe, rel, var, gps):
+    """int32 F NK W n_gps latest closest 0 0 | pose_each_frame [F][7] = t, q | keyframe_id_in_frame [NK] int32, padded to a multiple of 2 | rel [7] var [6] |
+    n_gps x (frame, xyz[3], var[3]) doubles"""
+    P = np.ascontiguousarray(pose_each_frame, np.float64).reshape(-1, 7)
+    kf = np.ascontiguousarray(keyframe_id_in_frame, np.int32)
+    with open(path, "wb") as f:
+        f.write(np.array([len(P), len(kf), W, len(gps), latest_keyframe, closest_keyframe, 0, 0], np.int32).tobytes())
+        f.write(P.tobytes())
+        f.write(kf.tobytes() + (b"\0\0\0\0" if len(kf) & 1 else b""))
+        f.write(np.ascontiguousarray(rel, np.float64).reshape(7).tobytes()); f.write(np.ascontiguousarray(var, np.float64).reshape(6).tobytes())
+        for node, xyz, v in gps:
+            f.write(np.array([float(node), *xyz, *v], np.float64).tobytes())
+
+
+def run_demo_pose_graph(path, device=0, env=None):
+    """-> dict(iterations, termination, error_before, initial_error, final_error, separators, segments, poses [n][7], calls [(n_keyframes, first, last)], n_keyframe_poses)"""
+    r = subprocess.run([build_demo_pose_graph(), path, str(device)], capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError("host_demo_pose_graph failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
+    out, poses, calls = {}, [], []
+    for ln in r.stdout.splitlines():
+        w = ln.split()
+        if not w:
+            continue
+        if w[0] == "solve":
+            out.update(iterations=int(w[1]), termination=int(w[2]), error_before=float.fromhex(w[3]), initial_error=float.fromhex(w[4]),
+                       final_error=float.fromhex(w[5]), separators=int(w[6]), segments=int(w[7]))
+        elif w[0] == "pose":
+            poses.append([float.fromhex(x) for x in w[2:9]])
+        elif w[0] == "call":
+            calls.append((int(w[1]), int(w[3]), int(w[5])))
+        elif w[0] == "keyframes":
+            out["n_keyframe_poses"] = int(w[1])
+    out.update(poses=np.array(poses), calls=calls)
+    return out

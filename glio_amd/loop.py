@@ -6,7 +6,8 @@ loop (:5113-5128), which keyframes make the two submaps (:5133-5175), their pose
 (tests/test_loop_host_cpu.py).  Of correctPoses (:4658-4787) the window's share is here too -- correct_window_poses / glio::correctWindowPoses: the
 relative poses inside the sliding window taken before the correction, the older keyframes set to the caller's corrected poses, the window chained back on,
 Rs / Ps -- and its recent_surf_keyframes.clear() is sliding.ReferenceMapSchedule.loop_closed() (the next call rebuilds the local map from the resident
-keyframes at the corrected poses, glio_localmap_rebuild_from_frames).  GTSAM / iSAM2 (the corrected poses themselves), pose_each_frame and the prior reset
+keyframes at the corrected poses, glio_localmap_rebuild_from_frames).  The corrected poses themselves come from posegraph.GlobalGraph (glio_pgraph_*: the pose graph
+on the device; a caller may keep GTSAM / iSAM2 instead); pose_each_frame and the prior reset
 (:5249-5269, :4785 marg = false: glio_set_prior(NULL)) stay with the caller.  There is no CPU fallback for the submaps or the registration."""
 import ctypes as C
 import math

@@ -574,6 +574,68 @@ int glio_gmap_points_dev(glio_gmap* gm, const void** points_dev, int* n_voxels);
 int glio_gmap_last_device_ms(glio_gmap* gm, float* ms);
 int glio_gmap_last_stage_ms(glio_gmap* gm, float* ms4);
 
+/* ---- the pose graph on the device: what the reference keeps in one gtsam::ISAM2 -- the GLOBAL graph (Estimator.cpp:4586-4652: one node per frame, a
+ * PriorFactor<Pose3> on node 0, a BetweenFactor<Pose3> with odom_noise between consecutive frames, one BetweenFactor per loop closure, :5251-5256;
+ * global_estimated = isam->calculateEstimate() feeds correctPoses) and the LOCAL graph (:4561-4581, addLIOFactor :1999-2043, addGNSSFactor :1915-1997: one
+ * node per keyframe that left the window, gtsam::GPSFactor every >= 5 m, poseCovariance = isam->marginalCovariance(last)).  One object serves either.
+ * GTSAM is not part of the reference tree: every GTSAM-side rule below is UNPINNED -- restated from its published behaviour, never
+ * run against GTSAM here.  The host's share (which factor when: the gates of addGNSSFactor, the per-frame insertion) is glio_amd/posegraph.py and
+ * host/glio_posegraph_backend.hpp.
+ *
+ * State: a pose x = (R, t), handed over as t[3], q[4] (w first), the layout of glio_loop_build_submap / glio_gmap_add_frames / glio_localmap_rebuild_from_frames.
+ * Retraction: x [+] d = (R Exp(d_r), t + R d_t), d = (d_r, d_t): ROTATION FIRST, as gtsam::Pose3's tangent and the variance vectors of :864-865, :5246.
+ *   between (i, j; R_m, t_m; var[6]):  r = [Log(R_m^T R_i^T R_j) ; R_m^T (R_i^T (t_j - t_i) - t_m)], every row divided by sqrt(var)
+ *   prior   (i; R_p, t_p; var[6]):     r = [Log(R_p^T R) ; R_p^T (t - t_p)]
+ *   GPS     (i; p; var[3]):            r = t - p
+ * Log is the SO(3) logarithm (taken from the unit quaternion with w >= 0: phi = 2 atan2(|v|, w) v / |v|; for |v| < 1e-3 the series
+ * 2 / w (1 - u^2 / 3 + u^4 / 5), u = |v| / w).  The rotational Jacobians use the inverse right Jacobian I + 1/2 [phi]x + c [phi]x^2,
+ * c = 1 / theta^2 - (1 + cos theta) / (2 theta sin theta), and for theta < 1e-2 the series c = 1/12 + theta^2 / 720 + theta^4 / 30240.
+ * DEVIATION 1: a GTSAM 4.0 build without GTSAM_ROT3_EXPMAP uses the Cayley chart for Rot3; it differs from Log at third order in the residual angle.
+ * DEVIATION 2: iSAM2 with relinearizeThreshold 0.1 is an incremental approximation of the maximum-a-posteriori estimate; here every glio_pgraph_solve is the
+ * BATCH Gauss-Newton estimate of the whole graph, started from the current estimate, all in fp64.
+ * Gauss-Newton (no damping) with gtsam::GaussNewtonParams' termination, decided ON THE DEVICE on the total error E = 1/2 |r|^2: after every iteration
+ * stop CONVERGED when E_new <= 0, or (E - E_new) / E <= relative_error_tol, or E - E_new <= absolute_error_tol; stop ITERATION_LIMIT at max_iterations.
+ * Never on a step norm: with the reference's prior (translation variance 1e8 against odometry information 1e4) the absolute translation is numerically a gauge.
+ * Every iteration solves the normal equations by ONE exact Cholesky in a fixed order (nested dissection: node 0, the last node, every loop endpoint and evenly
+ * spaced nodes are separators; the chain between two separators is eliminated by one wavefront per segment; the separator system is factored as a band plus the
+ * full rows of loop endpoints).  No atomic takes part in a sum: two runs give the same bits.  A non-positive pivot ends the solve with termination
+ * NONPOSITIVE_PIVOT and the estimate the solve STARTED from is put back.  The iteration loop is enqueued ahead (the first 12 iterations, then, for a solve that needs more, the rest): the host waits once, or twice.
+ * A glio_pgraph owns one HIP stream and is not thread-safe.  Every refusal is GLIO_E_ARG and changes nothing. */
+typedef struct glio_pgraph glio_pgraph;
+void glio_pgraph_opts_default(glio_pgraph_opts* o);
+/* sizeof() of glio_pgraph_opts, glio_pgraph_info; returns how many there are (2) */
+int glio_pgraph_struct_sizes(int32_t* out, int n);
+/* GLIO_E_ARG: max_nodes outside [1, 2^24], max_loops outside [0, 1024], max_unary < 0, segment_nodes < 0, a tolerance or default variance that is not finite */
+int glio_pgraph_create(int device, const glio_pgraph_opts* opts, glio_pgraph** out);
+void glio_pgraph_destroy(glio_pgraph* pg);
+/* an empty graph again: no node, no factor, no prior (new gtsam::ISAM2, Estimator.cpp:864) */
+int glio_pgraph_clear(glio_pgraph* pg);
+/* PriorFactor<Pose3>(0, pose, prior_noise) (Estimator.cpp:4592-4594, :4565-4567): the prior of node 0; a second call replaces it.  var null: opts.prior_var */
+int glio_pgraph_set_prior(glio_pgraph* pg, const double pose[7], const double var[6]);
+/* n nodes at the end with poses[k] as their initial estimates, and per new node one BetweenFactor(previous, this, between(previous given pose, this given
+ * pose), odom_noise) (Estimator.cpp:4613-4633, addLIOFactor :2020-2040).  prev_pose is what the caller holds for the current last node (pose_each_frame[i-1]);
+ * null: its current estimate.  The first node of an empty graph gets no between factor (prev_pose is not read).  var null: opts.odom_var.
+ * Quaternions are normalised; a zero quaternion is refused. */
+int glio_pgraph_append(glio_pgraph* pg, int n, const double* poses /* [n][7] */, const double* prev_pose /* [7] or null */, const double* var /* [6] or null */);
+/* BetweenFactor<Pose3>(i, j, rel, Variances(var)) for a loop closure (Estimator.cpp:5251-5254: rel = poseFrom.between(poseTo) of glio::loopConstraint /
+ * loop.loop_constraint, var = six times icp.getFitnessScore()); i != j, in either order */
+int glio_pgraph_add_between(glio_pgraph* pg, int i, int j, const double rel[7], const double var[6]);
+/* gtsam::GPSFactor(i, xyz, Variances(max(var, gps_var_floor))) (Estimator.cpp:1985-1989) */
+int glio_pgraph_add_gps(glio_pgraph* pg, int i, const double xyz[3], const double var[3]);
+/* isam->update() + calculateEstimate() (Estimator.cpp:4572-4580, :4641-4650), as the batch estimate stated above.  info may be null.  GLIO_E_ARG before a
+ * node exists and before a prior or a GPS factor exists.  A NONPOSITIVE_PIVOT termination is reported in info with GLIO_OK. */
+int glio_pgraph_solve(glio_pgraph* pg, glio_pgraph_info* info);
+int glio_pgraph_size(glio_pgraph* pg, int* n_nodes);
+/* the current estimates of nodes [first, first + n): unit quaternions with w >= 0 */
+int glio_pgraph_read_poses(glio_pgraph* pg, int first, int n, double* out /* [n][7] */);
+/* isam->marginalCovariance(node) (Estimator.cpp:4578): the node's 6x6 block of the inverse of the normal matrix at the current estimate, row major, in the
+ * tangent frame stated above (rotation first; entries (3,3), (4,4) gate addGNSSFactor, :1938); symmetric to the bit.  GLIO_E_NUMERIC on a non-positive pivot. */
+int glio_pgraph_marginal_covariance(glio_pgraph* pg, int node, double* out /* [36] */);
+/* the total error 1/2 |r|^2 of the current estimate */
+int glio_pgraph_error(glio_pgraph* pg, double* error);
+/* the pose table on the device ([n_nodes][7] doubles t, q), valid until the next successful glio_pgraph_solve / glio_pgraph_append / glio_pgraph_clear */
+int glio_pgraph_poses_dev(glio_pgraph* pg, const double** poses_dev, int* n_nodes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -314,6 +314,37 @@ typedef struct glio_gmap_info {
     int32_t reserved_;
 } glio_gmap_info;
 
+/* ---- the pose graph: the global graph of Estimator.cpp:4586-4652, 5251-5256 and the local graph of :4561-4581, 1915-2043 on the device (glio_pgraph_*).
+ * GTSAM is not part of the reference tree: everything GTSAM-side is UNPINNED, restated from its published behaviour (include/glio_hip.h).
+ * Defaults (glio_pgraph_opts_default): prior_noise and odom_noise of Estimator.cpp:864-865 (variances, rotation first), max(noise, 1) of :1986,
+ * gtsam::GaussNewtonParams' published defaults (100 iterations, relative and absolute error tolerance 1e-5). */
+typedef struct glio_pgraph_opts {
+    double relative_error_tol;     /* 1e-5 */
+    double absolute_error_tol;     /* 1e-5 */
+    double prior_var[6];           /* 1e-2, 1e-2, pi^2, 1e8, 1e8, 1e8: what a null var of glio_pgraph_set_prior means */
+    double odom_var[6];            /* 1e-6 x3, 1e-4 x3: what a null var of glio_pgraph_append means */
+    double gps_var_floor;          /* 1: every GPS variance is max(var, gps_var_floor) */
+    int32_t max_iterations;        /* 100 */
+    int32_t max_nodes;             /* 65536 */
+    int32_t max_loops;             /* 64 (at most 1024) */
+    int32_t max_unary;             /* 4096: GPS factors */
+    int32_t segment_nodes;         /* interior nodes per segment of the elimination; 0 = chosen by the library (about sqrt(nodes), 4 .. 255) */
+    int32_t reserved_;
+} glio_pgraph_opts;
+enum { GLIO_PGRAPH_NOT_RUN = 0, GLIO_PGRAPH_CONVERGED = 1, GLIO_PGRAPH_ITERATION_LIMIT = 2, GLIO_PGRAPH_NONPOSITIVE_PIVOT = 3 };
+/* what glio_pgraph_solve reports */
+typedef struct glio_pgraph_info {
+    double initial_error;          /* 1/2 |r|^2 at the estimate the solve started from */
+    double final_error;            /* ... at the estimate it left */
+    float device_ms;               /* the whole solve */
+    float stage_ms[4];             /* the FIRST iteration by stage: linearise, segments, separator system, back-substitution + update */
+    int32_t iterations;
+    int32_t termination;           /* GLIO_PGRAPH_* */
+    int32_t separators;
+    int32_t segments;
+    int32_t reserved_;
+} glio_pgraph_info;
+
 #ifdef __cplusplus
 }
 #endif
