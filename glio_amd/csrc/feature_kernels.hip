@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "glio_device.h"
+#include "cloud_device.h"
 
 // the stencil, the neighbour gates, the voxel sums and the de-skew's double products round like the reference's scalar build
 #pragma clang fp contract(off)
@@ -57,30 +58,7 @@ struct FeatWork {
 };
 
 // ------------------------------------------------------------------------------------------------ block helpers (1024 threads = 16 wavefronts)
-// exclusive rank of a flag among the block's threads in thread order; total = flags set
-__device__ __forceinline__ int ft_blk_rank(const bool f, int* s_w, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const unsigned long long b = __ballot(f);
-    if (lane == 0) s_w[w] = __popcll(b);
-    __syncthreads();
-    int before = 0, tot = 0;
-    for (int k = 0; k < 16; ++k) { const int v = s_w[k]; before += k < w ? v : 0; tot += v; }
-    __syncthreads();
-    total = tot;
-    return before + __popcll(b & ((1ull << lane) - 1ull));
-}
-__device__ __forceinline__ int ft_blk_excl_int(const int v, int* s_w, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int incl = v;
-    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
-    if (lane == 63) s_w[w] = incl;
-    __syncthreads();
-    int before = 0, tot = 0;
-    for (int k = 0; k < 16; ++k) { const int x = s_w[k]; before += k < w ? x : 0; tot += x; }
-    __syncthreads();
-    total = tot;
-    return before + incl - v;
-}
+// (rank of a flag and exclusive scan of an int over the block: cloud_wg_rank<16>, cloud_wg_excl_scan<16>)
 template <bool MAX> __device__ __forceinline__ unsigned long long ft_blk_ext(unsigned long long v, unsigned long long* s_red) {
     for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(v, off, 64); v = MAX ? (o > v ? o : v) : (o < v ? o : v); }
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
@@ -155,7 +133,7 @@ __device__ int ft_voxel_grid(const float4* __restrict__ in, const int n, const f
         const int s = c0 + tid;
         const bool head = s < n && (s == 0 || (keys[s] >> 20) != (keys[s - 1] >> 20));
         int tot;
-        const int rk = ft_blk_rank(head, s_w, tot);
+        const int rk = cloud_wg_rank<16>(head, s_w, tot);
         if (head) {
             const unsigned long long v = keys[s] >> 20;
             float ax = 0.f, ay = 0.f, az = 0.f, ai = 0.f;
@@ -182,7 +160,7 @@ __global__ __launch_bounds__(1024) void k_ft_count(const float4* __restrict__ ra
     const int i = blockIdx.x * FT_TILE + threadIdx.x;
     const bool keep = i < n && ft_keep(raw[i], thr2);
     int tot;
-    ft_blk_rank(keep, s_w, tot);
+    cloud_wg_rank<16>(keep, s_w, tot);
     if (threadIdx.x == 0) tile_cnt[blockIdx.x] = tot;
 }
 __global__ __launch_bounds__(1024) void k_ft_scan_tiles(int* __restrict__ tile, const int nt, int* __restrict__ meta) {
@@ -190,7 +168,7 @@ __global__ __launch_bounds__(1024) void k_ft_scan_tiles(int* __restrict__ tile, 
     const int t = threadIdx.x;                         // nt <= 1024 (max_raw_points <= 400000)
     const int v = t < nt ? tile[t] : 0;
     int tot;
-    const int ex = ft_blk_excl_int(v, s_w, tot);
+    const int ex = cloud_wg_excl_scan<16>(v, s_w, tot);
     if (t < nt) tile[t] = ex;
     if (t == 0) { meta[M_SURV] = tot; meta[M_HALF] = INT_MAX; }
 }
@@ -202,7 +180,7 @@ __global__ __launch_bounds__(1024) void k_ft_compact(const float4* __restrict__ 
     bool keep = false;
     if (i < n) { p = raw[i]; keep = ft_keep(p, thr2); }
     int tot;
-    const int rk = ft_blk_rank(keep, s_w, tot);
+    const int rk = cloud_wg_rank<16>(keep, s_w, tot);
     if (keep) surv[tile_off[blockIdx.x] + rk] = p;
 }
 
@@ -450,7 +428,7 @@ __global__ __launch_bounds__(1024) void k_ft_rings(const float4* __restrict__ cu
             bool f = false;
             if (k <= ep) { p = cut[k]; f = !ft_near(p) && label[k] <= 0; }
             int tot;
-            const int rk = ft_blk_rank(f, s_w, tot);
+            const int rk = cloud_wg_rank<16>(f, s_w, tot);
             if (f) lf[start + n_lf + rk] = p;
             n_lf += tot;
         }

@@ -6,7 +6,7 @@
 // pcl::VoxelGrid sorts the points by voxel index and sums each run; so does this file -- every contribution is stored once and summed per destination in a
 // fixed order, no atomic takes part in a sum.  PCL's linear index ix + iy dx + iz dx dy orders the voxels lexicographically by (iz, iy, ix) whatever the bounding box
 // is, so a 63-bit ABSOLUTE key (21 biased bits per axis, iz highest) gives PCL's output order without a bounding-box pass.  One call:
-//   k_gm_transform    blockIdx.y = frame: transformCloud (k_lm_transform's arithmetic), the point's key, its rank in the concatenation; the call's bounding box
+//   k_gm_transform    blockIdx.y = frame: transformCloud (cloud_transform), the point's key, its rank in the concatenation; the call's bounding box
 //                     in voxel coordinates (for the sort's plan and the overflow flag), the range check of the key
 //   k_gm_plan         the digits of the call.  The absolute key is biased, so a cloud that straddles a coordinate's zero differs in all 21 bits of that axis -- all
 //                     eight digits would vary.  Inside ONE call the order of (iz, iy, ix) is also the order of the coordinates counted from the call's own
@@ -29,6 +29,7 @@
 #include <cstring>
 
 #include "glio_device.h"
+#include "cloud_device.h"
 
 // transformCloud and the voxel sums must round like scalar float / double code: no FMA contraction in this file
 #pragma clang fp contract(off)
@@ -81,11 +82,12 @@ __global__ void k_gm_begin(GmCtl* ctl) {
 
 __global__ __launch_bounds__(GM_TF_THREADS) void k_gm_transform(const GmFrame* __restrict__ fr, const float inv_leaf, float4* __restrict__ pts, gm_u64* __restrict__ key,
                                                                 unsigned* __restrict__ val, GmCtl* ctl) {
-    __shared__ int s_mn[GM_TF_THREADS / 64][3], s_mx[GM_TF_THREADS / 64][3];
+    __shared__ int s_box[GM_TF_THREADS / 64 * 6];
     const GmFrame d = fr[blockIdx.y];                            // (uniform over the workgroup)
     const int base = blockIdx.x * (GM_TF_THREADS * GM_TF_PER);
     if (base >= d.n) return;                                     // (the whole workgroup: the grid is sized for the largest frame)
-    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+    CloudBox b;
+    b.init();
     bool bad = false;
     float4 p[GM_TF_PER];
     // the clouds are read once: all of a thread's loads in flight together, past the caches' retention
@@ -98,13 +100,7 @@ __global__ __launch_bounds__(GM_TF_THREADS) void k_gm_transform(const GmFrame* _
     for (int k = 0; k < GM_TF_PER; ++k) {
         const int i = base + k * GM_TF_THREADS + (int)threadIdx.x;
         if (i >= d.n) continue;
-        // transformCloud exactly as k_lm_transform forms it (double q * v + t, products kept separate, float store)
-        const double v[3] = {(double)p[k].x, (double)p[k].y, (double)p[k].z};
-        double uv[3] = {d.q[2] * v[2] - d.q[3] * v[1], d.q[3] * v[0] - d.q[1] * v[2], d.q[1] * v[1] - d.q[2] * v[0]};
-        uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-        const double uuv[3] = {d.q[2] * uv[2] - d.q[3] * uv[1], d.q[3] * uv[0] - d.q[1] * uv[2], d.q[1] * uv[1] - d.q[2] * uv[0]};
-        const float4 g = make_float4((float)((v[0] + d.q[0] * uv[0] + uuv[0]) + d.t[0]), (float)((v[1] + d.q[0] * uv[1] + uuv[1]) + d.t[1]),
-                                     (float)((v[2] + d.q[0] * uv[2] + uuv[2]) + d.t[2]), p[k].w);
+        const float4 g = cloud_transform(d.q, d.t, p[k]);
         const float f[3] = {floorf(g.x * inv_leaf), floorf(g.y * inv_leaf), floorf(g.z * inv_leaf)};
         int c[3];
 #pragma unroll
@@ -112,30 +108,14 @@ __global__ __launch_bounds__(GM_TF_THREADS) void k_gm_transform(const GmFrame* _
             const bool ok = f[a] >= -(float)GM_BIAS && f[a] < (float)GM_BIAS;          // (false for NaN)
             if (!ok) bad = true;
             c[a] = ok ? (int)f[a] : 0;
-            mn[a] = min(mn[a], c[a]); mx[a] = max(mx[a], c[a]);
+            b.add(a, c[a]);
         }
         const gm_u64 kk = ((gm_u64)(unsigned)(c[2] + GM_BIAS) << 42) | ((gm_u64)(unsigned)(c[1] + GM_BIAS) << 21) | (gm_u64)(unsigned)(c[0] + GM_BIAS);
         const size_t e = (size_t)d.off + (size_t)i;
         pts[e] = g; key[e] = kk; val[e] = (unsigned)e;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { mn[a] = min(mn[a], __shfl_xor(mn[a], off, 64)); mx[a] = max(mx[a], __shfl_xor(mx[a], off, 64)); }
-    }
     if (bad) atomicOr(&ctl->bad, 1);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { s_mn[w][a] = mn[a]; s_mx[w][a] = mx[a]; }
-    }
-    __syncthreads();
-    // one set of six atomics per workgroup (they all hit the same words)
-    if (threadIdx.x < 6) {
-        const int a = threadIdx.x % 3;
-        if (threadIdx.x < 3) { int x = 0x7fffffff; for (int k = 0; k < GM_TF_THREADS / 64; ++k) x = min(x, s_mn[k][a]); atomicMin(&ctl->bb[a], x); }
-        else { int x = (int)0x80000000; for (int k = 0; k < GM_TF_THREADS / 64; ++k) x = max(x, s_mx[k][a]); atomicMax(&ctl->bb[3 + a], x); }
-    }
+    b.commit<GM_TF_THREADS / 64>(s_box, ctl->bb);
 }
 __global__ void k_gm_plan(GmCtl* ctl) {
     if (threadIdx.x != 0 || blockIdx.x != 0 || ctl->bad) return;         // (a refused call sorts nothing: npass stays 0)
@@ -154,6 +134,7 @@ __device__ __forceinline__ int gm_digit_of(const GmPlan& p, const gm_u64 k, cons
     return (int)((rel >> shift) & 255ull);
 }
 __device__ __forceinline__ bool gm_digit(const GmCtl* __restrict__ ctl, const int d, int& par) { par = d & 1; return d < ctl->npass && !ctl->bad; }
+struct GmDigit { GmPlan plan; int shift; __device__ __forceinline__ int operator()(const gm_u64 k) const { return gm_digit_of(plan, k, shift); } };
 // the buffer that holds the sorted pairs
 __device__ __forceinline__ int gm_sorted_par(const GmCtl* __restrict__ ctl) { return ctl->npass & 1; }
 
@@ -162,18 +143,7 @@ __global__ __launch_bounds__(64) void k_gm_hist(const gm_u64* __restrict__ key0,
     __shared__ int h[256];
     int par;
     if (!gm_digit(ctl, d, par)) return;
-    const gm_u64* __restrict__ key = par ? key1 : key0;
-    const GmPlan plan = gm_plan(ctl);
-    const int lane = threadIdx.x, t0 = blockIdx.x * GM_SORT_TILE, shift = 8 * d;
-    for (int b = lane; b < 256; b += 64) h[b] = 0;
-    GLIO_WAVE_LDS_SYNC();
-    gm_u64 kk[GM_SORT_TILE / 64];
-#pragma unroll
-    for (int q = 0; q < GM_SORT_TILE / 64; ++q) { const int e = t0 + 64 * q + lane; kk[q] = e < n ? key[e] : 0ull; }
-#pragma unroll
-    for (int q = 0; q < GM_SORT_TILE / 64; ++q) if (t0 + 64 * q + lane < n) atomicAdd(&h[gm_digit_of(plan, kk[q], shift)], 1);
-    GLIO_WAVE_LDS_SYNC();
-    for (int b = lane; b < 256; b += 64) hist[(size_t)blockIdx.x * 256 + b] = h[b];        // [tile][digit value]: coalesced here, in the scan and in the scatter
+    cloud_radix_hist<GM_SORT_TILE>(par ? key1 : key0, n, blockIdx.x, GmDigit{gm_plan(ctl), 8 * d}, h, hist + (size_t)blockIdx.x * 256);
 }
 // exclusive scan of hist over (digit value, tile) in that order.  a: per workgroup of GM_SCAN_CHUNK tiles and digit value, the sum; b (one workgroup over the
 // nchunk x 256 sums): where each workgroup's tiles of each digit value start; c: the tiles' counts rewritten as running offsets
@@ -205,45 +175,14 @@ __global__ __launch_bounds__(256) void k_gm_scan_c(int* __restrict__ hist, const
     int run = csum[(size_t)blockIdx.x * 256 + threadIdx.x];
     for (int t = ta; t < tb; ++t) { const int x = hist[(size_t)t * 256 + threadIdx.x]; hist[(size_t)t * 256 + threadIdx.x] = run; run += x; }
 }
-// one wavefront per tile walks its chunks of 64 in order; inside a chunk a pair's rank among the lanes with the same digit value comes from eight ballots (the
-// ranking of localmap_kernels.hip's k_rs_scatter): stable
+// one wavefront per tile: cloud_radix_scatter (stable)
 __global__ __launch_bounds__(64) void k_gm_scatter(gm_u64* __restrict__ key0, gm_u64* __restrict__ key1, unsigned* __restrict__ val0, unsigned* __restrict__ val1, const int n,
                                                    const int d, const GmCtl* __restrict__ ctl, const int* __restrict__ hist) {
     __shared__ int base[256];
     int par;
     if (!gm_digit(ctl, d, par)) return;
-    const gm_u64* __restrict__ key = par ? key1 : key0; const unsigned* __restrict__ val = par ? val1 : val0;
-    gm_u64* __restrict__ okey = par ? key0 : key1; unsigned* __restrict__ oval = par ? val0 : val1;
-    const GmPlan plan = gm_plan(ctl);
-    const int lane = threadIdx.x, t0 = blockIdx.x * GM_SORT_TILE, shift = 8 * d;
-    for (int b = lane; b < 256; b += 64) base[b] = hist[(size_t)blockIdx.x * 256 + b];
-    GLIO_WAVE_LDS_SYNC();
-    gm_u64 kk[GM_SORT_TILE / 64]; unsigned vv[GM_SORT_TILE / 64];
-#pragma unroll
-    for (int q = 0; q < GM_SORT_TILE / 64; ++q) {
-        const int e = t0 + 64 * q + lane;
-        kk[q] = e < n ? key[e] : 0ull;
-        vv[q] = e < n ? val[e] : 0u;
-    }
-#pragma unroll
-    for (int q = 0; q < GM_SORT_TILE / 64; ++q) {
-        const int e = t0 + 64 * q + lane;
-        const bool live = e < n;
-        const gm_u64 k = kk[q];
-        const int dg = live ? gm_digit_of(plan, k, shift) : 0;
-        gm_u64 same = __ballot(live);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const gm_u64 bal = __ballot((dg >> b) & 1);
-            same &= ((dg >> b) & 1) ? bal : ~bal;
-        }
-        const int rank = __popcll(same & ((1ull << lane) - 1ull));
-        const int pos = live ? base[dg] + rank : 0;
-        GLIO_WAVE_LDS_SYNC();
-        if (live && rank == 0) base[dg] += __popcll(same);           // the first lane of every digit group advances its run
-        GLIO_WAVE_LDS_SYNC();
-        if (live) { okey[pos] = k; oval[pos] = vv[q]; }              // (pos < n: the offsets are the scan of this very digit's counts)
-    }
+    cloud_radix_scatter<GM_SORT_TILE>(par ? key1 : key0, par ? val1 : val0, n, blockIdx.x, GmDigit{gm_plan(ctl), 8 * d}, base, hist + (size_t)blockIdx.x * 256,
+                                      par ? key0 : key1, par ? val0 : val1);
 }
 
 // ---- runs
@@ -262,7 +201,7 @@ __global__ __launch_bounds__(GM_RUN_BLOCK) void k_gm_runs(gm_u64* __restrict__ k
     const int par = gm_sorted_par(ctl);
     const gm_u64* __restrict__ sk = par ? key1 : key0;
     gm_u64* __restrict__ enc = par ? key0 : key1; unsigned* __restrict__ pre = par ? val0 : val1;
-    const int i = blockIdx.x * GM_RUN_BLOCK + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int i = blockIdx.x * GM_RUN_BLOCK + threadIdx.x, wv = threadIdx.x >> 6;
     int c = 0;
     if (i < n) {
         const gm_u64 k = sk[i];
@@ -273,10 +212,10 @@ __global__ __launch_bounds__(GM_RUN_BLOCK) void k_gm_runs(gm_u64* __restrict__ k
             c = !found;
         }
     }
-    int incl = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
-    if (lane == 63) s_w[wv] = incl;
+    // the workgroup scan written out: the wavefront totals chained by ONE thread.  cloud_wg_excl_scan (every thread sums the sixteen totals) measured
+    // 1.093 -> 1.114 ms in the runs + sums stage of 667 frames x 32768 points, outside the parent's spread of 0.003 (profiles/cloud_dedup_ab.txt)
+    const int incl = cloud_wave_incl_scan(c);
+    if ((threadIdx.x & 63) == 63) s_w[wv] = incl;
     __syncthreads();
     if (threadIdx.x == 0) { int t = 0; for (int k = 0; k < GM_RUN_BLOCK / 64; ++k) { const int x = s_w[k]; s_w[k] = t; t += x; } blk[blockIdx.x] = t; }
     __syncthreads();

@@ -23,6 +23,7 @@
 #include <chrono>
 
 #include "glio_device.h"
+#include "cloud_device.h"
 
 // the transform must round like the reference's scalar code (and the oracle): no FMA contraction in this file
 #pragma clang fp contract(off)
@@ -74,16 +75,10 @@ static inline float h_ord2f(int i) { const int u = i >= 0 ? i : i ^ 0x7fffffff; 
 
 __global__ void k_lm_transform(const float4* __restrict__ in, int n, const double q0, const double q1, const double q2, const double q3,
                                const double t0, const double t1, const double t2, float4* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;          // transformCloud, Estimator.cpp:1517-1546 (double q*v + t, float store)
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float4 p = in[i];
-    const double v[3] = {(double)p.x, (double)p.y, (double)p.z};
-    // Eigen: v + w * (2 u x v) + u x (2 u x v), products kept separate (no contraction) as in assoc_kernels.hip
-    double uv[3] = {q2 * v[2] - q3 * v[1], q3 * v[0] - q1 * v[2], q1 * v[1] - q2 * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    const double uuv[3] = {q2 * uv[2] - q3 * uv[1], q3 * uv[0] - q1 * uv[2], q1 * uv[1] - q2 * uv[0]};
-    out[i] = make_float4((float)((v[0] + q0 * uv[0] + uuv[0]) + t0), (float)((v[1] + q0 * uv[1] + uuv[1]) + t1),
-                         (float)((v[2] + q0 * uv[2] + uuv[2]) + t2), p.w);
+    const double q[4] = {q0, q1, q2, q3}, t[3] = {t0, t1, t2};
+    out[i] = cloud_transform(q, t, in[i]);
 }
 
 // the same from a cloud that is already on the device in the LiDAR frame: p_body = p - off in FLOAT (what a caller's float cloud minus the
@@ -93,19 +88,17 @@ __global__ void k_lm_transform_off(const float4* __restrict__ in, int n, const f
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float4 p = in[i];
-    const float bx = p.x - ox, by = p.y - oy, bz = p.z - oz;
-    const double v[3] = {(double)bx, (double)by, (double)bz};
-    double uv[3] = {q2 * v[2] - q3 * v[1], q3 * v[0] - q1 * v[2], q1 * v[1] - q2 * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    const double uuv[3] = {q2 * uv[2] - q3 * uv[1], q3 * uv[0] - q1 * uv[2], q1 * uv[1] - q2 * uv[0]};
-    out[i] = make_float4((float)((v[0] + q0 * uv[0] + uuv[0]) + t0), (float)((v[1] + q0 * uv[1] + uuv[1]) + t1),
-                         (float)((v[2] + q0 * uv[2] + uuv[2]) + t2), p.w);
+    const double q[4] = {q0, q1, q2, q3}, t[3] = {t0, t1, t2};
+    out[i] = cloud_transform(q, t, make_float4(p.x - ox, p.y - oy, p.z - oz, p.w));
 }
 
-__global__ void k_lm_clear(unsigned long long* keys, long long* sum, int* cnt, int cap, int* nkeys) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+// one slot of the voxel table emptied (thread i of a grid that covers cap slots); the key counter with slot 0
+__device__ __forceinline__ void lm_table_reset(const int i, unsigned long long* keys, long long* sum, int* cnt, const int cap, int* nkeys) {
     if (i < cap) { keys[i] = LM_EMPTY; cnt[i] = 0; sum[4 * (size_t)i] = 0; sum[4 * (size_t)i + 1] = 0; sum[4 * (size_t)i + 2] = 0; sum[4 * (size_t)i + 3] = 0; }
     if (i == 0) *nkeys = 0;
+}
+__global__ void k_lm_clear(unsigned long long* keys, long long* sum, int* cnt, int cap, int* nkeys) {
+    lm_table_reset(blockIdx.x * blockDim.x + threadIdx.x, keys, sum, cnt, cap, nkeys);
 }
 // (also records the slot's point count on the device: the build used to upload all `width` counts from pageable memory -- an API call of ~8 us in a
 //  chain of launches that is bound by the host's launch rate)
@@ -115,32 +108,14 @@ __global__ void k_lm_bbox_init(int* bbox, int* n_slot, const int n) {
 }
 // bounding box of one ring slot (ordered-int atomics)
 __global__ __launch_bounds__(1024) void k_lm_bbox(const float4* __restrict__ pts, int n, int* bbox) {
-    __shared__ int s_mn[16][3], s_mx[16][3];
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
-    for (; i < n; i += gridDim.x * blockDim.x) {
+    __shared__ int s_box[16 * 6];
+    CloudBox b;
+    b.init();
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float4 p = pts[i];
-        const int o[3] = {f2ord(p.x), f2ord(p.y), f2ord(p.z)};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { mn[c] = min(mn[c], o[c]); mx[c] = max(mx[c], o[c]); }
+        b.add(f2ord(p.x), f2ord(p.y), f2ord(p.z));
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { mn[c] = min(mn[c], __shfl_xor(mn[c], off, 64)); mx[c] = max(mx[c], __shfl_xor(mx[c], off, 64)); }
-    }
-    // one set of six atomics per 1024-thread workgroup (they all hit the same six words)
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { s_mn[threadIdx.x >> 6][c] = mn[c]; s_mx[threadIdx.x >> 6][c] = mx[c]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int c = threadIdx.x % 3;
-        const int nw = (blockDim.x + 63) >> 6;
-        if (threadIdx.x < 3) { int v = 0x7fffffff; for (int w = 0; w < nw; ++w) v = min(v, s_mn[w][c]); atomicMin(bbox + c, v); }
-        else { int v = (int)0x80000000; for (int w = 0; w < nw; ++w) v = max(v, s_mx[w][c]); atomicMax(bbox + 3 + c, v); }
-    }
+    b.commit<16>(s_box, bbox);
 }
 // union of the slot boxes (slots with n = 0 are skipped)
 __global__ void k_lm_bbox_union(const int* __restrict__ slot_bbox, const int* __restrict__ ns, int width, int* bbox, int* bm_over, int* nvox) {
@@ -159,15 +134,11 @@ __device__ __forceinline__ unsigned lm_hash(unsigned long long k) {
 __device__ __forceinline__ unsigned long long lm_key(int ix, int iy, int iz) {        // absolute voxel coordinates, 21 bits each, biased
     return ((unsigned long long)(unsigned)(ix + (1 << 20)) << 42) | ((unsigned long long)(unsigned)(iy + (1 << 20)) << 21) | (unsigned long long)(unsigned)(iz + (1 << 20));
 }
-// add (sign = +1) or remove (sign = -1) the points of one keyframe.
-// A removal may assume that its key is in the table only while every insertion since the last k_lm_clear found a place.  After an overflow (bit 30 of
+// add (sign = +1) or remove (sign = -1) one point.
+// A removal may assume that its key is in the table only while every insertion since the last table reset found a place.  After an overflow (bit 30 of
 // *nkeys) some points of a keyframe were never inserted: their removal meets an empty slot, or walks a table without one, and then leaves every slot
 // as it is -- the table is no longer what the ring holds anyway, and the host reconstructs it from the ring at the next build (lm_voxelize).
-__global__ void k_lm_accumulate(const float4* __restrict__ pts, int n, float inv_leaf, int sign, unsigned long long* keys, long long* sum, int* cnt,
-                                int cap, int* nkeys) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = pts[i];
+__device__ __forceinline__ void lm_table_add(const float4 p, const float inv_leaf, const int sign, unsigned long long* keys, long long* sum, int* cnt, const int cap, int* nkeys) {
     const unsigned long long key = lm_key((int)floorf(p.x * inv_leaf), (int)floorf(p.y * inv_leaf), (int)floorf(p.z * inv_leaf));
     unsigned s = lm_hash(key) & (cap - 1);
     int probes = 0;
@@ -183,6 +154,12 @@ __global__ void k_lm_accumulate(const float4* __restrict__ pts, int n, float inv
     for (int c = 0; c < 4; ++c) atomicAdd(reinterpret_cast<unsigned long long*>(sum + 4 * (size_t)s + c), (unsigned long long)(sign > 0 ? f[c] : -f[c]));
     atomicAdd(cnt + s, sign);
 }
+// the points of one keyframe added or removed
+__global__ void k_lm_accumulate(const float4* __restrict__ pts, int n, float inv_leaf, int sign, unsigned long long* keys, long long* sum, int* cnt,
+                                int cap, int* nkeys) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) lm_table_add(pts[i], inv_leaf, sign, keys, sum, cnt, cap, nkeys);
+}
 // list the live voxels with their pcl::VoxelGrid linear index (relative to the ring's bounding box) for the ordered output
 __global__ __launch_bounds__(1024) void k_lm_list(const unsigned long long* __restrict__ keys, const int* __restrict__ cnt, int cap, float inv_leaf,
                                                   const int* __restrict__ bbox, int* nvox, unsigned long long* vkey, int* vslot, int max_vox,
@@ -190,16 +167,11 @@ __global__ __launch_bounds__(1024) void k_lm_list(const unsigned long long* __re
     // one list position per live voxel: positions come from a block-wide count (ballot per wavefront, 16 wavefront totals through LDS)
     // and ONE atomic per 1024 slots -- an atomic per voxel (~1e5 on one address) made this kernel 100-500 us
     __shared__ int s_w[16], s_base;
-    const int s = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int s = blockIdx.x * 1024 + threadIdx.x;
     const bool live = s < cap && cnt[s] > 0;
-    const unsigned long long bal = __ballot(live);
-    if (lane == 0) s_w[wv] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int k = 0; k < 16; ++k) { const int v = s_w[k]; s_w[k] = t; t += v; }
-        s_base = t > 0 ? atomicAdd(nvox, t) : 0;
-    }
+    int tot;
+    const int rk = cloud_wg_rank<16>(live, s_w, tot);
+    if (threadIdx.x == 0) s_base = tot > 0 ? atomicAdd(nvox, tot) : 0;
     __syncthreads();
     if (!live) return;
     int min_b[3], div_b[3];
@@ -208,7 +180,7 @@ __global__ __launch_bounds__(1024) void k_lm_list(const unsigned long long* __re
     const unsigned long long k = keys[s];
     const int ix = (int)((k >> 42) & 0x1fffff) - (1 << 20), iy = (int)((k >> 21) & 0x1fffff) - (1 << 20), iz = (int)(k & 0x1fffff) - (1 << 20);
     const unsigned long long lin = (unsigned long long)((long long)(ix - min_b[0]) + (long long)(iy - min_b[1]) * div_b[0] + (long long)(iz - min_b[2]) * div_b[0] * (long long)div_b[1]);
-    const int v = s_base + s_w[wv] + __popcll(bal & ((1ull << lane) - 1ull));
+    const int v = s_base + rk;
     if (v < max_vox) { vkey[v] = lin; vslot[v] = s; }
     // the voxel's bit in the occupancy bitmap of the bounding box (k_bm_*: its rank among the set bits is its place in the ordered output)
     if (bm) { if (lin < bm_bits) atomicOr(&bm[lin >> 5], 1u << (unsigned)(lin & 31ull)); else *bm_over = 1; }
@@ -224,45 +196,20 @@ __global__ __launch_bounds__(1024) void k_lm_list(const unsigned long long* __re
 #define BM_MAX_BITS (1ull << 27)
 __global__ __launch_bounds__(1024) void k_bm_scan1(const unsigned* __restrict__ bm, const int nwords, int* __restrict__ pre, int* __restrict__ blk) {
     __shared__ int s_w[16];
-    const int w = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int c = w < nwords ? __popc(bm[w]) : 0;
-    int incl = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        const int v = threadIdx.x < 16 ? s_w[threadIdx.x] : 0;
-        int inc = v;
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1) { const int o = __shfl_up(inc, off, 64); if ((int)threadIdx.x >= off) inc += o; }
-        if (threadIdx.x < 16) s_w[threadIdx.x] = inc - v;
-        if (threadIdx.x == 15) blk[blockIdx.x] = inc;
-    }
-    __syncthreads();
-    if (w < nwords) pre[w] = s_w[wv] + incl - c;
+    const int w = blockIdx.x * 1024 + threadIdx.x;
+    int tot;
+    const int ex = cloud_wg_excl_scan<16>(w < nwords ? __popc(bm[w]) : 0, s_w, tot);
+    if (threadIdx.x == 0) blk[blockIdx.x] = tot;
+    if (w < nwords) pre[w] = ex;
 }
 // exclusive scan of the block totals in place (one workgroup; nblk <= 4096: four per thread)
 __global__ __launch_bounds__(1024) void k_bm_scan2(int* __restrict__ blk, const int nblk) {
     __shared__ int s_w[16];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    int a[4], tot = 0;
+    const int t = threadIdx.x;
+    int a[4], tot = 0, all;
 #pragma unroll
     for (int k = 0; k < 4; ++k) { a[k] = 4 * t + k < nblk ? blk[4 * t + k] : 0; tot += a[k]; }
-    int incl = tot;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    if (t < 64) {
-        const int v = t < 16 ? s_w[t] : 0;
-        int inc = v;
-#pragma unroll
-        for (int off = 1; off < 16; off <<= 1) { const int o = __shfl_up(inc, off, 64); if (t >= off) inc += o; }
-        if (t < 16) s_w[t] = inc - v;
-    }
-    __syncthreads();
-    int run = s_w[wv] + incl - tot;
+    int run = cloud_wg_excl_scan<16>(tot, s_w, all);
 #pragma unroll
     for (int k = 0; k < 4; ++k) { if (4 * t + k < nblk) blk[4 * t + k] = run; run += a[k]; }
 }
@@ -283,23 +230,14 @@ __device__ __forceinline__ void bm_clear_word(unsigned* __restrict__ bm, const u
 // Ordered output: the live voxels sorted by their pcl::VoxelGrid linear index.  A least-significant-digit radix sort on 8-bit
 // digits, hand-written for this case: the keys are bounded by the ring's bounding box (typically < 2^24), so the host -- which
 // reads the voxel count back anyway -- asks for only ceil(bits / 8) passes (3 instead of the 8 a generic 64-bit sort runs).
-//   k_rs_hist     one wavefront per tile of 1024 pairs: 256-bin digit histogram (LDS atomics) -> hist[tile][digit]
+//   k_rs_hist     one wavefront per tile of 1024 pairs: cloud_radix_hist -> hist[tile][digit]
 //   k_rs_scan     exclusive scan over (digit, tile) in that order: where each tile's run of each digit starts
-//   k_rs_scatter  the same wavefront per tile walks its 16 chunks of 64 in order; inside a chunk a pair's rank among the lanes
-//                 with the same digit comes from eight ballots (one per digit bit): stable, no LDS traffic for the ranking
+//   k_rs_scatter  the same wavefront per tile: cloud_radix_scatter
 #define RS_TILE 1024
+struct RsDigit { int shift; __device__ __forceinline__ int operator()(const unsigned long long k) const { return (int)((k >> shift) & 255ull); } };
 __global__ __launch_bounds__(64) void k_rs_hist(const unsigned long long* __restrict__ key, const int n, const int shift, const int nt, int* __restrict__ hist) {
     __shared__ int h[256];
-    const int lane = threadIdx.x, t0 = blockIdx.x * RS_TILE;
-    for (int d = lane; d < 256; d += 64) h[d] = 0;
-    GLIO_WAVE_LDS_SYNC();
-    unsigned long long kk[RS_TILE / 64];
-#pragma unroll
-    for (int q = 0; q < RS_TILE / 64; ++q) { const int e = t0 + 64 * q + lane; kk[q] = e < n ? key[e] : ~0ull; }
-#pragma unroll
-    for (int q = 0; q < RS_TILE / 64; ++q) if (t0 + 64 * q + lane < n) atomicAdd(&h[(int)((kk[q] >> shift) & 255ull)], 1);
-    GLIO_WAVE_LDS_SYNC();
-    for (int d = lane; d < 256; d += 64) hist[blockIdx.x * 256 + d] = h[d];           // [tile][digit]: coalesced here, in the scan and in the scatter
+    cloud_radix_hist<RS_TILE>(key, n, blockIdx.x, RsDigit{shift}, h, hist + (size_t)blockIdx.x * 256);
 }
 #define RS_SCAN_PER 64          /* tiles of one (digit, quarter) held in registers: up to 256 tiles = 262144 voxels */
 __global__ __launch_bounds__(1024) void k_rs_scan(int* __restrict__ hist, const int nt) {
@@ -328,10 +266,7 @@ __global__ __launch_bounds__(1024) void k_rs_scan(int* __restrict__ hist, const 
         const int l = threadIdx.x;
         const int a0 = dbase[4 * l], a1 = dbase[4 * l + 1], a2 = dbase[4 * l + 2], a3 = dbase[4 * l + 3];
         const int tot = a0 + a1 + a2 + a3;
-        int incl = tot;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (l >= off) incl += o; }
-        const int ex = incl - tot;
+        const int ex = cloud_wave_incl_scan(tot) - tot;
         dbase[4 * l] = ex; dbase[4 * l + 1] = ex + a0; dbase[4 * l + 2] = ex + a0 + a1; dbase[4 * l + 3] = ex + a0 + a1 + a2;
     }
     __syncthreads();
@@ -347,36 +282,7 @@ __global__ __launch_bounds__(1024) void k_rs_scan(int* __restrict__ hist, const 
 __global__ __launch_bounds__(64) void k_rs_scatter(const unsigned long long* __restrict__ key, const int* __restrict__ val, const int n, const int shift, const int nt,
                                                    const int* __restrict__ hist, unsigned long long* __restrict__ okey, int* __restrict__ oval) {
     __shared__ int base[256];
-    const int lane = threadIdx.x, t0 = blockIdx.x * RS_TILE;
-    for (int d = lane; d < 256; d += 64) base[d] = hist[blockIdx.x * 256 + d];
-    GLIO_WAVE_LDS_SYNC();
-    // all 16 chunks of the tile are fetched first (16 independent loads per lane in flight), then ranked chunk by chunk
-    unsigned long long kk[RS_TILE / 64]; int vv[RS_TILE / 64];
-#pragma unroll
-    for (int q = 0; q < RS_TILE / 64; ++q) {
-        const int e = t0 + 64 * q + lane;
-        kk[q] = e < n ? key[e] : 0ull;
-        vv[q] = e < n ? val[e] : 0;
-    }
-#pragma unroll
-    for (int q = 0; q < RS_TILE / 64; ++q) {
-        const int e = t0 + 64 * q + lane;
-        const bool live = e < n;
-        const unsigned long long k = kk[q];
-        const int dg = (int)((k >> shift) & 255ull);
-        unsigned long long same = __ballot(live);
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-            const unsigned long long bal = __ballot((dg >> b) & 1);
-            same &= ((dg >> b) & 1) ? bal : ~bal;
-        }
-        const int rank = __popcll(same & ((1ull << lane) - 1ull));
-        const int pos = live ? base[dg] + rank : 0;
-        GLIO_WAVE_LDS_SYNC();
-        if (live && rank == 0) base[dg] += __popcll(same);           // the first lane of every digit group advances its run
-        GLIO_WAVE_LDS_SYNC();
-        if (live) { okey[pos] = k; oval[pos] = vv[q]; }
-    }
+    cloud_radix_scatter<RS_TILE>(key, val, n, blockIdx.x, RsDigit{shift}, base, hist + (size_t)blockIdx.x * 256, okey, oval);
 }
 
 __global__ void k_lm_emit(const int* __restrict__ vslot_sorted, int nv, const long long* __restrict__ sum, const int* __restrict__ cnt,
@@ -469,8 +375,8 @@ __global__ void k_lm_emit_float(const int* __restrict__ vslot_sorted, const int 
 // Rebuild of the whole ring from resident keyframe clouds (glio_localmap_rebuild_from_frames): what n_frames pushes into a fresh ring do -- per frame a slot
 // initialisation, transformCloud, the row's bounding box and the voxel accumulation, three to four launches each -- in TWO launches whatever n_frames is:
 //   k_lm_rebuild_clear    the voxel table emptied; every slot's box and count initialised (slots behind n_frames: empty)
-//   k_lm_rebuild_frames   blockIdx.y = frame: k_lm_transform's arithmetic from the frame's cloud into ring row blockIdx.y, the row's box (one set of six atomics
-//                         per workgroup), k_lm_accumulate's insertion.  The sums are exact integers: whatever order the frames' workgroups run in, the table
+//   k_lm_rebuild_frames   blockIdx.y = frame: cloud_transform from the frame's cloud into ring row blockIdx.y, the row's box (one set of six atomics
+//                         per workgroup), lm_table_add.  The sums are exact integers: whatever order the frames' workgroups run in, the table
 //                         holds what the pushes would have left (keys may sit in other slots of the table: no reader depends on where).
 // ------------------------------------------------------------------------------------------------
 typedef float lm_v4f __attribute__((ext_vector_type(4)));
@@ -479,20 +385,20 @@ typedef float lm_v4f __attribute__((ext_vector_type(4)));
 __global__ void k_lm_rebuild_clear(unsigned long long* keys, long long* sum, int* cnt, int cap, int* nkeys, const LmFrame* __restrict__ fr, int n_frames, int width,
                                    int* slot_bbox, int* ns) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < cap) { keys[i] = LM_EMPTY; cnt[i] = 0; sum[4 * (size_t)i] = 0; sum[4 * (size_t)i + 1] = 0; sum[4 * (size_t)i + 2] = 0; sum[4 * (size_t)i + 3] = 0; }
-    if (i == 0) *nkeys = 0;
+    lm_table_reset(i, keys, sum, cnt, cap, nkeys);
     if (i < 6 * width) slot_bbox[i] = (i % 6) < 3 ? 0x7fffffff : (int)0x80000000;
     if (i < width) ns[i] = i < n_frames ? fr[i].n : 0;
 }
 __global__ __launch_bounds__(LM_RB_THREADS) void k_lm_rebuild_frames(const LmFrame* __restrict__ fr, float4* __restrict__ ring, const int ring_cap, const float inv_leaf,
                                                                      unsigned long long* keys, long long* sum, int* cnt, const int cap, int* nkeys, int* slot_bbox) {
-    __shared__ int s_mn[LM_RB_THREADS / 64][3], s_mx[LM_RB_THREADS / 64][3];
+    __shared__ int s_box[LM_RB_THREADS / 64 * 6];
     const int f = blockIdx.y;
     const LmFrame d = fr[f];                                     // (uniform over the workgroup)
     const int base = blockIdx.x * (LM_RB_THREADS * LM_RB_PER);
     if (base >= d.n) return;                                     // (the whole workgroup: the grid is sized for the largest frame)
     float4* __restrict__ row = ring + (size_t)f * ring_cap;
-    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+    CloudBox b;
+    b.init();
     float4 p[LM_RB_PER];
     // the clouds are read once: all of a thread's loads in flight together, past the caches' retention
 #pragma unroll
@@ -504,50 +410,12 @@ __global__ __launch_bounds__(LM_RB_THREADS) void k_lm_rebuild_frames(const LmFra
     for (int k = 0; k < LM_RB_PER; ++k) {
         const int i = base + k * LM_RB_THREADS + (int)threadIdx.x;
         if (i >= d.n) continue;
-        // transformCloud exactly as k_lm_transform forms it (double q * v + t, products kept separate, float store)
-        const double v[3] = {(double)p[k].x, (double)p[k].y, (double)p[k].z};
-        double uv[3] = {d.q[2] * v[2] - d.q[3] * v[1], d.q[3] * v[0] - d.q[1] * v[2], d.q[1] * v[1] - d.q[2] * v[0]};
-        uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-        const double uuv[3] = {d.q[2] * uv[2] - d.q[3] * uv[1], d.q[3] * uv[0] - d.q[1] * uv[2], d.q[1] * uv[1] - d.q[2] * uv[0]};
-        const float4 g = make_float4((float)((v[0] + d.q[0] * uv[0] + uuv[0]) + d.t[0]), (float)((v[1] + d.q[0] * uv[1] + uuv[1]) + d.t[1]),
-                                     (float)((v[2] + d.q[0] * uv[2] + uuv[2]) + d.t[2]), p[k].w);
+        const float4 g = cloud_transform(d.q, d.t, p[k]);
         row[i] = g;
-        const int o[3] = {f2ord(g.x), f2ord(g.y), f2ord(g.z)};
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { mn[c] = min(mn[c], o[c]); mx[c] = max(mx[c], o[c]); }
-        // k_lm_accumulate with sign = +1
-        const unsigned long long key = lm_key((int)floorf(g.x * inv_leaf), (int)floorf(g.y * inv_leaf), (int)floorf(g.z * inv_leaf));
-        unsigned s = lm_hash(key) & (cap - 1);
-        int probes = 0;
-        bool full = false;
-        for (;;) {
-            const unsigned long long kk = atomicCAS(keys + s, LM_EMPTY, key);
-            if (kk == LM_EMPTY) { atomicAdd(nkeys, 1); break; }
-            if (kk == key) break;
-            s = (s + 1) & (cap - 1);
-            if (++probes >= cap) { atomicOr(nkeys, 0x40000000); full = true; break; }          // table full: reported by the build
-        }
-        if (full) continue;
-        const long long fx[4] = {llrint((double)g.x * LM_FIX), llrint((double)g.y * LM_FIX), llrint((double)g.z * LM_FIX), llrint((double)g.w * LM_FIX)};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) atomicAdd(reinterpret_cast<unsigned long long*>(sum + 4 * (size_t)s + c), (unsigned long long)fx[c]);
-        atomicAdd(cnt + s, 1);
+        b.add(f2ord(g.x), f2ord(g.y), f2ord(g.z));
+        lm_table_add(g, inv_leaf, +1, keys, sum, cnt, cap, nkeys);
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { mn[c] = min(mn[c], __shfl_xor(mn[c], off, 64)); mx[c] = max(mx[c], __shfl_xor(mx[c], off, 64)); }
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) { s_mn[threadIdx.x >> 6][c] = mn[c]; s_mx[threadIdx.x >> 6][c] = mx[c]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int c = threadIdx.x % 3;
-        if (threadIdx.x < 3) { int v = 0x7fffffff; for (int w = 0; w < LM_RB_THREADS / 64; ++w) v = min(v, s_mn[w][c]); atomicMin(slot_bbox + 6 * f + c, v); }
-        else { int v = (int)0x80000000; for (int w = 0; w < LM_RB_THREADS / 64; ++w) v = max(v, s_mx[w][c]); atomicMax(slot_bbox + 6 * f + 3 + c, v); }
-    }
+    b.commit<LM_RB_THREADS / 64>(s_box, slot_bbox + 6 * f);
 }
 
 #define LM_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { glio_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); return GLIO_E_HIP; } } while (0)
@@ -955,7 +823,7 @@ int glio_localmap_read(glio_ctx* c, float* out_xyzi, int capacity, int* out_n) {
 
 }  // extern "C"
 
-// ---- the same VoxelGrid for a caller that is not a context: a list of device-resident clouds, each moved by transformCloud (k_lm_transform), concatenated in
+// ---- the same VoxelGrid for a caller that is not a context: a list of device-resident clouds, each moved by transformCloud (k_lm_transform: cloud_transform), concatenated in
 // list order and filtered with the float accumulation (accumulation = 1: pcl::VoxelGrid's arithmetic and output order, the oracle's bit for bit).  The ring is
 // used as a plain array of `width` slots, refilled by every build.  For the loop-closure submaps (loop_kernels.hip).
 int glio_vg_create(int width, int cap, float leaf, int max_vox, hipStream_t stream, LocalMap** out) {

@@ -25,6 +25,7 @@
 #include <cstring>
 
 #include "glio_device.h"
+#include "cloud_device.h"
 
 // d2 = dx*dx + dy*dy + dz*dz and T*p must round like scalar float code (and the numpy restatement): no FMA contraction in this file
 #pragma clang fp contract(off)
@@ -72,22 +73,16 @@ struct glio_loop {
 // ---- the target's grid
 __global__ void k_lp_bbox_init(int* bbox) { const int i = threadIdx.x; if (i < 3) bbox[i] = 0x7fffffff; else if (i < 6) bbox[i] = (int)0x80000000; }
 __global__ __launch_bounds__(256) void k_lp_bbox(const float4* __restrict__ pts, const int n, int* bbox) {
-    int mn[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, mx[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+    __shared__ int s_box[256 / 64 * 6];
+    CloudBox b;
+    b.init();
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float4 p = pts[i];
         const float c[3] = {p.x, p.y, p.z};
 #pragma unroll
-        for (int a = 0; a < 3; ++a) if (c[a] == c[a] && fabsf(c[a]) <= FLT_MAX) { const int o = f2ord(c[a]); mn[a] = min(mn[a], o); mx[a] = max(mx[a], o); }
+        for (int a = 0; a < 3; ++a) if (c[a] == c[a] && fabsf(c[a]) <= FLT_MAX) b.add(a, f2ord(c[a]));      // (finite coordinates only, per axis)
     }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { mn[a] = min(mn[a], __shfl_xor(mn[a], off, 64)); mx[a] = max(mx[a], __shfl_xor(mx[a], off, 64)); }
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { atomicMin(bbox + a, mn[a]); atomicMax(bbox + 3 + a, mx[a]); }
-    }
+    b.commit<256 / 64>(s_box, bbox);
 }
 __global__ void k_lp_grid_params(const int* __restrict__ bbox, const float cell0, LoopState* st) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
