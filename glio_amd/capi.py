@@ -18,7 +18,12 @@ LIDAR_F64, LIDAR_F32_MFMA = 0, 1
 
 
 class GlioError(RuntimeError):
-    pass
+    """code: the GLIO_E_* value where the raiser knows it; n_out: the output count a refused keyframe-cloud call still reports"""
+    code = None
+    n_out = None
+
+
+E_ARG, E_HIP, E_STATE = -1, -2, -3
 
 
 def load():
@@ -39,6 +44,7 @@ def load():
         lib.glio_last_error.restype = C.c_char_p
         lib.glio_destroy.restype = None
         lib.glio_opts_default.restype = None
+        T.apply_prototypes(lib)
         _LIB = lib
     return _LIB
 
@@ -210,6 +216,67 @@ class Context:
         n = C.c_int()
         _check(load().glio_localmap_push_scan_ahead_and_build(self._h, T.fptr(off), T.dptr(q), T.dptr(t), C.byref(n)))
         return n.value
+
+    # ---- the keyframe cloud: de-skew + pcl::VoxelGrid + set_scan on the device (glio_scan_filter_config, glio_set_scan_filtered*, glio_set_scan_from_features*)
+    def scan_filter_config(self, max_input_points):
+        _check(load().glio_scan_filter_config(self._h, int(max_input_points)))
+
+    @staticmethod
+    def _motion(deskew_trans, deskew_quat):
+        t = None if deskew_trans is None else np.ascontiguousarray(deskew_trans, np.float64).reshape(3)
+        q = None if deskew_quat is None else np.ascontiguousarray(deskew_quat, np.float64).reshape(4)
+        return t, q, (None if t is None else T.dptr(t)), (None if q is None else T.dptr(q))
+
+    @staticmethod
+    def _check_count(rc, n):
+        if rc != 0:
+            e = GlioError(f"libglio_hip error {rc}: {load().glio_last_error().decode()}")
+            e.code, e.n_out = rc, n.value
+            raise e
+        return n.value
+
+    def set_scan_filtered(self, slot, points, leaf, deskew_trans=None, deskew_quat=None, ioff=None, ahead=False):
+        """points: [n][4] float32 (x y z intensity), or records of any stride with the intensity float at byte `ioff` (capi.PCL_XYZI: 16).  The cloud
+        de-skewed by (deskew_trans, deskew_quat) -- None: no de-skew / the identity -- and voxel-filtered at `leaf` becomes window slot `slot`
+        (ahead=True: slot W - 1 after the next slide_window(); `slot` is not used).  Returns the slot's point count."""
+        n = C.c_int(0)
+        t, q, tp, qp = self._motion(deskew_trans, deskew_quat)
+        pts = np.ascontiguousarray(points)
+        if ioff is None:
+            pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 4)
+            stride, ioff = 16, 12
+        else:
+            stride = pts.dtype.itemsize if pts.ndim == 1 else pts.dtype.itemsize * pts.shape[1]
+        ptr = pts.ctypes.data_as(C.c_void_p) if len(pts) else None
+        if ahead:
+            rc = load().glio_set_scan_filtered_ahead_strided(self._h, ptr, len(pts), stride, int(ioff), float(leaf), tp, qp, C.byref(n))
+        else:
+            rc = load().glio_set_scan_filtered_strided(self._h, int(slot), ptr, len(pts), stride, int(ioff), float(leaf), tp, qp, C.byref(n))
+        return self._check_count(rc, n)
+
+    def set_scan_from_features(self, frontend, slot, leaf, deskew_trans=None, deskew_quat=None, ahead=False):
+        """the same from the surf features of `frontend`'s (a Context, possibly this one) last features_extract, read where they lie on the device"""
+        n = C.c_int(0)
+        t, q, tp, qp = self._motion(deskew_trans, deskew_quat)
+        if ahead:
+            rc = load().glio_set_scan_from_features_ahead(self._h, frontend._h, float(leaf), tp, qp, C.byref(n))
+        else:
+            rc = load().glio_set_scan_from_features(self._h, int(slot), frontend._h, float(leaf), tp, qp, C.byref(n))
+        return self._check_count(rc, n)
+
+    def get_scan(self, slot):
+        """what window slot `slot` holds, in the caller's order: [n][4] float32"""
+        n = C.c_int(0)
+        _check(load().glio_get_scan(self._h, int(slot), None, 0, C.byref(n)))
+        out = np.zeros((max(n.value, 1), 4), np.float32)
+        _check(load().glio_get_scan(self._h, int(slot), T.fptr(out), n.value, C.byref(n)))
+        return out[:n.value].copy()
+
+    def scan_filter_last_device_ms(self):
+        """device ms of the last non-empty keyframe-cloud call: (de-skew + box, VoxelGrid + copy, presort); needs GLIO_KFCLOUD_TIMING=1 at scan_filter_config"""
+        ms = np.zeros(3, np.float32)
+        _check(load().glio_scan_filter_last_device_ms(self._h, T.fptr(ms)))
+        return [float(x) for x in ms]
 
     def set_scan_ahead(self, scan):
         """the NEXT keyframe's scan into the ring row that is slot W - 1 after the next slide_window() (the current slot 0's scan is gone afterwards)"""

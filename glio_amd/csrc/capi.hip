@@ -264,7 +264,9 @@ void glio_destroy(glio_ctx* c) {
     if (c->extra && extra_of(c)->ev_ahead) { hipEventDestroy(extra_of(c)->ev_ahead); extra_of(c)->ev_ahead = nullptr; }
     glio_assoc_destroy(c);
     glio_localmap_destroy(c);
-    glio_features_destroy(c);
+    glio_features_destroy(c);          // (waits for a pending read of the surf features by another context's stream)
+    if (c->ev_feat_read) { hipEventDestroy(c->ev_feat_read); c->ev_feat_read = nullptr; }
+    glio_kfcloud_destroy(c);
     void* ptrs[] = {c->d_pts, c->d_planes, c->d_scores, c->d_pts_s, c->d_count, c->d_scan, c->d_imu, c->d_imu_blocks, c->d_gnss_blocks, c->d_groups,
                     c->d_ddt_blocks, c->d_dd, c->d_dop, c->d_prior_J0, c->d_prior_A0, c->d_prior_r0, c->d_prior_x0, c->d_prior_slot,
                     c->d_prior_kind, c->d_prior_idx, c->d_prior_index, c->d_prior_H, c->d_prior_g, c->d_prior_cost, c->d_prior_work,
@@ -410,27 +412,15 @@ int glio_set_scan_ahead_strided(glio_ctx* c, const void* scan, int n, int stride
     if (!c || c->W < 2 || n < 0 || n > c->cap || (n > 0 && !scan)) { glio_set_error("bad scan size"); return GLIO_E_ARG; }
     if (!glio_point_layout_ok(stride_bytes, intensity_offset)) { glio_set_error("bad point layout (stride %d, intensity at %d)", stride_bytes, intensity_offset); return GLIO_E_ARG; }
     GLIO_HIP_CHECK(hipSetDevice(c->device));
-    { const int rp = glio_assoc_finish_pending(c); if (rp != GLIO_OK) return rp; }              // every search that reads slot 0's scan has ended
+    hipStream_t up = nullptr;
+    { const int rb = glio_ahead_begin(c, &up); if (rb != GLIO_OK) return rb; }
     CtxExtra* ex = extra_of(c);
-    if (!ex->up_stream) {
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) GLIO_HIP_CHECK(hipStreamCreateWithPriority(&ex->up_stream, hipStreamNonBlocking, greatest));
-        else GLIO_HIP_CHECK(hipStreamCreateWithFlags(&ex->up_stream, hipStreamNonBlocking));
-        GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_up, hipEventDisableTiming));
-    }
-    if (!ex->ev_ahead) GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_ahead, hipEventDisableTiming));
-    if (!ex->ev_copy) GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_copy, hipEventDisableTiming));
-    // (another object's stream may still be reading a resident scan -- never slot 0's: glio_bassoc_set_frame_from_scan copies the newest -- but the event is cheap)
-    if (c->ext_read_pending) { GLIO_HIP_CHECK(hipStreamWaitEvent(ex->up_stream, c->ev_ext_read, 0)); }
     const size_t row = (size_t)glio_scan_row(c, 0) * c->cap;
     { const int ru = glio_upload_points(ex->up_stream, &c->raw_stage, scan, n, stride_bytes, intensity_offset, c->d_scan + row); if (ru != GLIO_OK) return ru; }
     GLIO_HIP_CHECK(hipEventRecord(ex->ev_copy, ex->up_stream));
     glio_assoc_presort_row(c, ex->up_stream, row, n);
-    GLIO_HIP_CHECK(hipEventRecord(ex->ev_ahead, ex->up_stream));
-    GLIO_HIP_CHECK(hipGetLastError());
+    { const int rk = glio_ahead_commit(c, n); if (rk != GLIO_OK) return rk; }
     GLIO_HIP_CHECK(hipEventSynchronize(ex->ev_copy));       // the caller's buffer has been read
-    ex->ahead_valid = 1; ex->ahead_n = n;
-    c->h_scan_count[0] = 0;                                  // (slot 0's scan is gone)
     return GLIO_OK;
 }
 // ... and the local map of the next keyframe's call, built during this one's tail too: the cloud glio_set_scan_ahead has just sent, pushed at the pose the caller
@@ -455,6 +445,33 @@ int glio_localmap_push_scan_ahead_and_build(glio_ctx* c, const float lidar_offse
     return GLIO_OK;
 }
 }  // extern "C"
+// the two ends of a scan sent ahead (glio_set_scan_ahead*, glio_set_scan_filtered_ahead*, glio_set_scan_from_features_ahead): _begin ends the searches that
+// read slot 0's row, creates the upload stream with its events on first use and orders it behind a pending read of the resident scans by another object;
+// _commit (behind the presort on the upload stream) records the event the next glio_slide_window waits for and hands it the count
+int glio_ahead_begin(glio_ctx* c, hipStream_t* up) {
+    { const int rp = glio_assoc_finish_pending(c); if (rp != GLIO_OK) return rp; }              // every search that reads slot 0's scan has ended
+    CtxExtra* ex = extra_of(c);
+    if (!ex->up_stream) {
+        int least = 0, greatest = 0;
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) GLIO_HIP_CHECK(hipStreamCreateWithPriority(&ex->up_stream, hipStreamNonBlocking, greatest));
+        else GLIO_HIP_CHECK(hipStreamCreateWithFlags(&ex->up_stream, hipStreamNonBlocking));
+        GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_up, hipEventDisableTiming));
+    }
+    if (!ex->ev_ahead) GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_ahead, hipEventDisableTiming));
+    if (!ex->ev_copy) GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_copy, hipEventDisableTiming));
+    // (another object's stream may still be reading a resident scan -- never slot 0's: glio_bassoc_set_frame_from_scan copies the newest -- but the event is cheap)
+    if (c->ext_read_pending) { GLIO_HIP_CHECK(hipStreamWaitEvent(ex->up_stream, c->ev_ext_read, 0)); }
+    *up = ex->up_stream;
+    return GLIO_OK;
+}
+int glio_ahead_commit(glio_ctx* c, int n) {
+    CtxExtra* ex = extra_of(c);
+    GLIO_HIP_CHECK(hipEventRecord(ex->ev_ahead, ex->up_stream));
+    GLIO_HIP_CHECK(hipGetLastError());
+    ex->ahead_valid = 1; ex->ahead_n = n;
+    c->h_scan_count[0] = 0;                                  // (slot 0's scan is gone)
+    return GLIO_OK;
+}
 int glio_order_behind_ahead(glio_ctx* c) {
     CtxExtra* ex = extra_of(c);
     if (ex && ex->ahead_valid && ex->ev_ahead) GLIO_HIP_CHECK(hipStreamWaitEvent(c->stream, ex->ev_ahead, 0));

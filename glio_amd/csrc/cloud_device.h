@@ -1,8 +1,11 @@
 // cloud_device.h -- the device routines that the point-cloud stages share (localmap_kernels.hip, globalmap_kernels.hip, loop_kernels.hip,
-// feature_kernels.hip): transformCloud of one point, the bounding box of a workgroup, the workgroup scan and ballot rank, one pass of the stable radix
-// sort.  Each has ONE definition here: the stages are held to the reference, the oracle or each other bit for bit, so a rounding or an ordering is
-// changed in one place or not at all.  The integer routines are exact whatever the order of their additions; cloud_transform is the only arithmetic.
+// feature_kernels.hip, keyframe_cloud_kernels.hip): transformCloud of one point, the de-skew's ratio and slerp, the bounding box of a workgroup, the
+// workgroup scan and ballot rank, one pass of the stable radix sort.  Each has ONE definition here: the stages are held to the reference, the oracle or
+// each other bit for bit, so a rounding or an ordering is changed in one place or not at all.  The integer routines are exact whatever the order of their
+// additions; cloud_transform, cloud_deskew_ratio and cloud_slerp_identity are the only arithmetic.
 #pragma once
+#include <cfloat>
+
 #include "glio_device.h"
 
 // transformCloud of one point (reference Estimator.cpp:1517-1546): double q * v + t, float store.  Eigen's q * v is v + w * (2 u x v) + u x (2 u x v) with
@@ -13,6 +16,35 @@ __device__ __forceinline__ float4 cloud_transform(const double q[4], const doubl
     double o[3];
     d_qrot_nc(q, v, o);
     return make_float4((float)(o[0] + t[0]), (float)(o[1] + t[1]), (float)(o[2] + t[2]), p.w);
+}
+
+// ---- the de-skew of one point by its intensity (reference Preprocessing.cpp:176-200, LidarOdometry.cpp:180-201: the same body twice)
+// ratio = (intensity - (float)(int)intensity) / 0.1: the difference in FLOAT, the quotient in double, capped at 1 and NOT clamped below (a negative intensity
+// truncates toward zero and gives a negative ratio)
+__device__ __forceinline__ double cloud_deskew_ratio(const float inten) {
+#pragma clang fp contract(off)
+    const int line = (int)inten;
+    const double dt_i = (double)(inten - (float)line);
+    double t = dt_i / 0.1;
+    if (t >= 1.0) t = 1.0;
+    return t;
+}
+// Eigen's Quaterniond::Identity().slerp(t, q): the linear branch at |d| >= 1 - DBL_EPSILON, the sign flipped for d < 0; every product rounded before it is
+// added (the zero products of the identity's coefficients are written out: they are what the reference's dot() and coeffs() sums hold)
+__device__ __forceinline__ void cloud_slerp_identity(const double q[4], const double t, double qs[4]) {
+#pragma clang fp contract(off)
+    const double qw = q[0], qx = q[1], qy = q[2], qz = q[3];
+    const double d = 0.0 * qx + 0.0 * qy + 0.0 * qz + 1.0 * qw;               // dot of the identity's and q's coefficients
+    const double ad = fabs(d);
+    double s0, s1;
+    if (ad >= 1.0 - DBL_EPSILON) { s0 = 1.0 - t; s1 = t; }
+    else {
+        const double th = acos(ad), sth = sin(th);
+        s0 = sin((1.0 - t) * th) / sth;
+        s1 = sin(t * th) / sth;
+    }
+    if (d < 0.0) s1 = -s1;
+    qs[0] = s0 * 1.0 + s1 * qw; qs[1] = s0 * 0.0 + s1 * qx; qs[2] = s0 * 0.0 + s1 * qy; qs[3] = s0 * 0.0 + s1 * qz;
 }
 
 // ---- bounding box of three ints (ordered floats, f2ord, or voxel coordinates): per thread, then per wavefront, then six atomics per workgroup

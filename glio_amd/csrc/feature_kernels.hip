@@ -253,21 +253,10 @@ __global__ __launch_bounds__(1024) void k_ft_deskew(const float4* __restrict__ s
         const float rel = (ori - so.start) / (so.end - so.start);
         const float inten = (float)((double)r + 0.1 * (double)rel);                // :512
         // undistortion (:176-200): dt_i = intensity - int(intensity) in float, ratio capped at 1, Eigen's slerp from the identity, q_lb * q_si * q_lb^-1, q * v
-        const int line = (int)inten;
-        const double dt_i = (double)(inten - (float)line);
-        double t = dt_i / 0.1;
-        if (t >= 1.0) t = 1.0;
-        const double d = 0.0 * qx + 0.0 * qy + 0.0 * qz + 1.0 * qw;               // dot of the identity's and qIMU's coefficients
-        const double ad = fabs(d);
-        double s0, s1;
-        if (ad >= 1.0 - DBL_EPSILON) { s0 = 1.0 - t; s1 = t; }
-        else {
-            const double th = acos(ad), sth = sin(th);
-            s0 = sin((1.0 - t) * th) / sth;
-            s1 = sin(t * th) / sth;
-        }
-        if (d < 0.0) s1 = -s1;
-        const double qs[4] = {s0 * 1.0 + s1 * qw, s0 * 0.0 + s1 * qx, s0 * 0.0 + s1 * qy, s0 * 0.0 + s1 * qz};
+        // (cloud_deskew_ratio, cloud_slerp_identity: cloud_device.h, shared with the keyframe cloud's de-skew)
+        const double qimu[4] = {qw, qx, qy, qz};
+        double qs[4];
+        cloud_slerp_identity(qimu, cloud_deskew_ratio(inten), qs);
         const double ql[4] = {lw, lx, ly, lz};
         double qa[4], qi[4], qf[4];
         d_qmul(ql, qs, qa);
@@ -474,7 +463,15 @@ static void ft_free(FeatWork* f) {
     delete f;
 }
 void glio_features_destroy(glio_ctx* c) {
+    // (another context's keyframe cloud stage may still be reading the surf features: glio_set_scan_from_features)
+    if (c->feat_read_pending) { hipEventSynchronize(c->ev_feat_read); c->feat_read_pending = 0; }
     if (c->features) { ft_free(c->features); c->features = nullptr; }
+}
+int glio_features_surf_view(glio_ctx* c, const float4** d_surf, int* n) {
+    FeatWork* f = c->features;
+    if (!f || !f->have) { glio_set_error("glio_features_extract first"); return GLIO_E_STATE; }
+    *d_surf = f->d_o_surf; *n = f->counts.surf;
+    return GLIO_OK;
 }
 
 #define FT_ALLOC(ptr, bytes) GLIO_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&(ptr)), (bytes)))
@@ -547,6 +544,8 @@ int glio_features_extract_strided(glio_ctx* c, const void* raw, int n, int strid
     if (!glio_point_layout_ok(stride_bytes, intensity_offset)) { glio_set_error("bad point layout (stride %d, intensity at %d)", stride_bytes, intensity_offset); return GLIO_E_ARG; }
     GLIO_HIP_CHECK(hipSetDevice(c->device));
     hipStream_t s = c->stream;
+    // (a keyframe cloud stage on another stream may still be reading the last extraction's surf features: this one overwrites them behind that read)
+    if (c->feat_read_pending) { GLIO_HIP_CHECK(hipStreamWaitEvent(s, c->ev_feat_read, 0)); c->feat_read_pending = 0; }
     { const int ru = glio_upload_points(s, &c->raw_stage, raw, n, stride_bytes, intensity_offset, f->d_raw); if (ru != GLIO_OK) return ru; }
     GLIO_HIP_CHECK(hipEventRecord(f->ev0, s));
     const int nt = (n + FT_TILE - 1) / FT_TILE, ntl = nt > 0 ? nt : 1;

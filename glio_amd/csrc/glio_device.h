@@ -250,6 +250,9 @@ struct glio_ctx {
     int prior_device_made;                    // the installed prior is glio_marginalize_keep's own product: block diagonal with EXACT zeros (a caller's prior is only held to a tolerance)
     int n_cu;                                 // compute units of THIS context's device (the helper workgroups of k_chain_step need 2 (1 + W) of them)
     struct FeatWork* features;                // raw-scan feature extraction (feature_kernels.hip), created by glio_features_config
+    hipEvent_t ev_feat_read; int feat_read_pending;   // another context's stream is still READING the surf features (glio_set_scan_from_features): the next
+                                                      // glio_features_extract*, glio_features_config and glio_destroy come behind this event
+    struct KfCloud* kfcloud;                  // the keyframe cloud stage (keyframe_cloud_kernels.hip), created by glio_scan_filter_config
     // ---- speed-bias priors of the windows after a loop closure (glio_set_speed_bias_priors, Estimator.cpp:2164-2176)
     int sbp_n;                                // slots 0 .. sbp_n - 1 carry one (0: none)
     double* d_sbp_target;                     // [W][9] their targets
@@ -508,12 +511,25 @@ int glio_assoc_run_window_async(glio_ctx* c, const double* quats, const double* 
 int glio_assoc_finish_pending(glio_ctx* c);
 void glio_localmap_destroy(glio_ctx* c);
 void glio_features_destroy(glio_ctx* c);          // feature_kernels.hip
+// feature_kernels.hip: the surf features of the last glio_features_extract* where they lie (GLIO_E_STATE before the first extraction)
+int glio_features_surf_view(glio_ctx* c, const float4** d_surf, int* n);
+void glio_kfcloud_destroy(glio_ctx* c);           // keyframe_cloud_kernels.hip
 // localmap_kernels.hip: the local map's VoxelGrid (float accumulation in concatenation order) over a list of device-resident clouds, without a context.
 // poses [n_frames][7] = t, q; the filtered cloud goes to `out` (nothing is copied when *nv_out > out_cap).  Waits for `stream` once, inside.
 struct LocalMap;
 int glio_vg_create(int width, int cap, float leaf, int max_vox, hipStream_t stream, LocalMap** out);
 void glio_vg_destroy(LocalMap* m);
 int glio_vg_build(LocalMap* m, hipStream_t stream, int n_frames, const float4* const* src, const int* n_src, const double* poses, float4* out, int out_cap, int* nv_out);
+// the same VoxelGrid over ONE cloud that its producer writes into the staging slot itself (keyframe_cloud_kernels.hip: the de-skew kernel stores the moved
+// points into glio_vg_staging and adds them to the six ordered ints of glio_vg_staging_box in the same pass), at a leaf chosen per call and with PCL's overflow
+// rule (a box of more than INT32_MAX cells: *passthrough = 1, *nv_out = n, the staged cloud is the output):
+//   glio_vg_staged_begin   table, box and count reset on `stream` -- before the producer's launch
+//   glio_vg_staged_finish  the accumulation and the ordered output into m's own buffer (glio_vg_output); waits for `stream` once, for the count
+int glio_vg_staged_begin(LocalMap* m, hipStream_t stream, int n);
+int glio_vg_staged_finish(LocalMap* m, hipStream_t stream, int n, float leaf, int* nv_out, int* passthrough);
+float4* glio_vg_staging(LocalMap* m);
+int* glio_vg_staging_box(LocalMap* m);
+const float4* glio_vg_output(LocalMap* m);
 // solver_kernels.hip
 void glio_launch_tr_step(glio_ctx* c, int n_ddt);
 void glio_chain_tabs_upload(glio_ctx* c);
@@ -540,6 +556,9 @@ int glio_bassoc_external_read(glio_bassoc* b, hipStream_t reader);
 // capi.hip: a scan / map sent ahead on the upload stream (glio_set_scan_ahead, glio_localmap_push_scan_ahead_and_build) is still pending -> the context's
 // stream waits for it (the next glio_slide_window still takes the scan over)
 int glio_order_behind_ahead(glio_ctx* c);
+// capi.hip: the two ends of a scan sent ahead on the upload stream (see there)
+int glio_ahead_begin(glio_ctx* c, hipStream_t* up);
+int glio_ahead_commit(glio_ctx* c, int n);
 
 // imu_kernels.hip: the device-resident store of IMU pre-integrations (glio_imu_*)
 struct glio_imu {

@@ -63,6 +63,9 @@ struct LocalMap {
     // glio_localmap_rebuild_from_frames: the frame table [width] (pinned, its device mirror, the event of its last upload) and the event that orders the context's
     // stream behind the frame copies of the batch association
     struct LmFrame* h_frames; struct LmFrame* d_frames; hipEvent_t ev_frames; int frames_in_flight; hipEvent_t ev_dep;
+    // glio_vg_staged_*: PCL's overflow rule is applied (a box of more than INT32_MAX cells passes the cloud through: the keyframe cloud's filter, as
+    // ft_voxel_grid); last_passthrough = the last build met it
+    int pcl_overflow, last_passthrough;
     hipEvent_t ev_rb0, ev_rb1; int time_rebuild, have_rebuild_ms;      // GLIO_LM_REBUILD_TIMING=1: timing events around the rebuild's two launches (glio_localmap_last_rebuild_device_ms)
 };
 // one keyframe of a rebuild: its own-frame cloud (resident in a batch association), its size and transformCloud's pose
@@ -649,6 +652,20 @@ static int lm_voxelize(LocalMap* m, hipStream_t stream, int* nv_out) {
     if (m->h_pin[1] & 0x40000000) { m->nkeys_seen = m->table_cap; glio_set_error("local map voxel table overflow (raise max_map_points)"); return GLIO_E_ARG; }
     m->nkeys_seen = m->h_pin[1];
     m->last_nv = nv;
+    m->last_passthrough = 0;
+    if (m->pcl_overflow && nv > 0) {
+        // pcl::VoxelGrid::applyFilter: (int64)((max - min) * inverse_leaf) + 1 per axis in float, a product above INT32_MAX leaves the cloud as it is.  (A factor
+        // beyond 2^31 settles it before the cast; two factors below 2^31 multiply without overflow.)
+        long long cells = 1;
+        bool over = false;
+        for (int c3 = 0; c3 < 3 && !over; ++c3) {
+            const float ext = (h_ord2f(m->h_pin[5 + c3]) - h_ord2f(m->h_pin[2 + c3])) * inv_leaf;
+            if (!(ext < 2147483648.0f)) { over = true; break; }
+            cells *= (long long)ext + 1;
+            if (cells > 2147483647ll) over = true;
+        }
+        if (over) { m->last_passthrough = 1; *nv_out = nv; return GLIO_OK; }      // (bm_dirty stays set: the next build wipes the bits k_lm_list left)
+    }
     if (nv > m->max_vox) { m->nkeys_seen = m->table_cap; glio_set_error("local map has %d voxels, max_map_points is %d", nv, m->max_vox); return GLIO_E_ARG; }
     if (nv > 0) {
         // number of key bits from the bounding box, exactly as k_lm_list forms the linear index
@@ -837,6 +854,30 @@ int glio_vg_create(int width, int cap, float leaf, int max_vox, hipStream_t stre
     return GLIO_OK;
 }
 void glio_vg_destroy(LocalMap* m) { lm_free(m); }
+float4* glio_vg_staging(LocalMap* m) { return m->d_ring; }
+int* glio_vg_staging_box(LocalMap* m) { return m->d_slot_bbox; }
+const float4* glio_vg_output(LocalMap* m) { return m->d_out; }
+int glio_vg_staged_begin(LocalMap* m, hipStream_t stream, int n) {
+    if (n < 1 || n > m->cap) return GLIO_E_ARG;
+    hipLaunchKernelGGL(k_lm_clear, dim3((m->table_cap + 255) / 256), dim3(256), 0, stream, m->d_keys, m->d_sum, m->d_cnt, m->table_cap, m->d_nkeys);
+    if (m->width > 1) LM_CHECK(hipMemsetAsync(m->d_n, 0, (size_t)m->width * 4, stream));
+    hipLaunchKernelGGL(k_lm_bbox_init, dim3(1), dim3(64), 0, stream, m->d_slot_bbox, m->d_n, n);
+    LM_CHECK(hipGetLastError());
+    m->head = 0; m->count = 1; m->nkeys_seen = 0; m->pcl_overflow = 1;
+    for (int f = 0; f < m->width; ++f) m->h_n[f] = f == 0 ? n : 0;
+    return GLIO_OK;
+}
+int glio_vg_staged_finish(LocalMap* m, hipStream_t stream, int n, float leaf, int* nv_out, int* passthrough) {
+    if (n < 1 || n > m->cap || !(leaf > 0.f)) return GLIO_E_ARG;
+    m->leaf = leaf;
+    hipLaunchKernelGGL(k_lm_accumulate, dim3((n + 255) / 256), dim3(256), 0, stream, m->d_ring, n, 1.0f / leaf, +1, m->d_keys, m->d_sum, m->d_cnt, m->table_cap, m->d_nkeys);
+    LM_CHECK(hipGetLastError());
+    int nv = 0;
+    { const int rv = lm_voxelize(m, stream, &nv); if (rv != GLIO_OK) return rv; }
+    *passthrough = m->last_passthrough;
+    *nv_out = m->last_passthrough ? n : nv;
+    return GLIO_OK;
+}
 int glio_vg_build(LocalMap* m, hipStream_t stream, int n_frames, const float4* const* src, const int* n_src, const double* poses, float4* out, int out_cap, int* nv_out) {
     if (n_frames < 1 || n_frames > m->width) return GLIO_E_ARG;
     const float inv_leaf = 1.0f / m->leaf;

@@ -224,3 +224,28 @@ class WindowState:
 
 def preint_array(n):
     return (GlioPreint * max(n, 1))()
+
+
+# ---- the keyframe cloud (glio_scan_filter_config, glio_set_scan_filtered*, glio_set_scan_from_features*, glio_get_scan): the argument types as
+# include/glio_hip.h declares them; capi.load() applies them, so a call with a float where the header has an int fails in Python, not in the library
+c_int_p = C.POINTER(C.c_int)
+KEYFRAME_CLOUD_PROTOTYPES = {
+    "glio_scan_filter_config": [C.c_void_p, C.c_int],
+    "glio_set_scan_filtered_strided": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, c_double_p, c_double_p, c_int_p],
+    "glio_set_scan_filtered": [C.c_void_p, C.c_int, c_float_p, C.c_int, C.c_float, c_double_p, c_double_p, c_int_p],
+    "glio_set_scan_filtered_ahead_strided": [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, c_double_p, c_double_p, c_int_p],
+    "glio_set_scan_filtered_ahead": [C.c_void_p, c_float_p, C.c_int, C.c_float, c_double_p, c_double_p, c_int_p],
+    "glio_set_scan_from_features": [C.c_void_p, C.c_int, C.c_void_p, C.c_float, c_double_p, c_double_p, c_int_p],
+    "glio_set_scan_from_features_ahead": [C.c_void_p, C.c_void_p, C.c_float, c_double_p, c_double_p, c_int_p],
+    "glio_get_scan": [C.c_void_p, C.c_int, c_float_p, C.c_int, c_int_p],
+    "glio_scan_filter_last_device_ms": [C.c_void_p, c_float_p],
+}
+
+
+def apply_prototypes(lib):
+    for name, args in KEYFRAME_CLOUD_PROTOTYPES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
+            raise AttributeError(f"{name} is missing from the library: it is stale, rebuild it with `python -m glio_amd.build`")
+        fn.argtypes = args
+        fn.restype = C.c_int

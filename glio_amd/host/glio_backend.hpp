@@ -223,6 +223,7 @@ inline LocalMapPlan localMapPlan(int recent_size, int n_keyframes, int width, in
     return p;
 }
 
+class ScanToMapOdometry;          // (3) below: the front end whose surf features setScanFromFrontEnd reads where they lie
 class SlidingWindowBackend {
 public:
     explicit SlidingWindowBackend(const glio_opts& opts, int device = 0) : opts_(opts), W_(opts.window) {
@@ -399,6 +400,46 @@ public:
     // the NEXT keyframe's cloud, sent during this keyframe's call (after the solve): the next call's slideWindow() finds it in slot W - 1 and makes no setScan()
     void setScanAhead(const float* scan_xyzi, int n) { check(glio_set_scan_ahead(ctx_, scan_xyzi, n), "glio_set_scan_ahead"); }
     void setScanAhead(const void* points, int n, PointLayout l) { check(glio_set_scan_ahead_strided(ctx_, points, n, l.stride_bytes, l.intensity_offset), "glio_set_scan_ahead_strided"); }
+
+    // ---- the keyframe cloud: LidarOdometry::publishCloudLast's undistortion(surf_features, trans, quat) (LidarOdometry.cpp:180-201, :619-627, only with
+    // if_to_deskew) + Estimator::downSampleCloud's ds_filter_surf (Estimator.cpp:3628-3630, surfDSRange) + setScan, on the device.  The cloud is the
+    // UNFILTERED surf cloud; deskew_trans = nullptr: if_to_deskew false; deskew_quat = nullptr: the identity (the reference's only call).  Returns the
+    // slot's point count (surf_frames[slot]->size()).
+    void configureScanFilter(int max_input_points) { check(glio_scan_filter_config(ctx_, max_input_points), "glio_scan_filter_config"); }
+    int setScanFiltered(int slot, const float* xyzi, int n, float leaf, const double* deskew_trans = nullptr, const double* deskew_quat = nullptr) {
+        int out = 0;
+        check(glio_set_scan_filtered(ctx_, slot, xyzi, n, leaf, deskew_trans, deskew_quat, &out), "glio_set_scan_filtered");
+        return out;
+    }
+    int setScanFiltered(int slot, const void* points, int n, PointLayout l, float leaf, const double* deskew_trans = nullptr, const double* deskew_quat = nullptr) {
+        int out = 0;
+        check(glio_set_scan_filtered_strided(ctx_, slot, points, n, l.stride_bytes, l.intensity_offset, leaf, deskew_trans, deskew_quat, &out), "glio_set_scan_filtered_strided");
+        return out;
+    }
+    // ... into the row that is slot W - 1 after the next slideWindow() (setScanAhead), on the upload stream
+    int setScanFilteredAhead(const float* xyzi, int n, float leaf, const double* deskew_trans = nullptr, const double* deskew_quat = nullptr) {
+        int out = 0;
+        check(glio_set_scan_filtered_ahead(ctx_, xyzi, n, leaf, deskew_trans, deskew_quat, &out), "glio_set_scan_filtered_ahead");
+        return out;
+    }
+    int setScanFilteredAhead(const void* points, int n, PointLayout l, float leaf, const double* deskew_trans = nullptr, const double* deskew_quat = nullptr) {
+        int out = 0;
+        check(glio_set_scan_filtered_ahead_strided(ctx_, points, n, l.stride_bytes, l.intensity_offset, leaf, deskew_trans, deskew_quat, &out), "glio_set_scan_filtered_ahead_strided");
+        return out;
+    }
+    // the same from the surf features of the front end's last runRaw(), read where they lie on the device.  deskew = true: the reference's call with
+    // if_to_deskew -- the translation of the front end's rel_pose, the identity rotation (:620-624).  (Defined behind ScanToMapOdometry.)
+    inline int setScanFromFrontEnd(int slot, const ScanToMapOdometry& front_end, float leaf, bool deskew);
+    inline int setScanFromFrontEndAhead(const ScanToMapOdometry& front_end, float leaf, bool deskew);
+    // what a slot holds, in the caller's order
+    std::vector<float> getScan(int slot) {
+        int n = 0;
+        check(glio_get_scan(ctx_, slot, nullptr, 0, &n), "glio_get_scan");
+        std::vector<float> out((size_t)n * 4 + 4);
+        check(glio_get_scan(ctx_, slot, out.data(), n, &n), "glio_get_scan");
+        out.resize((size_t)n * 4);
+        return out;
+    }
     // ... and the next call's local map behind it (the cloud just sent ahead pushed at the new keyframe's pose, the ring map and its search structure rebuilt): the
     // next call makes no pushScanAndBuildLocalMap()
     int pushScanAheadAndBuildLocalMap(const float lidar_offset[3], const double q[4], const double t[3]) {
@@ -697,6 +738,39 @@ private:
 };
 static_assert(sizeof(ImuStore::Start) == 12 * sizeof(double), "glio_imu_integrate takes start values as [n][12] doubles");
 
+// ---- the keyframe rule of the front end (LidarOdometry.cpp:566-578, with the initial values of :71-75): which scans are handed over to the window.
+//   dis = |t - t_last_kf|, ang = 2 acos((q_last_kf^-1 q).w)                  (a NaN ang -- acos beyond 1 by rounding -- compares false)
+//   kf  = ((dis > 0.2 || ang > 0.1) && size - kf_num > 1) || size - kf_num > 2 || size <= 1
+// size = pose_cloud_frame->points.size() when the scan is judged: the scans saved BEFORE it (savePoses follows, :682).  A keyframe takes the pose over
+// and sets kf_num to the size after savePoses (:684-685).  The initialisation scan (:671-675) is not judged and publishes nothing.
+// glio_amd/odometry.py::KeyframeGate is the Python twin (tests/test_keyframe_cloud_abi.py holds the two to each other).
+class KeyframeGate {
+public:
+    bool update(const double q[4], const double t[3], int size) {
+        const double d[3] = {t[0] - t_last_[0], t[1] - t_last_[1], t[2] - t_last_[2]};
+        const double dis = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        const double n2 = q_last_[0] * q_last_[0] + q_last_[1] * q_last_[1] + q_last_[2] * q_last_[2] + q_last_[3] * q_last_[3];      // inverse(): conjugate / squaredNorm
+        const double iw = q_last_[0] / n2, ix = -q_last_[1] / n2, iy = -q_last_[2] / n2, iz = -q_last_[3] / n2;
+        const double w = iw * q[0] - ix * q[1] - iy * q[2] - iz * q[3];
+        const double ang = 2 * std::acos(w);
+        kf_ = ((dis > 0.2 || ang > 0.1) && size - kf_num_ > 1) || size - kf_num_ > 2 || size <= 1;
+        if (kf_) {
+            for (int k = 0; k < 3; ++k) t_last_[k] = t[k];
+            for (int k = 0; k < 4; ++k) q_last_[k] = q[k];
+            kf_num_ = size + 1;
+        }
+        return kf_;
+    }
+    // after run() / runRaw() of the front end: its abs_pose, judged with the scans saved before this one (false for the initialisation scan)
+    inline bool update(const ScanToMapOdometry& front_end);
+    bool keyframe() const { return kf_; }
+    int keyframeNumber() const { return kf_num_; }
+private:
+    bool kf_ = true;
+    int kf_num_ = 0;
+    double t_last_[3] = {0, 0, 0}, q_last_[4] = {1, 0, 0, 0};
+};
+
 // ---- (3) the front end -------------------------------------------------------------------------------
 // LidarOdometry (GLIO/src/LidarOdometry.cpp): scan-to-map odometry on the same C-ABI with a one-keyframe window.  Per scan, run() (:661-699):
 //   poseInitialization (:405-432)  abs_pose <- abs_pose o rel_pose
@@ -883,5 +957,21 @@ private:
     std::array<double, 7> last_pose_{{1, 0, 0, 0, 0, 0, 0}};
     std::vector<float> last_cloud_;
 };
+
+inline bool KeyframeGate::update(const ScanToMapOdometry& fe) {
+    const int size = fe.frames() - 1;
+    if (size < 1) return false;
+    return update(&fe.abs_pose[0], &fe.abs_pose[4], size);
+}
+inline int SlidingWindowBackend::setScanFromFrontEnd(int slot, const ScanToMapOdometry& fe, float leaf, bool deskew) {
+    int out = 0;
+    check(glio_set_scan_from_features(ctx_, slot, fe.ctx(), leaf, deskew ? &fe.rel_pose[4] : nullptr, nullptr, &out), "glio_set_scan_from_features");
+    return out;
+}
+inline int SlidingWindowBackend::setScanFromFrontEndAhead(const ScanToMapOdometry& fe, float leaf, bool deskew) {
+    int out = 0;
+    check(glio_set_scan_from_features_ahead(ctx_, fe.ctx(), leaf, deskew ? &fe.rel_pose[4] : nullptr, nullptr, &out), "glio_set_scan_from_features_ahead");
+    return out;
+}
 
 }  // namespace glio

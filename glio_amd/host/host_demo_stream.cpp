@@ -95,6 +95,10 @@ int main(int argc, char** argv) {
         // rebuild branch on every call (Estimator.cpp:3545-3579).  The last local_map_width - 1 keyframes of the stream so far; a stream shorter than
         // that repeats its keyframes (same point count, the timing's concern).  Not with defer=1 (the newest keyframe's cloud must be resident).
         bool map_rebuild = false;
+        // filter=LEAF (opt-in): the stream's clouds are taken as UNFILTERED surf clouds and Estimator::downSampleCloud's ds_filter_surf (Estimator.cpp:3628-3630,
+        // surfDSRange: 0.9 in config_urban_hk.yaml) runs on the device on their way into the window (setScanFiltered / setScanFilteredAhead) -- what a drop-in
+        // Estimator does per keyframe instead of its pcl::VoxelGrid + setScan.  Default: the clouds go in as they are.
+        float filter_leaf = 0.f;
         std::vector<uint64_t> table;
         size_t table_k = 0;
         for (int a = 5; a < argc; ++a) {
@@ -106,6 +110,7 @@ int main(int argc, char** argv) {
             else if (!strncmp(argv[a], "ahead=", 6)) ahead = atoi(argv[a] + 6) != 0;
             else if (!strncmp(argv[a], "map_ahead=", 10)) map_ahead = atoi(argv[a] + 10) != 0;
             else if (!strncmp(argv[a], "map_rebuild=", 12)) map_rebuild = atoi(argv[a] + 12) != 0;
+            else if (!strncmp(argv[a], "filter=", 7)) filter_leaf = (float)atof(argv[a] + 7);
             else if (!strncmp(argv[a], "sleep_ms=", 9)) sleep_ms = atoi(argv[a] + 9);
             else if (!strncmp(argv[a], "sleep_at=", 9)) sleep_at = atoi(argv[a] + 9);
             else if (!strncmp(argv[a], "draws=", 6)) {
@@ -116,6 +121,7 @@ int main(int argc, char** argv) {
             } else { fprintf(stderr, "unknown argument %s\n", argv[a]); return 2; }
         }
         if (timed_last < 1 || timed_last > NK) timed_last = NK;
+        if (filter_leaf > 0.f) be.configureScanFilter(pts);
         if (map_rebuild && (defer || map_ahead)) { fprintf(stderr, "map_rebuild=1 goes with neither defer=1 nor map_ahead=1\n"); return 2; }
         std::mt19937_64 rng(20260925);
         auto rand_u64 = [&]() -> uint64_t { return table.empty() ? (uint64_t)rng() : table[table_k++ % table.size()]; };
@@ -145,7 +151,7 @@ int main(int argc, char** argv) {
             if (sleep_ms > 0 && sleep_at == 1) std::this_thread::sleep_for(std::chrono::milliseconds(sleep_ms));
             const double t0 = now_s();
             be.slideWindow();
-            if (!have_ahead) be.setScan(W - 1, scans[nw].data(), pts);
+            if (!have_ahead) { if (filter_leaf > 0.f) be.setScanFiltered(W - 1, scans[nw].data(), pts, filter_leaf); else be.setScan(W - 1, scans[nw].data(), pts); }
             have_ahead = false;
             // the keyframe's cloud goes to the batch association's store as soon as it is on the device (body frame: nothing of it depends on the solve); with the
             // deferred variant the previous keyframe's searches are still in flight on that store's stream, and the copy is made once they were collected
@@ -199,7 +205,8 @@ int main(int argc, char** argv) {
             const double t5b = now_s();
             if (ahead && j < NK) {
                 be.marginalizeAndKeepAsync(&ddt);
-                be.setScanAhead(scans[nw + 1].data(), pts);             // (the host would only wait for the marginalization here)
+                if (filter_leaf > 0.f) be.setScanFilteredAhead(scans[nw + 1].data(), pts, filter_leaf);
+                else be.setScanAhead(scans[nw + 1].data(), pts);        // (the host would only wait for the marginalization here)
                 have_ahead = true;
                 if (map_ahead) { map_pts = be.pushScanAheadAndBuildLocalMap(tlb, &gtq[4 * (nw + 1)], &gtt[3 * (nw + 1)]); have_map_ahead = true; }
                 be.marginalizeFinish();
@@ -245,7 +252,9 @@ int main(int argc, char** argv) {
         long total_iters = 0; for (int v : iters) total_iters += v;
         // (of the solver steps of the booked keyframes, how many took the helper workgroups' speculative build: slot 300 counts since the context was made,
         //  the warm-up keyframe included)
-        printf("], \"steps_with_the_helpers_build\": %lld, \"iterations_booked\": %ld, \"trans_checksum\": %.17g}\n", stamps[300], total_iters, checksum);
+        printf("]");
+        if (filter_leaf > 0.f) printf(", \"scan_filter_leaf\": %.9g", (double)filter_leaf);          // (only with filter=: the default line is what it was)
+        printf(", \"steps_with_the_helpers_build\": %lld, \"iterations_booked\": %ld, \"trans_checksum\": %.17g}\n", stamps[300], total_iters, checksum);
     } catch (const std::exception& e) {
         fprintf(stderr, "error: %s\n", e.what());
         return 1;

@@ -170,8 +170,9 @@ def write_stream(path, long, wins, W, n_keyframes, pts, lm_width=50, leaf=0.4, b
                 f.write(bytes(d))
 
 
-def run_demo_stream(path, device=0, env=None, search_range=6, defer=False, feature_res_num=0, draws=None, timed=None, per_slot=False, sleep_ms=0, sleep_at=0, stream_draws=True, prepare_early=True, ahead=False, map_ahead=False, map_rebuild=False):
-    """feature_res_num > 0: featureSelection behind every slot's search (Estimator.cpp:2223); draws: file of uint64 both hosts draw from (sliding.TableRng);
+def run_demo_stream(path, device=0, env=None, search_range=6, defer=False, feature_res_num=0, draws=None, timed=None, per_slot=False, sleep_ms=0, sleep_at=0, stream_draws=True, prepare_early=True, ahead=False, map_ahead=False, map_rebuild=False, filter=None):
+    """filter=LEAF: the stream's clouds are filtered on the device on their way into the window (setScanFiltered*; opt-in);
+    feature_res_num > 0: featureSelection behind every slot's search (Estimator.cpp:2223); draws: file of uint64 both hosts draw from (sliding.TableRng);
     timed: only the last `timed` keyframes enter the time averages"""
     import json
     cmd = [build_demo_stream(), path, str(device), str(search_range), str(int(defer))]
@@ -194,6 +195,8 @@ def run_demo_stream(path, device=0, env=None, search_range=6, defer=False, featu
         cmd.append("map_ahead=1")
     if map_rebuild:
         cmd.append("map_rebuild=1")
+    if filter:
+        cmd.append(f"filter={float(filter)!r}")
     r = subprocess.run(cmd, capture_output=True, text=True, env=env)
     if r.returncode != 0:
         raise RuntimeError("host_demo_stream failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
@@ -275,6 +278,37 @@ def run_demo_frontend_raw(path, device=0, env=None):
             rows.append({"rounds": int(w[9]), "kept": int(w[10]), "iterations": int(w[11]), "final_cost": float(w[12]), "map_points": int(w[13]), "surf": int(w[14])})
     info = json.loads(next(ln for ln in r.stdout.splitlines() if ln.startswith("{")))
     return np.array(poses), rows, info
+
+
+DEMO_KEYFRAME_CLOUD = os.path.join(HERE, "host_demo_keyframe_cloud")
+
+
+def build_demo_keyframe_cloud(force=False):
+    """The C++ hand-over of the keyframes' surf clouds (host_demo_keyframe_cloud.cpp: runRaw -> glio::KeyframeGate -> setScanFromFrontEnd / setScanFiltered)."""
+    src = [os.path.join(HERE, "host_demo_keyframe_cloud.cpp"), os.path.join(HERE, "glio_backend.hpp")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_KEYFRAME_CLOUD) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_KEYFRAME_CLOUD) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_KEYFRAME_CLOUD])
+    return DEMO_KEYFRAME_CLOUD
+
+
+def run_demo_keyframe_cloud(path, device=0, leaf=0.9, deskew=True, window=3, env=None):
+    """the stream file of write_frontend_raw_stream -> (per-scan dicts {kf, surf}, per-keyframe dicts {scan, slot, n_resident, hash_resident, n_host, hash_host}, info)"""
+    import json
+    r = subprocess.run([build_demo_keyframe_cloud(), path, str(device), f"leaf={leaf!r}", f"deskew={int(bool(deskew))}", f"window={int(window)}"],
+                       capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError(f"host_demo_keyframe_cloud failed: {r.stderr}")
+    scans, kfs, info = [], [], None
+    for line in r.stdout.strip().splitlines():
+        v = line.split()
+        if v[0] == "scan":
+            scans.append({"kf": int(v[2]), "surf": int(v[3])})
+        elif v[0] == "kf":
+            kfs.append({"scan": int(v[1]), "slot": int(v[2]), "n_resident": int(v[3]), "hash_resident": int(v[4]), "n_host": int(v[5]), "hash_host": int(v[6])})
+        else:
+            info = json.loads(line)
+    return scans, kfs, info
 
 
 DEMO_LOOP = os.path.join(HERE, "host_demo_loop")

@@ -8,6 +8,8 @@ DEFAULT trust-region strategy (Levenberg-Marquardt), `max_num_iter` iterations (
 unification (:532-542)].  The reference also caps the solve at 15 ms wall time (:524) -- a non-deterministic
 termination that is not restated; with max_num_iter = 12 (yaml:19) the iteration cap binds first on the GPU.
 """
+import math
+
 import numpy as np
 
 from . import ctypes_types as T
@@ -43,6 +45,42 @@ def _rotate(q, v):
     uv = uv + uv
     uuv = np.array([q[2] * uv[2] - q[3] * uv[1], q[3] * uv[0] - q[1] * uv[2], q[1] * uv[1] - q[2] * uv[0]])
     return np.array([v[k] + q[0] * uv[k] + uuv[k] for k in range(3)])
+
+
+class KeyframeGate:
+    """The front end's keyframe rule (LidarOdometry.cpp:566-578, initial values of :71-75): which scans are handed over to the window.
+    dis = |t - t_last_kf|, ang = 2 acos((q_last_kf^-1 q).w) (NaN -- acos beyond 1 by rounding -- compares false),
+    kf = ((dis > 0.2 or ang > 0.1) and size - kf_num > 1) or size - kf_num > 2 or size <= 1, size = the scans saved BEFORE the one judged
+    (pose_cloud_frame->points.size() at :568).  A keyframe takes the pose over and sets kf_num to the size after savePoses (:684-685).
+    glio::KeyframeGate (glio_backend.hpp) is the same class in C++."""
+
+    def __init__(self):
+        self.kf = True
+        self.kf_num = 0
+        self.t_last = (0.0, 0.0, 0.0)
+        self.q_last = (1.0, 0.0, 0.0, 0.0)
+
+    def update(self, q, t, size):
+        q = [float(v) for v in q]; t = [float(v) for v in t]
+        ql, tl = self.q_last, self.t_last
+        d = (t[0] - tl[0], t[1] - tl[1], t[2] - tl[2])
+        dis = math.sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2])
+        n2 = ql[0] * ql[0] + ql[1] * ql[1] + ql[2] * ql[2] + ql[3] * ql[3]           # inverse(): conjugate / squaredNorm
+        iw, ix, iy, iz = ql[0] / n2, -ql[1] / n2, -ql[2] / n2, -ql[3] / n2
+        w = iw * q[0] - ix * q[1] - iy * q[2] - iz * q[3]
+        ang = 2 * math.acos(w) if -1.0 <= w <= 1.0 else math.nan                     # (C's acos returns NaN there; math.acos raises)
+        self.kf = bool(((dis > 0.2 or ang > 0.1) and size - self.kf_num > 1) or size - self.kf_num > 2 or size <= 1)
+        if self.kf:
+            self.t_last, self.q_last = tuple(t), tuple(q)
+            self.kf_num = size + 1
+        return self.kf
+
+    def update_from(self, front_end):
+        """after run() / run_raw() of a ScanToMapOdometry: its abs_pose, judged with the scans saved before this one (False for the initialisation scan)"""
+        size = front_end.poses - 1
+        if size < 1:
+            return False
+        return self.update(front_end.abs_pose[:4], front_end.abs_pose[4:], size)
 
 
 class ScanToMapOdometry:

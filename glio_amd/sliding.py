@@ -91,10 +91,20 @@ def set_imu_edges(backend, preints):
         backend.set_imu(preints)
 
 
+FILTER_MAX_INPUT_POINTS = 1 << 17        # glio_scan_filter_config of a driver with filter=LEAF, unless the caller gives filter_max_points
+
+
+def _scan_filter_config(ctx, scans, filter_max_points):
+    ctx.scan_filter_config(filter_max_points or max(FILTER_MAX_INPUT_POINTS, max(len(s) for s in scans)))
+
+
 class SlidingWindowDriver:
-    def __init__(self, backend, opts, lidar_pose=capi.lidar_pose):
+    def __init__(self, backend, opts, lidar_pose=capi.lidar_pose, filter=None, filter_max_points=None):
+        """filter=LEAF (opt-in, capi.Context only): step() takes the keyframes' UNFILTERED surf clouds and downSampleCloud's ds_filter_surf
+        (Estimator.cpp:3628-3630, surfDSRange) runs on the device with the upload (glio_set_scan_filtered); the default takes filtered clouds."""
         self.be, self.opts, self.W = backend, opts, opts.window
         self.lidar_pose = lidar_pose
+        self.filter, self.filter_max_points, self._filter_ready = filter, filter_max_points, False
         self.prior = None
         self.state = None
         self.first = 0                   # index (into the keyframe stream) of slot 0
@@ -127,7 +137,14 @@ class SlidingWindowDriver:
                 counts.append(0)
                 continue
             q2, t2 = self.lidar_pose(self.opts, self.state.quat[s], self.state.trans[s])
-            counts.append(be.associate(s, scans[s], q2, t2))
+            if self.filter is None:
+                counts.append(be.associate(s, scans[s], q2, t2))
+            else:
+                if not self._filter_ready:
+                    _scan_filter_config(be, scans, self.filter_max_points)
+                    self._filter_ready = True
+                be.set_scan_filtered(s, scans[s], self.filter)
+                counts.append(be.associate_resident(s, q2, t2))
         set_imu_edges(be, preints)
         be.set_prior(self.prior)
         be.set_gnss(None, [], [])
@@ -224,9 +241,11 @@ class ResidentSlidingWindow:
     scans slide with `glio_slide_window`, only the NEW keyframe's scan is uploaded, all slots are associated in one call,
     and the marginalization result stays resident as the next prior (`glio_marginalize_keep`)."""
 
-    def __init__(self, ctx, opts, lidar_pose=capi.lidar_pose):
+    def __init__(self, ctx, opts, lidar_pose=capi.lidar_pose, filter=None, filter_max_points=None):
+        """filter=LEAF (opt-in): as SlidingWindowDriver -- the new keyframe's unfiltered surf cloud is filtered on the device on its way into slot W - 1"""
         self.ctx, self.opts, self.W = ctx, opts, opts.window
         self.lidar_pose = lidar_pose
+        self.filter, self.filter_max_points = filter, filter_max_points
         self.state = None
         self.first = 0
         self._have_scans = False
@@ -246,13 +265,19 @@ class ResidentSlidingWindow:
     def step(self, map_pts, scans, preints):
         ctx, W = self.ctx, self.W
         ctx.set_map(map_pts)
+        if self.filter is None:
+            put = ctx.set_scan
+        else:
+            if not self._have_scans:
+                _scan_filter_config(ctx, scans, self.filter_max_points)
+            put = lambda slot, cloud: ctx.set_scan_filtered(slot, cloud, self.filter)
         if not self._have_scans:
             for s in range(W):
-                ctx.set_scan(s, scans[s])
+                put(s, scans[s])
             self._have_scans = True
         else:
             ctx.slide_window()
-            ctx.set_scan(W - 1, scans[W - 1])
+            put(W - 1, scans[W - 1])
         poses = [self.lidar_pose(self.opts, self.state.quat[s], self.state.trans[s]) for s in range(W)]
         if len(map_pts) <= MIN_MAP_POINTS:              # Estimator.cpp:2221
             for s in range(W):

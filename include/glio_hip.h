@@ -449,6 +449,46 @@ int glio_features_to_scan(glio_ctx* ctx, int slot, float leaf, int* n);
 /* device time of the last extraction's kernels (HIP events around them, after the raw upload), ms */
 int glio_features_last_device_ms(glio_ctx* ctx, float* ms);
 
+/* ---- The keyframe cloud: the hand-over of a keyframe's UNFILTERED surf cloud from the front end to the sliding window, on the device.
+ * Replaces LidarOdometry::publishCloudLast's undistortion(surf_features, trans, quat) (GLIO/src/LidarOdometry.cpp:180-201, :619-627; only with
+ * if_to_deskew) and Estimator::downSampleCloud's ds_filter_surf (Estimator.cpp:3628-3630: pcl::VoxelGrid at surfDSRange, 0.9 m in the released yaml)
+ * together with the glio_set_scan of the filtered cloud: de-skew per point (line = (int)intensity, ratio = (intensity - line) / 0.1 capped at 1 and
+ * not clamped below, q_si = Identity.slerp(ratio, quat), t_si = ratio * trans, pt = q_si * pt + t_si stored as float, intensity unchanged), then
+ * pcl::VoxelGrid at `leaf` (all four fields averaged, float sums in input order, PCL's output order; a box of more than INT32_MAX cells passes the
+ * cloud through; leaf <= 0 copies it), then the slot's row and its presort as glio_set_scan / glio_set_scan_ahead leave them.
+ *   deskew_trans  [3], NULL = if_to_deskew false (no de-skew at all)
+ *   deskew_quat   [4] w first, NULL = the identity (the reference's only call)
+ *   *n_out        the points the slot holds afterwards
+ * One host wait per call, for the output count, on the stream that carries the work (the context's for the slot forms, the upload stream for the
+ * _ahead forms, which do not wait for the context's stream); when it returns a host source has been read.
+ * Errors leave the slot and its count untouched: GLIO_E_ARG for a bad slot or point layout, n > max_input_points, contexts on different devices, a
+ * non-finite motion, or more outputs than max_points_per_scan (*n_out still tells the count); GLIO_E_STATE before glio_scan_filter_config, or for a
+ * front end without an extraction.  n == 0 gives an empty slot and GLIO_OK.
+ * Not built: the de-skew of edge_features / full_cloud (:625-626), fullDS (Estimator.cpp:3623-3626, its only use is commented out), pub_full_cloud_map. */
+/* allocates the stage's buffers: staging for max_input_points (1 .. GLIO_FEAT_MAX_RAW_POINTS) input points and the voxel table (a context that
+ * never calls it allocates nothing for it) */
+int glio_scan_filter_config(glio_ctx* ctx, int max_input_points);
+/* (a) host source: records of stride_bytes as glio_set_scan_strided takes them, or a packed [n][4] array */
+int glio_set_scan_filtered_strided(glio_ctx* ctx, int slot, const void* points, int n, int stride_bytes, int intensity_offset, float leaf,
+                                   const double* deskew_trans, const double* deskew_quat, int* n_out);
+int glio_set_scan_filtered(glio_ctx* ctx, int slot, const float* xyzi, int n, float leaf, const double* deskew_trans, const double* deskew_quat, int* n_out);
+/* ... into the row that is slot W - 1 after the next glio_slide_window (see glio_set_scan_ahead), on the upload stream */
+int glio_set_scan_filtered_ahead_strided(glio_ctx* ctx, const void* points, int n, int stride_bytes, int intensity_offset, float leaf,
+                                         const double* deskew_trans, const double* deskew_quat, int* n_out);
+int glio_set_scan_filtered_ahead(glio_ctx* ctx, const float* xyzi, int n, float leaf, const double* deskew_trans, const double* deskew_quat, int* n_out);
+/* (b) resident source: the surf features of `frontend`'s last glio_features_extract*, read where they lie (GLIO_FEAT_SURF of the front end stays what
+ * it was: the de-skew is out of place).  The work runs on ctx's stream (its upload stream for _ahead) behind an event recorded on frontend's stream;
+ * frontend's next glio_features_extract*, its glio_features_config and its glio_destroy are ordered behind the read on the device -- no host wait
+ * is added on frontend.  frontend == ctx is allowed. */
+int glio_set_scan_from_features(glio_ctx* ctx, int slot, glio_ctx* frontend, float leaf, const double* deskew_trans, const double* deskew_quat, int* n_out);
+int glio_set_scan_from_features_ahead(glio_ctx* ctx, glio_ctx* frontend, float leaf, const double* deskew_trans, const double* deskew_quat, int* n_out);
+/* (c) what window slot `slot` holds, in the caller's order: [n][4] x y z intensity; *n = its size (out may be null to ask for it); capacity too
+ * small: GLIO_E_ARG.  Waits for the context's stream. */
+int glio_get_scan(glio_ctx* ctx, int slot, float* out_xyzi, int capacity, int* n);
+/* device time of the last non-empty keyframe-cloud call, ms: [0] de-skew + bounding box, [1] the VoxelGrid and the copy into the row, [2] the presort --
+ * only when GLIO_KFCLOUD_TIMING=1 was set at glio_scan_filter_config (the events are not recorded otherwise); GLIO_E_STATE without */
+int glio_scan_filter_last_device_ms(glio_ctx* ctx, float ms[3]);
+
 /* ---- IMU pre-integration from raw samples: class Preintegration (GLIO/include/factors/Preintegration.h:29-194) on the device.
  * A glio_imu is the reference's pre_integrations vector (Estimator.cpp:1582-1600) kept on the device: edge e is built from its start values and
  * its run of samples (one wavefront per edge, any number of edges per call), digested there into the form the ImuFactor kernels read
