@@ -24,6 +24,15 @@
 // Interior nodes first, separators last, each in index order: one exact Cholesky in one fixed order.  Every kernel returns at once when the device has
 // decided that the solve is over, so glio_pgraph_solve enqueues its iterations ahead (the first 12, then -- for a solve that needs them -- all the rest) and
 // waits once for each of the two batches.
+//
+// One trial of the damped solve (glio_pgraph_solve_damped, include/glio_pgraph_lm.h), enqueued ahead the same way:
+//   k_pg_lin_nodes / k_pg_lin_loops at x -- skipped while the tables still hold that linearisation (the start of a solve, and after an accepted trial)
+//   k_pg_damping      d_i / rho from the node's complete diagonal, and its complete gradient: the one definition the next three use
+//   the linear solve above with d / rho on the diagonal blocks of k_pg_segments and k_pg_sep_assemble; k_pg_backsub
+//   k_pg_update       into the candidate table, with the node's share of the model decrease
+//   k_pg_lin_nodes / k_pg_lin_loops at the candidate
+//   k_pg_lm_decide    one workgroup: the candidate's error and the model decrease in k_pg_error's fixed order, the gain, the radius, the history, the termination
+//   k_pg_lm_commit    the accepted candidate becomes x
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -46,7 +55,14 @@ struct PgCtl {
     double err_cur, err0;
     int done, reason, iterations, pivot_fail;
     double cov[36];
+    // the damped solve (k_pg_lm_decide): the radius the NEXT trial uses, the factor its rejection divides by, the counters; lin_fresh: D, C, g, lp_out are the
+    // linearisation at x (the start of a solve, and after an accepted trial, whose candidate they were evaluated at); commit_trial: the trial whose candidate
+    // k_pg_lm_commit copies into x
+    double radius, decrease_factor;
+    int accepted, rejected, invalid, lin_fresh, commit_trial, pad_;
 };
+// glio_pgraph_lm_opts as the decision kernel takes it
+struct PgLm { double max_radius, min_radius, min_relative_decrease, min_diagonal, max_diagonal; int max_trials; };
 
 // ------------------------------------------------------------------------------------------------------------------------------------ small algebra
 __host__ __device__ static inline void pg_qmul(const double* a, const double* b, double* o) {
@@ -203,6 +219,7 @@ struct PgPlan {
     double* wide;               // [6 nW + nrhs][n]
     double* ldiag;              // [n]
     double* delta;              // [N][6]
+    const double* dr;           // [N][6] the damping d_i / rho of a damped trial (k_pg_damping), null for an undamped solve
 };
 
 __device__ static inline double* pg_A(const PgPlan& p, int r, int c) {
@@ -213,8 +230,9 @@ __device__ static inline double* pg_A(const PgPlan& p, int r, int c) {
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------ linearise
-__global__ void __launch_bounds__(64) k_pg_lin_nodes(PgGraph G, PgLin out, const PgCtl* ctl) {
-    if (ctl->done || ctl->pivot_fail) return;
+// skip_fresh (both linearisation kernels): the launch at the start of a damped trial, which has nothing to do when the tables already hold the linearisation at x
+__global__ void __launch_bounds__(64) k_pg_lin_nodes(PgGraph G, PgLin out, const PgCtl* ctl, int skip_fresh) {
+    if (ctl->done || ctl->pivot_fail || (skip_fresh && ctl->lin_fresh)) return;
     const int i = blockIdx.x * 64 + threadIdx.x;
     if (i >= G.N) return;
     double D[36], g[6], r[6], Ji[36], Jj[36];
@@ -276,8 +294,8 @@ __global__ void __launch_bounds__(64) k_pg_lin_nodes(PgGraph G, PgLin out, const
     out.nerr[i] = err;
 }
 
-__global__ void __launch_bounds__(64) k_pg_lin_loops(PgGraph G, PgLin out, const PgCtl* ctl) {
-    if (ctl->done || ctl->pivot_fail) return;
+__global__ void __launch_bounds__(64) k_pg_lin_loops(PgGraph G, PgLin out, const PgCtl* ctl, int skip_fresh) {
+    if (ctl->done || ctl->pivot_fail || (skip_fresh && ctl->lin_fresh)) return;
     const int l = blockIdx.x * 64 + threadIdx.x;
     if (l >= G.L) return;
     double r[6], Ji[36], Jj[36];
@@ -301,6 +319,26 @@ __global__ void __launch_bounds__(64) k_pg_lin_loops(PgGraph G, PgLin out, const
     o[120] = 0.5 * s;
 }
 
+// the sum of v[0 .. n) by one workgroup of 1024 threads in a fixed order: strided partial sums, an LDS tree.  Every thread calls it; every thread gets the sum.
+__device__ static inline double pg_block_sum(int n, const double* v, double* sh) {
+    const int t = threadIdx.x;
+    double s = 0;
+    for (int i = t; i < n; i += 1024) s += v[i];
+    __syncthreads();                            // a second call: nobody still reads sh[0]
+    sh[t] = s;
+    __syncthreads();
+    for (int h = 512; h > 0; h >>= 1) {
+        if (t < h) sh[t] += sh[t + h];
+        __syncthreads();
+    }
+    return sh[0];
+}
+// the convergence test on a decrease of the error from cur to e (gtsam::checkConvergence, unpinned)
+__device__ static inline bool pg_error_converged(double cur, double e, double rel_tol, double abs_tol) {
+    const double dec = cur - e;
+    return (e <= 0.0) || (rel_tol != 0.0 && dec / cur <= rel_tol) || (dec <= abs_tol);
+}
+
 // phase -1: the sum only; 0: the start of a solve; 1: the end of an iteration (gtsam::checkConvergence, unpinned)
 __global__ void __launch_bounds__(1024) k_pg_error(int N, int L, const double* nerr, const double* lp_out, PgCtl* ctl, int phase, int max_iter, double rel_tol, double abs_tol) {
     if (ctl->done) return;
@@ -310,16 +348,8 @@ __global__ void __launch_bounds__(1024) k_pg_error(int N, int L, const double* n
         if (t == 0) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_NONPOSITIVE_PIVOT; }
         return;
     }
-    double s = 0;
-    for (int i = t; i < N; i += 1024) s += nerr[i];
-    sh[t] = s;
-    __syncthreads();
-    for (int h = 512; h > 0; h >>= 1) {
-        if (t < h) sh[t] += sh[t + h];
-        __syncthreads();
-    }
+    double e = pg_block_sum(N, nerr, sh);
     if (t != 0) return;
-    double e = sh[0];
     for (int l = 0; l < L; ++l) e += lp_out[(size_t)PG_LOOP_OUT * l + 120];
     ctl->err = e;
     if (phase < 0) return;
@@ -332,9 +362,7 @@ __global__ void __launch_bounds__(1024) k_pg_error(int N, int L, const double* n
     const int it = ctl->iterations + 1;
     ctl->iterations = it;
     ctl->err_cur = e;
-    const double dec = cur - e;
-    const bool conv = (e <= 0.0) || (rel_tol != 0.0 && dec / cur <= rel_tol) || (dec <= abs_tol);
-    if (conv) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_CONVERGED; }
+    if (pg_error_converged(cur, e, rel_tol, abs_tol)) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_CONVERGED; }
     else if (it >= max_iter) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_ITERATION_LIMIT; }
 }
 
@@ -391,7 +419,12 @@ __global__ void __launch_bounds__(64) k_pg_segments(PgPlan P, PgLin lin, PgCtl* 
     }
     __shared__ double sD[36], sE[36], sg[6], sC[36], sY[PG_YS];
     const int r6 = lane < 36 ? lane / 6 : (lane < 42 ? lane - 36 : 0), c6 = lane < 36 ? lane % 6 : 0;
-    if (lane < 36) { sD[lane] = lin.D[(size_t)36 * a + lane]; sE[lane] = lin.C[(size_t)36 * sL + 6 * c6 + r6]; }
+    const bool damp = P.dr != nullptr && lane < 36 && r6 == c6;        // a damped trial: d / rho onto the diagonal of every node's block as it enters
+    if (lane < 36) {
+        double v = lin.D[(size_t)36 * a + lane];
+        if (damp) v += P.dr[(size_t)6 * a + r6];
+        sD[lane] = v; sE[lane] = lin.C[(size_t)36 * sL + 6 * c6 + r6];
+    }
     else if (lane < 42) sg[lane - 36] = lin.g[(size_t)6 * a + lane - 36];
     double acc = 0;                             // lanes < 36: S_LL entry; lanes 36 .. 41: g_L entry
     for (int i = a; i <= b; ++i) {
@@ -426,7 +459,9 @@ __global__ void __launch_bounds__(64) k_pg_segments(PgPlan P, PgLin lin, PgCtl* 
                 double s1 = 0, s2 = 0, s3 = 0;
 #pragma unroll
                 for (int q = 0; q < 6; ++q) { s1 += sC[6 * q + r6] * sY[6 * q + c6]; s2 += sC[6 * q + r6] * sY[36 + 6 * q + c6]; s3 += sE[6 * q + r6] * sY[36 + 6 * q + c6]; }
-                nD = lin.D[(size_t)36 * (i + 1) + lane] - s1; nE = -s2; acc -= s3;
+                double dn = lin.D[(size_t)36 * (i + 1) + lane];
+                if (damp) dn += P.dr[(size_t)6 * (i + 1) + r6];
+                nD = dn - s1; nE = -s2; acc -= s3;
             } else if (lane < 42) {
                 double s1 = 0, s3 = 0;
 #pragma unroll
@@ -499,6 +534,7 @@ __global__ void __launch_bounds__(64) k_pg_sep_assemble(PgPlan P, PgLin lin, con
             const int l = P.sl_idx[q] >> 1, end = P.sl_idx[q] & 1;
             v += lin.lp_out[(size_t)PG_LOOP_OUT * l + (end ? 72 : 0) + e];
         }
+        if (P.dr && c == r) v += P.dr[(size_t)6 * s + r];
         if (c <= r) *pg_A(P, 6 * k + r, 6 * k + c) = v;
         if (segl) *pg_A(P, 6 * k + r, 6 * (k - 1) + c) = segl[36 + 6 * c + r];       // H[k][k-1] = S_LR^T
         for (int q = P.sl_off[k]; q < P.sl_off[k + 1]; ++q) {
@@ -600,11 +636,15 @@ __global__ void __launch_bounds__(PG_SEP_THREADS) k_pg_sep_factor(PgPlan P, PgCt
     }
 }
 
-__global__ void __launch_bounds__(256) k_pg_update(int N, double* x, const double* delta, const PgCtl* ctl) {
+// xo = x [+] delta per node (xo may be x).  A damped trial (dr not null) retracts into the candidate table and leaves the node's share of the model decrease,
+// sum_a delta_a (dr_a delta_a - g_a) with dr = d / rho the very numbers the factorisation added and g the node's COMPLETE gradient (both from k_pg_damping), in
+// nm[i]: no H delta product.
+__global__ void __launch_bounds__(256) k_pg_update(int N, const double* x, double* xo, const double* delta, const PgCtl* ctl, const double* dr, const double* g, double* nm) {
     if (ctl->done || ctl->pivot_fail) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= N) return;
-    double* p = x + (size_t)7 * i;
+    const double* p = x + (size_t)7 * i;
+    double* o = xo + (size_t)7 * i;
     const double* d = delta + (size_t)6 * i;
     double R[9], dq[4], q[4], dt[3];
     pg_qmat(p + 3, R);
@@ -613,8 +653,97 @@ __global__ void __launch_bounds__(256) k_pg_update(int N, double* x, const doubl
     pg_qmul(p + 3, dq, q);
     double nrm = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
     if (q[0] < 0) nrm = -nrm;
-    for (int k = 0; k < 3; ++k) p[k] += dt[k];
-    for (int k = 0; k < 4; ++k) p[3 + k] = q[k] / nrm;
+    for (int k = 0; k < 3; ++k) o[k] = p[k] + dt[k];
+    for (int k = 0; k < 4; ++k) o[3 + k] = q[k] / nrm;
+    if (dr) {
+        double s = 0;
+        for (int k = 0; k < 6; ++k) s += d[k] * (dr[(size_t)6 * i + k] * d[k] - g[(size_t)6 * i + k]);
+        nm[i] = s;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------ the damped trial
+// d_i / rho for every scalar unknown, d_i = clamp(H_ii, min_diagonal, max_diagonal) from the node's COMPLETE diagonal: lin.D (chain factors, prior, GPS) and, at a
+// loop endpoint, the loops' diagonal blocks in insertion order -- they reach the matrix only in the separator assembly, and every loop endpoint is a separator.
+// The ONE definition of the damping: k_pg_segments and k_pg_sep_assemble add these numbers, k_pg_update forms the model decrease with them.
+// The node's complete gradient goes the same way into gf (lin.g holds the chain and unary share alone): what the model decrease is formed with.
+__global__ void __launch_bounds__(256) k_pg_damping(int N, PgPlan P, PgLin lin, const PgCtl* ctl, double* dr, double* gf, double min_diag, double max_diag) {
+    if (ctl->done) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= N) return;
+    int lo = 0, hi = P.S;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (P.sep_node[mid] < i) lo = mid + 1; else hi = mid; }
+    const bool sep = lo < P.S && P.sep_node[lo] == i;
+    const double rho = ctl->radius;
+    for (int a = 0; a < 6; ++a) {
+        double v = lin.D[(size_t)36 * i + 7 * a], gv = lin.g[(size_t)6 * i + a];
+        if (sep)
+            for (int q = P.sl_off[lo]; q < P.sl_off[lo + 1]; ++q) {
+                const int l = P.sl_idx[q] >> 1, end = P.sl_idx[q] & 1;
+                v += lin.lp_out[(size_t)PG_LOOP_OUT * l + (end ? 72 : 0) + 7 * a];
+                gv += lin.lp_out[(size_t)PG_LOOP_OUT * l + (end ? 114 : 108) + a];
+            }
+        v = v < min_diag ? min_diag : (v > max_diag ? max_diag : v);
+        dr[(size_t)6 * i + a] = v / rho;
+        gf[(size_t)6 * i + a] = gv;
+    }
+}
+
+__global__ void k_pg_lm_begin(PgCtl* ctl, double initial_radius) {
+    ctl->radius = initial_radius; ctl->decrease_factor = 2.0; ctl->lin_fresh = 1;
+}
+
+// ONE workgroup, the end of a trial: the error at the candidate and the model decrease in the fixed order of k_pg_error, then Ceres 1.14's
+// LevenbergMarquardtStrategy / monotonic TrustRegionMinimizer rule (include/glio_pgraph_lm.h).  hist row: E tried, the radius used, m, 1 / 0 / -1.
+__global__ void __launch_bounds__(1024) k_pg_lm_decide(int N, int L, const double* nerr, const double* lp_out, const double* nm, PgCtl* ctl, double* hist, PgLm o,
+                                                       double rel_tol, double abs_tol) {
+    if (ctl->done) return;
+    __shared__ double sh[1024];
+    const int t = threadIdx.x;
+    const bool pivot = ctl->pivot_fail != 0;                    // uniform; after it the kernels of this trial returned: nerr and nm are stale
+    __syncthreads();                                            // everyone has read it before thread 0 clears it
+    double e = 0, m = 0;
+    if (!pivot) {
+        e = pg_block_sum(N, nerr, sh);
+        m = 0.5 * pg_block_sum(N, nm, sh);
+    }
+    if (t != 0) return;
+    for (int l = 0; l < L && !pivot; ++l) e += lp_out[(size_t)PG_LOOP_OUT * l + 120];
+    const double cur = ctl->err_cur, rho = ctl->radius;
+    const int trial = ctl->iterations + 1;
+    ctl->iterations = trial;
+    ctl->pivot_fail = 0;
+    const bool valid = !pivot && m > 0.0 && m <= DBL_MAX;
+    int verdict = valid ? 0 : -1;
+    if (valid) {
+        const double gain = (cur - e) / m;
+        if (gain > o.min_relative_decrease) verdict = 1;        // (a candidate error that is not finite makes the gain NaN or -inf: rejected)
+        if (verdict == 1) {
+            const double c = 2.0 * gain - 1.0;
+            ctl->radius = fmin(o.max_radius, rho / fmax(1.0 / 3.0, 1.0 - c * c * c));
+            ctl->decrease_factor = 2.0;
+            ctl->err_cur = e; ctl->accepted += 1; ctl->commit_trial = trial;
+            if (pg_error_converged(cur, e, rel_tol, abs_tol)) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_CONVERGED; }
+        }
+    }
+    ctl->lin_fresh = verdict == 1;
+    if (verdict != 1) {
+        ctl->rejected += 1;
+        if (verdict < 0) ctl->invalid += 1;
+        const double r = rho / ctl->decrease_factor;
+        ctl->radius = r; ctl->decrease_factor *= 2.0;
+        if (r <= o.min_radius) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_MIN_RADIUS; }
+    }
+    if (!ctl->done && trial >= o.max_trials) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_ITERATION_LIMIT; }
+    double* h = hist + (size_t)4 * (trial - 1);
+    h[0] = valid ? e : cur; h[1] = rho; h[2] = pivot ? 0.0 : m; h[3] = (double)verdict;
+}
+
+// the accepted candidate becomes the estimate; trial is the launch's own number, so the launches enqueued behind the end of a solve copy nothing
+__global__ void __launch_bounds__(256) k_pg_lm_commit(int N, double* x, const double* xc, const PgCtl* ctl, int trial) {
+    if (ctl->commit_trial != trial) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 7 * N) x[i] = xc[i];
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------------ the object
@@ -639,6 +768,11 @@ struct glio_pgraph {
     int* d_plan; size_t plan_cap;               // one int block: sep_node, sep_w, w_blk, w_lo, lp_si, lp_sj, sl_off, sl_idx
     double* d_sys; size_t sys_cap;              // band, wide, ldiag
     PgCtl* d_ctl; PgCtl* h_ctl;
+    // the damped solve's own tables (allocated by the first glio_pgraph_solve_damped): candidate poses, d / rho, the complete gradient, the nodes' shares of the
+    // model decrease, history
+    double* d_xc; double* d_dr; double* d_gf; double* d_nm; double* d_hist; size_t hist_cap;
+    std::vector<double> lm_hist;                // [trials][4] of the last damped solve that returned GLIO_OK
+    std::vector<double> lm_hist_in;             // where a running solve's rows arrive
 };
 
 #define PG_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { glio_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); return GLIO_E_HIP; } } while (0)
@@ -781,17 +915,22 @@ static int pg_make_plan(glio_pgraph* pg, int cov_node, PgPlan* P) {
     P->cov_sep = cov_node >= 0 ? sep_of(cov_node) : -1;
     P->sep_node = pg->d_plan + o_sep; P->sep_w = pg->d_plan + o_sw; P->w_blk = pg->d_plan + o_wb; P->w_lo = pg->d_plan + o_wl;
     P->lp_si = pg->d_plan + o_si; P->lp_sj = pg->d_plan + o_sj; P->sl_off = pg->d_plan + o_off; P->sl_idx = pg->d_plan + o_idx;
-    P->Y = pg->d_Y; P->seg = pg->d_seg; P->delta = pg->d_delta;
+    P->Y = pg->d_Y; P->seg = pg->d_seg; P->delta = pg->d_delta; P->dr = nullptr;
     P->band = pg->d_sys; P->wide = pg->d_sys + (size_t)n * 12; P->ldiag = P->wide + (size_t)(6 * nW + nrhs) * n;
     return GLIO_OK;
 }
 
-static void pg_enqueue_linearise(glio_pgraph* pg, int phase) {
-    const PgGraph G = pg_graph(pg);
+// the two linearisation kernels at the pose table x; skip_fresh: see k_pg_lin_nodes
+static void pg_enqueue_lin_at(glio_pgraph* pg, const double* x, int skip_fresh) {
+    PgGraph G = pg_graph(pg);
+    G.x = x;
     const PgLin lin = pg_lin(pg);
-    hipLaunchKernelGGL(k_pg_lin_nodes, dim3((G.N + 63) / 64), dim3(64), 0, pg->stream, G, lin, pg->d_ctl);
-    if (G.L) hipLaunchKernelGGL(k_pg_lin_loops, dim3((G.L + 63) / 64), dim3(64), 0, pg->stream, G, lin, pg->d_ctl);
-    hipLaunchKernelGGL(k_pg_error, dim3(1), dim3(1024), 0, pg->stream, G.N, G.L, pg->d_nerr, pg->d_lp_out, pg->d_ctl, phase, pg->o.max_iterations,
+    hipLaunchKernelGGL(k_pg_lin_nodes, dim3((G.N + 63) / 64), dim3(64), 0, pg->stream, G, lin, pg->d_ctl, skip_fresh);
+    if (G.L) hipLaunchKernelGGL(k_pg_lin_loops, dim3((G.L + 63) / 64), dim3(64), 0, pg->stream, G, lin, pg->d_ctl, skip_fresh);
+}
+static void pg_enqueue_linearise(glio_pgraph* pg, int phase, int max_iter) {
+    pg_enqueue_lin_at(pg, pg->d_x, 0);
+    hipLaunchKernelGGL(k_pg_error, dim3(1), dim3(1024), 0, pg->stream, pg->N, (int)pg->lp_i.size(), pg->d_nerr, pg->d_lp_out, pg->d_ctl, phase, max_iter,
                        pg->o.relative_error_tol, pg->o.absolute_error_tol);
 }
 // segments, separator system, back-substitution of one linear solve; ev (may be null): events after the segments and after the separator system
@@ -828,7 +967,7 @@ void glio_pgraph_destroy(glio_pgraph* pg) {
     (void)hipSetDevice(pg->device);
     if (pg->stream) (void)hipStreamSynchronize(pg->stream);
     void* p[] = {pg->d_x, pg->d_x0, pg->d_cm, pg->d_cw, pg->d_un_node, pg->d_un_type, pg->d_un_m, pg->d_un_w, pg->d_lp_i, pg->d_lp_j, pg->d_lp_m, pg->d_lp_w,
-                 pg->d_D, pg->d_C, pg->d_g, pg->d_nerr, pg->d_lp_out, pg->d_Y, pg->d_seg, pg->d_delta, pg->d_plan, pg->d_sys, pg->d_ctl};
+                 pg->d_D, pg->d_C, pg->d_g, pg->d_nerr, pg->d_lp_out, pg->d_Y, pg->d_seg, pg->d_delta, pg->d_plan, pg->d_sys, pg->d_ctl, pg->d_xc, pg->d_dr, pg->d_gf, pg->d_nm, pg->d_hist};
     for (void* q : p) if (q) (void)hipFree(q);
     if (pg->h_ctl) (void)hipHostFree(pg->h_ctl);
     if (pg->ev_done) (void)hipEventDestroy(pg->ev_done);
@@ -981,16 +1120,16 @@ int glio_pgraph_solve(glio_pgraph* pg, glio_pgraph_info* info) {
     PG_CHECK(hipMemsetAsync(pg->d_ctl, 0, sizeof(PgCtl), pg->stream));
     PG_CHECK(hipMemcpyAsync(pg->d_x0, pg->d_x, (size_t)N * 56, hipMemcpyDeviceToDevice, pg->stream));
     PG_CHECK(hipEventRecord(pg->ev_t[0], pg->stream));
-    pg_enqueue_linearise(pg, 0);
+    pg_enqueue_linearise(pg, 0, pg->o.max_iterations);
     PG_CHECK(hipEventRecord(pg->ev_t[1], pg->stream));
     // The first PG_AHEAD iterations are enqueued ahead and waited for once; Gauss-Newton on these graphs ends within them.  A solve that does not gets the
     // rest of its max_iterations enqueued ahead the same way, behind one more wait.
     for (int it = 0; it < pg->o.max_iterations; ++it) {
         pg_enqueue_linear_solve(pg, P, it == 0 ? &pg->ev_t[2] : nullptr);
         if (P.S > 1) hipLaunchKernelGGL(k_pg_backsub, dim3(P.S - 1), dim3(64), 0, pg->stream, P, pg->d_ctl);
-        hipLaunchKernelGGL(k_pg_update, dim3((N + 255) / 256), dim3(256), 0, pg->stream, N, pg->d_x, pg->d_delta, pg->d_ctl);
+        hipLaunchKernelGGL(k_pg_update, dim3((N + 255) / 256), dim3(256), 0, pg->stream, N, pg->d_x, pg->d_x, pg->d_delta, pg->d_ctl, nullptr, nullptr, nullptr);
         if (it == 0) PG_CHECK(hipEventRecord(pg->ev_t[4], pg->stream));
-        pg_enqueue_linearise(pg, 1);
+        pg_enqueue_linearise(pg, 1, pg->o.max_iterations);
         if (it + 1 == PG_AHEAD || it + 1 == pg->o.max_iterations) {
             PG_CHECK(hipEventRecord(pg->ev_t[5], pg->stream));
             PG_CHECK(hipMemcpyAsync(pg->h_ctl, pg->d_ctl, sizeof(PgCtl), hipMemcpyDeviceToHost, pg->stream));
@@ -1030,6 +1169,121 @@ int glio_pgraph_solve(glio_pgraph* pg, glio_pgraph_info* info) {
     return GLIO_OK;
 }
 
+void glio_pgraph_lm_opts_default(glio_pgraph_lm_opts* o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->initial_radius = 1e4; o->max_radius = 1e16; o->min_radius = 1e-32; o->min_relative_decrease = 1e-3;      // ceres::Solver::Options (1.14)
+    o->min_diagonal = 1e-6; o->max_diagonal = 1e32; o->max_trials = 0;
+}
+int glio_pgraph_lm_struct_sizes(int32_t* out, int n) {
+    const int32_t v[2] = {(int32_t)sizeof(glio_pgraph_lm_opts), (int32_t)sizeof(glio_pgraph_lm_info)};
+    for (int i = 0; i < n && i < 2; ++i) out[i] = v[i];
+    return 2;
+}
+
+// the copy of the control block (and, for a damped solve, of the history) behind everything enqueued so far, and the wait for it
+static int pg_wait_ctl(glio_pgraph* pg, int hist_rows) {
+    PG_CHECK(hipEventRecord(pg->ev_t[5], pg->stream));
+    PG_CHECK(hipMemcpyAsync(pg->h_ctl, pg->d_ctl, sizeof(PgCtl), hipMemcpyDeviceToHost, pg->stream));
+    if (hist_rows > 0) PG_CHECK(hipMemcpyAsync(pg->lm_hist_in.data(), pg->d_hist, (size_t)hist_rows * 32, hipMemcpyDeviceToHost, pg->stream));
+    PG_CHECK(hipEventRecord(pg->ev_done, pg->stream));
+    PG_CHECK(hipEventSynchronize(pg->ev_done));
+    return GLIO_OK;
+}
+
+int glio_pgraph_solve_damped(glio_pgraph* pg, const glio_pgraph_lm_opts* lm_opts, glio_pgraph_info* info, glio_pgraph_lm_info* lm_info) {
+    GLIO_TRACE("glio_pgraph_solve_damped");
+    if (!pg) return GLIO_E_ARG;
+    glio_pgraph_lm_opts lo;
+    if (lm_opts) lo = *lm_opts; else glio_pgraph_lm_opts_default(&lo);
+    const double pos[5] = {lo.initial_radius, lo.max_radius, lo.min_radius, lo.min_diagonal, lo.max_diagonal};
+    if (!pg_var_ok(pos, 5) || lo.min_radius > lo.initial_radius || lo.initial_radius > lo.max_radius || lo.min_diagonal > lo.max_diagonal ||
+        !(lo.min_relative_decrease >= 0.0) || !(lo.min_relative_decrease < 1.0) || lo.max_trials < 0) {
+        glio_set_error("bad glio_pgraph_lm_opts (a radius or a diagonal bound that is not finite and positive, min_radius <= initial_radius <= max_radius or "
+                       "min_diagonal <= max_diagonal violated, min_relative_decrease outside [0, 1), or max_trials %d < 0)", lo.max_trials);
+        return GLIO_E_ARG;
+    }
+    { const int rc = pg_ready(pg, "glio_pgraph_solve_damped"); if (rc != GLIO_OK) return rc; }
+    PgPlan P;
+    { const int rc = pg_make_plan(pg, -1, &P); if (rc != GLIO_OK) return rc; }
+    const int N = pg->N, L = (int)pg->lp_i.size(), max_trials = lo.max_trials > 0 ? lo.max_trials : pg->o.max_iterations;
+    {                                           // each table by its own pointer: a call that failed half way is finished by the next one
+        const size_t cap = (size_t)pg->o.max_nodes;
+        if (!pg->d_xc) PG_CHECK(hipMalloc((void**)&pg->d_xc, cap * 56));
+        if (!pg->d_dr) PG_CHECK(hipMalloc((void**)&pg->d_dr, cap * 48));
+        if (!pg->d_gf) PG_CHECK(hipMalloc((void**)&pg->d_gf, cap * 48));
+        if (!pg->d_nm) PG_CHECK(hipMalloc((void**)&pg->d_nm, cap * 8));
+    }
+    if ((size_t)max_trials > pg->hist_cap) {
+        if (pg->d_hist) { hipFree(pg->d_hist); pg->d_hist = nullptr; pg->hist_cap = 0; }
+        PG_CHECK(hipMalloc((void**)&pg->d_hist, (size_t)max_trials * 32));
+        pg->hist_cap = (size_t)max_trials;
+    }
+    pg->lm_hist_in.assign((size_t)4 * std::max(max_trials, 0), 0.0);
+    P.dr = pg->d_dr;
+    PgLm o;
+    o.max_radius = lo.max_radius; o.min_radius = lo.min_radius; o.min_relative_decrease = lo.min_relative_decrease;
+    o.min_diagonal = lo.min_diagonal; o.max_diagonal = lo.max_diagonal; o.max_trials = max_trials;
+    const PgLin lin = pg_lin(pg);
+    PG_CHECK(hipMemsetAsync(pg->d_ctl, 0, sizeof(PgCtl), pg->stream));
+    hipLaunchKernelGGL(k_pg_lm_begin, dim3(1), dim3(1), 0, pg->stream, pg->d_ctl, lo.initial_radius);
+    PG_CHECK(hipEventRecord(pg->ev_t[0], pg->stream));
+    pg_enqueue_linearise(pg, 0, max_trials);
+    PG_CHECK(hipEventRecord(pg->ev_t[1], pg->stream));
+    // The trials are enqueued ahead as glio_pgraph_solve's iterations are.  A trial: the linearisation at x (skipped while the tables still hold it), the
+    // damping, the damped linear solve, the candidate with the model decrease, the linearisation at the candidate (its error; and the next trial's tables when
+    // the candidate is accepted), the decision, the copy of an accepted candidate.  x itself is written by that copy alone.
+    bool waited = false;
+    for (int it = 0; it < max_trials; ++it) {
+        pg_enqueue_lin_at(pg, pg->d_x, 1);
+        hipLaunchKernelGGL(k_pg_damping, dim3((N + 255) / 256), dim3(256), 0, pg->stream, N, P, lin, pg->d_ctl, pg->d_dr, pg->d_gf, lo.min_diagonal, lo.max_diagonal);
+        pg_enqueue_linear_solve(pg, P, it == 0 ? &pg->ev_t[2] : nullptr);
+        if (P.S > 1) hipLaunchKernelGGL(k_pg_backsub, dim3(P.S - 1), dim3(64), 0, pg->stream, P, pg->d_ctl);
+        hipLaunchKernelGGL(k_pg_update, dim3((N + 255) / 256), dim3(256), 0, pg->stream, N, pg->d_x, pg->d_xc, pg->d_delta, pg->d_ctl, pg->d_dr, pg->d_gf, pg->d_nm);
+        if (it == 0) PG_CHECK(hipEventRecord(pg->ev_t[4], pg->stream));
+        pg_enqueue_lin_at(pg, pg->d_xc, 0);
+        hipLaunchKernelGGL(k_pg_lm_decide, dim3(1), dim3(1024), 0, pg->stream, N, L, pg->d_nerr, pg->d_lp_out, pg->d_nm, pg->d_ctl, pg->d_hist, o,
+                           pg->o.relative_error_tol, pg->o.absolute_error_tol);
+        hipLaunchKernelGGL(k_pg_lm_commit, dim3((7 * N + 255) / 256), dim3(256), 0, pg->stream, N, pg->d_x, pg->d_xc, pg->d_ctl, it + 1);
+        if (it + 1 == PG_AHEAD || it + 1 == max_trials) {
+            { const int rc = pg_wait_ctl(pg, it + 1); if (rc != GLIO_OK) return rc; }
+            waited = true;
+            if (pg->h_ctl->done) break;
+        }
+    }
+    if (!waited) { const int rc = pg_wait_ctl(pg, 0); if (rc != GLIO_OK) return rc; }
+    PG_CHECK(hipGetLastError());
+    const PgCtl& c = *pg->h_ctl;
+    pg->lm_hist_in.resize((size_t)4 * c.iterations);
+    pg->lm_hist.swap(pg->lm_hist_in);            // only now: a solve that returned early leaves the last history in place
+    if (info) {
+        memset(info, 0, sizeof *info);
+        info->initial_error = c.err0; info->final_error = c.err_cur;
+        info->iterations = c.iterations; info->termination = c.reason;
+        info->separators = P.S; info->segments = P.S - 1;
+        (void)hipEventElapsedTime(&info->device_ms, pg->ev_t[0], pg->ev_t[5]);
+        if (max_trials > 0) {
+            (void)hipEventElapsedTime(&info->stage_ms[0], pg->ev_t[0], pg->ev_t[1]);
+            (void)hipEventElapsedTime(&info->stage_ms[1], pg->ev_t[1], pg->ev_t[2]);
+            (void)hipEventElapsedTime(&info->stage_ms[2], pg->ev_t[2], pg->ev_t[3]);
+            (void)hipEventElapsedTime(&info->stage_ms[3], pg->ev_t[3], pg->ev_t[4]);
+        }
+    }
+    if (lm_info) {
+        lm_info->final_radius = c.radius;
+        lm_info->accepted = c.accepted; lm_info->rejected = c.rejected; lm_info->invalid = c.invalid; lm_info->trials = c.iterations;
+    }
+    return GLIO_OK;
+}
+
+int glio_pgraph_lm_history(glio_pgraph* pg, int first, int n, double* out) {
+    if (!pg) return GLIO_E_ARG;
+    const long long rows = (long long)(pg->lm_hist.size() / 4);
+    if (first < 0 || n < 0 || (long long)first + n > rows || (n > 0 && !out)) { glio_set_error("glio_pgraph_lm_history: rows [%d, %d + %d) of %lld", first, first, n, rows); return GLIO_E_ARG; }
+    if (n > 0) memcpy(out, pg->lm_hist.data() + (size_t)4 * first, (size_t)n * 32);
+    return GLIO_OK;
+}
+
 int glio_pgraph_size(glio_pgraph* pg, int* n_nodes) {
     if (!pg || !n_nodes) return GLIO_E_ARG;
     *n_nodes = pg->N;
@@ -1050,7 +1304,7 @@ int glio_pgraph_error(glio_pgraph* pg, double* error) {
     if (!pg || !error) return GLIO_E_ARG;
     { const int rc = pg_ready(pg, "glio_pgraph_error"); if (rc != GLIO_OK) return rc; }
     PG_CHECK(hipMemsetAsync(pg->d_ctl, 0, sizeof(PgCtl), pg->stream));
-    pg_enqueue_linearise(pg, -1);
+    pg_enqueue_linearise(pg, -1, 0);
     PG_CHECK(hipMemcpyAsync(pg->h_ctl, pg->d_ctl, sizeof(PgCtl), hipMemcpyDeviceToHost, pg->stream));
     PG_CHECK(hipStreamSynchronize(pg->stream));
     PG_CHECK(hipGetLastError());
@@ -1066,7 +1320,7 @@ int glio_pgraph_marginal_covariance(glio_pgraph* pg, int node, double* out) {
     PgPlan P;
     { const int rc = pg_make_plan(pg, node, &P); if (rc != GLIO_OK) return rc; }
     PG_CHECK(hipMemsetAsync(pg->d_ctl, 0, sizeof(PgCtl), pg->stream));
-    pg_enqueue_linearise(pg, -1);
+    pg_enqueue_linearise(pg, -1, 0);
     pg_enqueue_linear_solve(pg, P, nullptr);
     PG_CHECK(hipMemcpyAsync(pg->h_ctl, pg->d_ctl, sizeof(PgCtl), hipMemcpyDeviceToHost, pg->stream));
     PG_CHECK(hipStreamSynchronize(pg->stream));

@@ -176,6 +176,19 @@ class GlioPgraphInfo(C.Structure):
 
 PGRAPH_NOT_RUN, PGRAPH_CONVERGED, PGRAPH_ITERATION_LIMIT, PGRAPH_NONPOSITIVE_PIVOT = range(4)
 PGRAPH_TERMINATION_NAMES = ("NOT_RUN", "CONVERGED", "ITERATION_LIMIT", "NONPOSITIVE_PIVOT")
+PGRAPH_MIN_RADIUS = 4                   # glio_pgraph_solve_damped alone
+PGRAPH_LM_TERMINATION_NAMES = PGRAPH_TERMINATION_NAMES + ("MIN_RADIUS",)
+
+
+class GlioPgraphLmOpts(C.Structure):
+    """glio_pgraph_lm_opts: the damped solve's radius rule (Ceres 1.14's LevenbergMarquardtStrategy defaults)"""
+    _fields_ = [("initial_radius", C.c_double), ("max_radius", C.c_double), ("min_radius", C.c_double), ("min_relative_decrease", C.c_double),
+                ("min_diagonal", C.c_double), ("max_diagonal", C.c_double), ("max_trials", C.c_int32), ("reserved_", C.c_int32)]
+
+
+class GlioPgraphLmInfo(C.Structure):
+    """glio_pgraph_lm_info: what glio_pgraph_solve_damped reports beside glio_pgraph_info"""
+    _fields_ = [("final_radius", C.c_double), ("accepted", C.c_int32), ("rejected", C.c_int32), ("invalid", C.c_int32), ("trials", C.c_int32)]
 
 
 LOOP_SOURCE, LOOP_TARGET = 0, 1

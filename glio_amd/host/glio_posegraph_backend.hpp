@@ -58,6 +58,19 @@ public:
     void addBetween(int i, int j, const double rel[7], const double var[6]) { check(glio_pgraph_add_between(h_, i, j, rel, var), "glio_pgraph_add_between"); }
     void addGps(int i, const double xyz[3], const double var[3]) { check(glio_pgraph_add_gps(h_, i, xyz, var), "glio_pgraph_add_gps"); }
     glio_pgraph_info solve() { glio_pgraph_info info; check(glio_pgraph_solve(h_, &info), "glio_pgraph_solve"); return info; }
+    // glio_pgraph_solve_damped: the solve that never leaves a worse estimate (lm_opts null: the defaults); lm (may be null): its counters and final radius;
+    // history (may be null): per trial E tried, the radius used, the model decrease, 1 accepted / 0 rejected / -1 invalid
+    glio_pgraph_info solveDamped(const glio_pgraph_lm_opts* lm_opts = nullptr, glio_pgraph_lm_info* lm = nullptr, std::vector<double>* history = nullptr) {
+        glio_pgraph_info info;
+        glio_pgraph_lm_info li;
+        check(glio_pgraph_solve_damped(h_, lm_opts, &info, &li), "glio_pgraph_solve_damped");
+        if (lm) *lm = li;
+        if (history) {
+            history->assign((size_t)4 * li.trials, 0.0);
+            check(glio_pgraph_lm_history(h_, 0, li.trials, history->data()), "glio_pgraph_lm_history");
+        }
+        return info;
+    }
     int size() { int n = 0; check(glio_pgraph_size(h_, &n), "glio_pgraph_size"); return n; }
     std::vector<double> readPoses(int first, int n) {
         std::vector<double> out((size_t)(n > 0 ? n : 0) * 7);
@@ -99,12 +112,14 @@ public:
         g_->append((int)ids.size(), P + (size_t)7 * ids[0], P + (size_t)7 * (ids[0] - 1));
         return ids;
     }
-    // rel [7], var [6] = glio::loopConstraint's; adds the edge (:5251-5254) and solves (:5255-5261)
-    glio_pgraph_info loopClosed(const std::vector<int32_t>& keyframe_id_in_frame, int latest_keyframe, int closest_keyframe, const double rel[7], const double var[6]) {
+    // rel [7], var [6] = glio::loopConstraint's; adds the edge (:5251-5254) and solves (:5255-5261).  damped: PoseGraph::solveDamped instead -- the call for a
+    // loop over a long drive, where the undamped step can raise the error; lm (may be null): its counters
+    glio_pgraph_info loopClosed(const std::vector<int32_t>& keyframe_id_in_frame, int latest_keyframe, int closest_keyframe, const double rel[7], const double var[6],
+                                bool damped = false, glio_pgraph_lm_info* lm = nullptr) {
         int i, j;
         loopEdgeFrames(keyframe_id_in_frame, latest_keyframe, closest_keyframe, &i, &j);
         g_->addBetween(i, j, rel, var);
-        return g_->solve();
+        return damped ? g_->solveDamped(nullptr, lm) : g_->solve();
     }
     // pose_each_frame[keyframe_id_in_frame[i]] of the corrected estimate, keyframes 0 .. n - 1 (:4702-4713): rows t, q
     std::vector<double> keyframePoses(const std::vector<int32_t>& keyframe_id_in_frame, int n) {

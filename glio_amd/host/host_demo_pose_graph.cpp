@@ -3,19 +3,23 @@
 // solved (:5251-5261); the corrected poses are printed as hex floats.  The case file is written by glio_amd/host/window_io.py::write_pose_graph_case:
 //   int32 F NK W n_gps latest_kf closest_kf 0 0 | pose_each_frame [F][7] = t, q | keyframe_id_in_frame [NK] int32 (padded to a multiple of 2) |
 //   rel [7] var [6] | n_gps x (frame, xyz[3], var[3]) doubles
-// usage: host_demo_pose_graph case.bin [device]
+// usage: host_demo_pose_graph case.bin [device] [damped=1]
+// damped=1: the loop is closed with glio_pgraph_solve_damped (GlobalGraph::loopClosed(..., true)); one more line, `damped accepted rejected invalid trials
+// final_radius`, and one `trial k E radius m verdict` per trial are printed.  Without it the output is what it always was.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <iostream>
 
 #include "glio_posegraph_backend.hpp"
 
 int main(int argc, char** argv) {
-    if (argc < 2) { std::fprintf(stderr, "usage: %s case.bin [device]\n", argv[0]); return 2; }
+    if (argc < 2) { std::fprintf(stderr, "usage: %s case.bin [device] [damped=1]\n", argv[0]); return 2; }
     std::ifstream in(argv[1], std::ios::binary);
     if (!in) { std::fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
-    const int device = argc > 2 ? std::atoi(argv[2]) : 0;
+    const bool damped = argc > 2 && std::strcmp(argv[argc - 1], "damped=1") == 0;
+    const int device = argc > (damped ? 3 : 2) ? std::atoi(argv[2]) : 0;
     int32_t h[8];
     in.read((char*)h, sizeof h);
     const int F = h[0], NK = h[1], W = h[2], n_gps = h[3], latest = h[4], closest = h[5];
@@ -43,8 +47,15 @@ int main(int argc, char** argv) {
         }
         for (int k = 0; k < n_gps; ++k) graph.addGps((int)gps[(size_t)7 * k], &gps[(size_t)7 * k + 1], &gps[(size_t)7 * k + 4]);
         const double before = graph.error();
-        const glio_pgraph_info info = global.loopClosed(kf, latest, closest, rel, var);
+        glio_pgraph_lm_info lm = {};
+        const glio_pgraph_info info = global.loopClosed(kf, latest, closest, rel, var, damped, &lm);
         std::printf("solve %d %d %a %a %a %d %d\n", info.iterations, info.termination, before, info.initial_error, info.final_error, info.separators, info.segments);
+        if (damped) {
+            std::printf("damped %d %d %d %d %a\n", lm.accepted, lm.rejected, lm.invalid, lm.trials, lm.final_radius);
+            std::vector<double> hist((size_t)4 * lm.trials);
+            if (glio_pgraph_lm_history(graph.handle(), 0, lm.trials, hist.data()) != GLIO_OK) throw std::runtime_error(glio_last_error());
+            for (int k = 0; k < lm.trials; ++k) std::printf("trial %d %a %a %a %d\n", k, hist[(size_t)4 * k], hist[(size_t)4 * k + 1], hist[(size_t)4 * k + 2], (int)hist[(size_t)4 * k + 3]);
+        }
         const std::vector<double> x = graph.readPoses();
         for (int i = 0; i < graph.size(); ++i) {
             std::printf("pose %d", i);

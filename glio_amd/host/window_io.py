@@ -10,7 +10,7 @@ from .. import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEMO = os.path.join(HERE, "host_demo")
-_ABI_HEADERS = [os.path.join(HERE, "..", "..", "include", h) for h in ("glio_hip.h", "glio_types.h")]      # a changed struct must rebuild the demos
+_ABI_HEADERS = [os.path.join(HERE, "..", "..", "include", h) for h in ("glio_hip.h", "glio_types.h", "glio_pgraph_lm.h")]      # a changed struct must rebuild the demos
 
 
 def build_demo(force=False):
@@ -482,12 +482,13 @@ def write_pose_graph_case(path, pose_each_frame, keyframe_id_in_frame, W, latest
             f.write(np.array([float(node), *xyz, *v], np.float64).tobytes())
 
 
-def run_demo_pose_graph(path, device=0, env=None):
-    """-> dict(iterations, termination, error_before, initial_error, final_error, separators, segments, poses [n][7], calls [(n_keyframes, first, last)], n_keyframe_poses)"""
-    r = subprocess.run([build_demo_pose_graph(), path, str(device)], capture_output=True, text=True, env=env)
+def run_demo_pose_graph(path, device=0, env=None, damped=False, keep_stdout=False):
+    """-> dict(iterations, termination, error_before, initial_error, final_error, separators, segments, poses [n][7], calls [(n_keyframes, first, last)], n_keyframe_poses)
+    damped: the loop closed by glio_pgraph_solve_damped; also accepted, rejected, invalid, trials, final_radius, history [trials][4].  keep_stdout: the demo's output as `stdout`."""
+    r = subprocess.run([build_demo_pose_graph(), path, str(device)] + (["damped=1"] if damped else []), capture_output=True, text=True, env=env)
     if r.returncode != 0:
         raise RuntimeError("host_demo_pose_graph failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
-    out, poses, calls = {}, [], []
+    out, poses, calls, hist = ({"stdout": r.stdout} if keep_stdout else {}), [], [], []
     for ln in r.stdout.splitlines():
         w = ln.split()
         if not w:
@@ -501,5 +502,11 @@ def run_demo_pose_graph(path, device=0, env=None):
             calls.append((int(w[1]), int(w[3]), int(w[5])))
         elif w[0] == "keyframes":
             out["n_keyframe_poses"] = int(w[1])
+        elif w[0] == "damped":
+            out.update(accepted=int(w[1]), rejected=int(w[2]), invalid=int(w[3]), trials=int(w[4]), final_radius=float.fromhex(w[5]))
+        elif w[0] == "trial":
+            hist.append([float.fromhex(x) for x in w[2:5]] + [float(w[5])])
+    if damped:
+        out["history"] = np.array(hist, np.float64).reshape(-1, 4)
     out.update(poses=np.array(poses), calls=calls)
     return out

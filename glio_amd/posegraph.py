@@ -46,11 +46,38 @@ class SolveInfo:
 
     @property
     def termination_name(self):
-        return T.PGRAPH_TERMINATION_NAMES[self.termination]
+        return T.PGRAPH_LM_TERMINATION_NAMES[self.termination]
 
     def as_dict(self):
         return dict(iterations=self.iterations, termination=self.termination_name, initial_error=self.initial_error, final_error=self.final_error,
                     separators=self.separators, segments=self.segments, device_ms=self.device_ms, stage_ms=self.stage_ms)
+
+
+def default_lm_opts(**kw):
+    """glio_pgraph_lm_opts: Ceres 1.14's LevenbergMarquardtStrategy defaults; keywords override fields"""
+    lib = capi.load()
+    lib.glio_pgraph_lm_opts_default.restype = None
+    o = T.GlioPgraphLmOpts()
+    lib.glio_pgraph_lm_opts_default(C.byref(o))
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
+class DampedSolveInfo(SolveInfo):
+    """SolveInfo (iterations = trials) with glio_pgraph_lm_info and the per-trial history [trials][4]: E tried, the radius used, the model decrease,
+    1 accepted / 0 rejected / -1 invalid"""
+
+    def __init__(self, r, lm, history):
+        SolveInfo.__init__(self, r)
+        self.final_radius = float(lm.final_radius)
+        self.accepted, self.rejected, self.invalid, self.trials = int(lm.accepted), int(lm.rejected), int(lm.invalid), int(lm.trials)
+        self.history = history
+
+    def as_dict(self):
+        return dict(SolveInfo.as_dict(self), final_radius=self.final_radius, accepted=self.accepted, rejected=self.rejected, invalid=self.invalid, trials=self.trials,
+                    verdicts=[int(v) for v in self.history[:, 3]])
 
 
 def _p7(a):
@@ -106,6 +133,15 @@ class PoseGraph:
         r = T.GlioPgraphInfo()
         capi._check(capi.load().glio_pgraph_solve(self._h, C.byref(r)))
         return SolveInfo(r)
+
+    def solve_damped(self, lm_opts=None):
+        """glio_pgraph_solve_damped: the solve that never leaves a worse estimate (lm_opts None: the defaults); returns DampedSolveInfo"""
+        lib = capi.load()
+        r, lm = T.GlioPgraphInfo(), T.GlioPgraphLmInfo()
+        capi._check(lib.glio_pgraph_solve_damped(self._h, None if lm_opts is None else C.byref(lm_opts), C.byref(r), C.byref(lm)))
+        hist = np.zeros((lm.trials, 4))
+        capi._check(lib.glio_pgraph_lm_history(self._h, 0, int(lm.trials), T.dptr(hist) if lm.trials else None))
+        return DampedSolveInfo(r, lm, hist)
 
     def size(self):
         n = C.c_int(0)
@@ -172,11 +208,12 @@ class GlobalGraph:
         self.graph.append(P[ids[0]:ids[-1] + 1], prev_pose=P[ids[0] - 1])
         return ids
 
-    def loop_closed(self, keyframe_id_in_frame, latest_keyframe, closest_keyframe, constraint):
-        """constraint = loop.loop_constraint(...) = (rel [7], var [6]); adds the edge (:5251-5254), solves (:5255-5261); returns SolveInfo"""
+    def loop_closed(self, keyframe_id_in_frame, latest_keyframe, closest_keyframe, constraint, damped=False):
+        """constraint = loop.loop_constraint(...) = (rel [7], var [6]); adds the edge (:5251-5254), solves (:5255-5261); returns SolveInfo.
+        damped: PoseGraph.solve_damped instead (DampedSolveInfo) -- the call for a loop over a long drive, where the undamped step can raise the error"""
         i, j = loop_edge_frames(keyframe_id_in_frame, latest_keyframe, closest_keyframe)
         self.graph.add_between(i, j, constraint[0], constraint[1])
-        return self.graph.solve()
+        return self.graph.solve_damped() if damped else self.graph.solve()
 
     def keyframe_poses(self, keyframe_id_in_frame, n):
         """pose_each_frame[keyframe_id_in_frame[i]] of the corrected estimate for keyframes 0 .. n - 1 (correctPoses, :4702-4713): rows t, q"""

@@ -636,6 +636,9 @@ int glio_gmap_last_stage_ms(glio_gmap* gm, float* ms4);
  * Gauss-Newton (no damping) with gtsam::GaussNewtonParams' termination, decided ON THE DEVICE on the total error E = 1/2 |r|^2: after every iteration
  * stop CONVERGED when E_new <= 0, or (E - E_new) / E <= relative_error_tol, or E - E_new <= absolute_error_tol; stop ITERATION_LIMIT at max_iterations.
  * Never on a step norm: with the reference's prior (translation variance 1e8 against odometry information 1e4) the absolute translation is numerically a gauge.
+ * A NEGATIVE decrease passes both tests: an iteration that RAISES the error ends the solve CONVERGED with that worse estimate kept in the pose table
+ * (final_error > initial_error; a long drive with accumulated drift does this on its first full step).  glio_pgraph_solve_damped (include/glio_pgraph_lm.h, below)
+ * is the solve that never leaves a worse estimate: use it after a loop closure over a long drive.
  * Every iteration solves the normal equations by ONE exact Cholesky in a fixed order (nested dissection: node 0, the last node, every loop endpoint and evenly
  * spaced nodes are separators; the chain between two separators is eliminated by one wavefront per segment; the separator system is factored as a band plus the
  * full rows of loop endpoints).  No atomic takes part in a sum: two runs give the same bits.  A non-positive pivot ends the solve with termination
@@ -675,6 +678,8 @@ int glio_pgraph_marginal_covariance(glio_pgraph* pg, int node, double* out /* [3
 int glio_pgraph_error(glio_pgraph* pg, double* error);
 /* the pose table on the device ([n_nodes][7] doubles t, q), valid until the next successful glio_pgraph_solve / glio_pgraph_append / glio_pgraph_clear */
 int glio_pgraph_poses_dev(glio_pgraph* pg, const double** poses_dev, int* n_nodes);
+/* the damped (Levenberg-Marquardt) solve on the same object: its entry points and its contract (final_error <= initial_error, always) */
+#include "glio_pgraph_lm.h"
 
 #ifdef __cplusplus
 }

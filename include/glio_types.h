@@ -344,6 +344,26 @@ typedef struct glio_pgraph_info {
     int32_t segments;
     int32_t reserved_;
 } glio_pgraph_info;
+/* a termination of glio_pgraph_solve_damped alone (appended: the four values above keep their numbers) */
+enum { GLIO_PGRAPH_MIN_RADIUS = 4 };
+/* ---- the damped solve (glio_pgraph_solve_damped, include/glio_pgraph_lm.h): Ceres 1.14's LevenbergMarquardtStrategy and its monotonic trust-region loop on the
+ * pose graph's own normal equations (UNPINNED like everything Ceres- or GTSAM-side; the rule is restated in include/glio_pgraph_lm.h).  Defaults
+ * (glio_pgraph_lm_opts_default) are Ceres' published ones. */
+typedef struct glio_pgraph_lm_opts {
+    double initial_radius;         /* 1e4: every solve starts from it */
+    double max_radius;             /* 1e16 */
+    double min_radius;             /* 1e-32: a radius at or below it ends the solve MIN_RADIUS */
+    double min_relative_decrease;  /* 1e-3: a trial is accepted when (E - E_candidate) / model decrease exceeds it; in [0, 1) */
+    double min_diagonal;           /* 1e-6: the damping is clamp(H_ii, min_diagonal, max_diagonal) / radius */
+    double max_diagonal;           /* 1e32 */
+    int32_t max_trials;            /* 0 = glio_pgraph_opts.max_iterations; accepted, rejected and invalid trials all count */
+    int32_t reserved_;
+} glio_pgraph_lm_opts;
+/* what glio_pgraph_solve_damped reports beside glio_pgraph_info */
+typedef struct glio_pgraph_lm_info {
+    double final_radius;
+    int32_t accepted, rejected, invalid, trials;     /* rejected counts the invalid trials too: trials = accepted + rejected */
+} glio_pgraph_lm_info;
 
 #ifdef __cplusplus
 }

@@ -6,8 +6,11 @@ Every case: the wall time of the synchronous call, the device time of the whole 
 linearise, segments, separator system, back-substitution + update), the iterations.  Medians of --reps runs after --warmup, min and max as the spread; every
 run solves the same freshly rebuilt graph.  Nothing existed before this object to compare against.  As CONTEXT ONLY, beside each case: one linear solve of the
 restatement (tests/pose_graph_restated.py: scipy.sparse J^T J + splu) on the host this script runs on -- another machine, another algorithm, one thread.
+  (damped) the same global graphs through glio_pgraph_solve_damped: trials, accepted and rejected counts, the whole solve, ms per trial -- and next to each the
+           undamped solve of the same graph in the same session (iterations, ms per iteration, its initial and final error).
 Prints ONE JSON line.
-    python scripts/pose_graph_timing.py [--reps 10] [--warmup 2] [--out profiles/pose_graph_timing.json] [--sizes 3500,36000,65536]"""
+    python scripts/pose_graph_timing.py [--reps 10] [--warmup 2] [--out profiles/pose_graph_timing.json] [--sizes 3500,36000,65536] [--only-damped]
+--only-damped: the damped section alone; with --out, it is merged into the file that is there (the other sections stay as they were measured)."""
 import argparse
 import json
 import os
@@ -63,6 +66,29 @@ def timed(pg, build, reps, warmup, covariance_of=None):
     return out
 
 
+def timed_damped(pg, build, reps, warmup):
+    """the damped solve, and the undamped one of the same graph beside it"""
+    d_wall, d_dev, u_dev, di, ui = [], [], [], None, None
+    for r in range(warmup + reps):
+        pg.clear()
+        build(pg)
+        pg.read_poses(0, 1)
+        ui = pg.solve()
+        pg.clear()
+        build(pg)
+        pg.read_poses(0, 1)
+        t0 = time.perf_counter()
+        di = pg.solve_damped()
+        t1 = time.perf_counter()
+        if r >= warmup:
+            d_wall.append(1e3 * (t1 - t0)); d_dev.append(di.device_ms); u_dev.append(ui.device_ms)
+    return {"trials": di.trials, "accepted": di.accepted, "rejected": di.rejected, "invalid": di.invalid, "termination": di.termination_name,
+            "initial_error": di.initial_error, "final_error": di.final_error, "final_radius": di.final_radius, "separators": di.separators,
+            "solve_wall_ms": spread(d_wall), "solve_device_ms": spread(d_dev), "device_ms_per_trial": spread(np.array(d_dev) / max(di.trials, 1)),
+            "undamped": {"iterations": ui.iterations, "termination": ui.termination_name, "initial_error": ui.initial_error, "final_error": ui.final_error,
+                         "solve_device_ms": spread(u_dev), "device_ms_per_iteration": spread(np.array(u_dev) / max(ui.iterations, 1))}}
+
+
 def witness_linear_solve(x0, loops, gps=()):
     g = W.Graph()
     g.add_prior(0, x0[0])
@@ -83,9 +109,36 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--sizes", default="3500,36000,65536")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--only-damped", action="store_true")
     a = ap.parse_args()
     res = {"metric": "pose_graph", "device": "MI355X (gfx950)", "reps": a.reps, "warmup": a.warmup, "cases": {},
            "compared_by": "nothing existed before this object; wall time of the synchronous call, device times from HIP events inside it"}
+    damped = {"reps": a.reps, "warmup": a.warmup, "what": "glio_pgraph_solve_damped on the global graphs, the undamped solve of the same graph beside it, one session",
+              "cases": {}}
+    for n in [int(s) for s in a.sizes.split(",") if s]:
+        truth, x0 = drive(n, 31)
+        pg = posegraph.PoseGraph(posegraph.default_opts(max_nodes=n, max_loops=32, max_unary=1))
+        for count in (1, 8, 32):
+            loops = loops_of(truth, n, count)
+
+            def build(p, loops=loops):
+                p.set_prior(x0[0])
+                p.append(x0)
+                for lp in loops:
+                    p.add_between(*lp)
+            damped["cases"][f"global_{n}_frames_{count}_loops"] = timed_damped(pg, build, a.reps, a.warmup)
+        pg.close()
+    if a.only_damped:
+        if a.out and os.path.exists(a.out):
+            res = json.loads(open(a.out).read())
+        res["damped"] = damped
+        line = json.dumps(res)
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(line + "\n")
+        print(json.dumps(damped))
+        return
+    res["damped"] = damped
     for n in [int(s) for s in a.sizes.split(",") if s]:
         truth, x0 = drive(n, 31)
         pg = posegraph.PoseGraph(posegraph.default_opts(max_nodes=n, max_loops=32, max_unary=1))
