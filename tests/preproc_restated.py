@@ -111,44 +111,81 @@ def undistort(p, inten, q_imu, q_lb):
     return out
 
 
-def project(raw, n_scans=32, q_imu=(1.0, 0, 0, 0), q_lb=(1.0, 0, 0, 0), min_range=3.0):
-    """Steps 1-3: survivors, startOri / endOri, scanID, orientation, relTime, intensity, undistortion, the stable ring bucketing (:396-526).
-    Returns (cut [n][4] float32, ring_start[n_scans], ring_size[n_scans], kept, ring of every survivor (-1 dropped))."""
+def _dist(values, const):
+    """smallest |value - const| in radians (inf over nothing): how far a comparison is from going the other way"""
+    v = np.abs(np.asarray(values, np.float64) - const)
+    return float(v.min()) if v.size else math.inf
+
+
+def _project(raw, n_scans, q_imu, q_lb, min_range):
+    """project() and orientation_report() in one pass: the masks that pick every orientation are the ones the report counts"""
     raw = np.asarray(raw, np.float32)
     keep = survivors(raw[:, :3], min_range)
     p = raw[keep, :3]
     ns = len(p)
     if ns == 0:
-        return np.zeros((0, 4), np.float32), np.zeros(n_scans, int), np.zeros(n_scans, int), 0, np.zeros(0, int)
+        return (np.zeros((0, 4), np.float32), np.zeros(n_scans, int), np.zeros(n_scans, int), 0, np.zeros(0, int)), None
     start = -atan2f(p[0, 1], p[0, 0])                                                 # :401
     end = F(float(-atan2f(p[-1, 1], p[-1, 0])) + 2 * math.pi)                         # :402-404
-    if float(end - start) > 3 * math.pi:                                              # :406-410
+    span0 = float(end - start)
+    end_minus = span0 > 3 * math.pi                                                   # :406-410
+    end_plus = not end_minus and span0 < math.pi
+    if end_minus:
         end = F(float(end) - 2 * math.pi)
-    elif float(end - start) < math.pi:
+    elif end_plus:
         end = F(float(end) + 2 * math.pi)
     sid, _ = scan_ids(p, n_scans)
-    ori_raw = -_vec(_M.atan2f, p[:, 1], p[:, 0])                                      # :494
+    ori_raw = -_vec(_M.atan2f, p[:, 1], p[:, 0])                                      # :489
     o64 = ori_raw.astype(np.float64)
-    first = np.where(o64 < float(start) - math.pi / 2, (o64 + 2 * math.pi).astype(np.float32),
-                     np.where(o64 > float(start) + math.pi * 3 / 2, (o64 - 2 * math.pi).astype(np.float32), ori_raw))
+    f_lo = o64 < float(start) - math.pi / 2                                           # :491
+    f_hi = ~f_lo & (o64 > float(start) + math.pi * 3 / 2)                             # :493
+    first = np.where(f_lo, (o64 + 2 * math.pi).astype(np.float32), np.where(f_hi, (o64 - 2 * math.pi).astype(np.float32), ori_raw))
     valid = sid >= 0
-    flip = np.nonzero(valid & ((first - start).astype(np.float64) > math.pi))[0]      # halfPassed (:500-507): the first valid point that sets it
+    turn = (first - start).astype(np.float64)
+    flip = np.nonzero(valid & (turn > math.pi))[0]                                    # halfPassed (:496-497): the first valid point that sets it
     half = flip[0] if len(flip) else ns
-    sec = (o64 + 2 * math.pi).astype(np.float32)                                      # :509-513
+    sec = (o64 + 2 * math.pi).astype(np.float32)                                      # :500-504
     s64 = sec.astype(np.float64)
-    sec = np.where(s64 < float(end) - math.pi * 3 / 2, (s64 + 2 * math.pi).astype(np.float32),
-                   np.where(s64 > float(end) + math.pi / 2, (s64 - 2 * math.pi).astype(np.float32), sec))
-    ori = np.where(np.arange(ns) <= half, first, sec)
-    rel = (ori - start) / (end - start)                                               # :515
-    inten = (sid.astype(np.float64) + 0.1 * rel.astype(np.float64)).astype(np.float32)   # :517
+    s_lo = s64 < float(end) - math.pi * 3 / 2                                         # :501
+    s_hi = ~s_lo & (s64 > float(end) + math.pi / 2)                                   # :503
+    sec = np.where(s_lo, (s64 + 2 * math.pi).astype(np.float32), np.where(s_hi, (s64 - 2 * math.pi).astype(np.float32), sec))
+    in_first = np.arange(ns) <= half                                                  # the point that sets halfPassed is still on the first branch
+    ori = np.where(in_first, first, sec)
+    rel = (ori - start) / (end - start)                                               # :507
+    inten = (sid.astype(np.float64) + 0.1 * rel.astype(np.float64)).astype(np.float32)   # :509
     vi = np.nonzero(valid)[0]
     und = undistort(p[vi], inten[vi], q_imu, q_lb)
     pts = np.concatenate([und, inten[vi, None]], 1)
-    order = np.argsort(sid[vi], kind="stable")                                        # laserCloudScans[scanID].push_back, concatenated (:519-526)
+    order = np.argsort(sid[vi], kind="stable")                                        # laserCloudScans[scanID].push_back, concatenated (:514, :522-526)
     cut = np.ascontiguousarray(pts[order])
     size = np.bincount(sid[vi], minlength=n_scans)[:n_scans]
     rstart = np.concatenate([[0], np.cumsum(size)[:-1]])
-    return cut, rstart, size, ns, sid
+    a, b = valid & in_first, valid & ~in_first                                        # the points whose comparisons decide an output
+    margin = min(_dist([span0], 3 * math.pi), _dist([span0], math.pi),
+                 _dist(o64[a], float(start) - math.pi / 2), _dist(o64[a], float(start) + math.pi * 3 / 2), _dist(turn[a], math.pi),
+                 _dist(s64[b], float(end) - math.pi * 3 / 2), _dist(s64[b], float(end) + math.pi / 2))
+    report = {"start": float(start), "end": float(end), "end_minus": bool(end_minus), "end_plus": bool(end_plus),
+              "n491": int((a & f_lo).sum()), "n493": int((a & f_hi).sum()), "n501": int((b & s_lo).sum()), "n503": int((b & s_hi).sum()),
+              "half_passed": bool(len(flip)), "half": int(half), "rel_min": float(rel[valid].min()) if len(vi) else math.nan,
+              "rel_max": float(rel[valid].max()) if len(vi) else math.nan, "margin": margin, "rel": rel[vi].copy(), "ring": sid[vi].copy()}
+    return (cut, rstart, size, ns, sid), report
+
+
+def project(raw, n_scans=32, q_imu=(1.0, 0, 0, 0), q_lb=(1.0, 0, 0, 0), min_range=3.0):
+    """Steps 1-3: survivors, startOri / endOri, scanID, orientation, relTime, intensity, undistortion, the stable ring bucketing (:396-526).
+    Returns (cut [n][4] float32, ring_start[n_scans], ring_size[n_scans], kept, ring of every survivor (-1 dropped))."""
+    return _project(raw, n_scans, q_imu, q_lb, min_range)[0]
+
+
+def orientation_report(raw, n_scans=32, min_range=3.0):
+    """What the orientation state machine (:401-410, :489-507) did on this scan, from the pass that project() is: end_minus / end_plus (:406 / :409
+    fired), n491 / n493 / n501 / n503 (valid points that took each adjustment), half_passed and the index of the survivor that set it (the number
+    of survivors if none did), rel_min / rel_max, start / end, rel and ring of every valid survivor in raw order, and margin: the smallest
+    distance in radians between a compared quantity and its constant -- endOri - startOri before its adjustment against 3 pi and pi, the raw ori
+    of every valid first-branch point against startOri - pi/2 and startOri + 3 pi/2 and its ori - startOri against pi, ori + 2 pi of every
+    valid second-branch point against endOri - 3 pi/2 and endOri + pi/2.  A scan whose margin is far above an ulp of atan2f (2.4e-7 near pi)
+    takes the same branches with any atan2f.  None for a scan without survivors."""
+    return _project(raw, n_scans, (1.0, 0, 0, 0), (1.0, 0, 0, 0), min_range)[1]
 
 
 def voxel_grid(pts, leaf):

@@ -9,6 +9,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import preproc_restated as pr  # noqa: E402
+from features_cases import _bits, _ctx, _intensity_close, _same, _yaw_q  # noqa: E402,F401
 
 from glio_amd import capi, features, synth, synth_lidar as sl  # noqa: E402
 from glio_amd import ctypes_types as T  # noqa: E402
@@ -16,37 +17,6 @@ from glio_amd import ctypes_types as T  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 OUTPUTS = [("sharp", T.FEAT_SHARP), ("less_sharp", T.FEAT_EDGE_LESS_SHARP), ("flat", T.FEAT_FLAT), ("surf", T.FEAT_SURF)]
-
-
-def _ctx(n_scans, max_raw=T.FEAT_MAX_RAW_POINTS):
-    ctx = capi.Context(synth.default_opts(1, pts=1 << 16, map_pts=1 << 16))
-    ctx.features_config(features.default_opts(n_scans, max_raw_points=max_raw))
-    return ctx
-
-
-def _yaw_q(yaw):
-    return np.array([math.cos(yaw / 2), 0.0, 0.0, math.sin(yaw / 2)])
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _intensity_close(a, b):
-    """intensity = scanID + 0.1 relTime within 2 float ulps taken at the scale of the ring's value (scanID + 0.1).  glibc's atan2f is not correctly
-    rounded and neither is the device's: one ulp of the orientation moves relTime by ~1e-8, which near relTime = 0 on ring 0 is many ulps of the tiny
-    intensity itself: the gate is 2 ulps of the ring's value or 2 ulps of an orientation near 4 pi carried through relTime, whichever is larger"""
-    scale = np.spacing((np.rint(b.astype(np.float64)) + 0.1).astype(np.float32)).astype(np.float64)
-    ori = 0.1 * float(np.spacing(np.float32(4 * math.pi))) / (2 * math.pi)        # one ulp of an orientation near 4 pi, through relTime
-    err = np.abs(a.astype(np.float64) - b.astype(np.float64))
-    tol = 2 * np.maximum(scale, ori)
-    i = int(np.argmax(err / tol))
-    print(f"intensity: max |d| {err.max():.3e}, worst d / tol {err[i] / tol[i]:.3f} at {i} ({b[i]!r})")
-    return bool((err <= tol).all())
-
-
-def _same(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
 
 
 @pytest.mark.parametrize("n_scans,yaw,stride", [(16, 0.0, 16), (16, 0.08, 32), (32, 0.0, 32), (32, 0.08, 16), (64, 0.0, 16), (64, 0.08, 32)])
