@@ -112,58 +112,8 @@ __global__ __launch_bounds__(64) void k_small_eval(const BtSel sel, const int n_
         //   NON-normalised inverse -- what the reference's Jets differentiate; global Jacobians, then Ceres' QuaternionParameterization.  Lane k = row k.
         nr = 6;
         if (lane < 6) {
-            const double* cst = rp_const + 7 * (size_t)fidx[f];
-            const double* q1 = pa + 3;
-            const double* q2 = pb + 3;
-            double A[4], u[4], Au[4], p[4], v[3];
-            fm_qdiff_products(cst, q1, q2, A, u, Au, p);
-            for (int k = 0; k < 3; ++k) v[k] = pb[k] - pa[k];
-            const int k = lane < 3 ? lane : lane - 3;
-            double Jg1[4], Jg2[4] = {0, 0, 0, 0}, Jp[3] = {0, 0, 0};        // this row's global Jacobians wrt q1, q2 and wrt p2 (= - wrt p1)
-            double G[4];                                                       // the row of d r / d u (u = q1^-1), before d u / d q1
-            double res;
-            if (lane < 3) {
-                double LA[16], Rv[16], LAu[16];
-                d_qleft(A, LA); d_qright(q2, Rv); d_qleft(Au, LAu);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) {
-                    double sM = 0;
-#pragma unroll
-                    for (int x = 0; x < 4; ++x) sM += (k == 0 ? LA[4 + x] : (k == 1 ? LA[8 + x] : LA[12 + x])) * Rv[x * 4 + m];
-                    G[m] = sM;
-                    Jg2[m] = 20.0 * (k == 0 ? LAu[4 + m] : (k == 1 ? LAu[8 + m] : LAu[12 + m]));
-                }
-                res = 20.0 * (k == 0 ? p[1] : (k == 1 ? p[2] : p[3]));
-            } else {
-                // M(u) v = v + 2 w (q x v) + 2 q x (q x v);  d/dw = 2 (q x v),  d/dq = -2 w [v]x + 2 ((q.v) I + q v^T - 2 v q^T);  d/dv = M(u)
-                const double w = u[0], qx = u[1], qy = u[2], qz = u[3];
-                const double cx = qy * v[2] - qz * v[1], cy = qz * v[0] - qx * v[2], cz = qx * v[1] - qy * v[0];          // q x v
-                const double ccx = qy * cz - qz * cy, ccy = qz * cx - qx * cz, ccz = qx * cy - qy * cx;                  // q x (q x v)
-                const double rv = k == 0 ? v[0] + 2.0 * w * cx + 2.0 * ccx : (k == 1 ? v[1] + 2.0 * w * cy + 2.0 * ccy : v[2] + 2.0 * w * cz + 2.0 * ccz);
-                res = 20.0 * (rv - cst[4 + k]);
-                const double qv = qx * v[0] + qy * v[1] + qz * v[2];
-                const double qk = k == 0 ? qx : (k == 1 ? qy : qz), vk = k == 0 ? v[0] : (k == 1 ? v[1] : v[2]);
-                const double qq[3] = {qx, qy, qz};
-                // row k of [v]x: (0, -v2, v1), (v2, 0, -v0), (-v1, v0, 0)
-                const double sv[3] = {k == 0 ? 0.0 : (k == 1 ? v[2] : -v[1]), k == 0 ? -v[2] : (k == 1 ? 0.0 : v[0]), k == 0 ? v[1] : (k == 1 ? -v[0] : 0.0)};
-                // row k of [q]x and of [q]x [q]x = q q^T - (q.q) I
-                const double sq[3] = {k == 0 ? 0.0 : (k == 1 ? qz : -qy), k == 0 ? -qz : (k == 1 ? 0.0 : qx), k == 0 ? qy : (k == 1 ? -qx : 0.0)};
-                const double q2n = qx * qx + qy * qy + qz * qz;
-                G[0] = 2.0 * (k == 0 ? cx : (k == 1 ? cy : cz));
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    G[1 + c] = -2.0 * w * sv[c] + 2.0 * ((k == c ? qv : 0.0) + qk * v[c] - 2.0 * vk * qq[c]);
-                    Jp[c] = 20.0 * ((k == c ? 1.0 : 0.0) + 2.0 * w * sq[c] + 2.0 * (qk * qq[c] - (k == c ? q2n : 0.0)));
-                }
-            }
-            fm_qinv_chain(G, q1, Jg1);
-#pragma unroll
-            for (int c = 0; c < 4; ++c) Jg1[c] = 20.0 * Jg1[c];
-            rr[lane] = res;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { Ja[lane * 6 + c] = -Jp[c]; Jb[lane * 6 + c] = Jp[c]; }
-            fm_quat_local(Jg1, q1, Ja + lane * 6 + 3);
-            fm_quat_local(Jg2, q2, Jb + lane * 6 + 3);
+            // rows 10 * 2 (..).vec and 20 (..): the one definition of the functor's rows, factor_math.h
+            fm_relative_pose_row(lane, 10.0, 20.0, rp_const + 7 * (size_t)fidx[f], pa, pb, rr[lane], Ja + lane * 6, Jb + lane * 6);
         }
     } else {
 #pragma clang fp contract(off)

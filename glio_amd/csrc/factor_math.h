@@ -152,3 +152,67 @@ __device__ __forceinline__ void fm_quat_local(const double Jg[4], const double q
 #pragma unroll
     for (int c = 0; c < 3; ++c) Jl[c] = Jg[0] * P[c] + Jg[1] * P[3 + c] + Jg[2] * P[6 + c] + Jg[3] * P[9 + c];
 }
+
+// ------------------------------------------------------------------------------------------------
+// Row `row` (0..5) of the relative-pose functor shared by LidarPoseFactorBatchRelativeAutoDiff (LidarPoseFactor.h:55-97, weights 10 and 20) and by
+// LidarPoseFactorAutoDiff / LidarPoseLeftFactorAutoDiff / LidarPoseRightFactorAutoDiff (:11-52, :128-221, both weights 0.2):
+//   r[0:3] = wq * 2 (dq^-1 q1^-1 q2).vec,  r[3:6] = wp (q1^-1 (p2 - p1) - dp),  Eigen's inverse() = conjugate / |q|^2 and Eigen's q * v on the
+//   NON-normalised inverse -- what the reference's Jets differentiate; global Jacobians, then Ceres' QuaternionParameterization.
+// cst = dq (w, x, y, z), dp; pa, pb = t, q (w first) of the two poses.  Ja, Jb: this row's six local columns (t, then the rotation) of either pose;
+// the left / right factors are this row with Ja / Jb dropped by the caller.  wq * 2 is an exact doubling, so 10 * (2 x) and 20 x give the same bits.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void fm_relative_pose_row(const int row, const double wq, const double wp, const double* cst, const double* pa, const double* pb,
+                                                     double& r, double* Ja, double* Jb) {
+    const double* q1 = pa + 3;
+    const double* q2 = pb + 3;
+    const double wt = row < 3 ? 2.0 * wq : wp;
+    double A[4], u[4], Au[4], p[4], v[3];
+    fm_qdiff_products(cst, q1, q2, A, u, Au, p);
+    for (int k = 0; k < 3; ++k) v[k] = pb[k] - pa[k];
+    const int k = row < 3 ? row : row - 3;
+    double Jg1[4], Jg2[4] = {0, 0, 0, 0}, Jp[3] = {0, 0, 0};        // this row's global Jacobians wrt q1, q2 and wrt p2 (= - wrt p1)
+    double G[4];                                                       // the row of d r / d u (u = q1^-1), before d u / d q1
+    double res;
+    if (row < 3) {
+        double LA[16], Rv[16], LAu[16];
+        d_qleft(A, LA); d_qright(q2, Rv); d_qleft(Au, LAu);
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            double sM = 0;
+#pragma unroll
+            for (int x = 0; x < 4; ++x) sM += (k == 0 ? LA[4 + x] : (k == 1 ? LA[8 + x] : LA[12 + x])) * Rv[x * 4 + m];
+            G[m] = sM;
+            Jg2[m] = wt * (k == 0 ? LAu[4 + m] : (k == 1 ? LAu[8 + m] : LAu[12 + m]));
+        }
+        res = wt * (k == 0 ? p[1] : (k == 1 ? p[2] : p[3]));
+    } else {
+        // M(u) v = v + 2 w (q x v) + 2 q x (q x v);  d/dw = 2 (q x v),  d/dq = -2 w [v]x + 2 ((q.v) I + q v^T - 2 v q^T);  d/dv = M(u)
+        const double w = u[0], qx = u[1], qy = u[2], qz = u[3];
+        const double cx = qy * v[2] - qz * v[1], cy = qz * v[0] - qx * v[2], cz = qx * v[1] - qy * v[0];          // q x v
+        const double ccx = qy * cz - qz * cy, ccy = qz * cx - qx * cz, ccz = qx * cy - qy * cx;                  // q x (q x v)
+        const double rv = k == 0 ? v[0] + 2.0 * w * cx + 2.0 * ccx : (k == 1 ? v[1] + 2.0 * w * cy + 2.0 * ccy : v[2] + 2.0 * w * cz + 2.0 * ccz);
+        res = wt * (rv - cst[4 + k]);
+        const double qv = qx * v[0] + qy * v[1] + qz * v[2];
+        const double qk = k == 0 ? qx : (k == 1 ? qy : qz), vk = k == 0 ? v[0] : (k == 1 ? v[1] : v[2]);
+        const double qq[3] = {qx, qy, qz};
+        // row k of [v]x: (0, -v2, v1), (v2, 0, -v0), (-v1, v0, 0)
+        const double sv[3] = {k == 0 ? 0.0 : (k == 1 ? v[2] : -v[1]), k == 0 ? -v[2] : (k == 1 ? 0.0 : v[0]), k == 0 ? v[1] : (k == 1 ? -v[0] : 0.0)};
+        // row k of [q]x and of [q]x [q]x = q q^T - (q.q) I
+        const double sq[3] = {k == 0 ? 0.0 : (k == 1 ? qz : -qy), k == 0 ? -qz : (k == 1 ? 0.0 : qx), k == 0 ? qy : (k == 1 ? -qx : 0.0)};
+        const double q2n = qx * qx + qy * qy + qz * qz;
+        G[0] = 2.0 * (k == 0 ? cx : (k == 1 ? cy : cz));
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            G[1 + c] = -2.0 * w * sv[c] + 2.0 * ((k == c ? qv : 0.0) + qk * v[c] - 2.0 * vk * qq[c]);
+            Jp[c] = wt * ((k == c ? 1.0 : 0.0) + 2.0 * w * sq[c] + 2.0 * (qk * qq[c] - (k == c ? q2n : 0.0)));
+        }
+    }
+    fm_qinv_chain(G, q1, Jg1);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) Jg1[c] = wt * Jg1[c];
+    r = res;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { Ja[c] = -Jp[c]; Jb[c] = Jp[c]; }
+    fm_quat_local(Jg1, q1, Ja + 3);
+    fm_quat_local(Jg2, q2, Jb + 3);
+}

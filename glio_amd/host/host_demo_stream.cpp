@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <thread>
 #include <vector>
 
@@ -17,6 +18,7 @@
 
 #include "glio_backend.hpp"
 #include "glio_batch_backend.hpp"
+#include "glio_trajectory_backend.hpp"
 
 template <typename T> static void rd(FILE* f, T* p, size_t n) { if (n && fread(p, sizeof(T), n, f) != n) { fprintf(stderr, "short read\n"); exit(2); } }
 static double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -99,6 +101,9 @@ int main(int argc, char** argv) {
         // surfDSRange: 0.9 in config_urban_hk.yaml) runs on the device on their way into the window (setScanFiltered / setScanFilteredAhead) -- what a drop-in
         // Estimator does per keyframe instead of its pcl::VoxelGrid + setScan.  Default: the clouds go in as they are.
         float filter_leaf = 0.f;
+        // traj=1 (opt-in; scripts/trajectory_timing.py): one gap of the every-frame trajectory (3 in-between frames, 44 sample rows) is pushed per keyframe call
+        // right after the solve, on the trajectory's own stream (glio_traj_push_gap), and read after the loop.  Default: no trajectory object exists.
+        bool traj_gap = false;
         std::vector<uint64_t> table;
         size_t table_k = 0;
         for (int a = 5; a < argc; ++a) {
@@ -111,6 +116,7 @@ int main(int argc, char** argv) {
             else if (!strncmp(argv[a], "map_ahead=", 10)) map_ahead = atoi(argv[a] + 10) != 0;
             else if (!strncmp(argv[a], "map_rebuild=", 12)) map_rebuild = atoi(argv[a] + 12) != 0;
             else if (!strncmp(argv[a], "filter=", 7)) filter_leaf = (float)atof(argv[a] + 7);
+            else if (!strncmp(argv[a], "traj=", 5)) traj_gap = atoi(argv[a] + 5) != 0;
             else if (!strncmp(argv[a], "sleep_ms=", 9)) sleep_ms = atoi(argv[a] + 9);
             else if (!strncmp(argv[a], "sleep_at=", 9)) sleep_at = atoi(argv[a] + 9);
             else if (!strncmp(argv[a], "draws=", 6)) {
@@ -123,6 +129,25 @@ int main(int argc, char** argv) {
         if (timed_last < 1 || timed_last > NK) timed_last = NK;
         if (filter_leaf > 0.f) be.configureScanFilter(pts);
         if (map_rebuild && (defer || map_ahead)) { fprintf(stderr, "map_rebuild=1 goes with neither defer=1 nor map_ahead=1\n"); return 2; }
+        std::unique_ptr<glio::TrajectoryStore> tstore;
+        glio::FrameSegments tseg;
+        if (traj_gap) {
+            glio_traj_opts to;
+            glio_traj_opts_default(&to);
+            to.max_gaps = NK + 1;
+            tstore.reset(new glio::TrajectoryStore(&to, device));
+            tseg.seg_offset.push_back(0);
+            for (int sgm = 0; sgm < 4; ++sgm) {
+                for (int r = 0; r < 11; ++r) {
+                    glio_imu_sample x;
+                    x.dt = r == 0 ? 0.0 : 0.005;
+                    x.acc[0] = 0.1 * ((r + sgm) % 3); x.acc[1] = -0.05 * (r % 2); x.acc[2] = 9.805;
+                    x.gyr[0] = 0.01 * (r % 4); x.gyr[1] = -0.02; x.gyr[2] = 0.05;
+                    tseg.samples.push_back(x);
+                }
+                tseg.seg_offset.push_back((int32_t)tseg.samples.size());
+            }
+        }
         std::mt19937_64 rng(20260925);
         auto rand_u64 = [&]() -> uint64_t { return table.empty() ? (uint64_t)rng() : table[table_k++ % table.size()]; };
         auto rand_below = [&](uint64_t n) -> uint64_t {
@@ -196,6 +221,13 @@ int main(int argc, char** argv) {
                 for (int c = 0; c < 3; ++c) kf_poses[7 * (size_t)g + c] = be.tmpTrans[3 * s + c];
                 for (int c = 0; c < 4; ++c) kf_poses[7 * (size_t)g + 3 + c] = be.tmpQuat[4 * s + c];
             }
+            if (traj_gap) {          // the gap between the two oldest keyframes of the window, from the pose table the solve just left
+                const double* L = &kf_poses[7 * (size_t)j];
+                const double* Rr = &kf_poses[7 * (size_t)(j + 1)];
+                double st15[15] = {L[0], L[1], L[2], (Rr[0] - L[0]) / 0.2, (Rr[1] - L[1]) / 0.2, (Rr[2] - L[2]) / 0.2, 1, 0, 0, 0, 1, 0, 0, 0, 1};
+                const double grav[3] = {0, 0, 9.805};
+                tstore->pushGap(j, 3, tseg, st15, grav, L, L, Rr);
+            }
             std::vector<int64_t> found;
             double slept2 = 0;
             if (sleep_ms > 0 && sleep_at == 2) { const double ts = now_s(); std::this_thread::sleep_for(std::chrono::milliseconds(sleep_ms)); slept2 = now_s() - ts; }
@@ -254,6 +286,14 @@ int main(int argc, char** argv) {
         //  the warm-up keyframe included)
         printf("]");
         if (filter_leaf > 0.f) printf(", \"scan_filter_leaf\": %.9g", (double)filter_leaf);          // (only with filter=: the default line is what it was)
+        if (traj_gap) {
+            glio_traj_summary ts;
+            tstore->readSolved(NK, &ts);
+            float tms = 0.f;
+            glio_traj_last_device_ms(tstore->handle(), &tms);
+            printf(", \"trajectory_gap_per_call\": true, \"trajectory_last_gap\": {\"frames\": %d, \"termination\": %d, \"iterations\": %d, \"device_ms\": %.5f}", ts.n_frames, ts.termination,
+                   ts.iterations, (double)tms);
+        }
         printf(", \"steps_with_the_helpers_build\": %lld, \"iterations_booked\": %ld, \"trans_checksum\": %.17g}\n", stamps[300], total_iters, checksum);
     } catch (const std::exception& e) {
         fprintf(stderr, "error: %s\n", e.what());

@@ -133,7 +133,8 @@ DEMO_STREAM = os.path.join(HERE, "host_demo_stream")
 
 def build_demo_stream(force=False):
     """The C++ moving-stream keyframe cycle (host_demo_stream.cpp): what bench.py times as keyframe_pipeline_cpp."""
-    src = [os.path.join(HERE, "host_demo_stream.cpp"), os.path.join(HERE, "glio_backend.hpp"), os.path.join(HERE, "glio_batch_backend.hpp")] + _ABI_HEADERS
+    src = [os.path.join(HERE, "host_demo_stream.cpp"), os.path.join(HERE, "glio_backend.hpp"), os.path.join(HERE, "glio_batch_backend.hpp"),
+           os.path.join(HERE, "glio_trajectory_backend.hpp"), os.path.join(HERE, "..", "..", "include", "glio_traj.h")] + _ABI_HEADERS
     if force or not os.path.exists(DEMO_STREAM) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_STREAM) for s in src):
         subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
                                "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_STREAM])
@@ -170,8 +171,8 @@ def write_stream(path, long, wins, W, n_keyframes, pts, lm_width=50, leaf=0.4, b
                 f.write(bytes(d))
 
 
-def run_demo_stream(path, device=0, env=None, search_range=6, defer=False, feature_res_num=0, draws=None, timed=None, per_slot=False, sleep_ms=0, sleep_at=0, stream_draws=True, prepare_early=True, ahead=False, map_ahead=False, map_rebuild=False, filter=None):
-    """filter=LEAF: the stream's clouds are filtered on the device on their way into the window (setScanFiltered*; opt-in);
+def run_demo_stream(path, device=0, env=None, search_range=6, defer=False, feature_res_num=0, draws=None, timed=None, per_slot=False, sleep_ms=0, sleep_at=0, stream_draws=True, prepare_early=True, ahead=False, map_ahead=False, map_rebuild=False, filter=None, traj=False):
+    """traj: a gap of the every-frame trajectory is pushed per keyframe call (opt-in); filter=LEAF: the stream's clouds are filtered on the device on their way into the window (setScanFiltered*; opt-in);
     feature_res_num > 0: featureSelection behind every slot's search (Estimator.cpp:2223); draws: file of uint64 both hosts draw from (sliding.TableRng);
     timed: only the last `timed` keyframes enter the time averages"""
     import json
@@ -197,6 +198,8 @@ def run_demo_stream(path, device=0, env=None, search_range=6, defer=False, featu
         cmd.append("map_rebuild=1")
     if filter:
         cmd.append(f"filter={float(filter)!r}")
+    if traj:
+        cmd.append("traj=1")
     r = subprocess.run(cmd, capture_output=True, text=True, env=env)
     if r.returncode != 0:
         raise RuntimeError("host_demo_stream failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
@@ -510,3 +513,56 @@ def run_demo_pose_graph(path, device=0, env=None, damped=False, keep_stdout=Fals
         out["history"] = np.array(hist, np.float64).reshape(-1, 4)
     out.update(poses=np.array(poses), calls=calls)
     return out
+
+
+DEMO_TRAJECTORY = os.path.join(HERE, "host_demo_trajectory")
+
+
+def build_demo_trajectory(force=False):
+    """The C++ every-frame trajectory (host_demo_trajectory.cpp over glio::Trajectory, glio_trajectory_backend.hpp, into glio::GlobalGraph)."""
+    src = [os.path.join(HERE, "host_demo_trajectory.cpp"), os.path.join(HERE, "glio_trajectory_backend.hpp"), os.path.join(HERE, "glio_posegraph_backend.hpp"),
+           os.path.join(HERE, "..", "..", "include", "glio_traj.h")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_TRAJECTORY) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_TRAJECTORY) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_TRAJECTORY])
+    return DEMO_TRAJECTORY
+
+
+def write_trajectory_case(path, imu, frame_stamps, keyframe_id_in_frame, imu_idx_in_kf, W, keyframe_poses, start_states, corrected):
+    """int32 n_imu F NK W 0 0 0 0 | imu [n_imu][7] = stamp, acc, gyr | frame_stamps [F] | keyframe_id_in_frame [NK] int32, padded to a multiple of 2 |
+    imu_idx_in_kf [NK] int32, padded | keyframe_poses [NK][7] | start_states [NK][15] | corrected [NK][7]"""
+    imu = np.ascontiguousarray(imu, np.float64).reshape(-1, 7)
+    fs = np.ascontiguousarray(frame_stamps, np.float64)
+    kf = np.ascontiguousarray(keyframe_id_in_frame, np.int32)
+    idx = np.ascontiguousarray(imu_idx_in_kf, np.int32)
+    pad = b"\0\0\0\0" if len(kf) & 1 else b""
+    with open(path, "wb") as f:
+        f.write(np.array([len(imu), len(fs), len(kf), W, 0, 0, 0, 0], np.int32).tobytes())
+        f.write(imu.tobytes()); f.write(fs.tobytes())
+        f.write(kf.tobytes() + pad); f.write(idx.tobytes() + pad)
+        f.write(np.ascontiguousarray(keyframe_poses, np.float64).reshape(len(kf), 7).tobytes())
+        f.write(np.ascontiguousarray(start_states, np.float64).reshape(len(kf), 15).tobytes())
+        f.write(np.ascontiguousarray(corrected, np.float64).reshape(len(kf), 7).tobytes())
+
+
+def run_demo_trajectory(path, device=0, env=None):
+    """-> dict(frames [F][7], nodes [n][7], resolved [F][7], calls [(n, gap, n_frames, termination, iterations)], graph [(n, first, last)],
+    resolves [(termination, iterations)])"""
+    r = subprocess.run([build_demo_trajectory(), path, str(device)], capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError("host_demo_trajectory failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
+    rows = {"frame": [], "node": [], "resolved": []}
+    calls, graph, resolves = [], [], []
+    for ln in r.stdout.splitlines():
+        w = ln.split()
+        if not w:
+            continue
+        if w[0] in rows:
+            rows[w[0]].append([float.fromhex(x) for x in w[2:9]])
+        elif w[0] == "call":
+            calls.append((int(w[1]), int(w[3]), int(w[5]), int(w[7]), int(w[9])))
+        elif w[0] == "graph":
+            graph.append((int(w[1]), int(w[3]), int(w[5])))
+        elif w[0] == "resolve":
+            resolves.append((int(w[3]), int(w[5])))
+    return dict(frames=np.array(rows["frame"]), nodes=np.array(rows["node"]), resolved=np.array(rows["resolved"]), calls=calls, graph=graph, resolves=resolves)
