@@ -1171,12 +1171,13 @@ extern "C++" void glio_lds_poison_stream(hipStream_t stream) {       // also cal
 static void lds_poison(glio_ctx* c) { glio_lds_poison_stream(c->stream); }
 // `dense`: also gather the blocks into the dense H, g (k_assemble).  The solve on the keyframe-chain path does not need it
 // (k_chain_step reads the factor blocks); glio_linearize and the other solver paths do.
-static void enqueue_linearize(glio_ctx* c, int use_status, int which, int n_ddt, int dense = 1) {
+// `first`: glio_launch_linearize_all's first mode (the opening group of a solve; enqueue_solve decides when it applies)
+static void enqueue_linearize(glio_ctx* c, int use_status, int which, int n_ddt, int dense = 1, int first = 0) {
     if (c->chain_tabs_dirty) glio_chain_tabs_upload(c);      // gather tables + zeroed slices, ahead of the factor kernels that fill them
     c->want_pair_H = dense;
     lds_poison(c);
     if (c->merged_linearize) {
-        glio_launch_linearize_all(c, use_status, which, n_ddt);
+        glio_launch_linearize_all(c, use_status, which, n_ddt, first);
         if (dense) glio_launch_assemble(c, use_status, which, n_ddt, dense == 2);
         return;
     }
@@ -1200,8 +1201,17 @@ static int enqueue_solve(glio_ctx* c, int n_ddt) {
     c->solve_id = c->solve_id % 30000 + 1;          // kernels of the previous solve's look-ahead group may still be draining:
     st.solve_id = c->solve_id;                      // their progress words carry the old tag and are ignored
     *c->h_status = st;
-    hipLaunchKernelGGL(k_stage_in, dim3(1), dim3(1024), 0, c->stream, reinterpret_cast<unsigned long long*>(c->d_status),
-                       reinterpret_cast<const unsigned long long*>(c->d_h_status), 64 + nx);                              // status + state
+    // Keyframe-chain solves with the merged linearisation have no staging launch (~4.7 us with its launch boundary): the first k_linearize_all reads the
+    // state from the mapped block itself and one of its workgroups leaves [status | state] in device memory for the step that follows in the stream.
+    // The mapped block is safe to read for as long as that launch can run: the host rewrites h_status / h_xbuf only in an entry point's pack_state and in
+    // glio_solve's reader, i.e. after the tag of a solve has arrived (published by a LATER launch of this stream) or after a stream synchronisation
+    // (glio_time_solve, the error paths below); the max_solver_time_s stop touches h_progress only.  No tag is compared on the device: the record is the
+    // one written two lines up, and the buffer to linearise is fixed by construction (cur = 1, candidate 0 pending), so the ids' wrap has nothing to fool.
+    const int dense = glio_chain_kind(c, n_ddt) == 3 ? 2 : glio_solver_needs_dense_H(c, n_ddt);      // (2: the band k_chain_solve<true> reads is enough)
+    const bool first_mapped = (glio_solve_ends_mask() & 2) && c->merged_linearize && dense == 0 && c->n_imu + c->n_groups + (c->prior_n > 0 ? 1 : 0) > 0;
+    if (!first_mapped)
+        hipLaunchKernelGGL(k_stage_in, dim3(1), dim3(1024), 0, c->stream, reinterpret_cast<unsigned long long*>(c->d_status),
+                           reinterpret_cast<const unsigned long long*>(c->d_h_status), 64 + nx);                          // status + state
     // The trust-region loop lives on the device (SolverStatus); the host only feeds it kernel groups
     // [linearise, step].  Instead of queueing all max_iterations+1 groups blindly -- after convergence the rest are
     // empty launches, ~2.5 us each -- it enqueues group k + 1 when k_tr_prepare of group k reports (through a progress word in
@@ -1215,7 +1225,6 @@ static int enqueue_solve(glio_ctx* c, int n_ddt) {
     const int lead = c->enqueue_lead < 1 ? total : c->enqueue_lead;
     const auto t_start = c->solve_t0;
     int enq = 0, spins = 0;
-    const int dense = glio_chain_kind(c, n_ddt) == 3 ? 2 : glio_solver_needs_dense_H(c, n_ddt);      // (2: the band k_chain_solve<true> reads is enough)
     // options.max_solver_time_in_seconds: when the budget is spent the host raises the stop word; the state machine of the next
     // group sees it and ends the solve.  One more group is fed regardless of the look-ahead rule so that such a state machine runs.
     const bool timed = c->opts.max_solver_time_s > 0.0;
@@ -1229,12 +1238,13 @@ static int enqueue_solve(glio_ctx* c, int n_ddt) {
         }
         if (enq - started() < lead || extra_group) {
             extra_group = false;
-            enqueue_linearize(c, 1, 0, n_ddt, dense);
+            enqueue_linearize(c, 1, 0, n_ddt, dense, first_mapped && enq == 0);
             lds_poison(c);
             glio_launch_tr_step(c, n_ddt);
             ++enq;
         } else if (((++spins) & 0xfff) == 0 && std::chrono::steady_clock::now() - t_start > std::chrono::seconds(20)) {
             glio_set_error("solver made no progress for 20 s (group %d of %d)", started(), total);
+            hipStreamSynchronize(c->stream);      // (nothing queued may still read the mapped block when the caller goes on)
             return GLIO_E_HIP;
         }
     }
@@ -1560,6 +1570,12 @@ int glio_debug_set_merged_linearize(glio_ctx* c, int on) { if (!c) return GLIO_E
 int glio_debug_set_enqueue_lead(glio_ctx* c, int lead) {
     if (!c || lead < 0) return GLIO_E_ARG;
     c->enqueue_lead = lead;
+    return GLIO_OK;
+}
+// test hook: the tag the NEXT solve derives its own from (they wrap at 30000)
+int glio_debug_set_solve_id(glio_ctx* c, int id) {
+    if (!c || id < 0 || id > 30000) return GLIO_E_ARG;
+    c->solve_id = id;
     return GLIO_OK;
 }
 int glio_debug_solver_path(glio_ctx* c) { return c ? c->arrow.last_path : -1; }

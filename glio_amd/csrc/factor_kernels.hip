@@ -740,6 +740,9 @@ __device__ void small_factors_body(const SmallArgs& a, const int role) {
 struct K3Args {
     const float4* pts; const float4* planes; const double* scores; const int* count; int cap;
     LidarConst lc; double* partials; size_t pstride; int n_small, nb, skip_lo, skip_hi, n_k3;
+    // the first group of a solve (first_words > 0): every workgroup reads the state from the mapped host copy (SmallArgs::x0 points there, no status
+    // check), and workgroup first_wg -- an idle one where there is one -- leaves [status | state] in device memory for the launches that follow
+    const unsigned long long* first_src; unsigned long long* first_dst; int first_words, first_wg;
 };
 template <bool F32>
 __global__ __launch_bounds__(SF_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_linearize_all(const SmallArgs a, const K3Args k) {
@@ -767,6 +770,9 @@ __global__ __launch_bounds__(SF_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     if (a.use_status) {
         if (a.st->done || !a.st->cand_pending) return;
         which = 1 - a.st->cur;
+    }
+    if (k.first_words > 0 && b == k.first_wg) {      // (what k_stage_in did in a launch of its own; nobody in THIS launch reads the destination)
+        for (int w = threadIdx.x; w < k.first_words; w += SF_THREADS) k.first_dst[w] = __builtin_nontemporal_load(k.first_src + w);
     }
     // workgroups [skip_lo, skip_hi) stay idle: in dispatch order they would land in the second slot of the CUs that run the
     // small-factor workgroups and slow those (the launch's long pole) down
@@ -1134,10 +1140,13 @@ void glio_launch_small_factors(glio_ctx* c, int use_status_cand, int which, int 
 }
 // K3 + small factors in one launch.  Two workgroups fit a CU (register file and LDS of the small-factor roles): the K3 share
 // of the grid is what is left of 2 x 256 slots after the small-factor workgroups, so that everything is resident at once.
-void glio_launch_linearize_all(glio_ctx* c, int use_status_cand, int which, int n_ddt) {
+// `first`: the launch opens a solve whose status record and initial state still sit in the mapped host block (capi.hip, enqueue_solve): the record is
+// what the host has just written (candidate buffer 0 pending), so the buffer is fixed and the state is read from the host copy.  Needs n_small > 0.
+void glio_launch_linearize_all(glio_ctx* c, int use_status_cand, int which, int n_ddt, int first) {
     SmallArgs a;
-    const int n_small = fill_small_args(c, use_status_cand, which, n_ddt, 0, a);
+    const int n_small = fill_small_args(c, first ? 0 : use_status_cand, first ? 0 : which, n_ddt, 0, a);
     if (n_small == 0) { glio_launch_lidar_linearize(c, use_status_cand, which); return; }
+    if (first) a.x0 = reinterpret_cast<const double*>(static_cast<const unsigned char*>(c->d_h_status) + 512);
     K3Args k;
     k.pts = c->d_pts; k.planes = c->d_planes; k.scores = c->d_scores; k.count = c->d_count; k.cap = c->cap;
     k.lc = glio_lidar_const(c); k.partials = c->d_lidar_partials; k.pstride = glio_partials_stride(c); k.n_small = n_small;
@@ -1159,6 +1168,10 @@ void glio_launch_linearize_all(glio_ctx* c, int use_status_cand, int which, int 
     k.nb = nb; k.n_k3 = c->W * nb;
     k.skip_lo = skip ? 256 : 0; k.skip_hi = skip ? 256 + n_small : 0;
     c->last_k3_nb = nb;
+    const int grid = n_small + k.n_k3 + (k.skip_hi - k.skip_lo);
+    k.first_src = reinterpret_cast<const unsigned long long*>(c->d_h_status); k.first_dst = reinterpret_cast<unsigned long long*>(c->d_status);
+    k.first_words = first ? 64 + glio_x_size(c->W, n_ddt) : 0;
+    k.first_wg = (skip && grid > k.skip_lo) ? k.skip_lo : grid - 1;      // (n_small <= 128 < skip_lo with `skip`; the last workgroup is a K3 one)
     if (c->opts.lidar_precision == GLIO_LIDAR_F32_MFMA) {
         glio_lidar_pack_f32(c);
         k.pts = c->d_pts_s;

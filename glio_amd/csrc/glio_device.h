@@ -219,7 +219,7 @@ struct glio_ctx {
                                   // one vector would otherwise also cache the head of the next, which the same kernel may rewrite)
     SolverStatus* d_status;
     SolverStatus* h_status;       // pinned
-    void* d_h_status;             // its device address: k_stage_in pulls status + initial state from it (no blit, no barrier packet behind it)
+    void* d_h_status;             // its device address: the first linearisation of a solve (or k_stage_in) pulls status + initial state from it (no blit, no barrier packet behind it)
     volatile int* h_progress;     // pinned + mapped: [0] (solve id << 16) | groups started, [1] id of the solve that is done -- written by the GPU, polled by the host; [2] written by the HOST, read by the GPU: id of the solve whose time budget is spent
     unsigned char* h_result; unsigned char* d_result;   // pinned + mapped: [SolverStatus | pad to 512 B | final state]: the last kernel of a solve
                                                         // publishes its result here, glio_solve reads it without a copy or a stream sync
@@ -498,7 +498,8 @@ void glio_launch_lidar_linearize(glio_ctx* c, int use_status_cand, int which, in
 void glio_lidar_pack_f32(glio_ctx* c);                      // no-op unless the f32 form is selected and the correspondences changed
 // factor_kernels.hip
 void glio_launch_small_factors(glio_ctx* c, int use_status_cand, int which, int n_ddt, int marg = 0);
-void glio_launch_linearize_all(glio_ctx* c, int use_status_cand, int which, int n_ddt);   // K3 + small factors, one launch
+void glio_launch_linearize_all(glio_ctx* c, int use_status_cand, int which, int n_ddt, int first = 0);   // K3 + small factors, one launch (first: factor_kernels.hip)
+int glio_solve_ends_mask();   // lab switch GLIO_SOLVE_ENDS / glio_debug_solve_ends (solver_kernels.hip)
 void glio_launch_lidar_reduce(glio_ctx* c, int which);      // K3 partials -> d_lidar_blocks (the marginalization's assembly reads the blocks)
 void glio_launch_assemble(glio_ctx* c, int use_status_cand, int which, int n_ddt, int band = 0);      // band: the block-tridiagonal part + epoch columns only
 int glio_chain_kind(const glio_ctx* c, int n_ddt);

@@ -495,6 +495,35 @@ __device__ __forceinline__ void finalize(const TrArgs& a, const SolverStatus& s)
     }
 }
 
+// finalize() for the caller that holds everything in LDS (k_chain_step's state machine, PrepMirror::fin_lds): the same payload, checksum and tag,
+// without the two round trips to global memory for the state.  xl: the current point in LDS; s lives in LDS as well, so the first wavefront
+// takes the record one word per lane -- the checksum is a sum of 64-bit integers and does not care who adds what -- and each lane stores the
+// word it mixed.  The stores to host memory go out first: they have the longer way.
+__device__ __forceinline__ void finalize_lds(const TrArgs& a, const SolverStatus& s, const double* xl) {
+    constexpr int NS = (int)(sizeof(SolverStatus) / 8), CW = (int)(offsetof(SolverStatus, checksum) / 8);
+    static_assert(NS <= 64 && offsetof(SolverStatus, checksum) % 8 == 0, "one status word per lane of the first wavefront");
+    const int tid = threadIdx.x, nx = 16 * a.W + a.n_ddt;
+    for (int k = tid; k < nx; k += blockDim.x) { const double v = xl[k]; a.xout_host[k] = v; a.xout[k] = v; }
+    if (tid < 64) {
+        unsigned long long part = 0, w = 0;
+        for (int k = tid; k < nx; k += 64) part += glio_result_mix((unsigned long long)__double_as_longlong(xl[k]), 64ull + (unsigned long long)k);
+        if (tid < NS) {
+            w = tid == CW ? 0ull : reinterpret_cast<const unsigned long long*>(&s)[tid];
+            part += glio_result_mix(w, (unsigned long long)tid);
+        }
+        for (int off = 32; off > 0; off >>= 1) {
+            const unsigned lo = __shfl_xor((unsigned)(part & 0xffffffffull), off, 64), hi = __shfl_xor((unsigned)(part >> 32), off, 64);
+            part += ((unsigned long long)hi << 32) | lo;
+        }
+        if (tid < NS) {
+            if (tid == CW) w = part;
+            reinterpret_cast<unsigned long long*>(a.status_host)[tid] = w;
+            reinterpret_cast<unsigned long long*>(a.status)[tid] = w;
+        }
+        if (tid == 0) __hip_atomic_store(a.progress + 1, s.solve_id, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // K7a  k_tr_prepare
 // ------------------------------------------------------------------------------------------------
@@ -517,6 +546,7 @@ struct PrepMirror {
     // requested at entry and checked before that store; *hprod is cleared when one of them had nothing to produce
     const int* hdone; int hseq; int helpers; int* hprod; int hpolls;
     int* hfat;                                                 // cleared when a helper did not deliver the fat products (bit 1 of its word)
+    int fin_lds;                                               // a solve that ends here is published from the mirrors (finalize_lds)
 };
 #ifdef GLIO_DEV_STAMPS
 #define PM_STAMP(k) do { if (FAST && m->dbg && threadIdx.x == 0) m->dbg[k] = wall_clock64(); } while (0)
@@ -609,7 +639,7 @@ __device__ __forceinline__ bool tr_prepare_body(const TrArgs& a, TrDecision* out
         if (tid == 0) s.cand_pending = 0;
         PB_SYNC();
     }
-    if (s.done) { finalize(a, s); return false; }
+    if (s.done) { if (FAST && m->fin_lds) finalize_lds(a, s, s.cur ? m->x1 : m->x0); else finalize(a, s); return false; }
     PM_STAMP(82);
 
     const double* H = s.cur ? a.H1 : a.H0;
@@ -653,7 +683,7 @@ __device__ __forceinline__ bool tr_prepare_body(const TrArgs& a, TrDecision* out
         else s.iteration += 1;
     }
     PB_SYNC();
-    if (s.done) { finalize(a, s); return false; }
+    if (s.done) { if (FAST && m->fin_lds) finalize_lds(a, s, s.cur ? m->x1 : m->x0); else finalize(a, s); return false; }
     // The solve goes on: only now is the host told to enqueue the next kernel group (it then has this whole step, ~70 us,
     // to do so).  Announcing the group at its start instead made the host queue one group beyond the last useful one
     // every time: ~9 empty launches (~20 us) between back-to-back solves.
@@ -3309,7 +3339,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
     if (ff) {
         PrepMirror pm;
         pm.st_in = &s_in; pm.x0 = xm0; pm.x1 = xm1; pm.hd = sHd; pm.g = sG; pm.cost = sCost; pm.scale = sS; pm.diag = sDg; pm.grad = sGr; pm.dbg = a.dbg;
-        pm.hdone = a.hdone; pm.hseq = a.hseq; pm.helpers = a.helpers; pm.hprod = &s_hprod; pm.hpolls = a.hpolls; pm.hfat = &s_hfat;
+        pm.hdone = a.hdone; pm.hseq = a.hseq; pm.helpers = a.helpers; pm.hprod = &s_hprod; pm.hpolls = a.hpolls; pm.hfat = &s_hfat; pm.fin_lds = (a.fast & 4) != 0;
         if (!tr_prepare_body<true>(tr, &dec, &pm)) return;
     } else if (!tr_prepare_body(tr, &dec)) return;
     AR_STAMP(43);
@@ -3869,6 +3899,16 @@ static int chain_fast_mask() {
     return g_chain_fast;
 }
 
+// GLIO_SOLVE_ENDS (bit 1: the first group of glio_solve reads status and state from the mapped host copy, no k_stage_in launch; bit 2: a solve that ends
+// in k_chain_step's state machine is published from LDS, finalize_lds; default both).  0 = the staging launch and finalize(): the A/B switch of
+// tests/test_hip_solve_ends.py.  (Bit 0 is not in use.)
+static int g_solve_ends = -1;
+int glio_solve_ends_mask() {
+    if (g_solve_ends < 0) { const char* e = getenv("GLIO_SOLVE_ENDS"); g_solve_ends = e ? atoi(e) & 6 : 6; }
+    return g_solve_ends;
+}
+extern "C" int glio_debug_solve_ends(int mask) { const int old = glio_solve_ends_mask(); g_solve_ends = mask & 6; return old; }
+
 // test hook (CPU-callable: host arithmetic only): where the four-front panels of k_chain_step would live for a window of W keyframes and nd clock-drift
 // epochs.  out = {regular dynamic LDS bytes, off_dds, bytes available at off_dds (the clock-drift copy), k0 (E slots placed there), off_r1, total bytes,
 // E slots in all, 1 if the launch would take four fronts}
@@ -3934,6 +3974,7 @@ void glio_launch_tr_step(glio_ctx* c, int n_ddt) {
         r.W = c->W; r.n = a.n; r.nd = n_ddt; r.ep_slots = c->arrow.d_ep_slots; r.ep_off = c->arrow.d_ep_off; r.ep_list = c->arrow.d_ep_list;
         r.z = c->arrow.d_z; r.flag = c->arrow.d_flag; r.status = c->d_status; r.dbg = c->arrow.d_dbg; r.force_fail = c->arrow.mode == 2; r.fast = chain_fast_mask(); r.blk = nullptr; r.helpers = 0; r.hseq = 0; r.hsum = nullptr; r.hdone = nullptr; r.hpolls = 0; r.fat = 0; r.fat_blk = nullptr; r.fat_ep = nullptr;
         if (chain_step_lds_bytes(c->W, n_ddt, a.n, true) + 2 * 1024 > 158 * 1024) r.fast = 0;      // no room for the LDS mirrors: generic bodies
+        if ((r.fast & 2) && (glio_solve_ends_mask() & 4)) r.fast |= 4;                            // (bit 2: finalize_lds)
         size_t lds_step = chain_step_lds_bytes(c->W, n_ddt, a.n, r.fast != 0);
         {   // separator + four fronts when the window is long enough for it to pay and its panels fit (chain_f4_layout)
             const ChainF4Layout L = chain_f4_layout(c->W, n_ddt, a.n, r.fast != 0);
