@@ -24,6 +24,16 @@ class GlioError(RuntimeError):
 
 
 E_ARG, E_HIP, E_STATE = -1, -2, -3
+E_NUMERIC = -4
+
+
+class GlioCovInfo(C.Structure):
+    """glio_cov_info (include/glio_cov.h)"""
+    _fields_ = [("n", C.c_int32), ("n_free", C.c_int32), ("n_free_asked", C.c_int32), ("bad_pivot", C.c_int32),
+                ("min_pivot", C.c_double), ("max_pivot", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 def load():
@@ -416,6 +426,45 @@ class Context:
         cs = state.c()
         _check(load().glio_linearize(self._h, C.byref(cs), T.dptr(H) if want_H else None, T.dptr(g) if want_H else None, C.byref(cost)))
         return H, g, cost.value
+
+    def covariance(self, state, slots=None, columns=None):
+        """Rows and columns of H^-1 at `state`, H the matrix linearize() returns (include/glio_cov.h: the coordinates, the free columns, the bits).
+        slots: the 15 columns of every listed keyframe, in list order; columns: any list of columns; neither: the newest keyframe.
+        Returns (cov [m][m], GlioCovInfo).  A matrix that is not positive definite raises GlioError with code E_NUMERIC and the record in .info."""
+        if slots is not None and columns is not None:
+            raise ValueError("covariance: slots or columns, not both")
+        if columns is None:
+            slots = [self.W - 1] if slots is None else slots
+        lst = np.ascontiguousarray(np.asarray(slots if columns is None else columns, np.int64).ravel().astype(np.int32))
+        m = len(lst) * (15 if columns is None else 1)
+        out = np.full((m, m), np.nan)
+        info = GlioCovInfo()
+        cs = state.c()
+        fn = load().glio_covariance_slots if columns is None else load().glio_covariance_columns
+        rc = fn(self._h, C.byref(cs), len(lst), T.iptr(lst), T.dptr(out), C.byref(info))
+        return self._cov_result(rc, out, info)
+
+    def covariance_of(self, H, columns):
+        """the same kernels on a caller's matrix (glio_debug_covariance_of: tests and timing); only the lower triangle of H is read"""
+        H = np.ascontiguousarray(H, np.float64)
+        lst = np.ascontiguousarray(np.asarray(columns, np.int64).ravel().astype(np.int32))
+        out = np.full((len(lst), len(lst)), np.nan)
+        info = GlioCovInfo()
+        rc = load().glio_debug_covariance_of(self._h, len(H), T.dptr(H), len(lst), T.iptr(lst), T.dptr(out), C.byref(info))
+        return self._cov_result(rc, out, info)
+
+    @staticmethod
+    def _cov_result(rc, out, info):
+        if rc != 0:
+            e = GlioError(f"libglio_hip error {rc}: {load().glio_last_error().decode()}")
+            e.code, e.info, e.out = rc, info, out
+            raise e
+        return out, info
+
+    def covariance_last_device_ms(self):
+        ms = C.c_float()
+        _check(load().glio_covariance_last_device_ms(self._h, C.byref(ms)))
+        return ms.value
 
     def solve(self, state):
         s = state.copy()

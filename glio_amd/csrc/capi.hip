@@ -14,8 +14,16 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/glio_cov.h"
 #include "glio_device.h"
 
+// covariance_kernels.hip
+struct GlioCovWs;
+int glio_cov_begin(glio_ctx* c, GlioCovWs** ws, int n, int m, const int32_t* cols);
+int glio_cov_finish(glio_ctx* c, GlioCovWs* ws, const double* d_H, int n, int m, double* out, glio_cov_info* info);
+double* glio_cov_staging(GlioCovWs* ws);
+int glio_cov_last_ms(GlioCovWs* ws, float* ms);
+void glio_cov_free(GlioCovWs* ws);
 void glio_launch_eval_imu(glio_ctx* c, const ImuEdgeDev* d_edge, const double* d_params, double* d_out);
 void glio_launch_eval_lidar(glio_ctx* c, const float cp[4], const float plane[4], double score, const double* d_params, double* d_out);
 void glio_launch_gram(glio_ctx* c, int np);
@@ -45,6 +53,7 @@ struct CtxExtra {
     int* marg_h_ok = nullptr;              // glio_marginalize_keep_async: the pinned "positive definite" flag its finish looks at
     hipEvent_t ev_ahead = nullptr; int ahead_valid = 0, ahead_n = 0;      // glio_set_scan_ahead: the upload + presort of the NEXT keyframe's scan on the upload stream
     char* sv_h = nullptr; char* sv_d = nullptr; size_t sv_cap = 0;
+    GlioCovWs* cov = nullptr;              // glio_covariance_*: the workspace, allocated by the first call
 };
 // the extras hang off the context itself (glio_ctx::extra): no process-global registry, so independent contexts can be
 // created, used and destroyed from different threads concurrently (Estimator.cpp:5398-5404)
@@ -298,6 +307,7 @@ void glio_destroy(glio_ctx* c) {
         if (ex->d_eval_out) hipFree(ex->d_eval_out);
         if (ex->d_eval_edge) hipFree(ex->d_eval_edge);
         if (ex->h_eval) hipHostFree(ex->h_eval);
+        glio_cov_free(ex->cov);
         delete ex;
         c->extra = nullptr;
     }
@@ -1353,6 +1363,60 @@ int glio_linearize(glio_ctx* c, const glio_state* s, double* H, double* g, doubl
     GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
     c->last_n_ddt = n_ddt;
     return GLIO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- marginal covariance (include/glio_cov.h)
+int glio_cov_struct_sizes(int32_t* out, int n) {
+    if (out && n > 0) out[0] = (int32_t)sizeof(glio_cov_info);
+    return 1;
+}
+int glio_covariance_columns(glio_ctx* c, const glio_state* s, int m, const int32_t* cols, double* out, glio_cov_info* info) {
+    GLIO_TRACE("glio_covariance_columns");
+    if (!c || !s || !cols || !out) { glio_set_error("null argument"); return GLIO_E_ARG; }
+    int rc = check_state(c, s);
+    if (rc) return rc;
+    rc = marg_pending_done(c);
+    if (rc) return rc;
+    rc = glio_assoc_finish_pending(c);
+    if (rc) return rc;
+    GLIO_HIP_CHECK(hipSetDevice(c->device));
+    const int n_ddt = s->n_ddt, nx = glio_x_size(c->W, n_ddt), n = 15 * c->W + n_ddt;
+    rc = glio_cov_begin(c, &extra_of(c)->cov, n, m, cols);
+    if (rc) return rc;
+    pack_state(c, s, c->h_xbuf);
+    GLIO_HIP_CHECK(hipMemcpyAsync(c->d_x[0], c->h_xbuf, (size_t)nx * 8, hipMemcpyHostToDevice, c->stream));
+    enqueue_linearize(c, 0, 0, n_ddt);
+    GLIO_HIP_CHECK(hipGetLastError());
+    return glio_cov_finish(c, extra_of(c)->cov, c->d_H[0], n, m, out, info);
+}
+int glio_covariance_slots(glio_ctx* c, const glio_state* s, int n_slots, const int32_t* slots, double* out, glio_cov_info* info) {
+    if (!c || !s || !slots || !out) { glio_set_error("null argument"); return GLIO_E_ARG; }
+    if (n_slots < 1 || n_slots > c->W) { glio_set_error("covariance: %d slots asked of a window of %d", n_slots, c->W); return GLIO_E_ARG; }
+    std::vector<int32_t> cols((size_t)15 * n_slots);
+    for (int k = 0; k < n_slots; ++k) {
+        if (slots[k] < 0 || slots[k] >= c->W) { glio_set_error("covariance: slot %d is outside [0, %d)", (int)slots[k], c->W); return GLIO_E_ARG; }
+        for (int j = 0; j < 15; ++j) cols[15 * k + j] = 15 * slots[k] + j;
+    }
+    return glio_covariance_columns(c, s, 15 * n_slots, cols.data(), out, info);      // (a slot listed twice is refused there, as the columns it repeats)
+}
+int glio_covariance_last_device_ms(glio_ctx* c, float* ms) {
+    if (!c || !ms) { glio_set_error("null argument"); return GLIO_E_ARG; }
+    GLIO_HIP_CHECK(hipSetDevice(c->device));
+    return glio_cov_last_ms(extra_of(c)->cov, ms);
+}
+int glio_debug_covariance_of(glio_ctx* c, int n, const double* H, int m, const int32_t* cols, double* out, glio_cov_info* info) {
+    if (!c || !H || !cols || !out) { glio_set_error("null argument"); return GLIO_E_ARG; }
+    if (n < 1 || n > c->n_max) { glio_set_error("covariance: n = %d is outside [1, %d]", n, c->n_max); return GLIO_E_ARG; }
+    int rc = marg_pending_done(c);
+    if (rc) return rc;
+    rc = glio_assoc_finish_pending(c);
+    if (rc) return rc;
+    GLIO_HIP_CHECK(hipSetDevice(c->device));
+    rc = glio_cov_begin(c, &extra_of(c)->cov, n, m, cols);
+    if (rc) return rc;
+    double* d_H = glio_cov_staging(extra_of(c)->cov);
+    GLIO_HIP_CHECK(hipMemcpyAsync(d_H, H, (size_t)n * n * 8, hipMemcpyHostToDevice, c->stream));
+    return glio_cov_finish(c, extra_of(c)->cov, d_H, n, m, out, info);
 }
 
 // ---------------------------------------------------------------------------------------------- marginalization

@@ -18,6 +18,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/glio_cov.h"
 #include "../../include/glio_hip.h"
 
 namespace glio {
@@ -26,6 +27,36 @@ struct Error : std::runtime_error {
     explicit Error(const std::string& what) : std::runtime_error(what + ": " + glio_last_error()) {}
 };
 inline void check(int rc, const char* what) { if (rc != GLIO_OK) throw Error(what); }
+
+// The 6 x 6 pose block of SlidingWindowBackend::covariance (columns 15 s .. 15 s + 5 of slot s: translation, then the quaternion's tangent) at the slot's
+// quaternion q = (w, x, y, z), in GTSAM's Pose3 order and chart: rotation first, body-frame rotation vector in radians, translation increment R v -- the
+// order glio_pgraph_* variances and the reference's poseCovariance(3,3), (4,4) gate are written in.  Row major in and out.
+//   The window moves a pose by  t' = t + dt,  q' = (cos |d|, sin |d| d / |d|) * q  (Ceres' QuaternionParameterization: d multiplies on the LEFT and is HALF a
+//   rotation vector), i.e. R' = Exp(2 d) R with R = R(q).  Pose3's chart moves it by  R' = R Exp(omega),  t' = t + R v.
+//   Exp(2 d) R = R Exp(R^T 2 d) exactly, so omega = 2 R^T d; and t + dt = t + R v gives v = R^T dt.  Both are linear in (dt, d): to first order (and for the
+//   rotation at any size) (omega, v) = A (dt, d) with the constant
+//       A = [ 0     2 R^T ]
+//           [ R^T   0     ]
+//   and the covariance maps as A Sigma A^T.  sliding.pose3_covariance is the Python twin.
+inline std::array<double, 36> pose3Covariance(const double* cov6, const double q_in[4]) {
+    const double nq = std::sqrt(q_in[0] * q_in[0] + q_in[1] * q_in[1] + q_in[2] * q_in[2] + q_in[3] * q_in[3]);
+    const double w = q_in[0] / nq, x = q_in[1] / nq, y = q_in[2] / nq, z = q_in[3] / nq;
+    const double R[9] = {1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                         2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                         2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)};
+    double A[36] = {0};
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) { A[6 * i + 3 + j] = 2.0 * R[3 * j + i]; A[6 * (3 + i) + j] = R[3 * j + i]; }
+    double AS[36];
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) { double s = 0; for (int k = 0; k < 6; ++k) s += A[6 * i + k] * cov6[6 * k + j]; AS[6 * i + j] = s; }
+    std::array<double, 36> P{};
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < 6; ++j) { double s = 0; for (int k = 0; k < 6; ++k) s += AS[6 * i + k] * A[6 * j + k]; P[6 * i + j] = s; }
+    for (int i = 0; i < 6; ++i)
+        for (int j = 0; j < i; ++j) { const double m = 0.5 * (P[6 * i + j] + P[6 * j + i]); P[6 * i + j] = m; P[6 * j + i] = m; }
+    return P;
+}
 
 // The marginalization result: last_marginalization_info (linearized_jacobians / residuals, keep_block_*) and
 // last_marginalization_parameter_blocks (MarginalizationFactor.h, Estimator.cpp:2584-2606) with blocks named by
@@ -315,6 +346,28 @@ public:
         for (int i = 0; i < W_; ++i)
             if (tmpQuat[4 * i] < 0) for (int k = 0; k < 4; ++k) tmpQuat[4 * i + k] = -tmpQuat[4 * i + k];   // unifyQuaternion
         return sum;
+    }
+
+    // The marginal covariance of the estimate (include/glio_cov.h) at the state solve() left: the 15 columns of every listed slot, in list order, as a
+    // row-major [15 k][15 k] matrix; covarianceColumns: any list of columns of glio_linearize's H.  Call after solve() and before marginalizeAndKeep*(): the
+    // marginalization replaces the prior, and with it the H the covariance belongs to.  A column no factor touches reports +inf ("no information"); a matrix
+    // that is not positive definite throws.  info (may be null): the call's record.
+    std::vector<double> covariance(const std::vector<int32_t>& slots, std::vector<double>* rcv_ddt = nullptr, glio_cov_info* info = nullptr) {
+        glio_state st;
+        st.trans = tmpTrans.data(); st.quat = tmpQuat.data(); st.speed_bias = tmpSpeedBias.data();
+        st.rcv_ddt = rcv_ddt && !rcv_ddt->empty() ? rcv_ddt->data() : nullptr; st.n_ddt = rcv_ddt ? (int)rcv_ddt->size() : 0;
+        const size_t m = 15 * slots.size();
+        std::vector<double> out(m * m, 0.0);
+        check(glio_covariance_slots(ctx_, &st, (int)slots.size(), slots.data(), out.data(), info), "glio_covariance_slots");
+        return out;
+    }
+    std::vector<double> covarianceColumns(const std::vector<int32_t>& cols, std::vector<double>* rcv_ddt = nullptr, glio_cov_info* info = nullptr) {
+        glio_state st;
+        st.trans = tmpTrans.data(); st.quat = tmpQuat.data(); st.speed_bias = tmpSpeedBias.data();
+        st.rcv_ddt = rcv_ddt && !rcv_ddt->empty() ? rcv_ddt->data() : nullptr; st.n_ddt = rcv_ddt ? (int)rcv_ddt->size() : 0;
+        std::vector<double> out(cols.size() * cols.size(), 0.0);
+        check(glio_covariance_columns(ctx_, &st, (int)cols.size(), cols.data(), out.data(), info), "glio_covariance_columns");
+        return out;
     }
 
     // Estimator.cpp:2462-2607: marginalize the oldest keyframe at the solved state (call after solve()); the

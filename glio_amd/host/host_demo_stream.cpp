@@ -104,6 +104,10 @@ int main(int argc, char** argv) {
         // traj=1 (opt-in; scripts/trajectory_timing.py): one gap of the every-frame trajectory (3 in-between frames, 44 sample rows) is pushed per keyframe call
         // right after the solve, on the trajectory's own stream (glio_traj_push_gap), and read after the loop.  Default: no trajectory object exists.
         bool traj_gap = false;
+        // cov=1 (opt-in; scripts/covariance_timing.py): after each solve the newest keyframe's 15 x 15 marginal covariance is asked for (glio_covariance_slots,
+        // between solve() and the marginalization) and its trace and Pose3 block booked.  Default: the covariance workspace is never allocated.
+        bool cov_newest = false;
+        std::vector<double> cov_traces, cov_pose3_last;
         std::vector<uint64_t> table;
         size_t table_k = 0;
         for (int a = 5; a < argc; ++a) {
@@ -117,6 +121,7 @@ int main(int argc, char** argv) {
             else if (!strncmp(argv[a], "map_rebuild=", 12)) map_rebuild = atoi(argv[a] + 12) != 0;
             else if (!strncmp(argv[a], "filter=", 7)) filter_leaf = (float)atof(argv[a] + 7);
             else if (!strncmp(argv[a], "traj=", 5)) traj_gap = atoi(argv[a] + 5) != 0;
+            else if (!strncmp(argv[a], "cov=", 4)) cov_newest = atoi(argv[a] + 4) != 0;
             else if (!strncmp(argv[a], "sleep_ms=", 9)) sleep_ms = atoi(argv[a] + 9);
             else if (!strncmp(argv[a], "sleep_at=", 9)) sleep_at = atoi(argv[a] + 9);
             else if (!strncmp(argv[a], "draws=", 6)) {
@@ -221,6 +226,16 @@ int main(int argc, char** argv) {
                 for (int c = 0; c < 3; ++c) kf_poses[7 * (size_t)g + c] = be.tmpTrans[3 * s + c];
                 for (int c = 0; c < 4; ++c) kf_poses[7 * (size_t)g + 3 + c] = be.tmpQuat[4 * s + c];
             }
+            if (cov_newest) {
+                const std::vector<double> cv = be.covariance({W - 1}, &ddt);
+                double tr = 0;
+                for (int c = 0; c < 15; ++c) tr += cv[16 * c];
+                cov_traces.push_back(tr);
+                double c6[36];
+                for (int r = 0; r < 6; ++r) for (int c = 0; c < 6; ++c) c6[6 * r + c] = cv[15 * r + c];
+                const std::array<double, 36> p3 = glio::pose3Covariance(c6, &be.tmpQuat[4 * (W - 1)]);
+                cov_pose3_last.assign(p3.begin(), p3.end());
+            }
             if (traj_gap) {          // the gap between the two oldest keyframes of the window, from the pose table the solve just left
                 const double* L = &kf_poses[7 * (size_t)j];
                 const double* Rr = &kf_poses[7 * (size_t)(j + 1)];
@@ -293,6 +308,15 @@ int main(int argc, char** argv) {
             glio_traj_last_device_ms(tstore->handle(), &tms);
             printf(", \"trajectory_gap_per_call\": true, \"trajectory_last_gap\": {\"frames\": %d, \"termination\": %d, \"iterations\": %d, \"device_ms\": %.5f}", ts.n_frames, ts.termination,
                    ts.iterations, (double)tms);
+        }
+        if (cov_newest) {
+            float cms = 0.f;
+            glio_covariance_last_device_ms(be.ctx(), &cms);
+            printf(", \"covariance_newest_trace\": [");
+            for (size_t i = 0; i < cov_traces.size(); ++i) printf("%s%.17g", i ? ", " : "", cov_traces[i]);
+            printf("], \"covariance_last_pose3\": [");
+            for (size_t i = 0; i < cov_pose3_last.size(); ++i) printf("%s%.17g", i ? ", " : "", cov_pose3_last[i]);
+            printf("], \"covariance_last_device_ms\": %.5f", (double)cms);
         }
         printf(", \"steps_with_the_helpers_build\": %lld, \"iterations_booked\": %ld, \"trans_checksum\": %.17g}\n", stamps[300], total_iters, checksum);
     } catch (const std::exception& e) {

@@ -10,7 +10,7 @@ from .. import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEMO = os.path.join(HERE, "host_demo")
-_ABI_HEADERS = [os.path.join(HERE, "..", "..", "include", h) for h in ("glio_hip.h", "glio_types.h", "glio_pgraph_lm.h")]      # a changed struct must rebuild the demos
+_ABI_HEADERS = [os.path.join(HERE, "..", "..", "include", h) for h in ("glio_hip.h", "glio_types.h", "glio_pgraph_lm.h", "glio_cov.h")]      # a changed struct must rebuild the demos
 
 
 def build_demo(force=False):
@@ -171,8 +171,9 @@ def write_stream(path, long, wins, W, n_keyframes, pts, lm_width=50, leaf=0.4, b
                 f.write(bytes(d))
 
 
-def run_demo_stream(path, device=0, env=None, search_range=6, defer=False, feature_res_num=0, draws=None, timed=None, per_slot=False, sleep_ms=0, sleep_at=0, stream_draws=True, prepare_early=True, ahead=False, map_ahead=False, map_rebuild=False, filter=None, traj=False):
-    """traj: a gap of the every-frame trajectory is pushed per keyframe call (opt-in); filter=LEAF: the stream's clouds are filtered on the device on their way into the window (setScanFiltered*; opt-in);
+def run_demo_stream(path, device=0, env=None, search_range=6, defer=False, feature_res_num=0, draws=None, timed=None, per_slot=False, sleep_ms=0, sleep_at=0, stream_draws=True, prepare_early=True, ahead=False, map_ahead=False, map_rebuild=False, filter=None, traj=False, cov=False):
+    """cov: the newest keyframe's marginal covariance is asked for after every solve (opt-in; covariance_newest_trace, one per keyframe call, the first included);
+    traj: a gap of the every-frame trajectory is pushed per keyframe call (opt-in); filter=LEAF: the stream's clouds are filtered on the device on their way into the window (setScanFiltered*; opt-in);
     feature_res_num > 0: featureSelection behind every slot's search (Estimator.cpp:2223); draws: file of uint64 both hosts draw from (sliding.TableRng);
     timed: only the last `timed` keyframes enter the time averages"""
     import json
@@ -200,6 +201,8 @@ def run_demo_stream(path, device=0, env=None, search_range=6, defer=False, featu
         cmd.append(f"filter={float(filter)!r}")
     if traj:
         cmd.append("traj=1")
+    if cov:
+        cmd.append("cov=1")
     r = subprocess.run(cmd, capture_output=True, text=True, env=env)
     if r.returncode != 0:
         raise RuntimeError("host_demo_stream failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))

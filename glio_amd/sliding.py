@@ -21,6 +21,28 @@ def unify_quaternions(state):
     return state
 
 
+def pose3_covariance(cov6, q):
+    """The 6 x 6 pose block of Context.covariance (columns 15 s .. 15 s + 5 of slot s: translation, then the quaternion's tangent) at the slot's
+    quaternion q = (w, x, y, z), in GTSAM's Pose3 order and chart: rotation first, body-frame rotation vector in radians, translation increment R v.
+      The window moves a pose by  t' = t + dt,  q' = (cos |d|, sin |d| d / |d|) * q  (Ceres' QuaternionParameterization: d multiplies on the LEFT and is HALF
+      a rotation vector), i.e. R' = Exp(2 d) R with R = R(q).  Pose3's chart moves it by  R' = R Exp(omega),  t' = t + R v.
+      Exp(2 d) R = R Exp(R^T 2 d) exactly, so omega = 2 R^T d; and t + dt = t + R v gives v = R^T dt.  Both are linear in (dt, d): to first order (and for the
+      rotation at any size) (omega, v) = A (dt, d) with the constant
+          A = [ 0     2 R^T ]
+              [ R^T   0     ]
+      and the covariance maps as A Sigma A^T.  glio::pose3Covariance (glio_backend.hpp) is the C++ twin."""
+    q = np.asarray(q, np.float64)
+    w, x, y, z = q / np.linalg.norm(q)
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
+                  [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
+                  [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
+    A = np.zeros((6, 6))
+    A[0:3, 3:6] = 2.0 * R.T
+    A[3:6, 0:3] = R.T
+    out = A @ np.asarray(cov6, np.float64).reshape(6, 6) @ A.T
+    return 0.5 * (out + out.T)
+
+
 def feature_selection_draws(count, feature_res_num, rng, random_select=True):
     """The index sequence `featureSelection` (Estimator.cpp:3894-3992) keeps, for `count` correspondences: nothing
     changes when count - 1 < feature_res_num (early return :3906-3909, quirk Q9); otherwise feature_res_num draws, each
@@ -99,9 +121,12 @@ def _scan_filter_config(ctx, scans, filter_max_points):
 
 
 class SlidingWindowDriver:
-    def __init__(self, backend, opts, lidar_pose=capi.lidar_pose, filter=None, filter_max_points=None):
+    def __init__(self, backend, opts, lidar_pose=capi.lidar_pose, filter=None, filter_max_points=None, covariance=False):
         """filter=LEAF (opt-in, capi.Context only): step() takes the keyframes' UNFILTERED surf clouds and downSampleCloud's ds_filter_surf
-        (Estimator.cpp:3628-3630, surfDSRange) runs on the device with the upload (glio_set_scan_filtered); the default takes filtered clouds."""
+        (Estimator.cpp:3628-3630, surfDSRange) runs on the device with the upload (glio_set_scan_filtered); the default takes filtered clouds.
+        covariance=True (opt-in, capi.Context only): step() asks for the newest keyframe's 15 x 15 marginal covariance at the solved state, after the solve
+        and before the marginalization (glio_covariance_slots), and returns it as a fourth value; last_covariance_info holds the call's record."""
+        self.covariance, self.last_covariance, self.last_covariance_info = covariance, None, None
         self.be, self.opts, self.W = backend, opts, opts.window
         self.lidar_pose = lidar_pose
         self.filter, self.filter_max_points, self._filter_ready = filter, filter_max_points, False
@@ -152,12 +177,16 @@ class SlidingWindowDriver:
             be.set_speed_bias_priors(self.state.speed_bias[:W - 1])
         sol, summ = be.solve(self.state)
         unify_quaternions(sol)
+        if self.covariance:
+            self.last_covariance, self.last_covariance_info = be.covariance(sol, slots=[W - 1])
         self.prior = be.marginalize(sol)
         if self.speed_bias_priors_armed:             # (marginalize leaves the backend as it found it)
             be.set_speed_bias_priors(None)
             self.speed_bias_priors_armed = False
         self.state = sol
         self.history.append((self.first, sol.copy(), summ, counts))
+        if self.covariance:
+            return sol, summ, counts, self.last_covariance
         return sol, summ, counts
 
     def slide(self, new_trans, new_quat, new_speed_bias):
@@ -241,8 +270,10 @@ class ResidentSlidingWindow:
     scans slide with `glio_slide_window`, only the NEW keyframe's scan is uploaded, all slots are associated in one call,
     and the marginalization result stays resident as the next prior (`glio_marginalize_keep`)."""
 
-    def __init__(self, ctx, opts, lidar_pose=capi.lidar_pose, filter=None, filter_max_points=None):
-        """filter=LEAF (opt-in): as SlidingWindowDriver -- the new keyframe's unfiltered surf cloud is filtered on the device on its way into slot W - 1"""
+    def __init__(self, ctx, opts, lidar_pose=capi.lidar_pose, filter=None, filter_max_points=None, covariance=False):
+        """filter=LEAF (opt-in): as SlidingWindowDriver -- the new keyframe's unfiltered surf cloud is filtered on the device on its way into slot W - 1.
+        covariance=True (opt-in): as SlidingWindowDriver -- the newest keyframe's 15 x 15 block, asked between solve and marginalize_keep, a fourth value."""
+        self.covariance, self.last_covariance, self.last_covariance_info = covariance, None, None
         self.ctx, self.opts, self.W = ctx, opts, opts.window
         self.lidar_pose = lidar_pose
         self.filter, self.filter_max_points = filter, filter_max_points
@@ -290,9 +321,13 @@ class ResidentSlidingWindow:
             ctx.set_speed_bias_priors(self.state.speed_bias[:W - 1])
         sol, summ = ctx.solve(self.state)
         unify_quaternions(sol)
+        if self.covariance:
+            self.last_covariance, self.last_covariance_info = ctx.covariance(sol, slots=[W - 1])
         ctx.marginalize_keep(sol)
         self.speed_bias_priors_armed = False
         self.state = sol
+        if self.covariance:
+            return sol, summ, [int(c) for c in counts], self.last_covariance
         return sol, summ, [int(c) for c in counts]
 
     def slide(self, new_trans, new_quat, new_speed_bias):
