@@ -42,6 +42,7 @@ struct glio_batch {
 struct BtSel { const int* cur; const int* skip; int want; };
 __device__ __forceinline__ int bt_pick(const BtSel& s) { return s.cur ? (((*s.cur) ^ s.want) & 1) : s.want; }
 __device__ __forceinline__ bool bt_skip(const BtSel& s) { return s.skip && *s.skip != 0; }
+static const BtSel BT_HOST_SEL = {nullptr, nullptr, 0};      // the calls a host drives one by one: buffer 0, never skipped
 
 // ---- the normal matrix of the batch problem as an operator: pose band (K8 + small factors) + IMU chain records
 struct HView { const double* Hg; const PairBlock* imu; int K, band, B; };
@@ -94,6 +95,8 @@ void glio_batch_enqueue_linearize(glio_batch* b, double* Hg_dev);
 // a solve); 2: evaluate the stored moments only (every later one).  glio_batch_moments_ensure sizes the moment buffer for the present pairs.
 void glio_batch_enqueue_linearize_sel(glio_batch* b, const BtSel& sel, const double* poses0, const double* poses1, double* Hg0, double* Hg1, int k0, int k1, int mode = 0);
 int glio_batch_moments_ensure(glio_batch* b);
+// host poses [K][7] -> the pinned buffer -> b->d_poses, on the batch stream
+int glio_batch_upload_poses(glio_batch* b, const double* poses);
 // factor_kernels.hip: ImuFactor of the batch chain, one workgroup per edge e in [e0, e1): rec[sel][e]
 void glio_launch_batch_imu(hipStream_t stream, const BtSel& sel, double gravity, const ImuEdgeDev* edges, int e0, int e1, const double* poses0, const double* poses1,
                            const double* sb0, const double* sb1, PairBlock* rec0, PairBlock* rec1);

@@ -60,6 +60,13 @@ __device__ __forceinline__ double uniform_d(const double v) {
     const int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffll)), hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
     return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
+// the two poses of a pair (a, b): rotation matrices and translations
+__device__ __forceinline__ void bp_pair_poses(const double* __restrict__ poses, const int a, const int b, double (&R1)[9], double (&R2)[9], double (&t1)[3], double (&t2)[3]) {
+    d_q2R(poses + 7 * (size_t)a + 3, R1);
+    d_q2R(poses + 7 * (size_t)b + 3, R2);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { t1[k] = poses[7 * (size_t)a + k]; t2[k] = poses[7 * (size_t)b + k]; }
+}
 __global__ __launch_bounds__(256) void k_batch_pairs(const float4* __restrict__ cp, const double* __restrict__ nc,
                                                      const double* __restrict__ score, const int* __restrict__ pair_i,
                                                      const int* __restrict__ pair_j, const long long* __restrict__ pair_off,
@@ -71,10 +78,7 @@ __global__ __launch_bounds__(256) void k_batch_pairs(const float4* __restrict__ 
     const double* poses = bt_pick(sel) ? poses1 : poses0;
     const int a = pair_i[p], b = pair_j[p];
     double R1[9], R2[9], t1[3], t2[3];
-    d_q2R(poses + 7 * (size_t)a + 3, R1);
-    d_q2R(poses + 7 * (size_t)b + 3, R2);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { t1[k] = poses[7 * (size_t)a + k]; t2[k] = poses[7 * (size_t)b + k]; }
+    bp_pair_poses(poses, a, b, R1, R2, t1, t2);
     // the two poses are the same for the whole wavefront: kept in scalar registers (24 doubles = 48 VGPRs less, which is what lets a
     // third wavefront per SIMD in: the kernel alternates between waiting for 72-byte records and ~160 fp64 multiply-adds on each)
 #pragma unroll
@@ -85,7 +89,10 @@ __global__ __launch_bounds__(256) void k_batch_pairs(const float4* __restrict__ 
 #pragma unroll
     for (int k = 0; k < 64; ++k) acc[k] = 0.0;
     const long long beg = pair_off[2 * p], end = pair_off[2 * p + 1];      // [begin, end) of the pair's records: pairs need not be adjacent in memory
-    // software pipeline: the next constraint's 72 bytes are requested before the present one's ~160 multiply-adds are issued
+    // software pipeline: the next constraint's 72 bytes are requested before the present one's ~160 multiply-adds are issued.  k_batch_moments
+    // carries the same stream, and both stay written out: with the stream as one routine -- the kernel's body as a lambda run per record, or only the
+    // record's load shared, by value or by reference -- the compiler scheduled and contracted this kernel's multiply-adds differently and the streamed
+    // linearisation changed its bits (11 of the 23 lines of scripts/batch_bits_ab.py DIFFERENT, every one through this kernel; profiles/batch_dedup_ab.txt)
     long long i = beg + lane;
     float4 pt_n = make_float4(0.f, 0.f, 0.f, 0.f);
     double2 n01_n = make_double2(0.0, 0.0), n2c0_n = n01_n, c12_n = n01_n;
@@ -172,10 +179,7 @@ __global__ __launch_bounds__(256) void k_batch_moments(const float4* __restrict_
     double th0[12];
     {
         double R1[9], R2[9], t1[3], t2[3];
-        d_q2R(poses + 7 * (size_t)a + 3, R1);
-        d_q2R(poses + 7 * (size_t)b + 3, R2);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { t1[k] = poses[7 * (size_t)a + k]; t2[k] = poses[7 * (size_t)b + k]; }
+        bp_pair_poses(poses, a, b, R1, R2, t1, t2);
         bm_theta(R1, R2, t1, t2, th0);
 #pragma unroll
         for (int k = 0; k < 12; ++k) th0[k] = uniform_d(th0[k]);
@@ -184,6 +188,7 @@ __global__ __launch_bounds__(256) void k_batch_moments(const float4* __restrict_
 #pragma unroll
     for (int k = 0; k < 128; ++k) acc[k] = 0.0;
     const long long beg = pair_off[2 * p], end = pair_off[2 * p + 1];      // [begin, end) of the pair's records: pairs need not be adjacent in memory
+    // (the record stream of k_batch_pairs, written out here as well: see the comment there)
     long long i = beg + lane;
     float4 pt_n = make_float4(0.f, 0.f, 0.f, 0.f);
     double2 n01_n = make_double2(0.0, 0.0), n2c0_n = n01_n, c12_n = n01_n;
@@ -252,10 +257,7 @@ __global__ __launch_bounds__(256) void k_batch_moment_eval(const double* __restr
     const double* poses = bt_pick(sel) ? poses1 : poses0;
     const int a = pair_i[p], b = pair_j[p];
     double R1[9], R2[9], t1[3], t2[3], th[12];
-    d_q2R(poses + 7 * (size_t)a + 3, R1);
-    d_q2R(poses + 7 * (size_t)b + 3, R2);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { t1[k] = poses[7 * (size_t)a + k]; t2[k] = poses[7 * (size_t)b + k]; }
+    bp_pair_poses(poses, a, b, R1, R2, t1, t2);
     bm_theta(R1, R2, t1, t2, th);
     const double* M = mom + (size_t)p * BM_REC;
     double* Phi = sPhi[wv]; double* D = sD[wv]; double* P = sP[wv]; double* V = sV[wv];
@@ -751,35 +753,47 @@ int glio_batch_set_stream(glio_batch* b, void* s) {
     return GLIO_OK;
 }
 
+// The pair list of a constraint set while the host builds it: pair q = keyframes (pi[q], pj[q]) with the records [off[2 q], off[2 q + 1]);
+// index[(ci, cj - ci)] = q, -1 where the band holds no pair.  Both ways of handing a constraint set over (sorted index arrays, pair list) fill one
+// and install it; each keeps its own checks of order and its own error texts.
+struct BatchPairs {
+    std::vector<int> pi, pj, index;
+    std::vector<long long> off;
+    const int K, band;
+    explicit BatchPairs(const glio_batch* b) : index((size_t)b->K * (2 * b->band + 1), -1), K(b->K), band(b->band) {}
+    bool in_band(const int a, const int c) const { return a >= 0 && a < K && c >= 0 && c < K && a != c && std::abs(a - c) <= band; }
+    int& slot(const int a, const int c) { return index[(size_t)a * (2 * band + 1) + (c - a) + band]; }
+    void add(const int a, const int c, const long long beg, const long long end) { slot(a, c) = (int)pi.size(); pi.push_back(a); pj.push_back(c); off.push_back(beg); off.push_back(end); }
+};
+static int install_pairs(glio_batch* b, BatchPairs& P, const long long n_con) {
+    b->src_min = P.pi.empty() ? 0 : P.pi.front(); b->src_max = P.pi.empty() ? -1 : P.pi.back();      // (sorted by ci)
+    b->n_pairs = (int)P.pi.size();
+    if (b->n_pairs) {
+        GLIO_HIP_CHECK(hipMemcpy(b->d_pair_i, P.pi.data(), P.pi.size() * 4, hipMemcpyHostToDevice));
+        GLIO_HIP_CHECK(hipMemcpy(b->d_pair_j, P.pj.data(), P.pj.size() * 4, hipMemcpyHostToDevice));
+    }
+    P.off.push_back(0); P.off.push_back(0);
+    GLIO_HIP_CHECK(hipMemcpy(b->d_pair_off, P.off.data(), P.off.size() * 8, hipMemcpyHostToDevice));
+    GLIO_HIP_CHECK(hipMemcpy(b->d_pair_index, P.index.data(), P.index.size() * 4, hipMemcpyHostToDevice));
+    b->n_con = n_con;
+    return GLIO_OK;
+}
+
 // pair segmentation from the (sorted) host index arrays
 static int build_pairs(glio_batch* b, int64_t n, const int32_t* ci, const int32_t* cj) {
-    const int K = b->K, band = b->band, wdt = 2 * band + 1;
-    std::vector<int> pi, pj, index((size_t)K * wdt, -1);
-    std::vector<long long> off;
+    BatchPairs P(b);
     for (int64_t i = 0; i < n; ++i) {
         const int a = ci[i], c = cj[i];
-        if (a < 0 || a >= K || c < 0 || c >= K || a == c || std::abs(a - c) > band) { glio_set_error("constraint %lld: keyframes (%d,%d) outside band %d", (long long)i, a, c, band); return GLIO_E_ARG; }
-        if (pi.empty() || pi.back() != a || pj.back() != c) {
-            if (!pi.empty() && (a < pi.back() || (a == pi.back() && c < pj.back()))) { glio_set_error("constraints must be sorted by (ci, cj)"); return GLIO_E_ARG; }
-            if (index[(size_t)a * wdt + (c - a) + band] >= 0) { glio_set_error("constraints must be sorted by (ci, cj)"); return GLIO_E_ARG; }
-            index[(size_t)a * wdt + (c - a) + band] = (int)pi.size();
-            pi.push_back(a); pj.push_back(c); off.push_back(i);
+        if (!P.in_band(a, c)) { glio_set_error("constraint %lld: keyframes (%d,%d) outside band %d", (long long)i, a, c, b->band); return GLIO_E_ARG; }
+        if (P.pi.empty() || P.pi.back() != a || P.pj.back() != c) {
+            if (!P.pi.empty() && (a < P.pi.back() || (a == P.pi.back() && c < P.pj.back()))) { glio_set_error("constraints must be sorted by (ci, cj)"); return GLIO_E_ARG; }
+            if (P.slot(a, c) >= 0) { glio_set_error("constraints must be sorted by (ci, cj)"); return GLIO_E_ARG; }
+            if (!P.off.empty()) P.off.back() = i;          // the previous pair ends where this one begins
+            P.add(a, c, i, n);
         }
     }
-    off.push_back(n);
-    if ((int)pi.size() > b->max_pairs) return GLIO_E_ARG;
-    b->src_min = pi.empty() ? 0 : pi.front(); b->src_max = pi.empty() ? -1 : pi.back();      // (sorted by ci)
-    b->n_pairs = (int)pi.size();
-    if (b->n_pairs) {
-        GLIO_HIP_CHECK(hipMemcpy(b->d_pair_i, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
-        GLIO_HIP_CHECK(hipMemcpy(b->d_pair_j, pj.data(), pj.size() * 4, hipMemcpyHostToDevice));
-    }
-    std::vector<long long> be(2 * pi.size() + 2, 0);
-    for (size_t q = 0; q < pi.size(); ++q) { be[2 * q] = off[q]; be[2 * q + 1] = off[q + 1]; }
-    GLIO_HIP_CHECK(hipMemcpy(b->d_pair_off, be.data(), be.size() * 8, hipMemcpyHostToDevice));
-    GLIO_HIP_CHECK(hipMemcpy(b->d_pair_index, index.data(), index.size() * 4, hipMemcpyHostToDevice));
-    b->n_con = n;
-    return GLIO_OK;
+    if ((int)P.pi.size() > b->max_pairs) return GLIO_E_ARG;
+    return install_pairs(b, P, n);
 }
 
 int glio_batch_set_constraints_dev(glio_batch* b, int64_t n, const int32_t* ci, const int32_t* cj, const float* cp_dev,
@@ -814,21 +828,19 @@ int glio_batch_update_constraints_pairs_at_dev(glio_batch* b, int n_pairs, const
                                                const int64_t* pair_offset, const float* cp_dev, const double* nc_dev, const double* score_dev, const uint8_t* pair_changed) {
     if (!b || n_pairs < 0 || (n_pairs > 0 && (!pair_ci || !pair_cj || !pair_count || !cp_dev || !nc_dev || !score_dev))) return GLIO_E_ARG;
     GLIO_HIP_CHECK(hipSetDevice(b->device));
-    const int K = b->K, band = b->band, wdt = 2 * band + 1;
-    std::vector<int> pi, pj, index((size_t)K * wdt, -1), changed_slots;
-    std::vector<long long> off;
+    BatchPairs P(b);
+    std::vector<int>& pi = P.pi; std::vector<int>& pj = P.pj; std::vector<int> changed_slots;
+    std::vector<long long>& off = P.off;
     long long run = 0;
     for (int p = 0; p < n_pairs; ++p) {
         const int a = pair_ci[p], c = pair_cj[p];
-        if (a < 0 || a >= K || c < 0 || c >= K || a == c || std::abs(a - c) > band || pair_count[p] < 0) { glio_set_error("pair %d: keyframes (%d,%d) outside band %d", p, a, c, band); return GLIO_E_ARG; }
+        if (!P.in_band(a, c) || pair_count[p] < 0) { glio_set_error("pair %d: keyframes (%d,%d) outside band %d", p, a, c, b->band); return GLIO_E_ARG; }
         if (p > 0 && (a < pair_ci[p - 1] || (a == pair_ci[p - 1] && c <= pair_cj[p - 1]))) { glio_set_error("pairs must be sorted by (ci, cj)"); return GLIO_E_ARG; }
         if (pair_offset && pair_offset[p] < 0) { glio_set_error("pair %d: negative record offset", p); return GLIO_E_ARG; }
         if (pair_count[p] > 0) {
-            index[(size_t)a * wdt + (c - a) + band] = (int)pi.size();
             if (!pair_changed || pair_changed[p]) changed_slots.push_back((int)pi.size());
-            pi.push_back(a); pj.push_back(c);
             const long long beg = pair_offset ? (long long)pair_offset[p] : run;
-            off.push_back(beg); off.push_back(beg + (long long)pair_count[p]);
+            P.add(a, c, beg, beg + (long long)pair_count[p]);
         }
         run += pair_count[p];
     }
@@ -839,7 +851,6 @@ int glio_batch_update_constraints_pairs_at_dev(glio_batch* b, int n_pairs, const
         std::sort(rg.begin(), rg.end());
         for (size_t q = 1; q < rg.size(); ++q) if (rg[q].first < rg[q - 1].second) { glio_set_error("record ranges of two pairs overlap ([%lld, %lld) and [%lld, %lld))", rg[q - 1].first, rg[q - 1].second, rg[q].first, rg[q].second); return GLIO_E_ARG; }
     }
-    b->src_min = pi.empty() ? 0 : pi.front(); b->src_max = pi.empty() ? -1 : pi.back();      // (sorted by ci)
     {   // do the moment records of the unmarked pairs still stand?  only when the list of non-empty pairs is the one they were taken for
         bool same = pair_changed && b->moments_valid && b->h_prev_n == (int)pi.size() && b->d_moments && b->moments_pairs >= (int)pi.size();
         for (size_t q = 0; same && q < pi.size(); ++q) same = b->h_prev_pi[q] == pi[q] && b->h_prev_pj[q] == pj[q];
@@ -870,15 +881,7 @@ int glio_batch_update_constraints_pairs_at_dev(glio_batch* b, int n_pairs, const
         if (!pi.empty()) { memcpy(b->h_prev_pi, pi.data(), pi.size() * 4); memcpy(b->h_prev_pj, pj.data(), pj.size() * 4); memcpy(b->h_prev_off, off.data(), 2 * pi.size() * 8); }
         b->h_prev_n = (int)pi.size();
     }
-    b->n_pairs = (int)pi.size();
-    if (b->n_pairs) {
-        GLIO_HIP_CHECK(hipMemcpy(b->d_pair_i, pi.data(), pi.size() * 4, hipMemcpyHostToDevice));
-        GLIO_HIP_CHECK(hipMemcpy(b->d_pair_j, pj.data(), pj.size() * 4, hipMemcpyHostToDevice));
-    }
-    off.push_back(0); off.push_back(0);
-    GLIO_HIP_CHECK(hipMemcpy(b->d_pair_off, off.data(), off.size() * 8, hipMemcpyHostToDevice));
-    GLIO_HIP_CHECK(hipMemcpy(b->d_pair_index, index.data(), index.size() * 4, hipMemcpyHostToDevice));
-    b->n_con = run;
+    { const int rc = install_pairs(b, P, run); if (rc) return rc; }
     b->cp = reinterpret_cast<const float4*>(cp_dev); b->nc = nc_dev; b->score = score_dev;
     return GLIO_OK;
 }
@@ -939,16 +942,34 @@ extern "C++" int glio_batch_moments_ensure(glio_batch* b) {
     return GLIO_OK;
 }
 static void enqueue_batch_linearize(glio_batch* b, double* Hg_dev) {
-    BtSel sel; sel.cur = nullptr; sel.skip = nullptr; sel.want = 0;
-    enqueue_batch_linearize_sel(b, sel, b->d_poses, b->d_poses, Hg_dev, Hg_dev, 0, b->K);
+    enqueue_batch_linearize_sel(b, BT_HOST_SEL, b->d_poses, b->d_poses, Hg_dev, Hg_dev, 0, b->K);
+}
+// host poses -> pinned buffer -> b->d_poses, on the batch stream
+extern "C++" int glio_batch_upload_poses(glio_batch* b, const double* poses) {
+    memcpy(b->h_poses, poses, (size_t)b->K * 7 * 8);
+    GLIO_HIP_CHECK(hipMemcpyAsync(b->d_poses, b->h_poses, (size_t)b->K * 7 * 8, hipMemcpyHostToDevice, b->stream));
+    return GLIO_OK;
+}
+// average ms of `reps` calls of enqueue() on the batch stream, between two events (the caller has warmed up)
+extern "C++" {
+template <class Enqueue>
+static int time_enqueues(glio_batch* b, const int reps, float* ms_out, Enqueue enqueue) {
+    GLIO_HIP_CHECK(hipEventRecord(b->ev0, b->stream));
+    for (int r = 0; r < reps; ++r) enqueue();
+    GLIO_HIP_CHECK(hipEventRecord(b->ev1, b->stream));
+    GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
+    float ms = 0;
+    GLIO_HIP_CHECK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
+    *ms_out = ms / reps;
+    return GLIO_OK;
+}
 }
 
 int glio_batch_linearize_dev(glio_batch* b, const double* poses, double* Hg_dev) {
     GLIO_TRACE("K8 glio_batch_linearize_dev");
     if (!b || !poses || !Hg_dev) return GLIO_E_ARG;
     GLIO_HIP_CHECK(hipSetDevice(b->device));
-    memcpy(b->h_poses, poses, (size_t)b->K * 7 * 8);
-    GLIO_HIP_CHECK(hipMemcpyAsync(b->d_poses, b->h_poses, (size_t)b->K * 7 * 8, hipMemcpyHostToDevice, b->stream));
+    { const int rc = glio_batch_upload_poses(b, poses); if (rc) return rc; }
     enqueue_batch_linearize(b, Hg_dev);
     GLIO_HIP_CHECK(hipGetLastError());
     GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
@@ -959,14 +980,7 @@ int glio_batch_time_linearize(glio_batch* b, const double* poses, double* Hg_dev
     if (!b || !poses || !Hg_dev || reps < 1 || !ms_out) return GLIO_E_ARG;
     int rc = glio_batch_linearize_dev(b, poses, Hg_dev);      // warm-up + pose upload
     if (rc) return rc;
-    GLIO_HIP_CHECK(hipEventRecord(b->ev0, b->stream));
-    for (int r = 0; r < reps; ++r) enqueue_batch_linearize(b, Hg_dev);
-    GLIO_HIP_CHECK(hipEventRecord(b->ev1, b->stream));
-    GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
-    float ms = 0;
-    GLIO_HIP_CHECK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-    *ms_out = ms / reps;
-    return GLIO_OK;
+    return time_enqueues(b, reps, ms_out, [&] { enqueue_batch_linearize(b, Hg_dev); });
 }
 
 // test hook: one linearisation of the pose problem's plane constraints through the moment form (mode 1: take the moments at `poses`, then
@@ -975,10 +989,8 @@ extern "C" int glio_debug_batch_linearize_mode(glio_batch* b, const double* pose
     if (!b || !poses || !Hg_dev || mode < 0 || mode > 2) return GLIO_E_ARG;
     GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rc = glio_batch_moments_ensure(b); if (rc) return rc; }
-    memcpy(b->h_poses, poses, (size_t)b->K * 7 * 8);
-    GLIO_HIP_CHECK(hipMemcpyAsync(b->d_poses, b->h_poses, (size_t)b->K * 7 * 8, hipMemcpyHostToDevice, b->stream));
-    BtSel sel; sel.cur = nullptr; sel.skip = nullptr; sel.want = 0;
-    enqueue_batch_linearize_sel(b, sel, b->d_poses, b->d_poses, Hg_dev, Hg_dev, 0, b->K, mode);
+    { const int rc = glio_batch_upload_poses(b, poses); if (rc) return rc; }
+    enqueue_batch_linearize_sel(b, BT_HOST_SEL, b->d_poses, b->d_poses, Hg_dev, Hg_dev, 0, b->K, mode);
     GLIO_HIP_CHECK(hipGetLastError());
     GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
     return GLIO_OK;
@@ -996,19 +1008,11 @@ extern "C" int glio_debug_batch_time_linearize_mode(glio_batch* b, const double*
     if (rc) return rc;
     rc = glio_batch_moments_ensure(b);
     if (rc) return rc;
-    BtSel sel; sel.cur = nullptr; sel.skip = nullptr; sel.want = 0;
-    enqueue_batch_linearize_sel(b, sel, b->d_poses, b->d_poses, Hg_dev, Hg_dev, 0, b->K, 1);
-    GLIO_HIP_CHECK(hipEventRecord(b->ev0, b->stream));
-    for (int r = 0; r < reps; ++r) {
+    enqueue_batch_linearize_sel(b, BT_HOST_SEL, b->d_poses, b->d_poses, Hg_dev, Hg_dev, 0, b->K, 1);
+    return time_enqueues(b, reps, ms_out, [&] {
         if (mode == 1) b->moments_valid = 0;          // (the records are a cache: every repetition of the measurement takes them again)
-        enqueue_batch_linearize_sel(b, sel, b->d_poses, b->d_poses, Hg_dev, Hg_dev, 0, b->K, mode);
-    }
-    GLIO_HIP_CHECK(hipEventRecord(b->ev1, b->stream));
-    GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
-    float ms = 0;
-    GLIO_HIP_CHECK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-    *ms_out = ms / reps;
-    return GLIO_OK;
+        enqueue_batch_linearize_sel(b, BT_HOST_SEL, b->d_poses, b->d_poses, Hg_dev, Hg_dev, 0, b->K, mode);
+    });
 }
 
 // ---- helpers for a host that never includes HIP headers (glio_amd/host/glio_batch_backend.hpp): the reduced buffer lives on
@@ -1044,32 +1048,30 @@ int glio_batch_synchronize(glio_batch* b) {
     return GLIO_OK;
 }
 
+// (H + lambda diag H) x = g, b->d_delta = -x with the selected solver: block cyclic reduction, or the sequential banded Cholesky (two band rows
+// per lane above 64 rows) and its back substitution.  Returns the device flag the solver reports a breakdown in.
+static int* enqueue_banded_solve(glio_batch* b, const double* Hg_dev, const double lambda) {
+    const int K = b->K, band = b->band;
+    int* d_fail = reinterpret_cast<int*>(b->d_scalar + 2);
+    if (b->solver_mode == 1) {
+        glio_bcr_solve(b->bcr, Hg_dev, lambda, b->d_delta, &d_fail, b->stream);
+        return d_fail;
+    }
+    if (BB_ROWS(band) > 64)
+        hipLaunchKernelGGL(k_batch_factor<true>, dim3(1), dim3(BBF_THREADS), batch_factor_lds_doubles(band) * 8, b->stream, Hg_dev, K, band, lambda, b->d_M, b->d_y, d_fail);
+    else
+        hipLaunchKernelGGL(k_batch_factor<false>, dim3(1), dim3(BBF_THREADS), batch_factor_lds_doubles(band) * 8, b->stream, Hg_dev, K, band, lambda, b->d_M, b->d_y, d_fail);
+    hipLaunchKernelGGL(k_batch_backsolve, dim3(1), dim3(64), 0, b->stream, b->d_M, b->d_y, K, band, b->d_delta);
+    return d_fail;
+}
+
 // timing hook: average ms of `reps` banded solves (H + lambda diag H) x = g with the selected solver (HIP events on the batch stream)
 int glio_batch_time_solve(glio_batch* b, const double* Hg_dev, double lambda, int reps, float* ms_out) {
     if (!b || !Hg_dev || reps < 1 || !ms_out) return GLIO_E_ARG;
     GLIO_HIP_CHECK(hipSetDevice(b->device));
-    const int K = b->K, band = b->band;
-    int* d_fail = reinterpret_cast<int*>(b->d_scalar + 2);
-    for (int pass = 0; pass < 2; ++pass) {
-        if (pass == 1) GLIO_HIP_CHECK(hipEventRecord(b->ev0, b->stream));
-        for (int r = 0; r < (pass == 0 ? 1 : reps); ++r) {
-            int* d_fail_bcr = nullptr;
-            if (b->solver_mode == 1) glio_bcr_solve(b->bcr, Hg_dev, lambda, b->d_delta, &d_fail_bcr, b->stream);
-            else {
-                if (BB_ROWS(band) > 64)
-                    hipLaunchKernelGGL(k_batch_factor<true>, dim3(1), dim3(BBF_THREADS), batch_factor_lds_doubles(band) * 8, b->stream, Hg_dev, K, band, lambda, b->d_M, b->d_y, d_fail);
-                else
-                    hipLaunchKernelGGL(k_batch_factor<false>, dim3(1), dim3(BBF_THREADS), batch_factor_lds_doubles(band) * 8, b->stream, Hg_dev, K, band, lambda, b->d_M, b->d_y, d_fail);
-                hipLaunchKernelGGL(k_batch_backsolve, dim3(1), dim3(64), 0, b->stream, b->d_M, b->d_y, K, band, b->d_delta);
-            }
-        }
-        if (pass == 1) GLIO_HIP_CHECK(hipEventRecord(b->ev1, b->stream));
-        GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
-    }
-    float ms = 0;
-    GLIO_HIP_CHECK(hipEventElapsedTime(&ms, b->ev0, b->ev1));
-    *ms_out = ms / reps;
-    return GLIO_OK;
+    enqueue_banded_solve(b, Hg_dev, lambda);          // warm-up
+    GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
+    return time_enqueues(b, reps, ms_out, [&] { enqueue_banded_solve(b, Hg_dev, lambda); });
 }
 
 int glio_batch_step_dev(glio_batch* b, const double* Hg_dev, double lambda, const double* poses_in, double* poses_out, double* model_decrease) {
@@ -1077,18 +1079,11 @@ int glio_batch_step_dev(glio_batch* b, const double* Hg_dev, double lambda, cons
     if (!b || !Hg_dev || !poses_in || !poses_out) return GLIO_E_ARG;
     GLIO_HIP_CHECK(hipSetDevice(b->device));
     const int K = b->K, band = b->band;
-    memcpy(b->h_poses, poses_in, (size_t)K * 7 * 8);
-    GLIO_HIP_CHECK(hipMemcpyAsync(b->d_poses, b->h_poses, (size_t)K * 7 * 8, hipMemcpyHostToDevice, b->stream));
+    { const int rc = glio_batch_upload_poses(b, poses_in); if (rc) return rc; }
     GLIO_HIP_CHECK(hipMemsetAsync(b->d_scalar, 0, 4 * 8, b->stream));
     int* d_fail = reinterpret_cast<int*>(b->d_scalar + 2);
-    int* d_fail_bcr = nullptr;
-    if (b->solver_mode == 1) glio_bcr_solve(b->bcr, Hg_dev, lambda, b->d_delta, &d_fail_bcr, b->stream);
-    else if (BB_ROWS(band) > 64)
-        hipLaunchKernelGGL(k_batch_factor<true>, dim3(1), dim3(BBF_THREADS), batch_factor_lds_doubles(band) * 8, b->stream, Hg_dev, K, band, lambda, b->d_M, b->d_y, d_fail);
-    else
-        hipLaunchKernelGGL(k_batch_factor<false>, dim3(1), dim3(BBF_THREADS), batch_factor_lds_doubles(band) * 8, b->stream, Hg_dev, K, band, lambda, b->d_M, b->d_y, d_fail);
-    if (b->solver_mode != 1) hipLaunchKernelGGL(k_batch_backsolve, dim3(1), dim3(64), 0, b->stream, b->d_M, b->d_y, K, band, b->d_delta);
-    if (d_fail_bcr) GLIO_HIP_CHECK(hipMemcpyAsync(d_fail, d_fail_bcr, 4, hipMemcpyDeviceToDevice, b->stream));
+    int* d_fail_solver = enqueue_banded_solve(b, Hg_dev, lambda);
+    if (d_fail_solver != d_fail) GLIO_HIP_CHECK(hipMemcpyAsync(d_fail, d_fail_solver, 4, hipMemcpyDeviceToDevice, b->stream));
     hipLaunchKernelGGL(k_batch_apply, dim3((K + 255) / 256), dim3(256), 0, b->stream, Hg_dev, b->d_delta, b->d_poses, K, band, b->d_newposes, b->d_parts);
     hipLaunchKernelGGL(k_batch_apply_sum, dim3(1), dim3(64), 0, b->stream, b->d_parts, (K + 255) / 256, b->d_scalar);
     GLIO_HIP_CHECK(hipGetLastError());

@@ -128,6 +128,32 @@ __device__ long long g_bcr_stamps[8];      // elim2, workgroup 0: [0] load, [1] 
 #define BCR_T(var) do { } while (0)
 #define BCR_ACC(k, t1, t0) do { } while (0)
 #endif
+// ------------------------------------------------------------------------------------------------ the register-step panel factorisation
+// N register steps over a panel of N columns, one row per lane (a = the lane's row; rows 0..N-1 the diagonal block, the rows below are solved
+// against it): the (unscaled) column j of the diagonal block goes through the double-buffered LDS row col[2][N], ONE workgroup barrier per
+// pivot.  ROWS: the rows of the panel (lanes past them idle); 0 = every launched lane is a row (k_bcr_elim launches BcrCfg<M>::THREADS lanes
+// and guards only row >= j).  Ends with a barrier.  Used by k_bcr_elim<M>, k_bcr_pre and k_bcr_pre12.
+template <int N, int ROWS>
+__device__ __forceinline__ void bcr_register_steps(double (&a)[N], const int row, double (*col)[N], int* s_bad) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+        if (row >= j && row < N) col[j & 1][row] = a[j];
+        __syncthreads();
+        const double piv = col[j & 1][j];
+        double rd;
+        if (!(piv > 0.0) || !isfinite(piv)) { rd = 1.0; if (row == j) *s_bad = 1; } else rd = rsqrt(piv);
+        if (row >= j && (ROWS == 0 || row < ROWS)) {
+            const double lj = a[j] * rd;
+            a[j] = lj;
+            if (row > j) {
+#pragma unroll
+                for (int c = j + 1; c < N; ++c) a[c] -= lj * (col[j & 1][c] * rd);
+            }
+        }
+    }
+    __syncthreads();
+}
+
 // ------------------------------------------------------------------------------------------------ pre-elimination of the inner speed-bias blocks
 // A super-block of 6 keyframes x 15 unknowns.  KEPT (54): keyframe 0 whole (15), the poses of keyframes 1..4 (4 x 6), keyframe 5 whole (15)
 // -- everything that couples to another super-block (the pose band reaches +-6 keyframes, the IMU edge 5 -> 0' the neighbour's first
@@ -135,14 +161,37 @@ __device__ long long g_bcr_stamps[8];      // elim2, workgroup 0: [0] load, [1] 
 // super-block only.  k_bcr_pre forms, from the operator, [A_ii; A_ki; y_i^T] (91 rows x 36), factors it in 36 register steps (one row
 // per lane, one barrier per pivot, as k_bcr_elim) and writes the Schur complement A_kk - U U^T, y_k - U w as the super-block's 54 x 54
 // node; k_bcr_post recovers z_i = L^-T (w - U^T z_k) and writes the step of the super-block's keyframes.
+//
+// The same for bands 7..12 (round 4).  The reference gives the first and the last search_range keyframes of a batch a window of
+// +-2 search_range (Estimator.cpp:3009-3017): with the ImuFactor chain that is 15 unknowns per keyframe under a pose band of 12.
+// Super-blocks of 12 keyframes then (180 unknowns); KEPT (90): keyframe 0 whole, the poses of keyframes 1..10, keyframe 11 whole -- all that
+// reaches another super-block -- INNER (90): the speed-bias blocks of keyframes 1..10.  The reduction runs on the same 90 x 90 nodes as
+// the un-reduced band-6 problem would (k_bcr_pre12 / k_bcr_post12).
+//
+// BcrPre<SBK> is the shape of either; what the two kernel pairs share takes it as its parameter.  What they do NOT share, on purpose:
+//   - k_bcr_pre gathers its panel SOURCE-major into LDS (coalesced band rows and edge records, A_kk beside the panel in `dk`); k_bcr_pre12,
+//     the rare shape (two windows per batch want it), gathers entry by entry through bcr_scaled_entry and reads A_kk from the operator
+//     when the Schur complement is formed: its panel alone takes 134.7 KB of LDS, there is no room for A_kk, and the entry-major form was
+//     what k_bcr_pre replaced because it was bound by the L1's address path (comment at its gather).
+//   - k_bcr_post substitutes back inside one wavefront (36 unknowns: v_readlane, no barrier); k_bcr_post12 has 90 unknowns on two
+//     wavefronts and takes two barriers per column.
+//   - h_entry (batch_device.h, k_bcr_init) branches on the data; bcr_scaled_entry is its branch-free restatement for the gathers
+//     where every thread takes many entries (1.3 us per entry per thread with the branches, measured: comment at bcr_scaled_entry).
 typedef double v4f64 __attribute__((ext_vector_type(4)));
-#define PRE_NI 36
-#define PRE_NK 54
-#define PRE_ROWS (PRE_NI + PRE_NK + 1)
-__device__ __forceinline__ void pre_kept(const int i, int& kl, int& r) {
-    if (i < 15) { kl = 0; r = i; } else if (i < 39) { kl = 1 + (i - 15) / 6; r = (i - 15) % 6; } else { kl = 5; r = i - 39; }
-}
-__device__ __forceinline__ void pre_inner(const int p, int& kl, int& r) { kl = 1 + p / 9; r = 6 + p % 9; }
+template <int SBK> struct BcrPre {
+    static constexpr int B = 15, NI = 9 * (SBK - 2), NP = 6 * (SBK - 2), NK = NP + 2 * B, ROWS = NI + NK + 1;
+    // row stride of the panel [A_ii; A_ki; y_i^T]: NI + 1 where NI is a multiple of 4, else up to the next multiple of 4 and one more -- the
+    // MFMA loop reads k in fours, the columns past NI are zero
+    static constexpr int KP = ((NI + 3) / 4) * 4, LDP = KP + 1;
+    // kept unknown i -> keyframe of the super-block, unknown of the keyframe; inner unknown p likewise; and back
+    static __device__ __forceinline__ void kept(const int i, int& kl, int& r) {
+        if (i < B) { kl = 0; r = i; } else if (i < B + NP) { kl = 1 + (i - B) / 6; r = (i - B) % 6; } else { kl = SBK - 1; r = i - (B + NP); }
+    }
+    static __device__ __forceinline__ void inner(const int p, int& kl, int& r) { kl = 1 + p / 9; r = 6 + p % 9; }
+    static __device__ __forceinline__ int kept_of(const int kl, const int r) { return kl == 0 ? r : (kl == SBK - 1 ? B + NP + r : B + (kl - 1) * 6 + r); }
+};
+static_assert(BcrPre<6>::NI == 36 && BcrPre<6>::NK == 54 && BcrPre<6>::LDP == 37, "the 6-keyframe super-block");
+static_assert(BcrPre<12>::NI == 90 && BcrPre<12>::NK == 90 && BcrPre<12>::LDP == 93, "the 12-keyframe super-block");
 // S (H_band + H_imu) S + shift, entry (r, c) of block (ka, kb) -- the value of h_entry (batch_device.h) with scale and shift, written WITHOUT
 // data-dependent branches: every load goes to a clamped address and is selected afterwards, so the entries a thread gathers are independent
 // loads the hardware overlaps (with the branches of h_entry each entry cost a full memory round trip: 1.3 us per entry per thread, measured)
@@ -175,10 +224,87 @@ __device__ __forceinline__ double bcr_scaled_entry(const BcrOp& op, const HView&
     if (ka == kb && r == c) x += op.dadd ? da : op.lambda * x + 1e-12;
     return x;
 }
+// the coupling A[s+1][s] between the KEPT unknowns of neighbouring super-blocks (the inner blocks do not reach the neighbour): a gather,
+// two workgroups (blockIdx.y = 1, 2), eight entries in flight per thread
+template <int SBK>
+__device__ __forceinline__ void bcr_pre_coupling(const BcrOp& op, const HView& v, const int K, const int k0, double* __restrict__ dst) {
+    using P = BcrPre<SBK>;
+    constexpr int B = P::B, NK = P::NK, U = 8;
+    const int tid = threadIdx.x;
+    const int half = (NK * NK + 1) / 2, eb = (blockIdx.y - 1) * half, ee = min(NK * NK, eb + half);
+    for (int e0 = eb + tid; e0 < ee; e0 += U * 256) {
+        double x[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int e = e0 + u * 256, eo = e < ee ? e : eb;
+            int kli, ri, klj, cj;
+            P::kept(eo / NK, kli, ri); P::kept(eo % NK, klj, cj);
+            x[u] = bcr_scaled_entry(op, v, K, B, k0 + SBK + kli, ri, k0 + klj, cj);          // (zero when either keyframe is padding: different blocks)
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) { const int e = e0 + u * 256; if (e < ee) dst[e] = x[u]; }
+    }
+}
+// the finished panel in LDS ([A_ii; A_ki; y_i^T], one row per lane) -> NI register steps -> [L (zeros above the diagonal); U; w] back in the
+// panel; a non-positive or non-finite pivot raises bit 0 of *fail
+template <int SBK>
+__device__ __forceinline__ void bcr_pre_factor(double* __restrict__ pan, double (*col)[BcrPre<SBK>::NI], int* s_bad, int* fail) {
+    using P = BcrPre<SBK>;
+    constexpr int NI = P::NI, ROWS = P::ROWS, LDP = P::LDP;
+    const int row = threadIdx.x;
+    double a[NI];
+#pragma unroll
+    for (int c = 0; c < NI; ++c) a[c] = row < ROWS ? pan[row * LDP + c] : 0.0;
+    bcr_register_steps<NI, ROWS>(a, row, col, s_bad);
+    if (row < ROWS) {
+#pragma unroll
+        for (int c = 0; c < NI; ++c) pan[row * LDP + c] = (row < NI && c > row) ? 0.0 : a[c];
+    }
+    if (row == 0 && *s_bad) atomicOr(fail, 1);
+    __syncthreads();
+}
+// from the factored panel: L, U, w out (coalesced); the super-block's node A_kk - U U^T on the matrix core -- T x T tiles of 16 x 16 over the four
+// wavefronts, the old block (akk(r, c), r and c inside the block) as the accumulator's initial value -- and its right-hand side yk - U w
+template <int SBK, class Akk>
+__device__ __forceinline__ void bcr_pre_schur(const double* __restrict__ pan, const size_t sb, double* __restrict__ preL, double* __restrict__ preU,
+                                              double* __restrict__ prew, double* __restrict__ D, double* __restrict__ y, const double yk, const Akk akk) {
+    using P = BcrPre<SBK>;
+    constexpr int NI = P::NI, NK = P::NK, LDP = P::LDP, T = (NK + 15) / 16;
+    const int tid = threadIdx.x;
+    for (int e = tid; e < NI * NI; e += 256) preL[sb * NI * NI + e] = pan[(e / NI) * LDP + e % NI];
+    for (int e = tid; e < NK * NI; e += 256) preU[sb * NK * NI + e] = pan[(NI + e / NI) * LDP + e % NI];
+    if (tid < NI) prew[sb * NI + tid] = pan[(NI + NK) * LDP + tid];
+    const int wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
+    for (int tile = wave; tile < T * T; tile += 4) {
+        const int I = tile / T, J = tile - T * I;
+        v4f64 c;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int r = 16 * I + lk + 4 * q, cc = 16 * J + li;
+            const double x = akk(r < NK ? r : 0, cc < NK ? cc : 0);
+            c[q] = (r < NK && cc < NK) ? x : 0.0;
+        }
+        const int ra = 16 * I + li, rb = 16 * J + li;
+        const double* pa = pan + (NI + (ra < NK ? ra : 0)) * LDP + lk;
+        const double* pb = pan + (NI + (rb < NK ? rb : 0)) * LDP + lk;
+#pragma unroll
+        for (int kk = 0; kk < P::KP; kk += 4) c = __builtin_amdgcn_mfma_f64_16x16x4f64(ra < NK ? -pa[kk] : 0.0, rb < NK ? pb[kk] : 0.0, c, 0, 0, 0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { const int r = 16 * I + lk + 4 * q, cc = 16 * J + li; if (r < NK && cc < NK) D[r * NK + cc] = c[q]; }
+    }
+    if (y && tid < NK) {
+        const double* ui = pan + (NI + tid) * LDP; const double* wv = pan + (NI + NK) * LDP;
+        double s0 = 0;
+#pragma unroll 6
+        for (int c = 0; c < NI; ++c) s0 += ui[c] * wv[c];
+        y[tid] = yk - s0;
+    }
+}
 __global__ __launch_bounds__(256) void k_bcr_pre(const BcrOp op, const BcrInit* __restrict__ tab, const int K, const int band, const int Slo, double* __restrict__ ws,
                                                  double* __restrict__ preL, double* __restrict__ preU, double* __restrict__ prew, int* fail) {
     if (op.skip && *op.skip) return;
-    constexpr int B = 15, NI = PRE_NI, NK = PRE_NK, LDP = NI + 1;
+    using P = BcrPre<6>;
+    constexpr int B = P::B, NI = P::NI, NK = P::NK, LDP = P::LDP, PRE_ROWS = P::ROWS;
     __shared__ double pan[PRE_ROWS * LDP];         // [A_ii; A_ki; y_i] rows of 36 (+1 pad), later U (rows 36..89) and w (row 90)
     __shared__ double dk[NK * NK + NK];            // A_kk, y_k
     __shared__ double col[2][NI];
@@ -190,22 +316,7 @@ __global__ __launch_bounds__(256) void k_bcr_pre(const BcrOp op, const BcrInit* 
     const int s = t.sblock, k0 = s * 6, tid = threadIdx.x;
     constexpr int U = 8;
     if (blockIdx.y > 0) {
-        // ---- the coupling A[s+1][s] between the KEPT unknowns (the inner blocks do not reach the neighbour): a gather, two workgroups
-        if (t.oC < 0) return;
-        const int half = (NK * NK + 1) / 2, eb = (blockIdx.y - 1) * half, ee = min(NK * NK, eb + half);
-        for (int e0 = eb + tid; e0 < ee; e0 += U * 256) {
-            double x[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int e = e0 + u * 256, eo = e < ee ? e : eb;
-                int kli, ri, klj, cj;
-                pre_kept(eo / NK, kli, ri); pre_kept(eo % NK, klj, cj);
-                const int kr = k0 + 6 + kli, kb = k0 + klj;
-                x[u] = bcr_scaled_entry(op, v, K, B, kr, ri, kb, cj);          // (zero when either keyframe is padding: different blocks)
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) { const int e = e0 + u * 256; if (e < ee) ws[t.oC + e] = x[u]; }
-        }
+        if (t.oC >= 0) bcr_pre_coupling<6>(op, v, K, k0, ws + t.oC);
         return;
     }
     if (t.oD < 0) return;
@@ -309,7 +420,7 @@ __global__ __launch_bounds__(256) void k_bcr_pre(const BcrOp op, const BcrInit* 
     __syncthreads();
     {   // pass 4: scale, shift, identity padding, right-hand sides
         auto u_inner = [&](const int pp) { return (1 + pp / 9) * B + 6 + pp % 9; };
-        auto u_kept = [&](const int i) { int kl, r; pre_kept(i, kl, r); return kl * B + r; };
+        auto u_kept = [&](const int i) { int kl, r; P::kept(i, kl, r); return kl * B + r; };
         auto finish = [&](double& cellv, const int ur, const int uc) {
             const bool pad = k0 + ur / B >= K || k0 + uc / B >= K;
             double x = cellv * (scl[ur] * scl[uc]);
@@ -328,74 +439,60 @@ __global__ __launch_bounds__(256) void k_bcr_pre(const BcrOp op, const BcrInit* 
     BCR_T(tq1);
     BCR_ACC(4, tq1, tq0);
     // ---- 36 register steps, one row per lane (rows 0..35 the inner block, 36..89 the kept rows, 90 the right-hand side)
-    const int row = tid;
-    double a[NI];
-#pragma unroll
-    for (int c = 0; c < NI; ++c) a[c] = row < PRE_ROWS ? pan[row * LDP + c] : 0.0;
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        if (row >= j && row < NI) col[j & 1][row] = a[j];
-        __syncthreads();
-        const double piv = col[j & 1][j];
-        double rd;
-        if (!(piv > 0.0) || !isfinite(piv)) { rd = 1.0; if (row == j) s_bad = 1; } else rd = rsqrt(piv);
-        if (row >= j && row < PRE_ROWS) {
-            const double lj = a[j] * rd;
-            a[j] = lj;
-            if (row > j) {
-#pragma unroll
-                for (int c = j + 1; c < NI; ++c) a[c] -= lj * (col[j & 1][c] * rd);
-            }
-        }
-    }
-    __syncthreads();
+    bcr_pre_factor<6>(pan, col, &s_bad, fail);
     BCR_T(tq2);
     BCR_ACC(5, tq2, tq1);
-    const size_t sb = (size_t)(s - Slo);
-    if (row < PRE_ROWS) {
-#pragma unroll
-        for (int c = 0; c < NI; ++c) pan[row * LDP + c] = (row < NI && c > row) ? 0.0 : a[c];
-    }
-    if (tid == 0 && s_bad) atomicOr(fail, 1);
-    __syncthreads();
-    // factors out (coalesced), Schur complement and right-hand side of the kept unknowns
-    for (int e = tid; e < NI * NI; e += 256) preL[sb * NI * NI + e] = pan[(e / NI) * LDP + e % NI];
-    for (int e = tid; e < NK * NI; e += 256) preU[sb * NK * NI + e] = pan[(NI + e / NI) * LDP + e % NI];
-    if (tid < NI) prew[sb * NI + tid] = pan[(NI + NK) * LDP + tid];
-    {   // A_kk - U U^T on the matrix core: 4 x 4 tiles of 16 x 16 over the four wavefronts, the old block as the accumulator's initial value
-        const int wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
-        for (int tile = wave; tile < 16; tile += 4) {
-            const int I = tile >> 2, J = tile & 3;
-            v4f64 c;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { const int r = 16 * I + lk + 4 * q, cc = 16 * J + li; c[q] = (r < NK && cc < NK) ? dk[r * NK + cc] : 0.0; }
-            const int ra = 16 * I + li, rb = 16 * J + li;
-            const double* pa = pan + (NI + (ra < NK ? ra : 0)) * LDP + lk;
-            const double* pb = pan + (NI + (rb < NK ? rb : 0)) * LDP + lk;
-#pragma unroll
-            for (int kk = 0; kk < NI; kk += 4) c = __builtin_amdgcn_mfma_f64_16x16x4f64(ra < NK ? -pa[kk] : 0.0, rb < NK ? pb[kk] : 0.0, c, 0, 0, 0);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { const int r = 16 * I + lk + 4 * q, cc = 16 * J + li; if (r < NK && cc < NK) ws[t.oD + r * NK + cc] = c[q]; }
-        }
-    }
-    if (t.oy >= 0 && tid < NK) {
-        const double* ui = pan + (NI + tid) * LDP; const double* wv = pan + (NI + NK) * LDP;
-        double s0 = 0;
-#pragma unroll
-        for (int c = 0; c < NI; ++c) s0 += ui[c] * wv[c];
-        ws[t.oy + tid] = dk[NK * NK + tid] - s0;
-    }
+    // factors out, Schur complement (A_kk from its LDS copy) and right-hand side of the kept unknowns
+    bcr_pre_schur<6>(pan, (size_t)(s - Slo), preL, preU, prew, ws + t.oD, t.oy >= 0 ? ws + t.oy : nullptr, tid < NK ? dk[NK * NK + tid] : 0.0,
+                     [&](const int r, const int c) { return dk[r * NK + c]; });
 #ifdef GLIO_DEV_STAMPS
     __syncthreads();
     { BCR_T(tq3); BCR_ACC(6, tq3, tq2); }
 #endif
+}
+// entry `i` of t = w - U^T z_k of super-block sb (i < NI): the column of U is eighteen independent global loads at a time, the sum keeps three
+// interleaved chains
+template <int SBK>
+__device__ __forceinline__ double bcr_post_rhs(const double* __restrict__ preU, const double* __restrict__ prew, const double* __restrict__ zk, const int sb, const int i) {
+    using P = BcrPre<SBK>;
+    constexpr int NI = P::NI, NK = P::NK;
+    static_assert(NK % 18 == 0, "chunk of the U^T z sums");
+    const double* Uc = preU + (size_t)sb * NK * NI + i;
+    double p3[3] = {0, 0, 0};
+#pragma unroll
+    for (int i0 = 0; i0 < NK; i0 += 18) {
+        double uv[18];
+#pragma unroll
+        for (int u = 0; u < 18; ++u) uv[u] = Uc[(size_t)(i0 + u) * NI];
+#pragma unroll
+        for (int u = 0; u < 18; ++u) p3[u % 3] += uv[u] * zk[i0 + u];
+    }
+    return prew[(size_t)sb * NI + i] - ((p3[0] + p3[1]) + p3[2]);
+}
+// the step of the super-block's keyframes: delta = -z, the inner unknowns from zi, the kept ones from the node's solution zk; a non-finite
+// entry raises bit 1 of *fail
+template <int SBK>
+__device__ __forceinline__ void bcr_post_scatter(const double* __restrict__ zi, const double* __restrict__ zk, const int k0, const int K, const int nthreads,
+                                                 double* __restrict__ delta, int* fail) {
+    using P = BcrPre<SBK>;
+    constexpr int B = P::B;
+    for (int e = threadIdx.x; e < SBK * B; e += nthreads) {
+        const int kl = e / B, r = e - B * kl, k = k0 + kl;
+        if (k >= K) continue;
+        double val;
+        if (r >= 6 && kl >= 1 && kl <= SBK - 2) val = zi[(kl - 1) * 9 + r - 6];
+        else val = zk[P::kept_of(kl, r)];
+        val = -val;
+        if (!isfinite(val)) atomicOr(fail, 2);
+        delta[(size_t)k * B + r] = val;
+    }
 }
 // z_i = L^-T (w - U^T z_k) of one owned super-block, then the step of its keyframes: delta = -z (kept unknowns from the node's solution)
 __global__ __launch_bounds__(64) void k_bcr_post(const int* skip, const double* __restrict__ z, const int* __restrict__ node_of, const int Slo, const int K,
                                                  const double* __restrict__ preL, const double* __restrict__ preU, const double* __restrict__ prew,
                                                  double* __restrict__ delta, int* fail) {
     if (skip && *skip) return;
-    constexpr int B = 15, NI = PRE_NI, NK = PRE_NK, LDL = NI + 1;
+    constexpr int NI = BcrPre<6>::NI, NK = BcrPre<6>::NK, LDL = NI + 1;
     __shared__ double Ls[NI * LDL], zk[NK], rd[NI], zi[NI];
     const int sb = blockIdx.x, lane = threadIdx.x, s = Slo + sb, k0 = s * 6;
     const int node = node_of[sb];
@@ -411,17 +508,7 @@ __global__ __launch_bounds__(64) void k_bcr_post(const int* skip, const double* 
     double t = 0.0;
     if (lane < NI) {
         rd[lane] = 1.0 / Ls[lane * LDL + lane];
-        const double* Uc = preU + (size_t)sb * NK * NI + lane;
-        double p3[3] = {0, 0, 0};
-#pragma unroll
-        for (int i0 = 0; i0 < NK; i0 += 18) {
-            double uv[18];
-#pragma unroll
-            for (int u = 0; u < 18; ++u) uv[u] = Uc[(size_t)(i0 + u) * NI];
-#pragma unroll
-            for (int u = 0; u < 18; ++u) p3[u % 3] += uv[u] * zk[i0 + u];
-        }
-        t = prew[(size_t)sb * NI + lane] - ((p3[0] + p3[1]) + p3[2]);
+        t = bcr_post_rhs<6>(preU, prew, zk, sb, lane);
     }
     __syncthreads();
 #pragma unroll
@@ -432,38 +519,18 @@ __global__ __launch_bounds__(64) void k_bcr_post(const int* skip, const double* 
     }
     if (lane < NI) zi[lane] = t;
     __syncthreads();
-    for (int e = lane; e < 6 * B; e += 64) {
-        const int kl = e / B, r = e - B * kl, k = k0 + kl;
-        if (k >= K) continue;
-        double val;
-        if (r >= 6 && kl >= 1 && kl <= 4) val = zi[(kl - 1) * 9 + r - 6];
-        else val = zk[kl == 0 ? r : (kl == 5 ? 39 + r : 15 + (kl - 1) * 6 + r)];
-        val = -val;
-        if (!isfinite(val)) atomicOr(fail, 2);
-        delta[(size_t)k * B + r] = val;
-    }
+    bcr_post_scatter<6>(zi, zk, k0, K, 64, delta, fail);
 }
 
-// ------------------------------------------------------------------------------------------------ the same for bands 7..12 (round 4)
-// The reference gives the first and the last search_range keyframes of a batch a window of +-2 search_range (Estimator.cpp:3009-3017): with
-// the ImuFactor chain that is 15 unknowns per keyframe under a pose band of 12.  Super-blocks of 12 keyframes then (180 unknowns); KEPT (90):
-// keyframe 0 whole, the poses of keyframes 1..10, keyframe 11 whole -- all that reaches another super-block -- INNER (90): the speed-bias
-// blocks of keyframes 1..10.  The reduction runs on the same 90 x 90 nodes as the un-reduced band-6 problem would.  This is the rare shape
-// (two windows per batch want it): the panel is gathered entry by entry through bcr_scaled_entry and lives in LDS ([A_ii; A_ki; y_i^T],
-// 181 rows of 90 + 2 zero columns = 134.7 KB, dynamic), A_kk is read from the operator when the Schur complement is formed.
-#define PRE12_NI 90
-#define PRE12_NK 90
-#define PRE12_LDP 93
-#define PRE12_ROWS (PRE12_NI + PRE12_NK + 1)
-#define PRE12_LDS ((size_t)(PRE12_ROWS * PRE12_LDP + 2 * PRE12_NI) * 8 + 16)
-__device__ __forceinline__ void pre12_kept(const int i, int& kl, int& r) {
-    if (i < 15) { kl = 0; r = i; } else if (i < 75) { kl = 1 + (i - 15) / 6; r = (i - 15) % 6; } else { kl = 11; r = i - 75; }
-}
-__device__ __forceinline__ void pre12_inner(const int p, int& kl, int& r) { kl = 1 + p / 9; r = 6 + p % 9; }
+// ------------------------------------------------------------------------------------------------ the same for bands 7..12 (BcrPre<12>, above)
+// The panel is gathered entry by entry through bcr_scaled_entry and lives in LDS ([A_ii; A_ki; y_i^T], 181 rows of 90 + 3 zero columns =
+// 134.7 KB, dynamic, then col[2][90] and the flag); A_kk is read from the operator when the Schur complement is formed.
+#define PRE12_LDS ((size_t)(BcrPre<12>::ROWS * BcrPre<12>::LDP + 2 * BcrPre<12>::NI) * 8 + 16)
 __global__ __launch_bounds__(256) void k_bcr_pre12(const BcrOp op, const BcrInit* __restrict__ tab, const int K, const int band, const int Slo, double* __restrict__ ws,
                                                    double* __restrict__ preL, double* __restrict__ preU, double* __restrict__ prew, int* fail) {
     if (op.skip && *op.skip) return;
-    constexpr int B = 15, NI = PRE12_NI, NK = PRE12_NK, LDP = PRE12_LDP, ROWS = PRE12_ROWS, SBK = 12;
+    using P = BcrPre<12>;
+    constexpr int B = P::B, NI = P::NI, NK = P::NK, LDP = P::LDP, ROWS = P::ROWS, SBK = 12;
     extern __shared__ double pre12_lds[];
     double* pan = pre12_lds;                              // [ROWS][LDP]
     double (*col)[NI] = reinterpret_cast<double (*)[NI]>(pre12_lds + ROWS * LDP);       // [2][NI]
@@ -475,27 +542,13 @@ __global__ __launch_bounds__(256) void k_bcr_pre12(const BcrOp op, const BcrInit
     const int s = t.sblock, k0 = s * SBK, tid = threadIdx.x;
     constexpr int U = 8;
     if (blockIdx.y > 0) {
-        // the coupling A[s+1][s] between the KEPT unknowns of neighbouring super-blocks (the inner blocks do not reach the neighbour)
-        if (t.oC < 0) return;
-        const int half = (NK * NK + 1) / 2, eb = (blockIdx.y - 1) * half, ee = min(NK * NK, eb + half);
-        for (int e0 = eb + tid; e0 < ee; e0 += U * 256) {
-            double x[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int e = e0 + u * 256, eo = e < ee ? e : eb;
-                int kli, ri, klj, cj;
-                pre12_kept(eo / NK, kli, ri); pre12_kept(eo % NK, klj, cj);
-                x[u] = bcr_scaled_entry(op, v, K, B, k0 + SBK + kli, ri, k0 + klj, cj);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) { const int e = e0 + u * 256; if (e < ee) ws[t.oC + e] = x[u]; }
-        }
+        if (t.oC >= 0) bcr_pre_coupling<12>(op, v, K, k0, ws + t.oC);
         return;
     }
     if (t.oD < 0) return;
     if (tid == 0) *s_bad = 0;
-    auto unk_inner = [&](const int pp, int& k, int& r) { int kl; pre12_inner(pp, kl, r); k = k0 + kl; };
-    auto unk_kept = [&](const int i, int& k, int& r) { int kl; pre12_kept(i, kl, r); k = k0 + kl; };
+    auto unk_inner = [&](const int pp, int& k, int& r) { int kl; P::inner(pp, kl, r); k = k0 + kl; };
+    auto unk_kept = [&](const int i, int& k, int& r) { int kl; P::kept(i, kl, r); k = k0 + kl; };
     auto rhs = [&](const int k, const int r) -> double {
         if (k >= K) return 0.0;
         return gsrc[(size_t)k * B + r] * (op.sc ? op.sc[(size_t)k * B + r] : 1.0);
@@ -519,73 +572,22 @@ __global__ __launch_bounds__(256) void k_bcr_pre12(const BcrOp op, const BcrInit
     for (int e = tid; e < ROWS * (LDP - NI); e += 256) pan[(e / (LDP - NI)) * LDP + NI + e % (LDP - NI)] = 0.0;
     __syncthreads();
     // ---- 90 register steps, one row per lane (rows 0..89 the inner block, 90..179 the kept rows, 180 the right-hand side)
-    const int row = tid;
-    double a[NI];
-#pragma unroll
-    for (int c = 0; c < NI; ++c) a[c] = row < ROWS ? pan[row * LDP + c] : 0.0;
-#pragma unroll
-    for (int j = 0; j < NI; ++j) {
-        if (row >= j && row < NI) col[j & 1][row] = a[j];
-        __syncthreads();
-        const double piv = col[j & 1][j];
-        double rd;
-        if (!(piv > 0.0) || !isfinite(piv)) { rd = 1.0; if (row == j) *s_bad = 1; } else rd = rsqrt(piv);
-        if (row >= j && row < ROWS) {
-            const double lj = a[j] * rd;
-            a[j] = lj;
-            if (row > j) {
-#pragma unroll
-                for (int c = j + 1; c < NI; ++c) a[c] -= lj * (col[j & 1][c] * rd);
-            }
-        }
-    }
-    __syncthreads();
-    const size_t sb = (size_t)(s - Slo);
-    if (row < ROWS) {
-#pragma unroll
-        for (int c = 0; c < NI; ++c) pan[row * LDP + c] = (row < NI && c > row) ? 0.0 : a[c];
-    }
-    if (tid == 0 && *s_bad) atomicOr(fail, 1);
-    __syncthreads();
-    for (int e = tid; e < NI * NI; e += 256) preL[sb * NI * NI + e] = pan[(e / NI) * LDP + e % NI];
-    for (int e = tid; e < NK * NI; e += 256) preU[sb * NK * NI + e] = pan[(NI + e / NI) * LDP + e % NI];
-    if (tid < NI) prew[sb * NI + tid] = pan[(NI + NK) * LDP + tid];
-    {   // A_kk - U U^T on the matrix core: 6 x 6 tiles of 16 x 16 over the four wavefronts; A_kk from the operator as the accumulator's start
-        const int wave = tid >> 6, lane = tid & 63, li = lane & 15, lk = lane >> 4;
-        for (int tile = wave; tile < 36; tile += 4) {
-            const int I = tile / 6, J = tile - 6 * I;
-            v4f64 c;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int r = 16 * I + lk + 4 * q, cc = 16 * J + li;
-                int ka, ra, kb, cb;
-                unk_kept(r < NK ? r : 0, ka, ra); unk_kept(cc < NK ? cc : 0, kb, cb);
-                c[q] = (r < NK && cc < NK) ? bcr_scaled_entry(op, v, K, B, ka, ra, kb, cb) : 0.0;
-            }
-            const int ra_ = 16 * I + li, rb_ = 16 * J + li;
-            const double* pa = pan + (NI + (ra_ < NK ? ra_ : 0)) * LDP + lk;
-            const double* pb = pan + (NI + (rb_ < NK ? rb_ : 0)) * LDP + lk;
-#pragma unroll
-            for (int kk = 0; kk < NI + 2; kk += 4) c = __builtin_amdgcn_mfma_f64_16x16x4f64(ra_ < NK ? -pa[kk] : 0.0, rb_ < NK ? pb[kk] : 0.0, c, 0, 0, 0);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) { const int r = 16 * I + lk + 4 * q, cc = 16 * J + li; if (r < NK && cc < NK) ws[t.oD + r * NK + cc] = c[q]; }
-        }
-    }
-    if (t.oy >= 0 && tid < NK) {
-        const double* ui = pan + (NI + tid) * LDP; const double* wv = pan + (NI + NK) * LDP;
-        double s0 = 0;
-#pragma unroll 6
-        for (int c = 0; c < NI; ++c) s0 += ui[c] * wv[c];
-        int k, r; unk_kept(tid, k, r);
-        ws[t.oy + tid] = rhs(k, r) - s0;
-    }
+    bcr_pre_factor<12>(pan, col, s_bad, fail);
+    // factors out, Schur complement (A_kk from the operator) and right-hand side of the kept unknowns
+    double yk = 0.0;
+    if (t.oy >= 0 && tid < NK) { int k, r; unk_kept(tid, k, r); yk = rhs(k, r); }
+    bcr_pre_schur<12>(pan, (size_t)(s - Slo), preL, preU, prew, ws + t.oD, t.oy >= 0 ? ws + t.oy : nullptr, yk, [&](const int r, const int c) {
+        int ka, ra, kb, cb;
+        unk_kept(r, ka, ra); unk_kept(c, kb, cb);
+        return bcr_scaled_entry(op, v, K, B, ka, ra, kb, cb);
+    });
 }
 // z_i = L^-T (w - U^T z_k) of one owned 12-keyframe super-block, then the step of its keyframes
 __global__ __launch_bounds__(128) void k_bcr_post12(const int* skip, const double* __restrict__ z, const int* __restrict__ node_of, const int Slo, const int K,
                                                     const double* __restrict__ preL, const double* __restrict__ preU, const double* __restrict__ prew,
                                                     double* __restrict__ delta, int* fail) {
     if (skip && *skip) return;
-    constexpr int B = 15, NI = PRE12_NI, NK = PRE12_NK, LDL = NI + 1, SBK = 12;
+    constexpr int NI = BcrPre<12>::NI, NK = BcrPre<12>::NK, LDL = NI + 1, SBK = 12;
     extern __shared__ double post12_lds[];
     double* Ls = post12_lds;                 // [NI][LDL]
     double* zk = Ls + NI * LDL;              // [NK]
@@ -595,15 +597,7 @@ __global__ __launch_bounds__(128) void k_bcr_post12(const int* skip, const doubl
     if (tid < NK) zk[tid] = z[(size_t)node * NK + tid];
     for (int e = tid; e < NI * NI; e += 128) Ls[(e / NI) * LDL + e % NI] = preL[(size_t)sb * NI * NI + e];
     __syncthreads();
-    if (tid < NI) {
-        const double* Uc = preU + (size_t)sb * NK * NI + tid;
-        double p3[3] = {0, 0, 0};
-        for (int i0 = 0; i0 < NK; i0 += 18) {
-#pragma unroll
-            for (int u = 0; u < 18; ++u) p3[u % 3] += Uc[(size_t)(i0 + u) * NI] * zk[i0 + u];
-        }
-        zi[tid] = prew[(size_t)sb * NI + tid] - ((p3[0] + p3[1]) + p3[2]);
-    }
+    if (tid < NI) zi[tid] = bcr_post_rhs<12>(preU, prew, zk, sb, tid);
     __syncthreads();
     for (int r = NI - 1; r >= 0; --r) {              // back substitution L^T z = t, one column per step
         if (tid == r) zi[r] = zi[r] / Ls[r * LDL + r];
@@ -611,18 +605,9 @@ __global__ __launch_bounds__(128) void k_bcr_post12(const int* skip, const doubl
         if (tid < r) zi[tid] -= Ls[r * LDL + tid] * zi[r];
         __syncthreads();
     }
-    for (int e = tid; e < SBK * B; e += 128) {
-        const int kl = e / B, r = e - B * kl, k = k0 + kl;
-        if (k >= K) continue;
-        double val;
-        if (r >= 6 && kl >= 1 && kl <= 10) val = zi[(kl - 1) * 9 + r - 6];
-        else val = zk[kl == 0 ? r : (kl == 11 ? 75 + r : 15 + (kl - 1) * 6 + r)];
-        val = -val;
-        if (!isfinite(val)) atomicOr(fail, 2);
-        delta[(size_t)k * B + r] = val;
-    }
+    bcr_post_scatter<12>(zi, zk, k0, K, 128, delta, fail);
 }
-#define POST12_LDS ((size_t)(PRE12_NI * (PRE12_NI + 1) + PRE12_NK + PRE12_NI) * 8)
+#define POST12_LDS ((size_t)(BcrPre<12>::NI * (BcrPre<12>::NI + 1) + BcrPre<12>::NK + BcrPre<12>::NI) * 8)
 
 // ------------------------------------------------------------------------------------------------ elimination
 template <int M> struct BcrCfg { static constexpr int ROWS = 3 * M + 1; static constexpr int THREADS = ((ROWS + 63) / 64) * 64; };
@@ -662,24 +647,7 @@ __global__ __launch_bounds__(BcrCfg<M>::THREADS) void k_bcr_elim(const int* skip
 #pragma unroll
         for (int c = 0; c < M; ++c) a[c] = src[c];
     }
-    // M register steps, one barrier each: the (unscaled) column j of the diagonal block goes through a double-buffered LDS row
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-        if (row >= j && row < M) col[j & 1][row] = a[j];
-        __syncthreads();
-        const double piv = col[j & 1][j];
-        double rd;
-        if (!(piv > 0.0) || !isfinite(piv)) { rd = 1.0; if (row == j) s_bad = 1; } else rd = rsqrt(piv);
-        if (row >= j) {
-            const double lj = a[j] * rd;
-            a[j] = lj;
-            if (row > j) {
-#pragma unroll
-                for (int c = j + 1; c < M; ++c) a[c] -= lj * (col[j & 1][c] * rd);
-            }
-        }
-    }
-    __syncthreads();
+    bcr_register_steps<M, 0>(a, row, col, &s_bad);          // (every launched lane is a row: the lanes past 3 M carry zeros)
     if (row == 0 && s_bad) atomicOr(fail, 1);
     if (row < M) {
         double* dst = L + (size_t)t.node * MM + (size_t)row * M;
@@ -706,7 +674,8 @@ __global__ __launch_bounds__(BcrCfg<M>::THREADS) void k_bcr_elim(const int* skip
 // redundantly, pivots and multipliers by v_readlane) and 48 of the rows below in lanes 16-63, so the 16 register steps factor the
 // block AND solve those rows; the trailing part takes its rank-16 update as v_mfma_f64_16x16x4 tiles with operands read from LDS
 // (the scheme of the window solver's packed LDS Cholesky, solver_kernels.hip, extended by the coupling rows).  Two barriers per
-// PANEL instead of one per pivot.  LDS: the packed lower triangle of A_pp (rows at i (i + 1) / 2) + M + 1 full rows
+// PANEL instead of one per pivot.  (Another algorithm than k_bcr_elim, not a second writing of it: both stay, chosen by size -- the
+// register steps are the faster ones at M = 36, 15 vs 19 us; see g_bcr_elim_mode.)  LDS: the packed lower triangle of A_pp (rows at i (i + 1) / 2) + M + 1 full rows
 // (A_ap, y, A_bp: 2 M + 1 rows; at M = 90 that is 159.3 of the 160 KB).
 #define BCR_E2_THREADS 512
 template <int M> struct BcrE2 {
@@ -1007,6 +976,7 @@ __global__ __launch_bounds__(BCR_UP_THREADS) void k_bcr_update(const int* skip, 
 }
 
 // ------------------------------------------------------------------------------------------------ back substitution
+template <int M> struct BcrBack { static constexpr size_t lds_bytes = (size_t)(M * (M + 1) + 3 * M + 4 * 128) * 8; };      // Ls, za, zb, rd, pt
 template <int M>
 __global__ __launch_bounds__(512) void k_bcr_back(const int* skip, const BcrElim* __restrict__ tab, const double* __restrict__ L, const double* __restrict__ Ua,
                                                   const double* __restrict__ Ub, const double* __restrict__ w, double* __restrict__ z) {
@@ -1135,13 +1105,23 @@ static void bcr_build_schedule(std::vector<int> act, std::vector<char> pinned, s
     if (final_edge) *final_edge = (act.size() == 2 && edgeC.size() == 1) ? edgeC[0] : -1;
 }
 
+// dynamic LDS above 64 KB has to be allowed per kernel
+template <class Kernel>
+static void bcr_allow_lds(Kernel* k, const size_t bytes) { hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes); }
+template <int M>
+static void bcr_allow_lds() {
+    bcr_allow_lds(k_bcr_update<M>, BcrUp<M>::lds_bytes);
+    bcr_allow_lds(k_bcr_elim2<M>, BcrE2<M>::lds_bytes);
+    bcr_allow_lds(k_bcr_back<M>, BcrBack<M>::lds_bytes);
+}
+
 void* glio_bcr_create2(int K, int band, int B, int rank, int world) {
     if (band > 12 || (B != 6 && B != 15) || world < 1 || rank < 0 || rank >= world) return nullptr;
     BcrDev* b = new BcrDev();
     b->K = K; b->band = band; b->B = B; b->rank = rank; b->world = world;
     b->sbk = band <= 6 ? 6 : 12;
     b->pre = B == 15;
-    b->M = b->pre ? (b->sbk == 12 ? PRE12_NK : PRE_NK) : b->sbk * B;
+    b->M = b->pre ? (b->sbk == 12 ? BcrPre<12>::NK : BcrPre<6>::NK) : b->sbk * B;
     b->preL = b->preU = b->prew = nullptr;
     b->S = (K + b->sbk - 1) / b->sbk;
     if (b->S < world) { delete b; glio_set_error("batch solver: %d super-blocks cannot be spread over %d ranks", b->S, world); return nullptr; }
@@ -1217,10 +1197,7 @@ void* glio_bcr_create2(int K, int band, int B, int rank, int world) {
         for (int s = 0; s < NS; ++s) tact[s] = nint + s;
         for (int s = 0; s + 1 < NS; ++s) tedge.push_back(oCsep + (long long)s * MM);
         // new couplings of the top levels go to private edge slots behind the local ones
-        std::vector<BcrElim> e2; std::vector<BcrKept> k2;
         long long top_edge = next_edge;
-        const long long need = (long long)(NS + 2) * MM;
-        (void)need;
         bcr_build_schedule(tact, tpin, tedge, oD, oy, top_edge, MM, elim, kept, b->h_elim_off, b->h_kept_off, nullptr);
         if (top_edge - edge_base > edge_cap) { delete b; glio_set_error("batch solver: edge workspace exceeded (top)"); return nullptr; }
     }
@@ -1233,7 +1210,7 @@ void* glio_bcr_create2(int K, int band, int B, int rank, int world) {
               A((void**)&b->init, (init.size() + 1) * sizeof(BcrInit)) && A((void**)&b->node_of_sblock_dev, (size_t)(nown + 1) * 4);
     if (ok && b->pre) {
         const size_t no = (size_t)std::max(nown, 1);
-        const size_t ni = b->sbk == 12 ? PRE12_NI : PRE_NI, nk = b->sbk == 12 ? PRE12_NK : PRE_NK;
+        const size_t ni = b->sbk == 12 ? BcrPre<12>::NI : BcrPre<6>::NI, nk = b->sbk == 12 ? BcrPre<12>::NK : BcrPre<6>::NK;
         ok = A((void**)&b->preL, no * ni * ni * 8) && A((void**)&b->preU, no * nk * ni * 8) && A((void**)&b->prew, no * ni * 8);
     }
     if (!ok) { glio_set_error("batch solver: device allocation failed"); return nullptr; }
@@ -1242,17 +1219,9 @@ void* glio_bcr_create2(int K, int band, int B, int rank, int world) {
     if (!kept.empty()) hipMemcpy(b->kept, kept.data(), kept.size() * sizeof(BcrKept), hipMemcpyHostToDevice);
     if (!init.empty()) hipMemcpy(b->init, init.data(), init.size() * sizeof(BcrInit), hipMemcpyHostToDevice);
     hipMemcpy(b->node_of_sblock_dev, b->node_of_sblock.data(), (size_t)nown * 4, hipMemcpyHostToDevice);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_bcr_update<54>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BcrUp<54>::lds_bytes);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_bcr_elim2<54>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BcrE2<54>::lds_bytes);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_bcr_back<54>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((54 * 55 + 3 * 54 + 512) * 8));
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_bcr_update<72>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BcrUp<72>::lds_bytes);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_bcr_update<90>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BcrUp<90>::lds_bytes);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_bcr_elim2<72>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BcrE2<72>::lds_bytes);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_bcr_elim2<90>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)BcrE2<90>::lds_bytes);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_bcr_back<72>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((72 * 73 + 3 * 72 + 512) * 8));
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_bcr_back<90>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)((90 * 91 + 3 * 90 + 512) * 8));
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_bcr_pre12), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PRE12_LDS);
-    hipFuncSetAttribute(reinterpret_cast<const void*>(k_bcr_post12), hipFuncAttributeMaxDynamicSharedMemorySize, (int)POST12_LDS);
+    bcr_allow_lds<54>(); bcr_allow_lds<72>(); bcr_allow_lds<90>();          // (M = 36 stays below the 64 KB every kernel may take)
+    bcr_allow_lds(k_bcr_pre12, PRE12_LDS);
+    bcr_allow_lds(k_bcr_post12, POST12_LDS);
     (void)hipGetLastError();
     return b;
 }
@@ -1295,10 +1264,9 @@ static void bcr_levels(BcrDev* b, const BcrOp& op, int l0, int l1, hipStream_t s
 }
 template <int M>
 static void bcr_back(BcrDev* b, const BcrOp& op, int l0, int l1, hipStream_t stream) {
-    const size_t lds_back = (size_t)(M * (M + 1) + 3 * M + 4 * 128) * 8;
     for (int l = l1 - 1; l >= l0; --l) {
         const int ne = b->h_elim_off[l + 1] - b->h_elim_off[l];
-        if (ne > 0) hipLaunchKernelGGL((k_bcr_back<M>), dim3(ne), dim3(512), lds_back, stream, op.skip, b->elim + b->h_elim_off[l], b->L, b->Ua, b->Ub, b->w, b->z);
+        if (ne > 0) hipLaunchKernelGGL((k_bcr_back<M>), dim3(ne), dim3(512), BcrBack<M>::lds_bytes, stream, op.skip, b->elim + b->h_elim_off[l], b->L, b->Ua, b->Ub, b->w, b->z);
     }
 }
 #define BCR_DISPATCH(fn, ...) do { if (b->M == 36) fn<36>(__VA_ARGS__); else if (b->M == 54) fn<54>(__VA_ARGS__); else if (b->M == 72) fn<72>(__VA_ARGS__); else fn<90>(__VA_ARGS__); } while (0)

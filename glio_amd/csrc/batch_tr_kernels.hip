@@ -27,6 +27,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <thread>
 #include <vector>
 
@@ -726,8 +727,6 @@ __global__ void k_bt_mcc(const BtBufs a, const double* __restrict__ stage_e) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
-#define BT_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { glio_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); return GLIO_E_HIP; } } while (0)
-
 struct BatchSmall {
     int n_dq, n_dd, n_fac;
     int* d_fa; int* d_fb; int* d_ftype; int* d_fidx;      // sorted by ordered pair (a, b); only the factors this rank owns (a in [lo, hi))
@@ -777,14 +776,14 @@ static int small_ensure(glio_batch* b) {
     memset(s, 0, sizeof *s);
     const int K = b->K, band = b->band;
     s->rank = 0; s->world = 1; s->lo = 0; s->hi = K; s->B = 6;
-    BT_CHECK(hipMalloc((void**)&s->d_small_index, (size_t)K * (2 * band + 1) * sizeof(int2)));
-    BT_CHECK(hipMemset(s->d_small_index, 0, (size_t)K * (2 * band + 1) * sizeof(int2)));
-    BT_CHECK(hipMalloc((void**)&s->d_rel, 12 * 8));
-    BT_CHECK(hipMemset(s->d_rel, 0, 12 * 8));
-    BT_CHECK(hipMalloc((void**)&s->d_bnd_kf, 64 * 4));
-    BT_CHECK(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
-    BT_CHECK(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
-    BT_CHECK(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
+    GLIO_HIP_CHECK(hipMalloc((void**)&s->d_small_index, (size_t)K * (2 * band + 1) * sizeof(int2)));
+    GLIO_HIP_CHECK(hipMemset(s->d_small_index, 0, (size_t)K * (2 * band + 1) * sizeof(int2)));
+    GLIO_HIP_CHECK(hipMalloc((void**)&s->d_rel, 12 * 8));
+    GLIO_HIP_CHECK(hipMemset(s->d_rel, 0, 12 * 8));
+    GLIO_HIP_CHECK(hipMalloc((void**)&s->d_bnd_kf, 64 * 4));
+    GLIO_HIP_CHECK(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking));
+    GLIO_HIP_CHECK(hipEventCreateWithFlags(&s->ev_fork, hipEventDisableTiming));
+    GLIO_HIP_CHECK(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
     b->small = s;
     return GLIO_OK;
 }
@@ -830,30 +829,30 @@ static int tr_build(glio_batch* b, const int B) {
     const int NB = s->world - 1;
     s->bnd_doubles = (long long)NB * 2 * band * (band + 1) * 36;
     s->stage_doubles = s->bnd_doubles + 2 * n + 2;
-    BT_CHECK(hipMalloc((void**)&s->d_vec, (size_t)V_COUNT * s->vstride * 8));
-    BT_CHECK(hipMemset(s->d_vec, 0, (size_t)V_COUNT * s->vstride * 8));
+    GLIO_HIP_CHECK(hipMalloc((void**)&s->d_vec, (size_t)V_COUNT * s->vstride * 8));
+    GLIO_HIP_CHECK(hipMemset(s->d_vec, 0, (size_t)V_COUNT * s->vstride * 8));
     for (int k = 0; k < 2; ++k) {
-        BT_CHECK(hipMalloc((void**)&s->d_hg[k], hg * 8)); BT_CHECK(hipMemset(s->d_hg[k], 0, hg * 8));
-        BT_CHECK(hipMalloc((void**)&s->d_A[k], (size_t)(2 * n + 2) * 8));
-        BT_CHECK(hipMalloc((void**)&s->d_x[k], (size_t)K * 7 * 8)); BT_CHECK(hipMalloc((void**)&s->d_s[k], (size_t)K * 9 * 8));
-        BT_CHECK(hipMemset(s->d_s[k], 0, (size_t)K * 9 * 8));
+        GLIO_HIP_CHECK(hipMalloc((void**)&s->d_hg[k], hg * 8)); GLIO_HIP_CHECK(hipMemset(s->d_hg[k], 0, hg * 8));
+        GLIO_HIP_CHECK(hipMalloc((void**)&s->d_A[k], (size_t)(2 * n + 2) * 8));
+        GLIO_HIP_CHECK(hipMalloc((void**)&s->d_x[k], (size_t)K * 7 * 8)); GLIO_HIP_CHECK(hipMalloc((void**)&s->d_s[k], (size_t)K * 9 * 8));
+        GLIO_HIP_CHECK(hipMemset(s->d_s[k], 0, (size_t)K * 9 * 8));
     }
-    BT_CHECK(hipMalloc((void**)&s->d_xmin, (size_t)K * 7 * 8)); BT_CHECK(hipMalloc((void**)&s->d_smin, (size_t)K * 9 * 8));
-    BT_CHECK(hipMemset(s->d_smin, 0, (size_t)K * 9 * 8));
-    BT_CHECK(hipMalloc((void**)&s->d_stage, (size_t)s->stage_doubles * 8));
-    BT_CHECK(hipMalloc((void**)&s->d_dz, (size_t)(n + 2) * 8));
-    BT_CHECK(hipMalloc((void**)&s->d_scal, 16 * 8)); BT_CHECK(hipMemset(s->d_scal, 0, 16 * 8));
-    BT_CHECK(hipMalloc((void**)&s->d_dot_parts, (BT_DOT_BLOCKS * 6 + 3 * (size_t)((K + BT_NORM_THREADS - 1) / BT_NORM_THREADS)) * 8)); BT_CHECK(hipMalloc((void**)&s->d_dot_ticket, 16)); BT_CHECK(hipMemset(s->d_dot_ticket, 0, 16));
-    BT_CHECK(hipMalloc((void**)&s->d_st, sizeof(BtStatus)));
-    BT_CHECK(hipHostMalloc((void**)&s->h_prog, 64, hipHostMallocMapped | hipHostMallocCoherent));
-    BT_CHECK(hipHostGetDevicePointer((void**)&s->d_prog, (void*)s->h_prog, 0));
-    BT_CHECK(hipHostMalloc((void**)&s->h_res, sizeof(BtStatus), hipHostMallocMapped | hipHostMallocCoherent));
-    BT_CHECK(hipHostGetDevicePointer((void**)&s->d_res, (void*)s->h_res, 0));
-    BT_CHECK(hipHostMalloc((void**)&s->h_x, (size_t)K * 16 * 8 + sizeof(BtStatus) + 64));
+    GLIO_HIP_CHECK(hipMalloc((void**)&s->d_xmin, (size_t)K * 7 * 8)); GLIO_HIP_CHECK(hipMalloc((void**)&s->d_smin, (size_t)K * 9 * 8));
+    GLIO_HIP_CHECK(hipMemset(s->d_smin, 0, (size_t)K * 9 * 8));
+    GLIO_HIP_CHECK(hipMalloc((void**)&s->d_stage, (size_t)s->stage_doubles * 8));
+    GLIO_HIP_CHECK(hipMalloc((void**)&s->d_dz, (size_t)(n + 2) * 8));
+    GLIO_HIP_CHECK(hipMalloc((void**)&s->d_scal, 16 * 8)); GLIO_HIP_CHECK(hipMemset(s->d_scal, 0, 16 * 8));
+    GLIO_HIP_CHECK(hipMalloc((void**)&s->d_dot_parts, (BT_DOT_BLOCKS * 6 + 3 * (size_t)((K + BT_NORM_THREADS - 1) / BT_NORM_THREADS)) * 8)); GLIO_HIP_CHECK(hipMalloc((void**)&s->d_dot_ticket, 16)); GLIO_HIP_CHECK(hipMemset(s->d_dot_ticket, 0, 16));
+    GLIO_HIP_CHECK(hipMalloc((void**)&s->d_st, sizeof(BtStatus)));
+    GLIO_HIP_CHECK(hipHostMalloc((void**)&s->h_prog, 64, hipHostMallocMapped | hipHostMallocCoherent));
+    GLIO_HIP_CHECK(hipHostGetDevicePointer((void**)&s->d_prog, (void*)s->h_prog, 0));
+    GLIO_HIP_CHECK(hipHostMalloc((void**)&s->h_res, sizeof(BtStatus), hipHostMallocMapped | hipHostMallocCoherent));
+    GLIO_HIP_CHECK(hipHostGetDevicePointer((void**)&s->d_res, (void*)s->h_res, 0));
+    GLIO_HIP_CHECK(hipHostMalloc((void**)&s->h_x, (size_t)K * 16 * 8 + sizeof(BtStatus) + 64));
     memset(s->h_prog, 0, 64);
     std::vector<int> bnd(std::max(NB, 1), 0);
     for (int j = 0; j < NB; ++j) { int l, h2; shard_range(K, band, j, s->world, &l, &h2); bnd[j] = h2; }
-    BT_CHECK(hipMemcpy(s->d_bnd_kf, bnd.data(), (size_t)std::max(NB, 1) * 4, hipMemcpyHostToDevice));
+    GLIO_HIP_CHECK(hipMemcpy(s->d_bnd_kf, bnd.data(), (size_t)std::max(NB, 1) * 4, hipMemcpyHostToDevice));
     return GLIO_OK;
 }
 static int tr_ensure(glio_batch* b) {
@@ -899,9 +898,8 @@ static void enqueue_small_accumulate(glio_batch* b, const BtSel& sel, double* Hg
     hipLaunchKernelGGL(k_small_cost, dim3(1), dim3(256), 0, b->stream, sel, s->d_frec, s->n_fac, Hg0 + tot - 1, Hg1 + tot - 1);
 }
 static void enqueue_small(glio_batch* b, const double* poses_dev, double* Hg_dev) {
-    BtSel sel; sel.cur = nullptr; sel.skip = nullptr; sel.want = 0;
-    enqueue_small_eval(b, sel, poses_dev, poses_dev, b->stream);
-    enqueue_small_accumulate(b, sel, Hg_dev, Hg_dev);
+    enqueue_small_eval(b, BT_HOST_SEL, poses_dev, poses_dev, b->stream);
+    enqueue_small_accumulate(b, BT_HOST_SEL, Hg_dev, Hg_dev);
 }
 
 // GLIO_BATCH_MOMENTS=0: every linearisation streams the constraints (k_batch_pairs), as before round 3's moment form -- kept for A/B runs and parity
@@ -960,6 +958,13 @@ static void enqueue_tr_group(const BtRun& r, const BtOpts& o) {
     const int nbv = (n + TRV_THREADS - 1) / TRV_THREADS;
     const int nbo = std::max(1, s->hi - s->lo);
     BtHost h; h.progress = s->d_prog; h.result = s->d_res;
+    // up to six dot products {va, vb, over the owned rows only, where the sum goes} in one launch (k_bt_dots)
+    struct DotJob { int va, vb, owned; double* out; };
+    auto dots = [&](const int solve_phase, std::initializer_list<DotJob> jobs) {
+        DotJobs j; memset(&j, 0, sizeof j); j.parts = s->d_dot_parts; j.ticket = s->d_dot_ticket;
+        for (const DotJob& d : jobs) { j.va[j.n] = d.va; j.vb[j.n] = d.vb; j.owned[j.n] = d.owned; j.out[j.n] = d.out; ++j.n; }
+        hipLaunchKernelGGL(k_bt_dots, dim3(BT_DOT_BLOCKS), dim3(256), 0, st, a, solve_phase, j);
+    };
     glio_lds_poison_stream(st);
     hipLaunchKernelGGL(k_bt_state_machine, dim3(1), dim3(64), 0, st, a, o, h);
     // ---- Cauchy point and Gauss-Newton step (skipped when the stored ones are reused)
@@ -968,13 +973,7 @@ static void enqueue_tr_group(const BtRun& r, const BtOpts& o) {
     long long sep_count = 0;
     double* sep = glio_bcr_sepbuf(s->bcr, &sep_count);
     double* extra = sep + sep_count - 16;
-    {
-        DotJobs j; memset(&j, 0, sizeof j); j.parts = s->d_dot_parts; j.ticket = s->d_dot_ticket;
-        j.n = 2;
-        j.va[0] = V_GR; j.vb[0] = V_GR; j.owned[0] = 0; j.out[0] = &s->d_st->gg;
-        j.va[1] = V_UU; j.vb[1] = V_T1; j.owned[1] = 1; j.out[1] = extra;          // the Cauchy curvature travels with the separator system
-        hipLaunchKernelGGL(k_bt_dots, dim3(BT_DOT_BLOCKS), dim3(256), 0, st, a, 1, j);
-    }
+    dots(1, {{V_GR, V_GR, 0, &s->d_st->gg}, {V_UU, V_T1, 1, extra}});          // the Cauchy curvature travels with the separator system
     glio_lds_poison_stream(st);
     BcrOp op; memset(&op, 0, sizeof op);
     for (int k = 0; k < 2; ++k) { op.Hg[k] = s->d_hg[k]; op.imu[k] = s->n_imu > 0 ? s->d_rec[k] : nullptr; op.gfull[k] = s->d_A[k] + n; }
@@ -985,37 +984,16 @@ static void enqueue_tr_group(const BtRun& r, const BtOpts& o) {
     hipLaunchKernelGGL(k_bt_dz_prepare, dim3((n + 1 + 255) / 256), dim3(256), 0, st, a, s->d_dz, glio_bcr_fail_flag(s->bcr));
     call_hook(r, s->d_dz, n + 2);
     hipLaunchKernelGGL(k_bt_gn, dim3(nbv), dim3(TRV_THREADS), 0, st, a, s->d_dz);
-    {
-        DotJobs j; memset(&j, 0, sizeof j); j.parts = s->d_dot_parts; j.ticket = s->d_dot_ticket;
-        j.n = 2;
-        j.va[0] = V_GN; j.vb[0] = V_GN; j.out[0] = &s->d_st->nn2;
-        j.va[1] = V_GR; j.vb[1] = V_GN; j.out[1] = &s->d_st->gd;
-        hipLaunchKernelGGL(k_bt_dots, dim3(BT_DOT_BLOCKS), dim3(256), 0, st, a, 1, j);
-    }
+    dots(1, {{V_GN, V_GN, 0, &s->d_st->nn2}, {V_GR, V_GN, 0, &s->d_st->gd}});
     hipLaunchKernelGGL(k_bt_basis, dim3(nbv), dim3(TRV_THREADS), 0, st, a, extra);
     hipLaunchKernelGGL(k_bt_matvec, dim3(nbo), dim3(64), 0, st, a, 1, (int)V_X1, (int)V_T1, (int)V_X2, (int)V_T2);
-    {
-        DotJobs j; memset(&j, 0, sizeof j); j.parts = s->d_dot_parts; j.ticket = s->d_dot_ticket;
-        j.n = 4;
-        j.va[0] = V_X1; j.vb[0] = V_T1; j.owned[0] = 1; j.out[0] = s->d_scal + 0;
-        j.va[1] = V_X1; j.vb[1] = V_T2; j.owned[1] = 1; j.out[1] = s->d_scal + 1;
-        j.va[2] = V_X2; j.vb[2] = V_T2; j.owned[2] = 1; j.out[2] = s->d_scal + 2;
-        j.va[3] = V_W2; j.vb[3] = V_W2; j.owned[3] = 0; j.out[3] = &s->d_st->w2;
-        hipLaunchKernelGGL(k_bt_dots, dim3(BT_DOT_BLOCKS), dim3(256), 0, st, a, 1, j);
-    }
+    dots(1, {{V_X1, V_T1, 1, s->d_scal + 0}, {V_X1, V_T2, 1, s->d_scal + 1}, {V_X2, V_T2, 1, s->d_scal + 2}, {V_W2, V_W2, 0, &s->d_st->w2}});
     call_hook(r, s->d_scal, 8);
     // ---- the step for the present radius, its model cost change, the candidate
     hipLaunchKernelGGL(k_bt_dogleg, dim3(1), dim3(64), 0, st, a, s->d_scal, o.dogleg_type);
     hipLaunchKernelGGL(k_bt_step, dim3((K + BT_STEP_KF - 1) / BT_STEP_KF), dim3(BT_STEP_KF * 15), 0, st, a);
     hipLaunchKernelGGL(k_bt_matvec, dim3(nbo), dim3(64), 0, st, a, 0, (int)V_ST, (int)V_T1, -1, -1);
-    {
-        DotJobs j; memset(&j, 0, sizeof j); j.parts = s->d_dot_parts; j.ticket = s->d_dot_ticket;
-        j.n = 3;
-        j.va[0] = V_GS; j.vb[0] = V_ST; j.out[0] = &s->d_st->lin;
-        j.va[1] = V_ST; j.vb[1] = V_T1; j.owned[1] = 1; j.out[1] = s->d_scal + 8;
-        j.va[2] = V_SD; j.vb[2] = V_SD; j.out[2] = &s->d_st->sd2;
-        hipLaunchKernelGGL(k_bt_dots, dim3(BT_DOT_BLOCKS), dim3(256), 0, st, a, 0, j);
-    }
+    dots(0, {{V_GS, V_ST, 0, &s->d_st->lin}, {V_ST, V_T1, 1, s->d_scal + 8}, {V_SD, V_SD, 0, &s->d_st->sd2}});
     call_hook(r, s->d_scal + 8, 8);
     hipLaunchKernelGGL(k_bt_mcc, dim3(1), dim3(64), 0, st, a, s->d_scal + 8);
     enqueue_tr_linearize(r, 1, false);          // the candidate's linearisation (returns at once when the group has no usable step)
@@ -1035,7 +1013,7 @@ int glio_batch_shard_range(int K, int band, int rank, int world, int32_t* lo, in
 // glio_batch_set_constraints* must have their source keyframe there; small factors and IMU edges are given whole, the library keeps its own.
 int glio_batch_set_shard(glio_batch* b, int rank, int world) {
     if (!b || world < 1 || rank < 0 || rank >= world) return GLIO_E_ARG;
-    BT_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rc = small_ensure(b); if (rc) return rc; }
     BatchSmall* s = b->small;
     if (s->n_fac > 0 && (rank != s->rank || world != s->world)) { glio_set_error("glio_batch_set_shard must precede glio_batch_set_small_factors"); return GLIO_E_STATE; }
@@ -1046,22 +1024,27 @@ int glio_batch_set_shard(glio_batch* b, int rank, int world) {
     return GLIO_OK;
 }
 
+// the chain's edge table and the two sets of edge records, once per stage
+static int imu_ensure(glio_batch* b) {
+    BatchSmall* s = b->small;
+    if (s->d_imu) return GLIO_OK;
+    GLIO_HIP_CHECK(hipMalloc((void**)&s->d_imu, (size_t)(b->K - 1) * sizeof(ImuEdgeDev)));
+    for (int k = 0; k < 2; ++k) GLIO_HIP_CHECK(hipMalloc((void**)&s->d_rec[k], (size_t)(b->K - 1) * sizeof(PairBlock)));
+    return GLIO_OK;
+}
 // The ImuFactor chain (Estimator.cpp:2990-3001): edges[k] is the pre-integration between keyframes k and k + 1 (n_edges = K - 1), or
 // n_edges = 0 for the pose-only problem.  With the chain every keyframe has 15 unknowns and glio_batch_solve_tr2 takes the speed-bias blocks.
 int glio_batch_set_imu(glio_batch* b, int n_edges, const glio_preint* edges, double gravity) {
     if (!b || (n_edges != 0 && n_edges != b->K - 1) || (n_edges > 0 && !edges)) return GLIO_E_ARG;
-    BT_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rc = small_ensure(b); if (rc) return rc; }
     BatchSmall* s = b->small;
-    if (n_edges > 0 && !s->d_imu) {
-        BT_CHECK(hipMalloc((void**)&s->d_imu, (size_t)(b->K - 1) * sizeof(ImuEdgeDev)));
-        for (int k = 0; k < 2; ++k) BT_CHECK(hipMalloc((void**)&s->d_rec[k], (size_t)(b->K - 1) * sizeof(PairBlock)));
-    }
     if (n_edges > 0) {
+        { const int rc = imu_ensure(b); if (rc) return rc; }
         std::vector<ImuEdgeDev> h((size_t)n_edges);
         for (int k = 0; k < n_edges; ++k)
             if (!glio_digest_imu_edge(&edges[k], k, &h[k])) { glio_set_error("IMU edge %d: covariance not invertible", k); return GLIO_E_ARG; }
-        BT_CHECK(hipMemcpy(s->d_imu, h.data(), (size_t)n_edges * sizeof(ImuEdgeDev), hipMemcpyHostToDevice));
+        GLIO_HIP_CHECK(hipMemcpy(s->d_imu, h.data(), (size_t)n_edges * sizeof(ImuEdgeDev), hipMemcpyHostToDevice));
     }
     s->n_imu = n_edges; s->gravity = gravity;
     return GLIO_OK;
@@ -1075,14 +1058,11 @@ int glio_batch_set_imu_from_store(glio_batch* b, glio_imu* st, int first_edge, d
     if (st->device != b->device) { glio_set_error("the IMU store lives on device %d, the batch stage on device %d", st->device, b->device); return GLIO_E_ARG; }
     if (n_edges < 1 || (long long)first_edge + n_edges > st->max_edges) { glio_set_error("IMU edges %d .. %d of a store of %d", first_edge, first_edge + n_edges - 1, st->max_edges); return GLIO_E_ARG; }
     { const int bad = glio_imu_known_flag(st, first_edge, n_edges, nullptr); if (bad >= 0) { glio_set_error("IMU edge %d: flagged by the store (non-finite input or covariance not invertible)", bad); return GLIO_E_NUMERIC; } }
-    BT_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rc = small_ensure(b); if (rc) return rc; }
     BatchSmall* s = b->small;
-    if (!s->d_imu) {
-        BT_CHECK(hipMalloc((void**)&s->d_imu, (size_t)(b->K - 1) * sizeof(ImuEdgeDev)));
-        for (int k = 0; k < 2; ++k) BT_CHECK(hipMalloc((void**)&s->d_rec[k], (size_t)(b->K - 1) * sizeof(PairBlock)));
-    }
-    BT_CHECK(hipStreamWaitEvent(b->stream, st->ev_done, 0));
+    { const int rc = imu_ensure(b); if (rc) return rc; }
+    GLIO_HIP_CHECK(hipStreamWaitEvent(b->stream, st->ev_done, 0));
     glio_imu_launch_gather_range(b->stream, st, first_edge, n_edges, s->d_imu);
     s->n_imu = n_edges; s->gravity = gravity;
     return GLIO_OK;
@@ -1091,7 +1071,7 @@ int glio_batch_set_imu_from_store(glio_batch* b, glio_imu* st, int first_edge, d
 int glio_batch_set_small_factors(glio_batch* b, const glio_gnss_frame* frame, int n_dq, const int32_t* dq_i, const int32_t* dq_j, const double* dq_const,
                                  int n_dd, const glio_dd_psr* dd) {
     if (!b || n_dq < 0 || n_dd < 0 || (n_dq > 0 && (!dq_i || !dq_j || !dq_const)) || (n_dd > 0 && (!dd || !frame))) return GLIO_E_ARG;
-    BT_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rc = small_ensure(b); if (rc) return rc; }
     BatchSmall* s = b->small;
     const int K = b->K, band = b->band, wdt = 2 * band + 1;
@@ -1125,39 +1105,39 @@ int glio_batch_set_small_factors(glio_batch* b, const glio_gnss_frame* frame, in
         for (void** q : p) { if (*q) hipFree(*q); *q = nullptr; }
         s->cap_fac = 0; s->n_fac = 0;
         const size_t cap = need_fac + need_fac / 2 + 16;
-        BT_CHECK(hipMalloc((void**)&s->d_fa, cap * 4)); BT_CHECK(hipMalloc((void**)&s->d_fb, cap * 4));
-        BT_CHECK(hipMalloc((void**)&s->d_ftype, cap * 4)); BT_CHECK(hipMalloc((void**)&s->d_fidx, cap * 4));
-        BT_CHECK(hipMalloc((void**)&s->d_dq_const, cap * 32)); BT_CHECK(hipMalloc((void**)&s->d_frec, cap * (SREC + 1) * 8));
+        GLIO_HIP_CHECK(hipMalloc((void**)&s->d_fa, cap * 4)); GLIO_HIP_CHECK(hipMalloc((void**)&s->d_fb, cap * 4));
+        GLIO_HIP_CHECK(hipMalloc((void**)&s->d_ftype, cap * 4)); GLIO_HIP_CHECK(hipMalloc((void**)&s->d_fidx, cap * 4));
+        GLIO_HIP_CHECK(hipMalloc((void**)&s->d_dq_const, cap * 32)); GLIO_HIP_CHECK(hipMalloc((void**)&s->d_frec, cap * (SREC + 1) * 8));
         s->cap_fac = cap;             // only after every allocation succeeded
     }
     if ((size_t)s->n_rp > s->cap_rp) {
         if (s->d_rp_const) { hipFree(s->d_rp_const); s->d_rp_const = nullptr; }
         s->cap_rp = 0;
         const size_t cap = (size_t)s->n_rp + s->n_rp / 2 + 16;
-        BT_CHECK(hipMalloc((void**)&s->d_rp_const, cap * 56));
+        GLIO_HIP_CHECK(hipMalloc((void**)&s->d_rp_const, cap * 56));
         s->cap_rp = cap;
     }
-    if (s->n_rp) BT_CHECK(hipMemcpy(s->d_rp_const, s->h_rp_c, (size_t)s->n_rp * 56, hipMemcpyHostToDevice));
+    if (s->n_rp) GLIO_HIP_CHECK(hipMemcpy(s->d_rp_const, s->h_rp_c, (size_t)s->n_rp * 56, hipMemcpyHostToDevice));
     if ((size_t)n_dd > s->cap_dd) {
         if (s->d_dd) { hipFree(s->d_dd); s->d_dd = nullptr; }
         s->cap_dd = 0; s->n_dd = 0;
         const size_t cap = (size_t)n_dd + n_dd / 2 + 16;
-        BT_CHECK(hipMalloc((void**)&s->d_dd, cap * sizeof(glio_dd_psr)));
+        GLIO_HIP_CHECK(hipMalloc((void**)&s->d_dd, cap * sizeof(glio_dd_psr)));
         s->cap_dd = cap;
     }
     if (nf) {
-        BT_CHECK(hipMemcpy(s->d_fa, fa.data(), (size_t)nf * 4, hipMemcpyHostToDevice)); BT_CHECK(hipMemcpy(s->d_fb, fb.data(), (size_t)nf * 4, hipMemcpyHostToDevice));
-        BT_CHECK(hipMemcpy(s->d_ftype, ft.data(), (size_t)nf * 4, hipMemcpyHostToDevice)); BT_CHECK(hipMemcpy(s->d_fidx, fi.data(), (size_t)nf * 4, hipMemcpyHostToDevice));
+        GLIO_HIP_CHECK(hipMemcpy(s->d_fa, fa.data(), (size_t)nf * 4, hipMemcpyHostToDevice)); GLIO_HIP_CHECK(hipMemcpy(s->d_fb, fb.data(), (size_t)nf * 4, hipMemcpyHostToDevice));
+        GLIO_HIP_CHECK(hipMemcpy(s->d_ftype, ft.data(), (size_t)nf * 4, hipMemcpyHostToDevice)); GLIO_HIP_CHECK(hipMemcpy(s->d_fidx, fi.data(), (size_t)nf * 4, hipMemcpyHostToDevice));
     }
-    if (n_dq) BT_CHECK(hipMemcpy(s->d_dq_const, dq_const, (size_t)n_dq * 32, hipMemcpyHostToDevice));
-    if (n_dd) BT_CHECK(hipMemcpy(s->d_dd, dd, (size_t)n_dd * sizeof(glio_dd_psr), hipMemcpyHostToDevice));
-    BT_CHECK(hipMemcpy(s->d_small_index, index.data(), index.size() * sizeof(int2), hipMemcpyHostToDevice));
+    if (n_dq) GLIO_HIP_CHECK(hipMemcpy(s->d_dq_const, dq_const, (size_t)n_dq * 32, hipMemcpyHostToDevice));
+    if (n_dd) GLIO_HIP_CHECK(hipMemcpy(s->d_dd, dd, (size_t)n_dd * sizeof(glio_dd_psr), hipMemcpyHostToDevice));
+    GLIO_HIP_CHECK(hipMemcpy(s->d_small_index, index.data(), index.size() * sizeof(int2), hipMemcpyHostToDevice));
     if (frame) {
         glio_host_ecef_local(frame->anc_ecef, frame->yaw_enu_local, s->R_ecef_local);
         for (int k = 0; k < 3; ++k) s->anc[k] = frame->anc_ecef[k];
         double rel[12];
         memcpy(rel, s->R_ecef_local, 72); memcpy(rel + 9, s->anc, 24);
-        BT_CHECK(hipMemcpy(s->d_rel, rel, 96, hipMemcpyHostToDevice));
+        GLIO_HIP_CHECK(hipMemcpy(s->d_rel, rel, 96, hipMemcpyHostToDevice));
     }
     s->n_dq = n_dq; s->n_dd = n_dd; s->n_fac = nf;
     return GLIO_OK;
@@ -1169,7 +1149,7 @@ int glio_batch_set_small_factors(glio_batch* b, const glio_gnss_frame* frame, in
 // table with them (call this first; n_rp = 0 removes them).
 int glio_batch_set_relative_pose_factors(glio_batch* b, int n_rp, const int32_t* rp_i, const int32_t* rp_j, const double* rp_const) {
     if (!b || n_rp < 0 || (n_rp > 0 && (!rp_i || !rp_j || !rp_const))) return GLIO_E_ARG;
-    BT_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rc = small_ensure(b); if (rc) return rc; }
     BatchSmall* s = b->small;
     free(s->h_rp_i); free(s->h_rp_j); free(s->h_rp_c);
@@ -1190,33 +1170,47 @@ __global__ void k_set_dd_threshold(glio_dd_psr* dd, const int n, const double th
 // DDpsr_threshold of the next outer round (Estimator.cpp:2764-2767) for every DD factor already on the device
 int glio_batch_set_dd_threshold(glio_batch* b, double threshold) {
     if (!b) return GLIO_E_ARG;
-    BT_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     BatchSmall* s = b->small;
     if (!s || s->n_dd == 0) return GLIO_OK;
     hipLaunchKernelGGL(k_set_dd_threshold, dim3((s->n_dd + 255) / 256), dim3(256), 0, b->stream, s->d_dd, s->n_dd, threshold);
-    BT_CHECK(hipGetLastError());
+    GLIO_HIP_CHECK(hipGetLastError());
     return GLIO_OK;
 }
 
 // adds the small factors evaluated at `poses` ([K][7], host) into a band buffer (the damped Gauss-Newton path; one rank)
 int glio_batch_add_small_dev(glio_batch* b, const double* poses, double* Hg_dev) {
     if (!b || !poses || !Hg_dev) return GLIO_E_ARG;
-    BT_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     if (!b->small || b->small->n_fac == 0) return GLIO_OK;
-    memcpy(b->h_poses, poses, (size_t)b->K * 7 * 8);
-    BT_CHECK(hipMemcpyAsync(b->d_poses, b->h_poses, (size_t)b->K * 7 * 8, hipMemcpyHostToDevice, b->stream));
+    { const int rc = glio_batch_upload_poses(b, poses); if (rc) return rc; }
     enqueue_small(b, b->d_poses, Hg_dev);
-    BT_CHECK(hipGetLastError());
-    BT_CHECK(hipStreamSynchronize(b->stream));
+    GLIO_HIP_CHECK(hipGetLastError());
+    GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
     return GLIO_OK;
 }
 
+// the starting point of a solve on the device, through the pinned buffer: the status record, poses and (with the IMU chain) speed-bias as point 0,
+// copied to point 1
+static int tr_upload_start(glio_batch* b, const BtStatus& st0, const double* poses, const double* speed_bias) {
+    BatchSmall* s = b->small;
+    const int K = b->K;
+    hipStream_t st = b->stream;
+    memcpy(s->h_x, poses, (size_t)K * 7 * 8);
+    if (s->n_imu > 0) memcpy(s->h_x + (size_t)K * 7, speed_bias, (size_t)K * 9 * 8);
+    GLIO_HIP_CHECK(hipMemcpyAsync(s->d_st, &st0, sizeof st0, hipMemcpyHostToDevice, st));
+    GLIO_HIP_CHECK(hipMemcpyAsync(s->d_x[0], s->h_x, (size_t)K * 7 * 8, hipMemcpyHostToDevice, st));
+    if (s->n_imu > 0) GLIO_HIP_CHECK(hipMemcpyAsync(s->d_s[0], s->h_x + (size_t)K * 7, (size_t)K * 9 * 8, hipMemcpyHostToDevice, st));
+    GLIO_HIP_CHECK(hipMemcpyAsync(s->d_x[1], s->d_x[0], (size_t)K * 7 * 8, hipMemcpyDeviceToDevice, st));
+    GLIO_HIP_CHECK(hipMemcpyAsync(s->d_s[1], s->d_s[0], (size_t)K * 9 * 8, hipMemcpyDeviceToDevice, st));
+    return GLIO_OK;
+}
 // One linearisation of the whole problem at (poses, speed_bias) through the solver's own path (shard, hook, assembly): the
 // replicated diagonal [n], gradient [n] and the cost, n = B K (parity checks; `allreduce` as in glio_batch_solve_tr2).
 int glio_batch_linearize_full(glio_batch* b, const double* poses, const double* speed_bias, glio_allreduce_fn allreduce, void* user, double* diag, double* grad,
                               double* cost) {
     if (!b || !poses) return GLIO_E_ARG;
-    BT_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rc = small_ensure(b); if (rc) return rc; }
     { const int rc = tr_ensure(b); if (rc) return rc; }
     if (g_batch_moments) { const int rm = glio_batch_moments_ensure(b); if (rm) return rm; }
@@ -1225,17 +1219,13 @@ int glio_batch_linearize_full(glio_batch* b, const double* poses, const double* 
     const int K = b->K, n = s->B * K;
     BtStatus st; memset(&st, 0, sizeof st);
     st.cur = 1; st.first = 1;
-    BT_CHECK(hipMemcpyAsync(s->d_st, &st, sizeof st, hipMemcpyHostToDevice, b->stream));
-    BT_CHECK(hipMemcpyAsync(s->d_x[0], poses, (size_t)K * 7 * 8, hipMemcpyHostToDevice, b->stream));
-    if (s->n_imu > 0) BT_CHECK(hipMemcpyAsync(s->d_s[0], speed_bias, (size_t)K * 9 * 8, hipMemcpyHostToDevice, b->stream));
-    BT_CHECK(hipMemcpyAsync(s->d_x[1], s->d_x[0], (size_t)K * 7 * 8, hipMemcpyDeviceToDevice, b->stream));
-    BT_CHECK(hipMemcpyAsync(s->d_s[1], s->d_s[0], (size_t)K * 9 * 8, hipMemcpyDeviceToDevice, b->stream));
+    { const int rc = tr_upload_start(b, st, poses, speed_bias); if (rc) return rc; }
     BtRun r; r.b = b; r.hook = allreduce; r.user = user;
     enqueue_tr_linearize(r, 1, true);
-    BT_CHECK(hipGetLastError());
+    GLIO_HIP_CHECK(hipGetLastError());
     std::vector<double> h((size_t)2 * n + 1);
-    BT_CHECK(hipMemcpyAsync(h.data(), s->d_A[0], ((size_t)2 * n + 1) * 8, hipMemcpyDeviceToHost, b->stream));
-    BT_CHECK(hipStreamSynchronize(b->stream));
+    GLIO_HIP_CHECK(hipMemcpyAsync(h.data(), s->d_A[0], ((size_t)2 * n + 1) * 8, hipMemcpyDeviceToHost, b->stream));
+    GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
     if (diag) memcpy(diag, h.data(), (size_t)n * 8);
     if (grad) memcpy(grad, h.data() + n, (size_t)n * 8);
     if (cost) *cost = h[(size_t)2 * n];
@@ -1249,7 +1239,7 @@ int glio_batch_linearize_full(glio_batch* b, const double* poses, const double* 
 int glio_batch_solve_tr2(glio_batch* b, double* poses, double* speed_bias, const glio_batch_tr_opts* o, glio_allreduce_fn allreduce, void* user, glio_summary* sum) {
     GLIO_TRACE("K8 + trust region glio_batch_solve_tr2");
     if (!b || !poses || !o || !sum) return GLIO_E_ARG;
-    BT_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rc = small_ensure(b); if (rc) return rc; }
     { const int rc = tr_ensure(b); if (rc) return rc; }
     if (g_batch_moments) { const int rm = glio_batch_moments_ensure(b); if (rm) return rm; }
@@ -1277,13 +1267,7 @@ int glio_batch_solve_tr2(glio_batch* b, double* poses, double* speed_bias, const
     s->solve_id = s->solve_id % 30000 + 1;
     init.solve_id = s->solve_id;
     const int id = s->solve_id;
-    memcpy(s->h_x, poses, (size_t)K * 7 * 8);
-    if (s->n_imu > 0) memcpy(s->h_x + (size_t)K * 7, speed_bias, (size_t)K * 9 * 8);
-    BT_CHECK(hipMemcpyAsync(s->d_st, &init, sizeof init, hipMemcpyHostToDevice, st));
-    BT_CHECK(hipMemcpyAsync(s->d_x[0], s->h_x, (size_t)K * 7 * 8, hipMemcpyHostToDevice, st));
-    if (s->n_imu > 0) BT_CHECK(hipMemcpyAsync(s->d_s[0], s->h_x + (size_t)K * 7, (size_t)K * 9 * 8, hipMemcpyHostToDevice, st));
-    BT_CHECK(hipMemcpyAsync(s->d_x[1], s->d_x[0], (size_t)K * 7 * 8, hipMemcpyDeviceToDevice, st));
-    BT_CHECK(hipMemcpyAsync(s->d_s[1], s->d_s[0], (size_t)K * 9 * 8, hipMemcpyDeviceToDevice, st));
+    { const int rc = tr_upload_start(b, init, poses, speed_bias); if (rc) return rc; }
     BtRun r; r.b = b; r.hook = allreduce; r.user = user;
     enqueue_tr_linearize(r, 1, true);            // the starting point is "the candidate" of a first group that accepts it unconditionally
     // The loop lives on the device; the host only keeps the queue fed.  Up to `lead` groups are in flight: group g is enqueued as soon as the state machine of
@@ -1325,13 +1309,13 @@ int glio_batch_solve_tr2(glio_batch* b, double* poses, double* speed_bias, const
         }
     }
     std::atomic_thread_fence(std::memory_order_acquire);
-    BT_CHECK(hipMemcpyAsync(s->h_x, s->d_xmin, (size_t)K * 7 * 8, hipMemcpyDeviceToHost, st));
-    if (s->n_imu > 0) BT_CHECK(hipMemcpyAsync(s->h_x + (size_t)K * 7, s->d_smin, (size_t)K * 9 * 8, hipMemcpyDeviceToHost, st));
+    GLIO_HIP_CHECK(hipMemcpyAsync(s->h_x, s->d_xmin, (size_t)K * 7 * 8, hipMemcpyDeviceToHost, st));
+    if (s->n_imu > 0) GLIO_HIP_CHECK(hipMemcpyAsync(s->h_x + (size_t)K * 7, s->d_smin, (size_t)K * 9 * 8, hipMemcpyDeviceToHost, st));
     // the final status by a stream-ordered copy of the device's own record (the mapped copy h_res only tells the loop above when to stop:
     // host-mapped words are not a safe carrier for a payload, see SolverStatus::checksum in glio_device.h)
     BtStatus* h_fin = reinterpret_cast<BtStatus*>(s->h_x + (size_t)K * 16);
-    BT_CHECK(hipMemcpyAsync(h_fin, s->d_st, sizeof(BtStatus), hipMemcpyDeviceToHost, st));
-    BT_CHECK(hipStreamSynchronize(st));
+    GLIO_HIP_CHECK(hipMemcpyAsync(h_fin, s->d_st, sizeof(BtStatus), hipMemcpyDeviceToHost, st));
+    GLIO_HIP_CHECK(hipStreamSynchronize(st));
     const BtStatus res = *h_fin;
     if (!res.done || res.solve_id != id) { glio_set_error("batch solve did not finish"); return GLIO_E_STATE; }
     memcpy(poses, s->h_x, (size_t)K * 7 * 8);
