@@ -275,6 +275,7 @@ void glio_destroy(glio_ctx* c) {
     glio_localmap_destroy(c);
     glio_features_destroy(c);          // (waits for a pending read of the surf features by another context's stream)
     if (c->ev_feat_read) { hipEventDestroy(c->ev_feat_read); c->ev_feat_read = nullptr; }
+    if (c->ev_cut_read) { hipEventDestroy(c->ev_cut_read); c->ev_cut_read = nullptr; }
     glio_kfcloud_destroy(c);
     void* ptrs[] = {c->d_pts, c->d_planes, c->d_scores, c->d_pts_s, c->d_count, c->d_scan, c->d_imu, c->d_imu_blocks, c->d_gnss_blocks, c->d_groups,
                     c->d_ddt_blocks, c->d_dd, c->d_dop, c->d_prior_J0, c->d_prior_A0, c->d_prior_r0, c->d_prior_x0, c->d_prior_slot,

@@ -465,12 +465,27 @@ static void ft_free(FeatWork* f) {
 void glio_features_destroy(glio_ctx* c) {
     // (another context's keyframe cloud stage may still be reading the surf features: glio_set_scan_from_features)
     if (c->feat_read_pending) { hipEventSynchronize(c->ev_feat_read); c->feat_read_pending = 0; }
+    if (c->cut_read_pending) { hipEventSynchronize(c->ev_cut_read); c->cut_read_pending = 0; }      // (... or a dense store the cut cloud)
     if (c->features) { ft_free(c->features); c->features = nullptr; }
 }
 int glio_features_surf_view(glio_ctx* c, const float4** d_surf, int* n) {
     FeatWork* f = c->features;
     if (!f || !f->have) { glio_set_error("glio_features_extract first"); return GLIO_E_STATE; }
     *d_surf = f->d_o_surf; *n = f->counts.surf;
+    return GLIO_OK;
+}
+
+int glio_features_cut_view(glio_ctx* c, const float4** d_cut, int* n) {
+    FeatWork* f = c->features;
+    if (!f || !f->have) { glio_set_error("glio_features_extract first"); return GLIO_E_STATE; }
+    *d_cut = f->d_cut; *n = f->counts.cut;
+    return GLIO_OK;
+}
+int glio_features_cut_external_read(glio_ctx* c, hipStream_t reader) {
+    if (!c->ev_cut_read) GLIO_HIP_CHECK(hipEventCreateWithFlags(&c->ev_cut_read, hipEventDisableTiming));
+    if (c->cut_read_pending) GLIO_HIP_CHECK(hipStreamWaitEvent(reader, c->ev_cut_read, 0));       // (another store's read: the new record covers it)
+    GLIO_HIP_CHECK(hipEventRecord(c->ev_cut_read, reader));
+    c->cut_read_pending = 1;
     return GLIO_OK;
 }
 
@@ -546,6 +561,8 @@ int glio_features_extract_strided(glio_ctx* c, const void* raw, int n, int strid
     hipStream_t s = c->stream;
     // (a keyframe cloud stage on another stream may still be reading the last extraction's surf features: this one overwrites them behind that read)
     if (c->feat_read_pending) { GLIO_HIP_CHECK(hipStreamWaitEvent(s, c->ev_feat_read, 0)); c->feat_read_pending = 0; }
+    // (... and a dense store the cut cloud: its own event, so that neither read hides the other)
+    if (c->cut_read_pending) { GLIO_HIP_CHECK(hipStreamWaitEvent(s, c->ev_cut_read, 0)); c->cut_read_pending = 0; }
     { const int ru = glio_upload_points(s, &c->raw_stage, raw, n, stride_bytes, intensity_offset, f->d_raw); if (ru != GLIO_OK) return ru; }
     GLIO_HIP_CHECK(hipEventRecord(f->ev0, s));
     const int nt = (n + FT_TILE - 1) / FT_TILE, ntl = nt > 0 ? nt : 1;

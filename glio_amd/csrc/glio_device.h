@@ -252,6 +252,8 @@ struct glio_ctx {
     struct FeatWork* features;                // raw-scan feature extraction (feature_kernels.hip), created by glio_features_config
     hipEvent_t ev_feat_read; int feat_read_pending;   // another context's stream is still READING the surf features (glio_set_scan_from_features): the next
                                                       // glio_features_extract*, glio_features_config and glio_destroy come behind this event
+    hipEvent_t ev_cut_read; int cut_read_pending;     // a dense store's stream (glio_dense_set_frame_from_features) is still READING the cut cloud: a SECOND event, so that
+                                                      // a pending read of the surf features and one of the cut cloud are both kept; the front end comes behind both
     struct KfCloud* kfcloud;                  // the keyframe cloud stage (keyframe_cloud_kernels.hip), created by glio_scan_filter_config
     // ---- speed-bias priors of the windows after a loop closure (glio_set_speed_bias_priors, Estimator.cpp:2164-2176)
     int sbp_n;                                // slots 0 .. sbp_n - 1 carry one (0: none)
@@ -514,7 +516,20 @@ void glio_localmap_destroy(glio_ctx* c);
 void glio_features_destroy(glio_ctx* c);          // feature_kernels.hip
 // feature_kernels.hip: the surf features of the last glio_features_extract* where they lie (GLIO_E_STATE before the first extraction)
 int glio_features_surf_view(glio_ctx* c, const float4** d_surf, int* n);
+// ... and the cut cloud (GLIO_FEAT_CUT_CLOUD: what the reference's undistortion reads), with the stream the extraction ran on
+int glio_features_cut_view(glio_ctx* c, const float4** d_cut, int* n);
+// `reader` has just been given work that reads the cut cloud: the front end's next extraction, config and destroy come behind this point on the device.  A read
+// that is still pending (another store's) is kept: `reader` is made to wait for it before the event is recorded again.
+int glio_features_cut_external_read(glio_ctx* c, hipStream_t reader);
 void glio_kfcloud_destroy(glio_ctx* c);           // keyframe_cloud_kernels.hip
+// keyframe_cloud_kernels.hip: the de-skew pass (k_kfc_deskew) for another stage (dense_cloud_kernels.hip).  The motion of the sweep: q_si = slerp(identity, q, ratio),
+// t_si = ratio t (on = 0: no de-skew, the points are copied)
+struct KfcMotion { double q[4], t[3]; int on, pad_; };
+bool glio_kfc_finite(const double* v, int n);
+// trans == null: off; quat == null: the identity
+void glio_kfc_motion(const double* trans, const double* quat, KfcMotion* m);
+// n records of `stride` bytes at the device address src -> out[n] moved (or copied), added to the six ordered ints of box6
+void glio_kfc_launch_deskew(hipStream_t s, const unsigned char* src, int n, int stride, int ioff, const KfcMotion& m, float4* out, int* box6);
 // localmap_kernels.hip: the local map's VoxelGrid (float accumulation in concatenation order) over a list of device-resident clouds, without a context.
 // poses [n_frames][7] = t, q; the filtered cloud goes to `out` (nothing is copied when *nv_out > out_cap).  Waits for `stream` once, inside.
 struct LocalMap;
@@ -528,6 +543,9 @@ int glio_vg_build(LocalMap* m, hipStream_t stream, int n_frames, const float4* c
 //   glio_vg_staged_finish  the accumulation and the ordered output into m's own buffer (glio_vg_output); waits for `stream` once, for the count
 int glio_vg_staged_begin(LocalMap* m, hipStream_t stream, int n);
 int glio_vg_staged_finish(LocalMap* m, hipStream_t stream, int n, float leaf, int* nv_out, int* passthrough);
+// lists longer than LM_WAVE_LIST_MIN are sorted and fetched by a whole wavefront (k_lm_emit_wave) instead of one thread; the same bytes.  Off by default: only
+// the dense store's VoxelGrid sets it.
+void glio_vg_set_wave_emit(LocalMap* m, int on);
 float4* glio_vg_staging(LocalMap* m);
 int* glio_vg_staging_box(LocalMap* m);
 const float4* glio_vg_output(LocalMap* m);
@@ -554,6 +572,10 @@ struct GlioBassocView { int device, K, cap; const float4* d_local; const int* h_
 int glio_bassoc_view(glio_bassoc* b, GlioBassocView* out);
 // `reader` (another object's stream) has just been given work that reads the resident clouds: the association's next write to one of them waits for this point
 int glio_bassoc_external_read(glio_bassoc* b, hipStream_t reader);
+// dense_cloud_kernels.hip: the same view of a dense store (glio_dense_*: [K][max_points_per_frame] full clouds), and the same hook
+struct glio_dense;
+int glio_dense_view(glio_dense* d, GlioBassocView* out);
+int glio_dense_external_read(glio_dense* d, hipStream_t reader);
 // capi.hip: a scan / map sent ahead on the upload stream (glio_set_scan_ahead, glio_localmap_push_scan_ahead_and_build) is still pending -> the context's
 // stream waits for it (the next glio_slide_window still takes the scan over)
 int glio_order_behind_ahead(glio_ctx* c);

@@ -36,9 +36,7 @@ struct KfCloud {
     int timed, have_ms; hipEvent_t ev_t[4];                      // GLIO_KFCLOUD_TIMING=1: around de-skew + box, VoxelGrid (+ the copy into the row), presort
 };
 
-// the motion of the sweep: q_si = slerp(identity, q, ratio), t_si = ratio t (on = 0: no de-skew, the points are copied)
-struct KfcMotion { double q[4], t[3]; int on, pad_; };
-
+// (KfcMotion, the motion of the sweep: glio_device.h -- the dense store runs the same pass)
 __global__ __launch_bounds__(KFC_THREADS) void k_kfc_deskew(const unsigned char* __restrict__ src, const int n, const int stride, const int ioff, const KfcMotion m,
                                                             float4* __restrict__ out, int* __restrict__ box6) {
     __shared__ int s_box[KFC_THREADS / 64 * 6];
@@ -88,9 +86,22 @@ void glio_kfcloud_destroy(glio_ctx* c) {
     c->kfcloud = nullptr;
 }
 
-static bool kfc_finite(const double* v, int n) {
+bool glio_kfc_finite(const double* v, int n) {
     for (int i = 0; i < n; ++i) if (!(fabs(v[i]) <= DBL_MAX)) return false;
     return true;
+}
+void glio_kfc_motion(const double* trans, const double* quat, KfcMotion* m) {
+    memset(m, 0, sizeof *m);
+    m->q[0] = 1.0;
+    if (trans) {
+        m->on = 1;
+        for (int e = 0; e < 3; ++e) m->t[e] = trans[e];
+        if (quat) for (int e = 0; e < 4; ++e) m->q[e] = quat[e];
+    }
+}
+void glio_kfc_launch_deskew(hipStream_t s, const unsigned char* src, int n, int stride, int ioff, const KfcMotion& m, float4* out, int* box6) {
+    const dim3 grid((n + KFC_THREADS * KFC_PER - 1) / (KFC_THREADS * KFC_PER));
+    hipLaunchKernelGGL(k_kfc_deskew, grid, dim3(KFC_THREADS), 0, s, src, n, stride, ioff, m, out, box6);
 }
 
 // slot >= 0: into window slot `slot` on the context's stream; slot < 0: ahead, into the row of the current slot 0 on the upload stream.
@@ -102,7 +113,7 @@ static int kfc_run(glio_ctx* c, const int slot, const void* host, glio_ctx* fe, 
     if (!ahead && slot >= c->W) { glio_set_error("bad slot %d", slot); return GLIO_E_ARG; }
     if (!fe && !glio_point_layout_ok(stride, ioff)) { glio_set_error("bad point layout (stride %d, intensity at %d)", stride, ioff); return GLIO_E_ARG; }
     if (fe && fe->device != c->device) { glio_set_error("the front end is on device %d, the context on %d", fe->device, c->device); return GLIO_E_ARG; }
-    if ((trans && !kfc_finite(trans, 3)) || (quat && !kfc_finite(quat, 4))) { glio_set_error("the de-skew motion is not finite"); return GLIO_E_ARG; }
+    if ((trans && !glio_kfc_finite(trans, 3)) || (quat && !glio_kfc_finite(quat, 4))) { glio_set_error("the de-skew motion is not finite"); return GLIO_E_ARG; }
     KfCloud* k = c->kfcloud;
     if (!k) { glio_set_error("glio_scan_filter_config first"); return GLIO_E_STATE; }
     const float4* d_feat = nullptr;
@@ -139,20 +150,13 @@ static int kfc_run(glio_ctx* c, const int slot, const void* host, glio_ctx* fe, 
             src = static_cast<const unsigned char*>(k->raw.d);
         }
         KfcMotion m;
-        memset(&m, 0, sizeof m);
-        m.q[0] = 1.0;
-        if (trans) {
-            m.on = 1;
-            for (int e = 0; e < 3; ++e) m.t[e] = trans[e];
-            if (quat) for (int e = 0; e < 4; ++e) m.q[e] = quat[e];
-        }
-        const dim3 grid((n + KFC_THREADS * KFC_PER - 1) / (KFC_THREADS * KFC_PER));
+        glio_kfc_motion(trans, quat, &m);
         const bool filter = leaf > 0.f;
         if (filter) { const int rb = glio_vg_staged_begin(k->vg, s, n); if (rb != GLIO_OK) return rb; }
         else if (c->ext_read_pending) { GLIO_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ext_read, 0)); if (!ahead) c->ext_read_pending = 0; }
         if (k->timed) GLIO_HIP_CHECK(hipEventRecord(k->ev_t[0], s));
         // leaf <= 0: the count is n, the moved points go straight into the row (the box is computed and not used)
-        hipLaunchKernelGGL(k_kfc_deskew, grid, dim3(KFC_THREADS), 0, s, src, n, stride, ioff, m, filter ? glio_vg_staging(k->vg) : c->d_scan + row, glio_vg_staging_box(k->vg));
+        glio_kfc_launch_deskew(s, src, n, stride, ioff, m, filter ? glio_vg_staging(k->vg) : c->d_scan + row, glio_vg_staging_box(k->vg));
         GLIO_HIP_CHECK(hipGetLastError());
         if (k->timed) GLIO_HIP_CHECK(hipEventRecord(k->ev_t[1], s));
         if (fe && fe->stream != s) {            // the front end's next extraction (and its destruction) come behind this read

@@ -66,6 +66,7 @@ struct LocalMap {
     // glio_vg_staged_*: PCL's overflow rule is applied (a box of more than INT32_MAX cells passes the cloud through: the keyframe cloud's filter, as
     // ft_voxel_grid); last_passthrough = the last build met it
     int pcl_overflow, last_passthrough;
+    int wave_emit;                  // accumulation = 1 emits through k_lm_emit_wave (glio_vg_set_wave_emit: the dense store's VoxelGrid only)
     hipEvent_t ev_rb0, ev_rb1; int time_rebuild, have_rebuild_ms;      // GLIO_LM_REBUILD_TIMING=1: timing events around the rebuild's two launches (glio_localmap_last_rebuild_device_ms)
 };
 // one keyframe of a rebuild: its own-frame cloud (resident in a batch association), its size and transformCloud's pose
@@ -372,6 +373,100 @@ __global__ void k_lm_emit_float(const int* __restrict__ vslot_sorted, const int 
     }
     const float c = (float)n;
     out[v] = make_float4(ax / c, ay / c, az / c, aw / c);
+}
+
+// ---- the same emit for clouds with LONG lists (glio_vg_set_wave_emit: the dense store's full clouds, whose voxels next to the sensor hold hundreds of points).
+// k_lm_emit_float gives a voxel's whole list to one thread: n^2 / 4 (or n log n) dependent round trips for the sort and n more for the points, while 63 lanes
+// wait.  Here a wavefront owns LM_WAVE_VOX voxels.  Lists of up to LM_WAVE_LIST_MIN entries keep one thread each (the insertion sort above).  The longer ones are
+// taken one after the other by the WHOLE wavefront: the list is sorted cooperatively -- a bitonic network in LDS, or in place in global memory for a list
+// longer than LM_WAVE_LIST_LDS -- the points are fetched 64 at a time (one load per lane, the next 64 already in flight), and the four float sums take them
+// from the lanes' registers one at a time in list order (v_readlane + v_add, every lane the same sum).  The adds are the same adds in the same order, the entries
+// are distinct so every sort leaves the same list: the bytes are k_lm_emit_float's.  No atomic, no scratch.
+#define LM_WAVE_VOX 16            /* voxels per wavefront (lanes 0 .. 15 hold one each) */
+#define LM_WAVE_LIST_MIN 16       /* longest list that stays with one thread */
+#define LM_WAVE_LIST_LDS 2048     /* longest list that is sorted in LDS (8 KB per wavefront: five wavefronts per SIMD keep their lists there) */
+// Bitonic merge sort in the form whose every exchange is ascending (the first step of a stage pairs i with its mirror image inside the block of k, the later
+// ones i with i + j): elements behind the end behave as +inf and never move, so a list of ANY length is sorted without padding.  One wavefront, `a` in LDS or
+// in global memory; every step ends with the ordering point that fits.
+template <bool IN_LDS> __device__ __forceinline__ void lm_wave_sync() {
+    if (IN_LDS) GLIO_WAVE_LDS_SYNC();
+    else { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); }
+}
+template <bool IN_LDS> __device__ __forceinline__ void lm_wave_bitonic(int* a, const int n, const int lane) {
+    for (int k = 2; (k >> 1) < n; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = lane;; t += 64) {
+                const int i = (t / j) * 2 * j + (t % j);                     // (j is a power of two)
+                if (i >= n) break;
+                const int p = (j == (k >> 1)) ? (i - (i % j)) + (k - 1 - (i % j)) : i + j;      // (i % j < j: the mirror image lies in the upper half of i's block)
+                if (p < n) { const int x = a[i], y = a[p]; if (x > y) { a[i] = y; a[p] = x; } }
+            }
+            lm_wave_sync<IN_LDS>();
+        }
+    }
+}
+__device__ __forceinline__ float4 lm_ring_point(const float4* __restrict__ ring, const int idx, const int cap, const int width, const int head) {
+    const int age = idx / cap, j = idx - age * cap;
+    return ring[(size_t)((head + age) % width) * cap + j];
+}
+__global__ __launch_bounds__(64) void k_lm_emit_wave(const int* __restrict__ vslot_sorted, const int nv, const int* __restrict__ cnt, const int* __restrict__ slot_start,
+                                                     int* plist, const float4* __restrict__ ring, const int cap, const int width, const int head, float4* __restrict__ out,
+                                                     unsigned* __restrict__ bm, const unsigned long long* __restrict__ vkey, const unsigned long long bm_bits) {
+    __shared__ int s_list[LM_WAVE_LIST_LDS];
+    const int lane = threadIdx.x, v = blockIdx.x * LM_WAVE_VOX + lane;
+    const bool mine = lane < LM_WAVE_VOX && v < nv;
+    int n = 0, st = 0;
+    if (mine) {
+        bm_clear_word(bm, vkey, v, bm_bits);
+        const int s = vslot_sorted[v];
+        n = cnt[s]; st = slot_start[s];
+    }
+    if (mine && n <= LM_WAVE_LIST_MIN) {
+        int* L = plist + st;
+        for (int a = 1; a < n; ++a) {
+            const int x = L[a];
+            int b = a - 1;
+            while (b >= 0 && L[b] > x) { L[b + 1] = L[b]; --b; }
+            L[b + 1] = x;
+        }
+        float ax = 0.f, ay = 0.f, az = 0.f, aw = 0.f;
+        for (int a = 0; a < n; ++a) {
+            const float4 p = lm_ring_point(ring, L[a], cap, width, head);
+            ax += p.x; ay += p.y; az += p.z; aw += p.w;
+        }
+        const float c = (float)n;
+        out[v] = make_float4(ax / c, ay / c, az / c, aw / c);
+    }
+    unsigned long long todo = __ballot(mine && n > LM_WAVE_LIST_MIN);
+    while (todo) {                                                           // (uniform over the wavefront)
+        const int l = __ffsll(todo) - 1;
+        todo &= todo - 1ull;
+        const int ln = __builtin_amdgcn_readlane(n, l), lst = __builtin_amdgcn_readlane(st, l);
+        int* L = plist + lst;
+        const bool in_lds = ln <= LM_WAVE_LIST_LDS;
+        if (in_lds) {
+            for (int a = lane; a < ln; a += 64) s_list[a] = L[a];
+            GLIO_WAVE_LDS_SYNC();
+            lm_wave_bitonic<true>(s_list, ln, lane);
+        } else lm_wave_bitonic<false>(L, ln, lane);
+        float ax = 0.f, ay = 0.f, az = 0.f, aw = 0.f;
+        float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (lane < ln) p = lm_ring_point(ring, in_lds ? s_list[lane] : L[lane], cap, width, head);
+        for (int a0 = 0; a0 < ln; a0 += 64) {
+            float4 q = make_float4(0.f, 0.f, 0.f, 0.f);                      // the next 64 points: in flight while these are summed
+            const int an = a0 + 64 + lane;
+            if (an < ln) q = lm_ring_point(ring, in_lds ? s_list[an] : L[an], cap, width, head);
+            const int m = min(64, ln - a0);
+            for (int i = 0; i < m; ++i) {
+                ax += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p.x), i)); ay += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p.y), i));
+                az += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p.z), i)); aw += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(p.w), i));
+            }
+            p = q;
+        }
+        const float c = (float)ln;
+        if (lane == l) out[v] = make_float4(ax / c, ay / c, az / c, aw / c);
+        GLIO_WAVE_LDS_SYNC();                                                // (s_list is refilled by the next list)
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -706,6 +801,10 @@ static int lm_voxelize(LocalMap* m, hipStream_t stream, int* nv_out) {
             LM_CHECK(hipMemsetAsync(m->d_fill, 0, (size_t)m->table_cap * 4, stream));
             hipLaunchKernelGGL(k_lm_scatter_idx, dim3((m->cap + 255) / 256, m->width), dim3(256), 0, stream, m->d_ring, m->d_n, m->cap, m->width, m->head, m->count,
                                inv_leaf, m->d_keys, m->table_cap, m->d_slot_start, m->d_fill, m->d_plist);
+            if (m->wave_emit)
+                hipLaunchKernelGGL(k_lm_emit_wave, dim3((nv + LM_WAVE_VOX - 1) / LM_WAVE_VOX), dim3(64), 0, stream, va, nv, m->d_cnt, m->d_slot_start, m->d_plist, m->d_ring, m->cap,
+                                   m->width, m->head, m->d_out, m->d_bm, keys_final, (unsigned long long)BM_MAX_BITS);
+            else
             hipLaunchKernelGGL(k_lm_emit_float, dim3((nv + 255) / 256), dim3(256), 0, stream, va, nv, m->d_cnt, m->d_slot_start, m->d_plist, m->d_ring, m->cap, m->width,
                                m->head, m->d_out, m->d_bm, keys_final, (unsigned long long)BM_MAX_BITS);
         } else
@@ -854,6 +953,7 @@ int glio_vg_create(int width, int cap, float leaf, int max_vox, hipStream_t stre
     return GLIO_OK;
 }
 void glio_vg_destroy(LocalMap* m) { lm_free(m); }
+void glio_vg_set_wave_emit(LocalMap* m, int on) { m->wave_emit = on ? 1 : 0; }
 float4* glio_vg_staging(LocalMap* m) { return m->d_ring; }
 int* glio_vg_staging_box(LocalMap* m) { return m->d_slot_bbox; }
 const float4* glio_vg_output(LocalMap* m) { return m->d_out; }

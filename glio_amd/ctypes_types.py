@@ -253,12 +253,27 @@ KEYFRAME_CLOUD_PROTOTYPES = {
     "glio_get_scan": [C.c_void_p, C.c_int, c_float_p, C.c_int, c_int_p],
     "glio_scan_filter_last_device_ms": [C.c_void_p, c_float_p],
 }
+# ---- the dense store and the global map over it (include/glio_dense.h)
+c_void_pp = C.POINTER(C.c_void_p)
+DENSE_PROTOTYPES = {
+    "glio_dense_create": [C.c_int, C.c_int, C.c_int, C.c_int, c_void_pp],
+    "glio_dense_set_frame_strided": [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, c_double_p, c_double_p, c_int_p],
+    "glio_dense_set_frame": [C.c_void_p, C.c_int, c_float_p, C.c_int, C.c_float, c_double_p, c_double_p, c_int_p],
+    "glio_dense_set_frame_from_features": [C.c_void_p, C.c_int, C.c_void_p, C.c_float, c_double_p, c_double_p, c_int_p],
+    "glio_dense_read_frame": [C.c_void_p, C.c_int, c_float_p, C.c_int, c_int_p],
+    "glio_dense_frame_count": [C.c_void_p, C.c_int, c_int_p],
+    "glio_dense_last_device_ms": [C.c_void_p, c_float_p],
+    "glio_dense_world_cloud": [C.c_void_p, c_double_p, c_float_p, C.c_int, c_int_p],
+    "glio_gmap_create_on_dense": [C.c_void_p, C.c_void_p, c_void_pp],
+}
 
 
 def apply_prototypes(lib):
-    for name, args in KEYFRAME_CLOUD_PROTOTYPES.items():
+    for name, args in list(KEYFRAME_CLOUD_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise AttributeError(f"{name} is missing from the library: it is stale, rebuild it with `python -m glio_amd.build`")
         fn.argtypes = args
         fn.restype = C.c_int
+    lib.glio_dense_destroy.argtypes = [C.c_void_p]
+    lib.glio_dense_destroy.restype = None

@@ -10,7 +10,7 @@ from .. import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEMO = os.path.join(HERE, "host_demo")
-_ABI_HEADERS = [os.path.join(HERE, "..", "..", "include", h) for h in ("glio_hip.h", "glio_types.h", "glio_pgraph_lm.h", "glio_cov.h")]      # a changed struct must rebuild the demos
+_ABI_HEADERS = [os.path.join(HERE, "..", "..", "include", h) for h in ("glio_hip.h", "glio_types.h", "glio_pgraph_lm.h", "glio_cov.h", "glio_dense.h")]      # a changed struct must rebuild the demos
 
 
 def build_demo(force=False):
@@ -315,6 +315,41 @@ def run_demo_keyframe_cloud(path, device=0, leaf=0.9, deskew=True, window=3, env
         else:
             info = json.loads(line)
     return scans, kfs, info
+
+
+DEMO_DENSE_MAP = os.path.join(HERE, "host_demo_dense_map")
+
+
+def build_demo_dense_map(force=False):
+    """The C++ dense map (host_demo_dense_map.cpp: runRaw -> glio::KeyframeGate -> glio::DenseClouds::setFrameFromFeatures -> glio::GlobalMap on the store)."""
+    src = [os.path.join(HERE, "host_demo_dense_map.cpp"), os.path.join(HERE, "glio_backend.hpp"), os.path.join(HERE, "glio_loop_backend.hpp"),
+           os.path.join(HERE, "glio_map_backend.hpp")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_DENSE_MAP) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_DENSE_MAP) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_DENSE_MAP])
+    return DEMO_DENSE_MAP
+
+
+def run_demo_dense_map(path, device=0, leaf=0.4, map_leaf=0.2, chunk=2, deskew=True, env=None):
+    """the stream file of write_frontend_raw_stream -> (per-scan dicts {kf, cut}, per-keyframe dicts {scan, frame, n, hash}, the map {n_voxels, hash, n_points,
+    frames}, info)"""
+    import json
+    r = subprocess.run([build_demo_dense_map(), path, str(device), f"leaf={leaf!r}", f"map_leaf={map_leaf!r}", f"chunk={int(chunk)}", f"deskew={int(bool(deskew))}"],
+                       capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError(f"host_demo_dense_map failed: {r.stderr}")
+    scans, kfs, gmap, info = [], [], None, None
+    for line in r.stdout.strip().splitlines():
+        v = line.split()
+        if v[0] == "scan":
+            scans.append({"kf": int(v[2]), "cut": int(v[3])})
+        elif v[0] == "kf":
+            kfs.append({"scan": int(v[1]), "frame": int(v[2]), "n": int(v[3]), "hash": int(v[4])})
+        elif v[0] == "map":
+            gmap = {"n_voxels": int(v[1]), "hash": int(v[2]), "n_points": int(v[3]), "frames": int(v[4])}
+        else:
+            info = json.loads(line)
+    return scans, kfs, gmap, info
 
 
 DEMO_LOOP = os.path.join(HERE, "host_demo_loop")

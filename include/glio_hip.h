@@ -464,7 +464,8 @@ int glio_features_last_device_ms(glio_ctx* ctx, float* ms);
  * Errors leave the slot and its count untouched: GLIO_E_ARG for a bad slot or point layout, n > max_input_points, contexts on different devices, a
  * non-finite motion, or more outputs than max_points_per_scan (*n_out still tells the count); GLIO_E_STATE before glio_scan_filter_config, or for a
  * front end without an extraction.  n == 0 gives an empty slot and GLIO_OK.
- * Not built: the de-skew of edge_features / full_cloud (:625-626), fullDS (Estimator.cpp:3623-3626, its only use is commented out), pub_full_cloud_map. */
+ * The full cloud's de-skew (:626), fullDS (Estimator.cpp:3623-3626) and pub_full_cloud_map are the dense store of include/glio_dense.h (glio_dense_*), which runs
+ * this same de-skew and VoxelGrid.  Not built: the de-skew of edge_features (:625). */
 /* allocates the stage's buffers: staging for max_input_points (1 .. GLIO_FEAT_MAX_RAW_POINTS) input points and the voxel table (a context that
  * never calls it allocates nothing for it) */
 int glio_scan_filter_config(glio_ctx* ctx, int max_input_points);
@@ -576,7 +577,8 @@ int glio_loop_last_device_ms(glio_loop* lp, float* ms);
 
 /* ---- the global map on the device.  Replaces the live part of mapVisualizationThread (Estimator.cpp:5315-5350: every mapping_interval-th keyframe's surf cloud
  * through transformCloud at its final pose, :5339-5341, the concatenation through ds_filter_global_map, :5342-5343) and the same computation of
- * publishCompleteMap (:5275-5313, poses composed at :5287-5288; its full_clouds_ds is never filled, the push at :3626 is commented out).  Writing the .pcd stays
+ * publishCompleteMap (:5275-5313, poses composed at :5287-5288) over the surf clouds.  publishCompleteMap as written -- over full_clouds_ds, the FULL cloud of
+ * every keyframe, whose push at :3626 the released source comments out -- is glio_gmap_create_on_dense (include/glio_dense.h).  Writing the .pcd stays
  * with the caller.
  * A glio_gmap is created on a glio_bassoc exactly like a glio_loop: same device, its own HIP stream, every call ordered behind the association's pending frame
  * copies by an event; it changes nothing the association holds.  glio_gmap_add_frames returns when its kernels are done, so the association's next write to a cloud
