@@ -154,6 +154,13 @@ def test_rejected_steps(hip, new_mask, steady20):
     assert info["new"]["path"] == 2
     assert m.successful_steps < m.iterations and m.iterations - m.successful_steps >= 2, m.as_dict()
     assert info["new"]["fat_steps"] < m.iterations, (info, m.as_dict())
+    # ... and the whole solve is the oracle's: counts, termination, costs, final radius, gradient norm, state (tests/window_tr_cases.py's gates)
+    import window_tr_cases as wc
+    from oracle import pyoracle as po
+    w2 = copy.copy(win)
+    w2.opts = opts2
+    so, mo = po.Problem(w2, corr).solve(far)
+    wc.compare_with_oracle(got[0][0], m, so, mo, label="rejected steps, W = 20")
 
 
 def test_start_at_the_optimum_and_one_iteration(hip, new_mask, steady20):

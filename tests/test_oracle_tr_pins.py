@@ -11,50 +11,13 @@ import np_ceres as nc
 from glio_amd import batch, synth
 from glio_amd import ctypes_types as T
 from oracle import pyoracle as po
-
-
-def _quat_plus(q, d):
-    n = np.linalg.norm(d)
-    if n == 0.0:
-        return q.copy()
-    dq = np.r_[np.cos(n), np.sin(n) / n * d]
-    w1, v1, w2, v2 = dq[0], dq[1:], q[0], q[1:]
-    return np.r_[w1 * w2 - v1 @ v2, w1 * v2 + w2 * v1 + np.cross(v1, v2)]
+# the window problem's callbacks for np_ceres.minimize live in tests/window_tr_cases.py (the trust-region branch cases use them too)
+from window_tr_cases import np_opts_from as _np_opts_from
+from window_tr_cases import quat_plus as _quat_plus
+from window_tr_cases import window_callbacks as _window_callbacks
 
 
 # ------------------------------------------------------------------ sliding-window problem (orc_solver.c)
-def _window_callbacks(prob):
-    W = prob.win.W
-
-    def plus(x, d):
-        y = x.copy()
-        for s in range(W):
-            y.trans[s] = x.trans[s] + d[15 * s:15 * s + 3]
-            y.quat[s] = _quat_plus(x.quat[s], d[15 * s + 3:15 * s + 6])
-            y.speed_bias[s] = x.speed_bias[s] + d[15 * s + 6:15 * s + 15]
-        if x.n_ddt:
-            y.rcv_ddt[:x.n_ddt] = x.rcv_ddt[:x.n_ddt] + d[15 * W:]
-        return y
-
-    def flat(x):
-        return np.concatenate([x.trans.ravel(), x.quat.ravel(), x.speed_bias.ravel(), x.rcv_ddt[:x.n_ddt]])
-
-    def evaluate(x):
-        H, g, c = prob.linearize(x)
-        if not (np.isfinite(c) and np.all(np.isfinite(H)) and np.all(np.isfinite(g))):
-            return c, H, g          # the oracle does not treat non-finite values as an evaluation failure either
-        return c, H, g
-
-    return evaluate, plus, flat
-
-
-def _np_opts_from(o, **kw):
-    return nc.Options(max_iterations=o.max_iterations, strategy="lm" if o.trust_region_strategy == 1 else "dogleg", dogleg="traditional",
-                      jacobi_scaling=bool(o.jacobi_scaling), initial_radius=o.initial_trust_region_radius, max_radius=o.max_trust_region_radius,
-                      min_radius=o.min_trust_region_radius, min_relative_decrease=o.min_relative_decrease, function_tolerance=o.function_tolerance,
-                      gradient_tolerance=o.gradient_tolerance, parameter_tolerance=o.parameter_tolerance, **kw)
-
-
 def _compare_window(win, corr, expect_rejected=False, **prob_kw):
     prob = po.Problem(win, corr, **prob_kw)
     sol, summ, hist = prob.solve_history(win.init)
