@@ -64,6 +64,22 @@ def _check(rc):
         raise GlioError(f"libglio_hip error {rc}: {load().glio_last_error().decode()}")
 
 
+def align_opts(**kw):
+    """glio_align_opts_default with fields replaced; `thresholds` (a sequence) also sets n_rounds"""
+    o = T.GlioAlignOpts()
+    load().glio_align_opts_default(C.byref(o))
+    th = kw.pop("thresholds", None)
+    if th is not None:
+        th = [float(x) for x in th]
+        o.n_rounds = len(th)
+        for k in range(min(len(th), T.ALIGN_MAX_ROUNDS)):
+            o.thresholds[k] = th[k]
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
 def device_count():
     return load().glio_device_count()
 

@@ -59,6 +59,65 @@ __device__ __forceinline__ void fm_dd_whiten(const double* W, const int i, const
 }
 
 // ------------------------------------------------------------------------------------------------
+// The frame the DD rows live in (include/glio_align.h): R_ecef_enu at an anchor, and the DD row with its derivatives wrt the frame
+// ------------------------------------------------------------------------------------------------
+// the device twin of capi.hip's ecef2rotation_host (gnss_utility.cpp:347-390, 738-748, closed form): the same expressions in the same order
+__device__ __forceinline__ void fm_ecef2rotation(const double xyz[3], double R[9]) {
+#pragma clang fp contract(off)
+    const double PI = 3.14159265358979323846;
+    const double e2 = 6.69437999014e-3, a = 6378137.0, R2D = 180.0 / PI, D2R = PI / 180.0;
+    const double a2 = a * a, b2 = a2 * (1 - e2), b = sqrt(b2), ep2 = (a2 - b2) / b2;
+    const double p = sqrt(xyz[0] * xyz[0] + xyz[1] * xyz[1]);
+    double s1 = xyz[2] * a, s2 = p * b;
+    const double h = sqrt(s1 * s1 + s2 * s2);
+    const double st = s1 / h, ct = s2 / h;
+    s1 = xyz[2] + ep2 * b * pow(st, 3.0);
+    s2 = p - a * e2 * pow(ct, 3.0);
+    const double lat = (atan(s1 / s2) * R2D) * D2R, lon = (atan2(xyz[1], xyz[0]) * R2D) * D2R;
+    const double sl = sin(lat), cl = cos(lat), so = sin(lon), co = cos(lon);
+    R[0] = -so; R[1] = -sl * co; R[2] = cl * co;
+    R[3] = co;  R[4] = -sl * so; R[5] = cl * so;
+    R[6] = 0;   R[7] = cl;       R[8] = sl;
+}
+// R_ecef_local = R_ecef_enu Rz(yaw), the product as glio_host_ecef_local forms it; c, s = cos, sin of the yaw
+__device__ __forceinline__ void fm_ecef_local(const double Ree[9], const double c, const double s, double R[9]) {
+#pragma clang fp contract(off)
+    const double Rel[9] = {c, -s, 0, s, c, 0, 0, 0, 1};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double acc = 0;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) acc += Ree[i * 3 + k] * Rel[k * 3 + j];
+            R[i * 3 + j] = acc;
+        }
+}
+// Row i of factor F against its master at the frame (psi, anc), R = ecef2rotation(anc) Rz(psi), before the whitening: the down-weighted residual and
+// its derivatives wrt the step (d_e, d_n, d_u, d_psi) with anc <- anc + ecef2rotation(anc) d_enu, psi <- psi + d_psi.  With g = -wgt (e_i - e_m) -- the
+// position Jacobian of fm_dd_row at ratio 1 -- and lp the interpolated local position: d r / d psi = g . (-lp_y, lp_x, 0), d r / d enu = Rz(psi) g.  The
+// dependence of ecef2rotation(anc) on anc is left out (|lp| / 6.4e6).  Jb is (d / d psi, 0, 0): the pair (Jenu, Jb) is whitened by fm_dd_whiten like
+// (Jri, Jrj).  down = the row was down-weighted.
+__device__ __forceinline__ void fm_align_row(const glio_dd_psr& F, const int i, const double threshold, const double Pi[3], const double Pj[3], const double R[9],
+                                             const double anc[3], const double c, const double s, double& raw, double Jenu[3], double Jb[3], int& down) {
+#pragma clang fp contract(off)
+    double Pe[3], lp[3], ru_i, rr_i, obs_i, e_i[3], ru_m, rr_m, obs_m, e_m[3], g[3], z[3], full, gf[3];
+    fm_dd_position(F.ratio, Pi, Pj, R, anc, Pe);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) lp[k] = F.ratio * Pi[k] + (1.0 - F.ratio) * Pj[k];
+    fm_dd_satellite(F, i, Pe, R, ru_i, rr_i, obs_i, e_i);
+    fm_dd_satellite(F, F.master, Pe, R, ru_m, rr_m, obs_m, e_m);
+    fm_dd_row(1.0, threshold, ru_i, rr_i, obs_i, e_i, ru_m, rr_m, obs_m, e_m, raw, g, z);
+    fm_dd_row(1.0, INFINITY, ru_i, rr_i, obs_i, e_i, ru_m, rr_m, obs_m, e_m, full, gf, z);     // weight 1: est - obs itself
+    down = fabs(full) > threshold ? 1 : 0;
+    Jenu[0] = c * g[0] - s * g[1];
+    Jenu[1] = s * g[0] + c * g[1];
+    Jenu[2] = g[2];
+    Jb[0] = g[1] * lp[0] - g[0] * lp[1];
+    Jb[1] = 0; Jb[2] = 0;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Doppler row, tcdopplerFactor with its analytic Jacobians (dopp_factor.hpp:24-75): the residual, 1 / var and the gradients wrt the interpolated
 // position and velocity in the local frame.  The callers scale them by ratio / (1 - ratio) and 1 / var, and apply the loss.
 // ------------------------------------------------------------------------------------------------

@@ -268,8 +268,48 @@ DENSE_PROTOTYPES = {
 }
 
 
+# ---- the GNSS frame estimate (include/glio_align.h)
+ALIGN_MAX_ROUNDS, ALIGN_MAX_HYPOTHESES, ALIGN_MAX_ITERATIONS = 8, 4096, 64
+ALIGN_OK, ALIGN_WEAK, ALIGN_UNOBSERVABLE = 0, 1, 2
+ALIGN_STATUS = {0: "OK", 1: "WEAK", 2: "UNOBSERVABLE"}
+
+
+class GlioAlignOpts(C.Structure):
+    """glio_align_opts"""
+    _fields_ = [("n_hypotheses", C.c_int32), ("n_rounds", C.c_int32), ("max_iterations_per_round", C.c_int32), ("reserved_", C.c_int32),
+                ("thresholds", C.c_double * ALIGN_MAX_ROUNDS), ("yaw_tolerance", C.c_double), ("pos_tolerance", C.c_double), ("max_yaw_sigma", C.c_double)]
+
+
+class GlioAlignInfo(C.Structure):
+    """glio_align_info"""
+    _fields_ = [("status", C.c_int32), ("winner", C.c_int32), ("n_rows", C.c_int32), ("n_rounds", C.c_int32),
+                ("round_iterations", C.c_int32 * ALIGN_MAX_ROUNDS), ("round_downweighted", C.c_int32 * ALIGN_MAX_ROUNDS),
+                ("coarse_cost", C.c_double), ("runner_up_cost", C.c_double), ("round_cost", C.c_double * ALIGN_MAX_ROUNDS),
+                ("yaw_sigma", C.c_double), ("yaw_schur", C.c_double), ("h_yaw_yaw", C.c_double), ("covariance", C.c_double * 16)]
+
+    def as_dict(self):
+        n = int(self.n_rounds)
+        return dict(status=int(self.status), status_name=ALIGN_STATUS.get(int(self.status), "?"), winner=int(self.winner), n_rows=int(self.n_rows),
+                    rounds=[(int(self.round_iterations[k]), float(self.round_cost[k]), int(self.round_downweighted[k])) for k in range(n)],
+                    coarse_cost=float(self.coarse_cost), runner_up_cost=float(self.runner_up_cost), yaw_sigma=float(self.yaw_sigma),
+                    yaw_schur=float(self.yaw_schur), h_yaw_yaw=float(self.h_yaw_yaw), covariance=np.array(self.covariance[:], float).reshape(4, 4))
+
+
+ALIGN_PROTOTYPES = {
+    "glio_align_struct_sizes": [c_int32_p, C.c_int],
+    "glio_align_create": [C.c_int, C.c_int, C.c_int, c_void_pp],
+    "glio_align_set_opts": [C.c_void_p, C.POINTER(GlioAlignOpts)],
+    "glio_align_set_factors": [C.c_void_p, C.c_int, C.c_void_p],
+    "glio_align_set_positions": [C.c_void_p, C.c_int, c_double_p, C.c_int],
+    "glio_align_solve": [C.c_void_p, C.POINTER(GlioGnssFrame), C.POINTER(GlioGnssFrame), C.POINTER(GlioAlignInfo)],
+    "glio_align_cost": [C.c_void_p, C.POINTER(GlioGnssFrame), C.c_double, c_double_p, c_int32_p],
+    "glio_align_read_coarse": [C.c_void_p, c_double_p, C.c_int, c_int32_p],
+    "glio_align_last_device_ms": [C.c_void_p, c_float_p],
+}
+
+
 def apply_prototypes(lib):
-    for name, args in list(KEYFRAME_CLOUD_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()):
+    for name, args in list(KEYFRAME_CLOUD_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise AttributeError(f"{name} is missing from the library: it is stale, rebuild it with `python -m glio_amd.build`")
@@ -277,3 +317,7 @@ def apply_prototypes(lib):
         fn.restype = C.c_int
     lib.glio_dense_destroy.argtypes = [C.c_void_p]
     lib.glio_dense_destroy.restype = None
+    lib.glio_align_destroy.argtypes = [C.c_void_p]
+    lib.glio_align_destroy.restype = None
+    lib.glio_align_opts_default.argtypes = [C.POINTER(GlioAlignOpts)]
+    lib.glio_align_opts_default.restype = None

@@ -604,3 +604,42 @@ def run_demo_trajectory(path, device=0, env=None):
         elif w[0] == "resolve":
             resolves.append((int(w[3]), int(w[5])))
     return dict(frames=np.array(rows["frame"]), nodes=np.array(rows["node"]), resolved=np.array(rows["resolved"]), calls=calls, graph=graph, resolves=resolves)
+
+
+DEMO_ALIGN = os.path.join(HERE, "host_demo_align")
+
+
+def build_demo_align(force=False):
+    """The C++ GNSS frame estimate (host_demo_align.cpp over glio::GnssAlignment, glio_align_backend.hpp)."""
+    src = [os.path.join(HERE, "host_demo_align.cpp"), os.path.join(HERE, "glio_align_backend.hpp"), os.path.join(HERE, "..", "..", "include", "glio_align.h")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_ALIGN) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_ALIGN) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_ALIGN])
+    return DEMO_ALIGN
+
+
+def write_align_case(path, opts, start, dd, positions):
+    """int32 n_dd n_pos stride 0 | glio_align_opts | glio_gnss_frame start | glio_dd_psr [n_dd] | double positions [n_pos][stride]"""
+    import ctypes as C
+    pos = np.ascontiguousarray(positions, np.float64)
+    with open(path, "wb") as f:
+        f.write(np.array([len(dd), pos.shape[0], pos.shape[1], 0], np.int32).tobytes())
+        f.write(bytes(opts)); f.write(bytes(start))
+        for d in dd:
+            f.write(C.string_at(C.addressof(d), C.sizeof(d)))
+        f.write(pos.tobytes())
+
+
+def run_demo_align(path, device=0, env=None):
+    """-> dict(frame, info, coarse, cost: the result's bytes; status, rows, downweighted)"""
+    r = subprocess.run([build_demo_align(), path, str(device)], capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError("host_demo_align failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
+    out = {}
+    for ln in r.stdout.splitlines():
+        w = ln.split()
+        if len(w) == 2 and w[0] in ("frame", "info", "coarse", "cost"):
+            out[w[0]] = bytes.fromhex(w[1])
+        elif w and w[0] == "status":
+            out.update(status=int(w[1]), rows=int(w[3]), downweighted=int(w[5]))
+    return out
