@@ -846,6 +846,35 @@ class BatchStage:
         capi._check(capi.load().glio_batch_linearize_full(self._h, T.dptr(poses), T.dptr(sb) if sb is not None else None, cb, None, T.dptr(diag), T.dptr(g), C.byref(cost)))
         return diag, g, cost.value
 
+    def covariance(self, poses, speed_bias=None, anchor=-1, cross=False):
+        """The marginal covariance of every keyframe at (poses, speed_bias) (glio_batch_covariance, include/glio_batch_cov.h): diag [K][B][B], the
+        blocks (k, k) of H^-1 with H the matrix solve_tr linearises (B = 15 with the IMU chain, 6 without); with `cross` also next [K-1][B][B], the
+        blocks (k, k + 1).  `anchor` >= 0 holds that keyframe's pose fixed (needed without GNSS factors: the gauge).  Returns (diag, info) or
+        (diag, next, info).  A matrix that is not positive definite raises GlioError with code E_NUMERIC, the record in .info and the untouched
+        output in .out."""
+        poses = np.ascontiguousarray(poses, np.float64)
+        B = 15 if getattr(self, "n_imu", 0) else 6
+        diag = np.zeros((self.K, B, B)); nxt = np.zeros((self.K - 1, B, B)) if cross else None
+        sb = np.ascontiguousarray(speed_bias, np.float64) if speed_bias is not None else None
+        info = T.GlioBatchCovInfo()
+        rc = capi.load().glio_batch_covariance(self._h, T.dptr(poses), T.dptr(sb) if sb is not None else None, int(anchor), T.dptr(diag),
+                                               T.dptr(nxt) if cross else None, C.byref(info))
+        if rc != 0:
+            e = capi.GlioError(f"libglio_hip error {rc}: {capi.load().glio_last_error().decode()}")
+            e.code, e.info, e.out = rc, info, (diag, nxt)
+            raise e
+        return (diag, nxt, info) if cross else (diag, info)
+
+    def covariance_last_device_ms(self, stages=False):
+        """device time of the last covariance() call, ms; `stages`: [linearise, factor, down-sweep, gather, copy]"""
+        if stages:
+            ms = (C.c_float * 5)()
+            capi._check(capi.load().glio_batch_covariance_last_stage_ms(self._h, ms))
+            return list(ms)
+        ms = C.c_float()
+        capi._check(capi.load().glio_batch_covariance_last_device_ms(self._h, C.byref(ms)))
+        return ms.value
+
     def add_small(self, poses, Hg):
         poses = np.ascontiguousarray(poses, np.float64)
         capi._check(capi.load().glio_batch_add_small_dev(self._h, T.dptr(poses), C.c_void_p(Hg.data_ptr())))

@@ -36,6 +36,7 @@ struct glio_batch {
     int* h_prev_pi; int* h_prev_pj; int h_prev_n;      // the pair list the records were taken for
     long long* h_prev_off;                             // [2 h_prev_n] and each pair's record range then: a pair whose range moved counts as replaced
     int src_min, src_max;      // smallest / largest SOURCE keyframe (ci) of the present constraint set (src_max < src_min: empty); a sharded solve checks them against its range
+    struct BatchCov* cov;      // workspaces of glio_batch_covariance (batch_cov_kernels.hip), allocated at its first call
 };
 // which of a pair of buffers a kernel of the device-resident batch solve works on, and whether it runs at all:
 // buffer = cur ? (*cur ^ want) : want   (want 0: the current point's, 1: the candidate's);  *skip != 0: the kernel returns
@@ -75,6 +76,21 @@ struct BcrOp {
     double lambda;             // when dadd == null: diag += lambda diag + 1e-12
     const int* skip;           // device flag: when *skip != 0 every kernel returns at once (null: never)
 };
+// one elimination of the schedule: node p between the active neighbours a < p < b (-1: none); where its blocks lie in the workspace; `ord`
+// is its place in elimination order (a bad pivot leaves the smallest one in fail[1], see BcrView)
+struct BcrElim { int node, a, b, ord; long long oD, oCa, oCb, oy; };
+// what the selected inversion (batch_cov_kernels.hip) reads of a factorisation left behind by glio_bcr_enqueue_local on ONE rank (node = super-block):
+// L, U_a = A_ap L^-T, U_b = A_bp L^-T per node [nnode][M M]; with the IMU chain the pre-elimination's L [S][NI NI] and U = A_ki L^-T [S][NK NI].
+// fail[0]: bit 0 = a pivot was not positive and finite; fail[1]: atomicMin of the failing eliminations' order, pre-eliminations (their
+// super-block) before the nodes (BCR_ORD_NODE + ord) -- meaningful only if the caller set it to INT_MAX before enqueue_local (the solves never read it).
+#define BCR_ORD_NODE (1 << 20)
+struct BcrView {
+    int M, sbk, S, K, band, B, nnode, levels, world, pre, NI, NK, n_elim;
+    const double* L; const double* Ua; const double* Ub; const double* preL; const double* preU;
+    const BcrElim* h_elim; const int* h_elim_off;          // host copy of the schedule: level l = entries [h_elim_off[l], h_elim_off[l + 1])
+    int* fail;
+};
+void glio_bcr_view(void* h, BcrView* out);
 void* glio_bcr_create(int K, int band);
 void* glio_bcr_create2(int K, int band, int B, int rank, int world);
 void glio_bcr_owned_range(void* h, int* lo, int* hi);
@@ -104,5 +120,11 @@ void glio_launch_batch_imu(hipStream_t stream, const BtSel& sel, double gravity,
 bool glio_digest_imu_edge(const glio_preint* p, int slot, ImuEdgeDev* e);
 // batch_tr_kernels.hip
 void glio_batch_small_destroy(glio_batch* b);
+// the linearisation glio_batch_linearize_full makes (one rank), left on the device: the operator of the current point (buffers 0 of `op`, cur = null), its
+// replicated diagonal [B K] and the trust-region solve's own BCR solver for the present B.  Enqueued on b->stream; no host wait.
+int glio_batch_tr_linearize_at(glio_batch* b, const double* poses, const double* speed_bias, BcrOp* op, const double** diag_dev, void** bcr, int* B);
+int glio_batch_tr_world(glio_batch* b, int* has_imu);
+// batch_cov_kernels.hip
+void glio_batch_cov_destroy(glio_batch* b);
 // capi.hip: GLIO_DEBUG_LDS_POISON=1 fills the LDS of every CU with NaNs (a kernel that reads LDS it never wrote then fails loudly); no-op otherwise
 void glio_lds_poison_stream(hipStream_t stream);

@@ -734,6 +734,7 @@ void glio_batch_destroy(glio_batch* b) {
     hipSetDevice(b->device);
     hipStreamSynchronize(b->stream);
     glio_bcr_destroy(b->bcr);
+    glio_batch_cov_destroy(b);
     glio_batch_small_destroy(b);
     if (b->d_moments) hipFree(b->d_moments);
     if (b->d_mom_slots) hipFree(b->d_mom_slots);

@@ -30,7 +30,7 @@
 
 #include "batch_device.h"
 
-struct BcrElim { int node, a, b, pad_; long long oD, oCa, oCb, oy; };   // blocks in the workspace; a / b: neighbour nodes (-1: none)
+// (BcrElim: batch_device.h -- blocks in the workspace; a / b: neighbour nodes (-1: none))
 struct BcrKept { int node, pl, pr, pad_; long long oD, oy, oCnew; };    // eliminated neighbours left / right (-1), new edge (-1: none)
 struct BcrInit { int sblock, pad_; long long oD, oy, oC; };             // global super-block; where D, y, A[sblock+1][sblock] go (-1: not wanted)
 
@@ -45,6 +45,7 @@ struct BcrDev {
     BcrElim* elim; BcrKept* kept; BcrInit* init;
     int n_init;
     std::vector<int> h_elim_off, h_kept_off;       // per level [levels_loc + levels_top + 1]
+    std::vector<BcrElim> h_elim;                   // the schedule as uploaded (BcrView)
     std::vector<int> node_of_sblock;               // owned super-block (global index - Slo) -> node id
     int* node_of_sblock_dev;
     int* fail;
@@ -260,7 +261,7 @@ __device__ __forceinline__ void bcr_pre_factor(double* __restrict__ pan, double 
 #pragma unroll
         for (int c = 0; c < NI; ++c) pan[row * LDP + c] = (row < NI && c > row) ? 0.0 : a[c];
     }
-    if (row == 0 && *s_bad) atomicOr(fail, 1);
+    if (row == 0 && *s_bad) { atomicOr(fail, 1); atomicMin(fail + 1, (int)blockIdx.x); }
     __syncthreads();
 }
 // from the factored panel: L, U, w out (coalesced); the super-block's node A_kk - U U^T on the matrix core -- T x T tiles of 16 x 16 over the four
@@ -648,7 +649,7 @@ __global__ __launch_bounds__(BcrCfg<M>::THREADS) void k_bcr_elim(const int* skip
         for (int c = 0; c < M; ++c) a[c] = src[c];
     }
     bcr_register_steps<M, 0>(a, row, col, &s_bad);          // (every launched lane is a row: the lanes past 3 M carry zeros)
-    if (row == 0 && s_bad) atomicOr(fail, 1);
+    if (row == 0 && s_bad) { atomicOr(fail, 1); atomicMin(fail + 1, BCR_ORD_NODE + t.ord); }
     if (row < M) {
         double* dst = L + (size_t)t.node * MM + (size_t)row * M;
 #pragma unroll
@@ -846,7 +847,7 @@ __global__ __launch_bounds__(BCR_E2_THREADS) void k_bcr_elim2(const int* skip, c
         Ub[(size_t)t.node * MM + e] = X[(size_t)(M + 1 + i) * C::XS + j];
     }
     for (int c = tid; c < M; c += BCR_E2_THREADS) w[(size_t)t.node * M + c] = X[(size_t)M * C::XS + c];
-    if (tid == 0 && s_bad) atomicOr(fail, 1);
+    if (tid == 0 && s_bad) { atomicOr(fail, 1); atomicMin(fail + 1, BCR_ORD_NODE + t.ord); }
 #ifdef GLIO_DEV_STAMPS
     __syncthreads();
     { BCR_T(ts3); BCR_ACC(3, ts3, ts2); }
@@ -1076,7 +1077,7 @@ static void bcr_build_schedule(std::vector<int> act, std::vector<char> pinned, s
         for (int p = 0; p < n; ++p) {
             if (!el[p]) continue;
             BcrElim t;
-            t.node = act[p]; t.pad_ = 0;
+            t.node = act[p]; t.ord = (int)elim.size();
             t.a = p > 0 ? act[p - 1] : -1; t.b = p + 1 < n ? act[p + 1] : -1;
             t.oD = oD[act[p]]; t.oy = oy[act[p]];
             t.oCa = p > 0 ? edgeC[p - 1] : -1; t.oCb = p + 1 < n ? edgeC[p] : -1;
@@ -1219,6 +1220,7 @@ void* glio_bcr_create2(int K, int band, int B, int rank, int world) {
     if (!kept.empty()) hipMemcpy(b->kept, kept.data(), kept.size() * sizeof(BcrKept), hipMemcpyHostToDevice);
     if (!init.empty()) hipMemcpy(b->init, init.data(), init.size() * sizeof(BcrInit), hipMemcpyHostToDevice);
     hipMemcpy(b->node_of_sblock_dev, b->node_of_sblock.data(), (size_t)nown * 4, hipMemcpyHostToDevice);
+    b->h_elim = elim;
     bcr_allow_lds<54>(); bcr_allow_lds<72>(); bcr_allow_lds<90>();          // (M = 36 stays below the 64 KB every kernel may take)
     bcr_allow_lds(k_bcr_pre12, PRE12_LDS);
     bcr_allow_lds(k_bcr_post12, POST12_LDS);
@@ -1245,6 +1247,16 @@ double* glio_bcr_sepbuf(void* h, long long* count) {
     return b->ws + b->sep_off;
 }
 int* glio_bcr_fail_flag(void* h) { return static_cast<BcrDev*>(h)->fail; }
+void glio_bcr_view(void* h, BcrView* v) {
+    BcrDev* b = static_cast<BcrDev*>(h);
+    v->M = b->M; v->sbk = b->sbk; v->S = b->S; v->K = b->K; v->band = b->band; v->B = b->B; v->nnode = b->nnode; v->levels = b->levels_loc + b->levels_top;
+    v->world = b->world; v->pre = b->pre ? 1 : 0;
+    v->NI = !b->pre ? 0 : (b->sbk == 12 ? BcrPre<12>::NI : BcrPre<6>::NI); v->NK = !b->pre ? 0 : (b->sbk == 12 ? BcrPre<12>::NK : BcrPre<6>::NK);
+    v->n_elim = (int)b->h_elim.size();
+    v->L = b->L; v->Ua = b->Ua; v->Ub = b->Ub; v->preL = b->preL; v->preU = b->preU;
+    v->h_elim = b->h_elim.data(); v->h_elim_off = b->h_elim_off.data();
+    v->fail = b->fail;
+}
 
 // -1 (default): by size -- the blocked elimination (k_bcr_elim2) for M >= 54, one register step per pivot with a workgroup barrier each
 // (k_bcr_elim) for M = 36, where it is the faster one (15 vs 19 us on MI355X); 1 / 0 force either (GLIO_BCR_ELIM, cross-checks)

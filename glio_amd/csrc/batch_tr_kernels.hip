@@ -1232,6 +1232,31 @@ int glio_batch_linearize_full(glio_batch* b, const double* poses, const double* 
     return GLIO_OK;
 }
 
+}  // extern "C"
+// (batch_device.h) what glio_batch_linearize_full enqueues, without its copy back: for glio_batch_covariance
+int glio_batch_tr_world(glio_batch* b, int* has_imu) {
+    if (has_imu) *has_imu = (b->small && b->small->n_imu > 0) ? 1 : 0;
+    return b->small ? b->small->world : 1;
+}
+int glio_batch_tr_linearize_at(glio_batch* b, const double* poses, const double* speed_bias, BcrOp* op, const double** diag_dev, void** bcr, int* B) {
+    { const int rc = small_ensure(b); if (rc) return rc; }
+    { const int rc = tr_ensure(b); if (rc) return rc; }
+    if (g_batch_moments) { const int rm = glio_batch_moments_ensure(b); if (rm) return rm; }
+    BatchSmall* s = b->small;
+    const int n = s->B * b->K;
+    BtStatus st; memset(&st, 0, sizeof st);
+    st.cur = 1; st.first = 1;
+    { const int rc = tr_upload_start(b, st, poses, speed_bias); if (rc) return rc; }
+    BtRun r; r.b = b; r.hook = nullptr; r.user = nullptr;
+    enqueue_tr_linearize(r, 1, true);
+    GLIO_HIP_CHECK(hipGetLastError());
+    memset(op, 0, sizeof *op);
+    for (int k = 0; k < 2; ++k) { op->Hg[k] = s->d_hg[0]; op->imu[k] = s->n_imu > 0 ? s->d_rec[0] : nullptr; op->gfull[k] = s->d_A[0] + n; }
+    *diag_dev = s->d_A[0]; *bcr = s->bcr; *B = s->B;
+    return GLIO_OK;
+}
+extern "C" {
+
 // The trust-region solve.  `allreduce` (NULL for one rank) is called with a device buffer, its length in doubles, the HIP stream the
 // buffer is produced and consumed on, and `user`; it must leave the SUM over the ranks in place, ORDERED ON THAT STREAM (ncclAllReduce on
 // it; torch.distributed.all_reduce with that stream current): the host does not wait for it.  Five calls per trust-region group (file

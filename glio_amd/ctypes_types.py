@@ -91,6 +91,15 @@ class GlioGnssFrame(C.Structure):
     _fields_ = [("yaw_enu_local", C.c_double), ("anc_ecef", C.c_double * 3)]
 
 
+class GlioBatchCovInfo(C.Structure):
+    """glio_batch_cov_info (include/glio_batch_cov.h)"""
+    _fields_ = [("n", C.c_int32), ("B", C.c_int32), ("anchor", C.c_int32), ("bad_keyframe", C.c_int32), ("levels", C.c_int32), ("pad_", C.c_int32),
+                ("min_pivot", C.c_double), ("max_pivot", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
 class GlioSummary(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("successful_steps", C.c_int32), ("termination", C.c_int32),
                 ("n_lidar_residuals", C.c_int32), ("initial_cost", C.c_double), ("final_cost", C.c_double),

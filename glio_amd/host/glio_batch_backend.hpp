@@ -17,6 +17,7 @@
 #include <utility>
 #include <vector>
 
+#include "glio_batch_cov.h"
 #include "glio_hip.h"
 
 namespace glio {
@@ -179,6 +180,24 @@ public:
         }
         return out;
     }
+    // the marginal covariance of every keyframe at (poses, speed_bias) (glio_batch_covariance, glio_batch_cov.h): diag [K][B][B], the blocks (k, k) of
+    // H^-1 with H the matrix solveTrustRegion linearises (B = 15 with the IMU chain, 6 without); with `cross` also next [K-1][B][B], the blocks
+    // (k, k + 1).  anchor >= 0 holds that keyframe's pose fixed -- needed without GNSS factors, where the gauge is free and the call throws otherwise
+    // (info.bad_keyframe names where the factorisation stopped; diag / next stay empty).  glio::pose3Covariance applies to the leading 6 x 6 of a block.
+    struct Covariance { int B = 0; std::vector<double> diag, next; glio_batch_cov_info info; };
+    Covariance covariance(const std::vector<double>& poses, const std::vector<double>* speed_bias = nullptr, int anchor = -1, bool cross = false) {
+        if (poses.size() != (size_t)K_ * 7) throw std::runtime_error("covariance: poses must be [K][7]");
+        if (have_imu_ && (!speed_bias || speed_bias->size() != (size_t)K_ * 9)) throw std::runtime_error("covariance: the IMU chain needs speed_bias [K][9]");
+        Covariance c;
+        c.B = have_imu_ ? 15 : 6;
+        std::vector<double> diag((size_t)K_ * c.B * c.B, 0.0), next(cross ? (size_t)(K_ - 1) * c.B * c.B : 0, 0.0);
+        const int rc = glio_batch_covariance(h_, poses.data(), have_imu_ ? speed_bias->data() : nullptr, anchor, diag.data(), cross ? next.data() : nullptr, &c.info);
+        if (rc == GLIO_E_NUMERIC) throw std::runtime_error(std::string("glio_batch_covariance: ") + glio_last_error());
+        check(rc, "glio_batch_covariance");
+        c.diag.swap(diag); c.next.swap(next);
+        return c;
+    }
+    float covarianceLastDeviceMs() { float ms = 0; check(glio_batch_covariance_last_device_ms(h_, &ms), "glio_batch_covariance_last_device_ms"); return ms; }
     glio_batch* handle() { return h_; }
     void* stream() { return stream_; }
 

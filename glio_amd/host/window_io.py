@@ -606,6 +606,60 @@ def run_demo_trajectory(path, device=0, env=None):
     return dict(frames=np.array(rows["frame"]), nodes=np.array(rows["node"]), resolved=np.array(rows["resolved"]), calls=calls, graph=graph, resolves=resolves)
 
 
+DEMO_BATCH_COV = os.path.join(HERE, "host_demo_batch_cov")
+
+
+def build_demo_batch_cov(force=False):
+    """The C++ per-keyframe covariance of the batch stage (host_demo_batch_cov.cpp over glio::BatchBackend::covariance)."""
+    src = [os.path.join(HERE, "host_demo_batch_cov.cpp"), os.path.join(HERE, "glio_batch_backend.hpp"), os.path.join(HERE, "..", "..", "include", "glio_batch_cov.h")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_BATCH_COV) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_BATCH_COV) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_BATCH_COV])
+    return DEMO_BATCH_COV
+
+
+def write_batch_cov_case(path, K, band, anchor, cross, poses, speed_bias, con, dq, frame, dd, imu, gravity):
+    """the case file of host_demo_batch_cov.cpp (layout in its header); imu: a list of dicts of synth.preintegrate or GlioPreint, or None"""
+    import ctypes as C
+    from .. import ctypes_types as T
+    from .. import synth
+    ci, cj, cp, nc, score = con
+    nc = np.ascontiguousarray(nc, np.float64)
+    imu = list(imu or [])
+    with open(path, "wb") as f:
+        f.write(np.array([K, band, anchor, 1 if cross else 0, len(dq[0]), len(dd), len(imu), nc.size // max(len(ci), 1)], np.int32).tobytes())
+        f.write(np.array([len(ci)], np.int64).tobytes())
+        f.write(np.ascontiguousarray(poses, np.float64).tobytes())
+        if imu:
+            f.write(np.ascontiguousarray(speed_bias, np.float64).tobytes())
+        f.write(np.ascontiguousarray(ci, np.int32).tobytes()); f.write(np.ascontiguousarray(cj, np.int32).tobytes())
+        f.write(np.ascontiguousarray(cp, np.float32).tobytes()); f.write(nc.tobytes()); f.write(np.ascontiguousarray(score, np.float64).tobytes())
+        f.write(np.ascontiguousarray(dq[0], np.int32).tobytes()); f.write(np.ascontiguousarray(dq[1], np.int32).tobytes()); f.write(np.ascontiguousarray(dq[2], np.float64).tobytes())
+        f.write(bytes(frame))
+        for d in dd:
+            f.write(C.string_at(C.addressof(d), C.sizeof(d)))
+        for d in imu:
+            if not isinstance(d, T.GlioPreint):
+                r = T.GlioPreint(); synth.fill_preint(r, d); d = r
+            f.write(C.string_at(C.addressof(d), C.sizeof(d)))
+        f.write(np.array([gravity], np.float64).tobytes())
+
+
+def run_demo_batch_cov(path, device=0, env=None):
+    """-> dict(diag, next (when asked), info: the result's bytes; B, levels, bad_keyframe)"""
+    r = subprocess.run([build_demo_batch_cov(), path, str(device)], capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError("host_demo_batch_cov failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
+    out = {}
+    for ln in r.stdout.splitlines():
+        w = ln.split()
+        if len(w) == 2 and w[0] in ("diag", "next", "info"):
+            out[w[0]] = bytes.fromhex(w[1])
+        elif w[:1] == ["B"]:
+            out.update({w[i]: int(w[i + 1]) for i in range(0, len(w) - 1, 2)})
+    return out
+
+
 DEMO_ALIGN = os.path.join(HERE, "host_demo_align")
 
 
