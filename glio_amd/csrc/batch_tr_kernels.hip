@@ -33,6 +33,8 @@
 
 #include "batch_device.h"
 #include "factor_math.h"
+#include "tr_math.h"
+#include "tr_math_device.h"
 
 #define SREC 124           // Haa 36 | Hbb 36 | Hab 36 | ga 6 | gb 6 | cost 1 | pad
 #define TRV_THREADS 256
@@ -323,14 +325,11 @@ __global__ __launch_bounds__(BT_NORM_THREADS) void k_bt_norms(const BtBufs a, co
 #pragma unroll
             for (int c = 0; c < 9; ++c) { sv[c] = s[9 * k + c]; scv[c] = sc[9 * k + c]; }
         }
-        double nd[3], qn[4];
 #pragma unroll
         for (int c = 0; c < 7; ++c) { const double v = xv[c], d = v - xcv[c]; d2 += d * d; x2 += v * v; }
 #pragma unroll
-        for (int c = 0; c < 3; ++c) { gm = fmax(gm, fabs(gv[c])); nd[c] = -gv[3 + c]; }
-        d_quat_plus(xcv + 3, nd, qn);
-#pragma unroll
-        for (int c = 0; c < 4; ++c) gm = fmax(gm, fabs(xcv[3 + c] - qn[c]));
+        for (int c = 0; c < 3; ++c) gm = fmax(gm, fabs(gv[c]));
+        gm = tr_grad_max_rot(xcv + 3, gv + 3, gm);
         if (B == 15) {
 #pragma unroll
             for (int c = 0; c < 9; ++c) { const double v = sv[c], d = v - scv[c]; d2 += d * d; x2 += v * v; gm = fmax(gm, fabs(gv[6 + c])); }
@@ -374,21 +373,20 @@ __global__ __launch_bounds__(64) void k_bt_state_machine(const BtBufs a, const B
                 s.grad_max = s.cand_grad_max;
                 sh_copy = 1;
             } else if (s.solve_failed) {
-                s.mu *= 10.0;                                         // ComputeGaussNewtonStep: while (mu < max_mu) { ...; mu *= 10 }
-                if (s.mu < 1.0) retry = true;
-                else { if (++s.invalid >= 5) { s.done = 1; s.termination = GLIO_TERM_FAILURE; } else { s.mu *= 10.0; s.reuse = 0; } }
+                s.mu *= TR_MU_INCREASE;                               // ComputeGaussNewtonStep: while (mu < max_mu) { ...; mu *= 10 }
+                if (s.mu < TR_MAX_MU) retry = true;
+                else { if (tr_invalid_limit(++s.invalid)) { s.done = 1; s.termination = GLIO_TERM_FAILURE; } else { s.mu *= TR_MU_INCREASE; s.reuse = 0; } }
             } else if (s.step_pending) {
                 const double ccost = s.cand_cost;
-                if (sqrt(s.dx2) <= o.ptol * (sqrt(s.xn2) + o.ptol)) { s.done = 1; s.termination = GLIO_TERM_PARAMETER_TOL; }
-                else if (fabs(s.cost - ccost) <= o.ftol * s.cost) { s.done = 1; s.termination = GLIO_TERM_FUNCTION_TOL; }
+                if (tr_parameter_converged(sqrt(s.dx2), sqrt(s.xn2), o.ptol)) { s.done = 1; s.termination = GLIO_TERM_PARAMETER_TOL; }
+                else if (tr_function_converged(s.cost, ccost, o.ftol)) { s.done = 1; s.termination = GLIO_TERM_FUNCTION_TOL; }
                 else {
-                    const double rel = (s.cost - ccost) / s.mcc, hist = (s.reference_cost - ccost) / (s.acc_ref + s.mcc);
+                    const double rel = tr_step_quality(s.cost, ccost, s.mcc), hist = (s.reference_cost - ccost) / (s.acc_ref + s.mcc);
                     const double quality = o.max_nonmono > 0 ? fmax(rel, hist) : rel;
-                    if (quality > o.min_rel) {
+                    if (tr_step_accepted(quality, o.min_rel)) {
                         s.cur ^= 1; s.successful += 1;
-                        if (quality < 0.25) s.radius *= 0.5;
-                        if (quality > 0.75) s.radius = fmax(s.radius, 3.0 * s.dogleg_step_norm);
-                        s.mu = fmax(1e-8, 2.0 * s.mu / 10.0);
+                        s.radius = tr_dogleg_accepted_radius(quality, s.dogleg_step_norm, s.radius);
+                        s.mu = tr_mu_accepted(s.mu);
                         s.reuse = 0;
                         s.cost = ccost; s.grad_max = s.cand_grad_max;
                         s.acc_cand += s.mcc; s.acc_ref += s.mcc;
@@ -396,22 +394,23 @@ __global__ __launch_bounds__(64) void k_bt_state_machine(const BtBufs a, const B
                         else { ++s.n_nonmono; if (s.cost > s.candidate_cost) { s.candidate_cost = s.cost; s.acc_cand = 0; } }
                         if (s.n_nonmono == o.max_nonmono) { s.reference_cost = s.candidate_cost; s.acc_ref = s.acc_cand; }
                         if (s.cost < s.user_min_cost) { s.user_min_cost = s.cost; sh_copy = 1; }     // the user's parameters follow the best point only
-                    } else { s.radius *= 0.5; s.reuse = 1; }
+                    } else { s.radius = tr_dogleg_rejected_radius(s.radius); s.reuse = 1; }
                 }
                 s.invalid = 0;
             } else {                                                  // the model cost change was not positive: an invalid step
-                if (++s.invalid >= 5) { s.done = 1; s.termination = GLIO_TERM_FAILURE; } else { s.mu *= 10.0; s.reuse = 0; }
+                if (tr_invalid_limit(++s.invalid)) { s.done = 1; s.termination = GLIO_TERM_FAILURE; } else { s.mu *= TR_MU_INCREASE; s.reuse = 0; }
             }
             // FinalizeIterationAndCheckIfMinimizerCanContinue, then the next iteration
             while (!s.done && !retry) {
+                // (tr_iteration_gate's order, written out: through the function this kernel's register allocation moves, 98 -> 92 VGPRs)
                 if (s.iteration >= o.max_iterations) { s.done = 1; s.termination = GLIO_TERM_NO_CONVERGENCE; break; }
                 if (s.grad_max <= o.gtol) { s.done = 1; s.termination = GLIO_TERM_GRADIENT_TOL; break; }
                 if (s.radius <= o.min_radius) { s.done = 1; s.termination = GLIO_TERM_MIN_RADIUS; break; }
                 ++s.iteration;
-                if (s.reuse || s.mu < 1.0) break;
+                if (s.reuse || s.mu < TR_MAX_MU) break;
                 // the linear solve cannot even be attempted (mu >= max_mu): this iteration's step is invalid at once
-                if (++s.invalid >= 5) { s.done = 1; s.termination = GLIO_TERM_FAILURE; break; }
-                s.mu *= 10.0; s.reuse = 0;
+                if (tr_invalid_limit(++s.invalid)) { s.done = 1; s.termination = GLIO_TERM_FAILURE; break; }
+                s.mu *= TR_MU_INCREASE; s.reuse = 0;
             }
             s.step_pending = 0; s.solve_failed = 0; s.retry = retry ? 1 : 0;
             s.skip_solve = (s.done || s.reuse) ? 1 : 0;
@@ -442,11 +441,9 @@ __global__ void k_bt_prepare(const BtBufs a, const int jacobi) {
     if (BT_SKIP_SOLVE(a)) return;
     const double h = a.A[cur][i], g = a.A[cur][n + i];
     double* sc = BVEC(a, V_SC);
-    if (a.st->group == 1 && !a.st->retry) sc[i] = jacobi ? 1.0 / (1.0 + sqrt(h)) : 1.0;
+    if (a.st->group == 1 && !a.st->retry) sc[i] = jacobi ? tr_jacobi_scale(h) : 1.0;
     const double s = sc[i];
-    double d = s * s * h;
-    d = d < 1e-6 ? 1e-6 : (d > 1e32 ? 1e32 : d);
-    const double D = sqrt(d);
+    const double D = sqrt(tr_clip_diagonal(s * s * h));
     BVEC(a, V_DG)[i] = D; BVEC(a, V_GS)[i] = s * g; BVEC(a, V_GR)[i] = s * g / D; BVEC(a, V_UU)[i] = (s * g / D) / D;
     BVEC(a, V_DA)[i] = a.st->mu * D * D;
 }
@@ -675,17 +672,7 @@ __global__ void k_bt_dogleg(const BtBufs a, const double* __restrict__ stage_d, 
             else traditional = true;
         }
     }
-    if (traditional) {
-        if (gnn <= radius) { cg = 0; cn = 1.0; norm = gnn; }
-        else if (gnorm * alpha >= radius) { cg = -(radius / gnorm); cn = 0; norm = radius; }
-        else {
-            const double b_dot_a = -alpha * gd, a_sq = alpha * alpha * gg;
-            const double b_minus_a_sq = nn2 - 2 * b_dot_a + a_sq, c = b_dot_a - a_sq;
-            const double d = sqrt(c * c + b_minus_a_sq * (radius * radius - a_sq));
-            const double beta = (c <= 0) ? (d - c) / b_minus_a_sq : (radius * radius - a_sq) / (d + c);
-            cg = -alpha * (1.0 - beta); cn = beta; norm = -1.0;
-        }
-    }
+    if (traditional) tr_dogleg_coeffs(false, gg, nn2, gd, gnorm, gnn, radius, alpha, cg, cn, norm);
     s.c_g = cg; s.c_n = cn; s.c_1 = c1; s.c_2 = c2; s.dogleg_step_norm = norm;
 }
 // step in D-space, in the scaled variables, in the parameters; the candidate x (+) delta; one thread per keyframe
@@ -1288,7 +1275,7 @@ int glio_batch_solve_tr2(glio_batch* b, double* poses, double* speed_bias, const
     bo.ptol = o->parameter_tolerance;
     BtStatus init; memset(&init, 0, sizeof init);
     init.cur = 1; init.first = 1; init.step_valid = 1;
-    init.radius = o->initial_trust_region_radius; init.mu = 1e-8;
+    init.radius = o->initial_trust_region_radius; init.mu = TR_MIN_MU;
     s->solve_id = s->solve_id % 30000 + 1;
     init.solve_id = s->solve_id;
     const int id = s->solve_id;

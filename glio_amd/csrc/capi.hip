@@ -16,6 +16,7 @@
 
 #include "../../include/glio_cov.h"
 #include "glio_device.h"
+#include "tr_math.h"
 
 // covariance_kernels.hip
 struct GlioCovWs;
@@ -108,8 +109,9 @@ void glio_opts_default(glio_opts* o) {
     o->q_lb[0] = 1.0; o->t_lb[2] = 0.28;
     o->lidar_const = 7.5; o->surf_dist_thres = 0.18; o->kd_max_radius = 1.5; o->weight_gate = 0.3; o->trust_region_strategy = GLIO_STRATEGY_DOGLEG; o->unit_scores = 0;
     o->gravity = 9.80511;
-    o->initial_trust_region_radius = 1e4; o->max_trust_region_radius = 1e16; o->min_trust_region_radius = 1e-32;
-    o->min_relative_decrease = 1e-3; o->function_tolerance = 1e-6; o->gradient_tolerance = 1e-10; o->parameter_tolerance = 1e-8;
+    o->initial_trust_region_radius = TR_INITIAL_RADIUS; o->max_trust_region_radius = TR_MAX_RADIUS; o->min_trust_region_radius = TR_MIN_RADIUS;
+    o->min_relative_decrease = TR_MIN_RELATIVE_DECREASE; o->function_tolerance = TR_FUNCTION_TOLERANCE; o->gradient_tolerance = TR_GRADIENT_TOLERANCE;
+    o->parameter_tolerance = TR_PARAMETER_TOLERANCE;
 }
 
 static int g_fill = getenv("GLIO_DEBUG_FILL") ? atoi(getenv("GLIO_DEBUG_FILL")) : -1;     // development aid: fill every allocation with this byte
@@ -1208,7 +1210,7 @@ static int enqueue_solve(glio_ctx* c, int n_ddt) {
     memset(&st, 0, sizeof st);
     st.cur = 1;                       // "candidate" buffer 0 holds the initial point
     st.cand_pending = 1;
-    st.radius = c->opts.initial_trust_region_radius; st.mu = 1e-8; st.n_ddt = n_ddt; st.decrease_factor = 2.0;
+    st.radius = c->opts.initial_trust_region_radius; st.mu = TR_MIN_MU; st.n_ddt = n_ddt; st.decrease_factor = TR_LM_DECREASE_FACTOR;
     c->solve_id = c->solve_id % 30000 + 1;          // kernels of the previous solve's look-ahead group may still be draining:
     st.solve_id = c->solve_id;                      // their progress words carry the old tag and are ignored
     *c->h_status = st;
@@ -1671,7 +1673,7 @@ int glio_time_kernel(glio_ctx* c, int which, int reps, float* ms_out) {
                 // one first-iteration step computation (scale, Cauchy, Cholesky, dogleg) on H[0]
                 SolverStatus st;
                 memset(&st, 0, sizeof st);
-                st.cur = 1; st.cand_pending = 1; st.radius = c->opts.initial_trust_region_radius; st.mu = 1e-8; st.n_ddt = n_ddt;
+                st.cur = 1; st.cand_pending = 1; st.radius = c->opts.initial_trust_region_radius; st.mu = TR_MIN_MU; st.n_ddt = n_ddt;
                 *c->h_status = st;
                 GLIO_HIP_CHECK(hipMemcpyAsync(c->d_status, c->h_status, sizeof st, hipMemcpyHostToDevice, c->stream));
                 glio_launch_tr_step(c, n_ddt);
@@ -1680,7 +1682,7 @@ int glio_time_kernel(glio_ctx* c, int which, int reps, float* ms_out) {
                 // last solve is in place, mu at its floor -- the step the helpers' speculative build applies to
                 SolverStatus st;
                 memset(&st, 0, sizeof st);
-                st.cur = 1; st.cand_pending = 1; st.phase = 1; st.iteration = 1; st.radius = c->opts.initial_trust_region_radius; st.mu = 1e-8; st.n_ddt = n_ddt;
+                st.cur = 1; st.cand_pending = 1; st.phase = 1; st.iteration = 1; st.radius = c->opts.initial_trust_region_radius; st.mu = TR_MIN_MU; st.n_ddt = n_ddt;
                 st.cost = 1e30; st.initial_cost = 1e30; st.model_cost_change = 1.0; st.dogleg_step_norm = 1.0;
                 *c->h_status = st;
                 GLIO_HIP_CHECK(hipMemcpyAsync(c->d_status, c->h_status, sizeof st, hipMemcpyHostToDevice, c->stream));

@@ -40,6 +40,8 @@
 #include <vector>
 
 #include "glio_device.h"
+#include "tr_math.h"
+#include "tr_math_device.h"
 
 #define PG_MAX_LOOPS 1024
 #define PG_SEP_THREADS 1024
@@ -683,14 +685,14 @@ __global__ void __launch_bounds__(256) k_pg_damping(int N, PgPlan P, PgLin lin, 
                 v += lin.lp_out[(size_t)PG_LOOP_OUT * l + (end ? 72 : 0) + 7 * a];
                 gv += lin.lp_out[(size_t)PG_LOOP_OUT * l + (end ? 114 : 108) + a];
             }
-        v = v < min_diag ? min_diag : (v > max_diag ? max_diag : v);
+        v = tr_clip_diagonal(v, min_diag, max_diag);
         dr[(size_t)6 * i + a] = v / rho;
         gf[(size_t)6 * i + a] = gv;
     }
 }
 
 __global__ void k_pg_lm_begin(PgCtl* ctl, double initial_radius) {
-    ctl->radius = initial_radius; ctl->decrease_factor = 2.0; ctl->lin_fresh = 1;
+    ctl->radius = initial_radius; ctl->decrease_factor = TR_LM_DECREASE_FACTOR; ctl->lin_fresh = 1;
 }
 
 // ONE workgroup, the end of a trial: the error at the candidate and the model decrease in the fixed order of k_pg_error, then Ceres 1.14's
@@ -716,12 +718,11 @@ __global__ void __launch_bounds__(1024) k_pg_lm_decide(int N, int L, const doubl
     const bool valid = !pivot && m > 0.0 && m <= DBL_MAX;
     int verdict = valid ? 0 : -1;
     if (valid) {
-        const double gain = (cur - e) / m;
-        if (gain > o.min_relative_decrease) verdict = 1;        // (a candidate error that is not finite makes the gain NaN or -inf: rejected)
+        const double gain = tr_step_quality(cur, e, m);
+        if (tr_step_accepted(gain, o.min_relative_decrease)) verdict = 1;        // (a candidate error that is not finite makes the gain NaN or -inf: rejected)
         if (verdict == 1) {
-            const double c = 2.0 * gain - 1.0;
-            ctl->radius = fmin(o.max_radius, rho / fmax(1.0 / 3.0, 1.0 - c * c * c));
-            ctl->decrease_factor = 2.0;
+            ctl->radius = tr_lm_accepted_radius(rho, tr_cube_mul(2.0 * gain - 1.0), o.max_radius);          // (the pose graph cubes with products, the window with pow)
+            ctl->decrease_factor = TR_LM_DECREASE_FACTOR;
             ctl->err_cur = e; ctl->accepted += 1; ctl->commit_trial = trial;
             if (pg_error_converged(cur, e, rel_tol, abs_tol)) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_CONVERGED; }
         }
@@ -730,8 +731,9 @@ __global__ void __launch_bounds__(1024) k_pg_lm_decide(int N, int L, const doubl
     if (verdict != 1) {
         ctl->rejected += 1;
         if (verdict < 0) ctl->invalid += 1;
-        const double r = rho / ctl->decrease_factor;
-        ctl->radius = r; ctl->decrease_factor *= 2.0;
+        double r = rho, df = ctl->decrease_factor;
+        tr_lm_rejected(r, df);
+        ctl->radius = r; ctl->decrease_factor = df;
         if (r <= o.min_radius) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_MIN_RADIUS; }
     }
     if (!ctl->done && trial >= o.max_trials) { ctl->done = 1; ctl->reason = GLIO_PGRAPH_ITERATION_LIMIT; }
@@ -1172,8 +1174,8 @@ int glio_pgraph_solve(glio_pgraph* pg, glio_pgraph_info* info) {
 void glio_pgraph_lm_opts_default(glio_pgraph_lm_opts* o) {
     if (!o) return;
     memset(o, 0, sizeof *o);
-    o->initial_radius = 1e4; o->max_radius = 1e16; o->min_radius = 1e-32; o->min_relative_decrease = 1e-3;      // ceres::Solver::Options (1.14)
-    o->min_diagonal = 1e-6; o->max_diagonal = 1e32; o->max_trials = 0;
+    o->initial_radius = TR_INITIAL_RADIUS; o->max_radius = TR_MAX_RADIUS; o->min_radius = TR_MIN_RADIUS; o->min_relative_decrease = TR_MIN_RELATIVE_DECREASE;
+    o->min_diagonal = TR_MIN_DIAGONAL; o->max_diagonal = TR_MAX_DIAGONAL; o->max_trials = 0;      // ceres::Solver::Options (1.14), tr_math.h
 }
 int glio_pgraph_lm_struct_sizes(int32_t* out, int n) {
     const int32_t v[2] = {(int32_t)sizeof(glio_pgraph_lm_opts), (int32_t)sizeof(glio_pgraph_lm_info)};

@@ -39,6 +39,8 @@
 
 #include "glio_device.h"
 #include "factor_math.h"
+#include "tr_math.h"
+#include "tr_math_device.h"
 
 #define TR_THREADS 512
 #define TR_WAVES (TR_THREADS / 64)
@@ -582,7 +584,7 @@ __device__ __forceinline__ bool tr_prepare_body(const TrArgs& a, TrDecision* out
             const double* hdc = cand ? a.hd1 : a.hd0;
             for (int i = tid; i < n; i += TR_THREADS) {
                 const double h = FAST ? m->hd[i] : (a.hd0 ? hdc[i] : Hc[(size_t)i * n + i]);
-                const double sc = a.jacobi_scaling ? 1.0 / (1.0 + sqrt(h)) : 1.0;
+                const double sc = a.jacobi_scaling ? tr_jacobi_scale(h) : 1.0;
                 scale[i] = sc;
                 if (FAST) m->scale[i] = sc;
             }
@@ -609,29 +611,17 @@ __device__ __forceinline__ bool tr_prepare_body(const TrArgs& a, TrDecision* out
             if (tid == 0) {
                 const double ccost = FAST ? *m->cost : *(cand ? a.c1 : a.c0);
                 const double step_norm = sqrt(d2), x_norm = sqrt(x2);
-                if (step_norm <= a.parameter_tolerance * (x_norm + a.parameter_tolerance)) {
-                    s.done = 1; s.termination = GLIO_TERM_PARAMETER_TOL;
-                } else if (fabs(s.cost - ccost) <= a.function_tolerance * s.cost) {
-                    s.done = 1; s.termination = GLIO_TERM_FUNCTION_TOL;
-                } else {
-                    const double rel = (s.cost - ccost) / s.model_cost_change;
-                    if (rel > a.min_relative_decrease) {
+                if (tr_parameter_converged(step_norm, x_norm, a.parameter_tolerance)) { s.done = 1; s.termination = GLIO_TERM_PARAMETER_TOL; }
+                else if (tr_function_converged(s.cost, ccost, a.function_tolerance)) { s.done = 1; s.termination = GLIO_TERM_FUNCTION_TOL; }
+                else {
+                    const double rel = tr_step_quality(s.cost, ccost, s.model_cost_change);
+                    if (tr_step_accepted(rel, a.min_relative_decrease)) {
                         s.cur = cand; s.cost = ccost; s.successful += 1;
-                        if (a.lm) {                                                           // LevenbergMarquardtStrategy::StepAccepted
-                            s.radius = s.radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * rel - 1.0, 3));
-                            s.radius = fmin(a.max_radius, s.radius);
-                            s.decrease_factor = 2.0;
-                        } else {
-                            if (rel < 0.25) s.radius *= 0.5;                                  // DoglegStrategy::StepAccepted
-                            if (rel > 0.75) s.radius = fmax(s.radius, 3.0 * s.dogleg_step_norm);
-                            s.mu = fmax(1e-8, 2.0 * s.mu / 10.0);
-                        }
+                        if (a.lm) { s.radius = tr_lm_accepted_radius(s.radius, tr_cube_pow(2.0 * rel - 1.0), a.max_radius); s.decrease_factor = TR_LM_DECREASE_FACTOR; }
+                        else { s.radius = tr_dogleg_accepted_radius(rel, s.dogleg_step_norm, s.radius); s.mu = tr_mu_accepted(s.mu); }
                         s.reuse = 0;
-                    } else if (a.lm) {
-                        s.radius /= s.decrease_factor; s.decrease_factor *= 2.0; s.reuse = 0;   // StepRejected: new damping, refactor
-                    } else {
-                        s.radius *= 0.5; s.reuse = 1;                                         // StepRejected
-                    }
+                    } else if (a.lm) { tr_lm_rejected(s.radius, s.decrease_factor); s.reuse = 0; }   // new damping, refactor
+                    else { s.radius = tr_dogleg_rejected_radius(s.radius); s.reuse = 1; }
                 }
             }
         }
@@ -653,12 +643,9 @@ __device__ __forceinline__ bool tr_prepare_body(const TrArgs& a, TrDecision* out
     auto grad_max = [&](const double* gv, const double* xv) {
         double gmx = 0;
         auto rot = [&](const int sl) {
-            const int k = 15 * sl + 3;
-            const double d[3] = {-gv[k], -gv[k + 1], -gv[k + 2]};
-            double q[4], qn[4];
+            double q[4];
             for (int c = 0; c < 4; ++c) q[c] = xv[3 * W + 4 * sl + c];
-            d_quat_plus(q, d, qn);
-            for (int c = 0; c < 4; ++c) gmx = fmax(gmx, fabs(q[c] - qn[c]));
+            gmx = tr_grad_max_rot(q, gv + 15 * sl + 3, gmx);
         };
         for (int k = tid; k < n; k += TR_THREADS) {
             if (k < 15 * W && (k % 15) >= 3 && (k % 15) < 6) {
@@ -677,10 +664,8 @@ __device__ __forceinline__ bool tr_prepare_body(const TrArgs& a, TrDecision* out
     if (tid == 0) {
         s.grad_max_norm = gm;
         const bool out_of_time = a.stop_word && *reinterpret_cast<const volatile int*>(a.stop_word) == s.solve_id;      // Ceres: MaxSolverTimeReached
-        if (s.iteration >= a.max_iterations || out_of_time) { s.done = 1; s.termination = GLIO_TERM_NO_CONVERGENCE; }
-        else if (gm <= a.gradient_tolerance) { s.done = 1; s.termination = GLIO_TERM_GRADIENT_TOL; }
-        else if (s.radius <= a.min_radius) { s.done = 1; s.termination = GLIO_TERM_MIN_RADIUS; }
-        else s.iteration += 1;
+        const int gate = tr_iteration_gate(s.iteration, a.max_iterations, out_of_time, gm, a.gradient_tolerance, s.radius, a.min_radius);
+        if (gate != TR_GO_ON) { s.done = 1; s.termination = gate; } else s.iteration += 1;
     }
     PB_SYNC();
     if (s.done) { if (FAST && m->fin_lds) finalize_lds(a, s, s.cur ? m->x1 : m->x0); else finalize(a, s); return false; }
@@ -700,7 +685,7 @@ __device__ __forceinline__ bool tr_prepare_body(const TrArgs& a, TrDecision* out
         auto work_vectors = [&](const double* sv, const double* hv, const double* gv) {
             for (int i = tid; i < n; i += TR_THREADS) {
                 double d = sv[i] * sv[i] * hv[i];
-                d = d < 1e-6 ? 1e-6 : (d > 1e32 ? 1e32 : d);
+                d = tr_clip_diagonal(d);
                 const double dd = sqrt(d);
                 diag[i] = dd;
                 const double gs = sv[i] * gv[i];
@@ -714,7 +699,7 @@ __device__ __forceinline__ bool tr_prepare_body(const TrArgs& a, TrDecision* out
         else {
             for (int i = tid; i < n; i += TR_THREADS) {
                 double d = scale[i] * scale[i] * H[(size_t)i * n + i];
-                d = d < 1e-6 ? 1e-6 : (d > 1e32 ? 1e32 : d);
+                d = tr_clip_diagonal(d);
                 const double dd = sqrt(d);
                 diag[i] = dd;
                 const double gs = scale[i] * g[i];
@@ -837,7 +822,7 @@ __device__ __forceinline__ void tr_factor_body(const TrArgs& a, const Builder& b
     }
     for (int attempt = 0; attempt < (a.lm ? 1 : 12) && !solved; ++attempt) {
         const double mu = *smu;
-        if (!a.lm && !(mu < 1.0)) break;
+        if (!a.lm && !(mu < TR_MAX_MU)) break;
         if (!Builder::kHasDenseH) { builder(a, mu); __syncthreads(); }
         else if (attempt > 0 || a.fused_chain) {    // breakdown (or nobody built it yet): S H S + mu D^2 with the current mu (rare)
             for (int i = tid >> 6; i < n; i += TR_WAVES) {
@@ -866,7 +851,7 @@ __device__ __forceinline__ void tr_factor_body(const TrArgs& a, const Builder& b
         bad = block_max(bad, red);
         if (bad == 0) { solved = true; break; }
         __syncthreads();
-        if (tid == 0) *smu = mu * 10.0;
+        if (tid == 0) *smu = mu * TR_MU_INCREASE;
         __syncthreads();
     }
     if (solved) {
@@ -886,23 +871,6 @@ __device__ __forceinline__ void tr_factor_body(const TrArgs& a, const Builder& b
 // ------------------------------------------------------------------------------------------------
 // K7d  k_tr_dogleg
 // ------------------------------------------------------------------------------------------------
-// Step selection: step (D-space) = ca * grad + cb * gn, from gg = |grad|^2, nn = |gn|^2, gd = grad . gn (gnorm, gnn: their roots) and the Cauchy
-// step length alpha.  snorm: the step's norm where it is known in closed form, -1 where the caller takes it from the step itself.
-__device__ __forceinline__ void dogleg_coeffs(const bool lm, const double gg, const double nn, const double gd, const double gnorm, const double gnn,
-                                              const double radius, const double alpha, double& ca, double& cb, double& snorm) {
-    if (lm) { ca = 0.0; cb = 1.0; snorm = gnn; }        // Levenberg-Marquardt: the damped step itself
-    else if (gnn <= radius) { ca = 0.0; cb = 1.0; snorm = gnn; }
-    else if (gnorm * alpha >= radius) { ca = -(radius / gnorm); cb = 0.0; snorm = radius; }
-    else {
-        const double b_dot_a = -alpha * gd;
-        const double a_sq = alpha * alpha * gg;
-        const double b_minus_a_sq = nn - 2 * b_dot_a + a_sq;
-        const double c = b_dot_a - a_sq;
-        const double d = sqrt(c * c + b_minus_a_sq * (radius * radius - a_sq));
-        const double beta = (c <= 0) ? (d - c) / b_minus_a_sq : (radius * radius - a_sq) / (d + c);
-        ca = -alpha * (1.0 - beta); cb = beta; snorm = -1.0;
-    }
-}
 __device__ __forceinline__ void tr_dogleg_body(const TrArgs& a) {
     double* red = reinterpret_cast<double*>(tr_lds);                       // the factorisation's panel buffer is free again
     SolverStatus& s = *reinterpret_cast<SolverStatus*>(red + 32);
@@ -920,21 +888,15 @@ __device__ __forceinline__ void tr_dogleg_body(const TrArgs& a) {
     { double v3[3] = {gg, nn, gd}; block_sum_n<3>(v3, red); gg = v3[0]; nn = v3[1]; gd = v3[2]; }
     const double gnorm = sqrt(gg), gnn = sqrt(nn), radius = s.radius, alpha = s.alpha;
     double ca, cb, snorm;
-    dogleg_coeffs(a.lm, gg, nn, gd, gnorm, gnn, radius, alpha, ca, cb, snorm);
-    // step_s = step / D = ca * (g~/D) + cb * (-y); w = S step_s.
-    // Hs step_s = ca * Hs (g~/D) - cb * Hs y, with Hs (g~/D) = S H u = S t and Hs y = S g - mu D^2 y
-    // -> model cost change = -(gs.step_s + step_s^T Hs step_s / 2) without another matrix pass.
+    tr_dogleg_coeffs(a.lm, gg, nn, gd, gnorm, gnn, radius, alpha, ca, cb, snorm);
+    // the step and the model cost change -(lin + quad / 2), element by element
     const double mu = s.mu_used;
     double sn2 = 0, lin = 0, quad = 0;
     for (int i = tid; i < n; i += TR_THREADS) {
-        const double sv = ca * grad[i] + cb * gn[i];
-        sn2 += sv * sv;
-        const double step_s = sv / diag[i];
-        wvec[i] = scale[i] * step_s;
-        const double gs = scale[i] * g[i];
-        const double hs_step = ca * (scale[i] * t[i]) - cb * (gs - mu * diag[i] * diag[i] * y[i]);
-        lin += gs * step_s;
-        quad += step_s * hs_step;
+        double sv, step_s, wi, li, qi;
+        tr_step_element(ca, cb, grad[i], gn[i], diag[i], scale[i], g[i], t[i], y[i], mu, sv, step_s, wi, li, qi);
+        wvec[i] = wi;
+        sn2 += sv * sv; lin += li; quad += qi;
     }
     { double v3[3] = {sn2, lin, quad}; block_sum_n<3>(v3, red); sn2 = v3[0]; lin = v3[1]; quad = v3[2]; }
     if (snorm < 0) snorm = sqrt(sn2);
@@ -943,10 +905,9 @@ __device__ __forceinline__ void tr_dogleg_body(const TrArgs& a) {
     if (tid == 0) {
         s.dogleg_step_norm = snorm;
         if (!valid) {
-            s.invalid += 1;
-            if (s.invalid >= 5) { s.done = 1; s.termination = GLIO_TERM_FAILURE; }
-            if (a.lm) { s.radius /= s.decrease_factor; s.decrease_factor *= 2.0; }
-            else s.mu *= 10.0;
+            if (tr_invalid_limit(++s.invalid)) { s.done = 1; s.termination = GLIO_TERM_FAILURE; }
+            if (a.lm) tr_lm_rejected(s.radius, s.decrease_factor);
+            else s.mu *= TR_MU_INCREASE;        // (the window pays this on the fifth invalid step too; the batch stage and the trajectory do not)
             s.lin_fail = 0;
             s.reuse = 0;                        // StepIsInvalid: consumes an iteration, no candidate
             s.cand_pending = 0;
@@ -2846,7 +2807,7 @@ __device__ __forceinline__ void chain_step_fat_helper(const ChainArgs& a, const 
         h_ph0 = st.phase == 0 ? 1 : 0;
         // mu as the state machine will leave it: the first step of a solve keeps the record's (and takes the point whatever it is, forming the Jacobi
         // scale from its diagonal); a later one is assumed accepted: DoglegStrategy::StepAccepted, tr_prepare_body
-        h_mu = st.phase == 0 ? st.mu : fmax(1e-8, 2.0 * st.mu / 10.0);
+        h_mu = st.phase == 0 ? st.mu : tr_mu_accepted(st.mu);
     }
     // the structure tables travel with the status: descriptors of the three keyframes, the prior index of their rows, the epoch tables
     if (tid < 24) { const int k = tid >> 3, kk = i - 1 + k; f_tab[tid] = (kk >= 0 && kk < W) ? gtab[8 * kk + (tid & 7)] : (short)-1; }
@@ -2963,9 +2924,9 @@ __device__ __forceinline__ void chain_step_fat_helper(const ChainArgs& a, const 
                     gacc += rd_.k1 >= 0 ? g5[3] : 0.0;
                     gacc += rpi >= 0 ? g5[4] : 0.0;
                     gg = gacc;
-                    if (ph0) rs = tr.jacobi_scaling ? 1.0 / (1.0 + sqrt(hv)) : 1.0;          // (the first step forms the scale: tr_prepare_body, phase 0)
+                    if (ph0) rs = tr.jacobi_scaling ? tr_jacobi_scale(hv) : 1.0;          // (the first step forms the scale: tr_prepare_body, phase 0)
                     double d = rs * rs * hv;
-                    d = d < 1e-6 ? 1e-6 : (d > 1e32 ? 1e32 : d);
+                    d = tr_clip_diagonal(d);
                     const double dd_ = sqrt(d);
                     const double gs = rs * gg;
                     const double grd = gs / dd_;
@@ -2977,10 +2938,10 @@ __device__ __forceinline__ void chain_step_fat_helper(const ChainArgs& a, const 
             for (int t = t0e + tid; t < t1e; t += KC_THREADS) {
                 const int e = f_elist[t];
                 const double he = f_dds[e * 15 + 12], ge = f_dds[e * 15 + 13];
-                const double se = ph0 ? (tr.jacobi_scaling ? 1.0 / (1.0 + sqrt(he)) : 1.0) : f_Se[e];
+                const double se = ph0 ? (tr.jacobi_scaling ? tr_jacobi_scale(he) : 1.0) : f_Se[e];
                 f_Se[e] = se;
                 double d = se * se * he;
-                d = d < 1e-6 ? 1e-6 : (d > 1e32 ? 1e32 : d);
+                d = tr_clip_diagonal(d);
                 const double de = sqrt(d);
                 const double gs = se * ge;
                 const double grd = gs / de;
@@ -3353,7 +3314,7 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
     // ---- fat helpers delivered and their assumptions hold (the candidate was accepted, mu is what an acceptance leaves): the blocks, the epoch columns and
     // t = H u are LOADED -- 60 KB of finished numbers instead of four LDS phases (epoch columns, block store, t = H u, epoch corrections: ~15 us)
     const bool fat_path = a.fat && a.helpers && s_hprod && s_hfat && ff && s_pending && dec.cur == cand && !tr.lm &&
-                          __double_as_longlong(mu) == __double_as_longlong(s_in.phase == 0 ? s_in.mu : fmax(1e-8, 2.0 * s_in.mu / 10.0));
+                          __double_as_longlong(mu) == __double_as_longlong(s_in.phase == 0 ? s_in.mu : tr_mu_accepted(s_in.mu));
     if (fat_path) {
         if (tid == 0 && a.dbg) a.dbg[300] += 1;            // (steps that took the fat helpers' products: glio_debug_arrow_stamps, slot 300)
         const double* xm = cand ? xm1 : xm0;
@@ -3737,21 +3698,16 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
         const double alpha = q2 / p;
         const double gnorm = sqrt(gg), gnn = sqrt(nn), radius = s0.radius;
         double ca, cb, snorm;
-        dogleg_coeffs(tr.lm, gg, nn, gd, gnorm, gnn, radius, alpha, ca, cb, snorm);
+        tr_dogleg_coeffs(tr.lm, gg, nn, gd, gnorm, gnn, radius, alpha, ca, cb, snorm);
         const double mu_u = s0.mu;                             // the factorisation succeeded with the record's mu: mu_used = mu
         double sn2 = 0, lin = 0, quad = 0;
         for (int i = tid; i < n; i += TR_THREADS) {
             const double yi = i < np15 ? zb[i] : wd[i - np15];
             const double gni = -sDg[i] * yi;
-            const double sv = ca * sGr[i] + cb * gni;
-            sn2 += sv * sv;
-            const double step_s = sv / sDg[i];
-            const double wi = sS[i] * step_s;
+            double sv, step_s, wi, li, qi;
+            tr_step_element(ca, cb, sGr[i], gni, sDg[i], sS[i], sG[i], sT[i], yi, mu_u, sv, step_s, wi, li, qi);
             V_W(tr)[i] = wi; sW[i] = wi;
-            const double gs = sS[i] * sG[i];
-            const double hs_step = ca * (sS[i] * sT[i]) - cb * (gs - mu_u * sDg[i] * sDg[i] * yi);
-            lin += gs * step_s;
-            quad += step_s * hs_step;
+            sn2 += sv * sv; lin += li; quad += qi;
         }
         AR_STAMP(71);
         { double v3[3] = {sn2, lin, quad}; block_sum_n<3, true>(v3, red + 40); sn2 = v3[0]; lin = v3[1]; quad = v3[2]; }
@@ -3764,10 +3720,9 @@ __global__ __launch_bounds__(KC_THREADS) void k_chain_step(const ChainArgs a, co
         sn.alpha = alpha; sn.mu_used = mu_u; sn.lin_fail = 0;
         sn.dogleg_step_norm = snorm;
         if (!valid) {
-            sn.invalid += 1;
-            if (sn.invalid >= 5) { sn.done = 1; sn.termination = GLIO_TERM_FAILURE; ended = true; }
-            if (tr.lm) { sn.radius /= sn.decrease_factor; sn.decrease_factor *= 2.0; }
-            else sn.mu *= 10.0;
+            if (tr_invalid_limit(++sn.invalid)) { sn.done = 1; sn.termination = GLIO_TERM_FAILURE; ended = true; }
+            if (tr.lm) tr_lm_rejected(sn.radius, sn.decrease_factor);
+            else sn.mu *= TR_MU_INCREASE;
             sn.reuse = 0;
             sn.cand_pending = 0;
         } else {

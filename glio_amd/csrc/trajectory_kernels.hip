@@ -23,8 +23,12 @@
 #include "../../include/glio_traj.h"
 #include "factor_math.h"
 #include "glio_device.h"
+#include "tr_math.h"
+#include "tr_math_device.h"
 
 namespace {
+static_assert(GLIO_TRAJ_NO_CONVERGENCE == TR_NO_CONVERGENCE && GLIO_TRAJ_FUNCTION_TOLERANCE == TR_FUNCTION_TOL && GLIO_TRAJ_PARAMETER_TOLERANCE == TR_PARAMETER_TOL &&
+              GLIO_TRAJ_GRADIENT_TOLERANCE == TR_GRADIENT_TOL && GLIO_TRAJ_MIN_RADIUS == TR_MIN_RADIUS_REACHED && GLIO_TRAJ_FAILURE == TR_FAILURE, "GLIO_TRAJ_* = GLIO_TERM_* on 0 .. 5");
 
 #define TJ_F GLIO_TRAJ_MAX_FRAMES
 #define TJ_N (6 * TJ_F)            // unknowns at most
@@ -159,7 +163,7 @@ __device__ __forceinline__ double gradient_max(const double* x, const double* g,
     double m = 0.0;
     for (int k = lane; k < N; k += 64) {
         for (int c = 0; c < 3; ++c) m = fmax(m, fabs(x[7 * k + c] - (x[7 * k + c] + -g[6 * k + c])));
-        const double d[3] = {-g[6 * k + 3], -g[6 * k + 4], -g[6 * k + 5]};
+        const double d[3] = {-g[6 * k + 3], -g[6 * k + 4], -g[6 * k + 5]};          // (tr_grad_max_rot, written out: through the helper this kernel's schedule moved)
         double o[4];
         d_quat_plus(x + 7 * k + 3, d, o);
         for (int c = 0; c < 4; ++c) m = fmax(m, fabs(x[7 * k + 3 + c] - o[c]));
@@ -268,9 +272,9 @@ __global__ __launch_bounds__(64) void k_traj_gap(const int mode, const int first
         double* xc = xbuf[1];
         cost = evaluate(x, anc, meas, Jr, Hbuf[0], Hbuf[0] + TJ_F * 36, gbuf[0], N, lane);
         initial = cost;
-        for (int i = lane; i < n; i += 64) scale[i] = 1.0 / (1.0 + sqrt(Hbuf[0][(i / 6) * 36 + (i % 6) * 7]));
+        for (int i = lane; i < n; i += 64) scale[i] = tr_jacobi_scale(Hbuf[0][(i / 6) * 36 + (i % 6) * 7]);
         GLIO_WAVE_LDS_SYNC();
-        double radius = 1e4, mu = 1e-8, alpha = 0.0, step_norm = 0.0, gn_norm = 0.0, g_norm = 0.0, g_dot_gn = 0.0;
+        double radius = TR_INITIAL_RADIUS, mu = TR_MIN_MU, alpha = 0.0, step_norm = 0.0, gn_norm = 0.0, g_norm = 0.0, g_dot_gn = 0.0;
         bool reuse = false;
         int invalid = 0;
         term = GLIO_TRAJ_NO_CONVERGENCE;
@@ -281,16 +285,17 @@ __global__ __launch_bounds__(64) void k_traj_gap(const int mode, const int first
             const double* g = gbuf[cur];
             double* band = Hbuf[cur ^ 1];
             const double gmax = gradient_max(x, g, N, lane);
+            // (tr_iteration_gate's order, written out: through the function the loop's scalar code moved -- four more spilled SGPRs)
             if (it >= st.max_iterations) break;
-            if (gmax <= 1e-10) { term = GLIO_TRAJ_GRADIENT_TOLERANCE; break; }
-            if (radius <= 1e-32) { term = GLIO_TRAJ_MIN_RADIUS; break; }
+            if (gmax <= TR_GRADIENT_TOLERANCE) { term = GLIO_TRAJ_GRADIENT_TOLERANCE; break; }
+            if (radius <= TR_MIN_RADIUS) { term = GLIO_TRAJ_MIN_RADIUS; break; }
             ++it;
             bool have_step = true;
             if (!reuse) {
                 // D = sqrt(clip(diag Hs)), grad = gs / D, alpha = |grad|^2 / (u^T Hs u) with u = grad / D
                 for (int i = lane; i < n; i += 64) {
-                    const double hs = (scale[i] * Hd[(i / 6) * 36 + (i % 6) * 7]) * scale[i];
-                    const double d = sqrt(fmin(fmax(hs, 1e-6), 1e32));
+                    const double hs = (scale[i] * Hd[(i / 6) * 36 + (i % 6) * 7]) * scale[i];          // (s h) s here, s s h in the window and the batch stage
+                    const double d = sqrt(tr_clip_diagonal_minmax(hs));                                // min/max: a NaN becomes the lower bound here
                     Dd[i] = d;
                     grad[i] = (scale[i] * g[i]) / d;
                     step[i] = grad[i] / d;              // u, for now
@@ -301,7 +306,7 @@ __global__ __launch_bounds__(64) void k_traj_gap(const int mode, const int first
                 alpha = gg / vdot(step, tmp, n, lane);
                 g_norm = sqrt(gg);
                 bool solved = false;
-                while (mu < 1.0) {
+                while (mu < TR_MAX_MU) {
                     // band = Hs + mu D^2, column j rows j .. j + 11
                     for (int e = lane; e < n * TJ_BW; e += 64) {
                         const int j = e / TJ_BW, r = e % TJ_BW, i = j + r;
@@ -348,7 +353,7 @@ __global__ __launch_bounds__(64) void k_traj_gap(const int mode, const int first
                         good = !__any(!fin);
                     }
                     if (good) { solved = true; break; }
-                    mu *= 10.0;
+                    mu *= TR_MU_INCREASE;
                 }
                 if (solved) {
                     for (int i = lane; i < n; i += 64) gn[i] = -Dd[i] * tmp[i];
@@ -361,18 +366,10 @@ __global__ __launch_bounds__(64) void k_traj_gap(const int mode, const int first
             double mcc = -1.0;
             if (have_step) {
                 // the traditional dogleg in the D-scaled variables: step = c_g grad + c_n gn
-                double c_g, c_n;
-                if (gn_norm <= radius) { c_g = 0.0; c_n = 1.0; step_norm = gn_norm; }
-                else if (g_norm * alpha >= radius) { c_g = -(radius / g_norm); c_n = 0.0; step_norm = radius; }
-                else {
-                    const double b_dot_a = -alpha * g_dot_gn;
-                    const double a2 = alpha * alpha * (g_norm * g_norm);
-                    const double bma2 = gn_norm * gn_norm - 2 * b_dot_a + a2;
-                    const double c = b_dot_a - a2;
-                    const double d = sqrt(c * c + bma2 * (radius * radius - a2));
-                    const double beta = c <= 0 ? (d - c) / bma2 : (radius * radius - a2) / (d + c);
-                    c_g = -alpha * (1 - beta); c_n = beta; step_norm = -1.0;
-                }
+                // (the squared norms go in as the squares of the rounded roots, not as the sums: this loop's bits)
+                double c_g, c_n, sn;
+                tr_dogleg_coeffs(false, 0.0, 0.0, g_dot_gn, g_norm, gn_norm, radius, alpha, c_g, c_n, sn, true);
+                step_norm = sn;
                 for (int i = lane; i < n; i += 64) {
                     const double s = c_n == 0.0 ? c_g * grad[i] : (c_g == 0.0 ? gn[i] : c_g * grad[i] + c_n * gn[i]);
                     tmp[i] = s;                          // D-space, for its norm
@@ -387,8 +384,8 @@ __global__ __launch_bounds__(64) void k_traj_gap(const int mode, const int first
                 mcc = -(lin + 0.5 * vdot(step, tmp, n, lane));
             }
             if (!have_step || !(mcc > 0.0)) {
-                if (++invalid >= 5) { term = GLIO_TRAJ_FAILURE; break; }
-                mu *= 10.0; reuse = false;
+                if (tr_invalid_limit(++invalid)) { term = GLIO_TRAJ_FAILURE; break; }
+                mu *= TR_MU_INCREASE; reuse = false;
                 continue;
             }
             invalid = 0;
@@ -402,25 +399,24 @@ __global__ __launch_bounds__(64) void k_traj_gap(const int mode, const int first
             }
             GLIO_WAVE_LDS_SYNC();
             const double ccost = evaluate(xc, anc, meas, Jr, Hbuf[cur ^ 1], Hbuf[cur ^ 1] + TJ_F * 36, gbuf[cur ^ 1], N, lane);
-            if (!isfinite(ccost)) { radius *= 0.5; reuse = true; continue; }
+            if (!isfinite(ccost)) { radius = tr_dogleg_rejected_radius(radius); reuse = true; continue; }
             double dx2 = 0.0, xn2 = 0.0;
             for (int i = lane; i < 7 * N; i += 64) { const double d = x[i] - xc[i]; dx2 += d * d; xn2 += x[i] * x[i]; }
             const double dx = sqrt(wave_sum(dx2)), xn = sqrt(wave_sum(xn2));
-            if (dx <= 1e-8 * (xn + 1e-8)) { term = GLIO_TRAJ_PARAMETER_TOLERANCE; break; }
-            if (fabs(cost - ccost) <= 1e-6 * cost) { term = GLIO_TRAJ_FUNCTION_TOLERANCE; break; }
-            const double q = (cost - ccost) / mcc;
-            if (q > 1e-3) {
+            if (tr_parameter_converged(dx, xn, TR_PARAMETER_TOLERANCE)) { term = GLIO_TRAJ_PARAMETER_TOLERANCE; break; }
+            if (tr_function_converged(cost, ccost, TR_FUNCTION_TOLERANCE)) { term = GLIO_TRAJ_FUNCTION_TOLERANCE; break; }
+            const double q = tr_step_quality(cost, ccost, mcc);
+            if (tr_step_accepted(q, TR_MIN_RELATIVE_DECREASE)) {
                 double* t = x; x = xc; xc = t;
                 cur ^= 1;
                 ++ok_steps;
                 if (it <= 32) mask |= 1u << (it - 1);
-                if (q < 0.25) radius *= 0.5;
-                if (q > 0.75) radius = fmax(radius, 3.0 * step_norm);
-                mu = fmax(1e-8, 2.0 * mu / 10.0);
+                radius = tr_dogleg_accepted_radius(q, step_norm, radius);
+                mu = tr_mu_accepted(mu);
                 reuse = false;
                 cost = ccost;
             } else {
-                radius *= 0.5; reuse = true;
+                radius = tr_dogleg_rejected_radius(radius); reuse = true;
             }
         }
         for (int i = lane; i < 7 * N; i += 64) { const double v = x[i]; g_sol[i] = v; finite = finite && isfinite(v); }

@@ -19,6 +19,7 @@
 
 #include "glio_batch_cov.h"
 #include "glio_hip.h"
+#include "../csrc/tr_math.h"                            // Ceres' defaults by name (host-compilable: no HIP header)
 
 namespace glio {
 
@@ -71,8 +72,9 @@ inline DeltaQPairs deltaQPairs(const std::vector<double>& odo, int K, int search
 inline glio_batch_tr_opts batchTrOpts(int max_iterations = 100) {
     glio_batch_tr_opts o;
     o.max_iterations = max_iterations; o.use_nonmonotonic_steps = 1; o.max_consecutive_nonmonotonic_steps = 5; o.jacobi_scaling = 1;
-    o.initial_trust_region_radius = 1e4; o.max_trust_region_radius = 1e16; o.min_trust_region_radius = 1e-32;
-    o.min_relative_decrease = 1e-3; o.function_tolerance = 1e-6; o.gradient_tolerance = 1e-10; o.parameter_tolerance = 1e-8;
+    o.initial_trust_region_radius = TR_INITIAL_RADIUS; o.max_trust_region_radius = TR_MAX_RADIUS; o.min_trust_region_radius = TR_MIN_RADIUS;
+    o.min_relative_decrease = TR_MIN_RELATIVE_DECREASE; o.function_tolerance = TR_FUNCTION_TOLERANCE; o.gradient_tolerance = TR_GRADIENT_TOLERANCE;
+    o.parameter_tolerance = TR_PARAMETER_TOLERANCE;
     o.dogleg_type = GLIO_DOGLEG_SUBSPACE; o.reserved_ = 0;        // options.dogleg_type = SUBSPACE_DOGLEG, Estimator.cpp:3278
     return o;
 }

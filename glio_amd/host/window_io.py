@@ -10,7 +10,8 @@ from .. import synth
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEMO = os.path.join(HERE, "host_demo")
-_ABI_HEADERS = [os.path.join(HERE, "..", "..", "include", h) for h in ("glio_hip.h", "glio_types.h", "glio_pgraph_lm.h", "glio_cov.h", "glio_dense.h")]      # a changed struct must rebuild the demos
+_ABI_HEADERS = [os.path.join(HERE, "..", "..", "include", h) for h in ("glio_hip.h", "glio_types.h", "glio_pgraph_lm.h", "glio_cov.h", "glio_dense.h")] + \
+    [os.path.join(HERE, "..", "csrc", "tr_math.h")]      # a changed struct must rebuild the demos
 
 
 def build_demo(force=False):
