@@ -84,6 +84,17 @@ def device_count():
     return load().glio_device_count()
 
 
+def switches():
+    """The library's environment switches (csrc/glio_switches.h; INTEGRATION.md, "Environment switches") as a list of dicts: name, default, scope
+    ("PROCESS": the process's snapshot, taken by the first query; "CREATE": read when an object is created), value (what the library works with now), doc."""
+    lib, out = load(), []
+    name, doc, dflt, scope, value = C.c_char_p(), C.c_char_p(), C.c_int(), C.c_int(), C.c_int()
+    while lib.glio_debug_switch_row(len(out), C.byref(name), C.byref(dflt), C.byref(scope), C.byref(doc)) == 0:
+        _check(lib.glio_debug_switch_value(name.value, C.byref(value)))
+        out.append({"name": name.value.decode(), "default": dflt.value, "scope": ("PROCESS", "CREATE")[scope.value], "value": value.value, "doc": doc.value.decode()})
+    return out
+
+
 # pcl::PointXYZI as numpy sees it (GLIO/include/utils/common.h: PointType): 32-byte records, x y z at 0, intensity at byte 16
 PCL_XYZI = np.dtype({"names": ["x", "y", "z", "intensity"], "formats": ["<f4", "<f4", "<f4", "<f4"], "offsets": [0, 4, 8, 16], "itemsize": 32})
 PCL_XYZI_INTENSITY_OFFSET = 16

@@ -1694,13 +1694,10 @@ __global__ __launch_bounds__(PF_BLOCK) void k_compact(const int* __restrict__ fl
 
 struct KnnBinHost { KnnBin d; int rows, cap, capq_max; };
 static unsigned long long* g_knn_dbg = nullptr;      // statistics of the near-block search (glio_debug_knn_stats)
-static int g_bassoc_local = -1;       // batch association, tables in the search frames' own frames: -1 = GLIO_BASSOC_LOCAL_TABLES (default on), test knob glio_debug_set_bassoc_local
-static int g_gbin_cap = 0;            // test knob (glio_debug_set_gbin_cap): cell-table size of the merged-window grouping, 0 = from the map
-static int knn_mode_from_env() { const char* e = getenv("GLIO_KNN_MODE"); const int m = e ? atoi(e) : 0; return m >= 0 && m <= 3 ? m : 0; }      // (A/B of whole programs, e.g. host_demo_stream)
-static int g_knn_mode = knn_mode_from_env();           // 0 = window calls: the queries of all slots grouped by cell together, near block first (k_knn5_near<64>), the rest by
-                                     //     k_knn5_rest; single rows: the 27-cell tiled search (k_knn5_tile);  1 = one 16-lane group per query (k_knn5);
-                                     // 2 = every query by the 27-cell tiled search (the round-4 path);  3 = near block first (k_knn5_near<16>), every launch
-                                     //     row by itself; glio_debug_set_knn_mode
+// GLIO_KNN_MODE / glio_debug_set_knn_mode (A/B of whole programs, e.g. host_demo_stream):
+// 0 = window calls: the queries of all slots grouped by cell together, near block first (k_knn5_near<64>), the rest by
+//     k_knn5_rest; single rows: the 27-cell tiled search (k_knn5_tile);  1 = one 16-lane group per query (k_knn5);
+// 2 = every query by the 27-cell tiled search (the round-4 path);  3 = near block first (k_knn5_near<16>), every launch row by itself
 // gcells > 0: also the buffers of the merged-window grouping, its cell table sized for gcells cells (0: rows are always searched one by one)
 static KnnBinHost* knn_bin_create(int rows, int cap, int gcells = 0) {
     KnnBinHost* h = new KnnBinHost();
@@ -1758,15 +1755,16 @@ static void enqueue_knn(hipStream_t stream, AssocArgs& a, KnnBinHost* kb, int ro
     // bin_rows > 0 (pair mode, a.pair_row / a.row_pair set): only that many launch rows are grouped by cell; every pair searches its bin row's units
     if (bin_rows <= 0 || !a.pair_row) { bin_rows = rows; a.pair_row = nullptr; a.row_pair = nullptr; }
     a.bin_pass = 0;
-    if (g_knn_mode == 1 || !kb) {
+    if (glio_switch<GLIO_SW_KNN_MODE>() == 1 || !kb) {
         memset(&a.kb, 0, sizeof a.kb);
         hipLaunchKernelGGL(k_knn5, dim3((maxn + AQ_PER_BLOCK - 1) / AQ_PER_BLOCK, rows), dim3(256), 0, stream, a, scan, map, ent, nn5);
         return;
     }
     a.kb = kb->d; a.w_stride_q = kb->cap; a.kb.dbg = g_knn_dbg;
     // merged window (mode 0, launch rows that share one map): the queries of all rows grouped by cell together, units of 64
-    if (g_knn_mode == 0 && map_n_max <= (1 << 24) && rows > 1 && map && kb->d.qs2 && !a.frames) {
-        int ge = g_gbin_cap > 0 ? next_pow2(g_gbin_cap) : next_pow2(map_n_max > 4096 ? map_n_max : 4096);      // (queried cells of the C2 window: ~10 k against a 70 k-point map)
+    if (glio_switch<GLIO_SW_KNN_MODE>() == 0 && map_n_max <= (1 << 24) && rows > 1 && map && kb->d.qs2 && !a.frames) {
+        const int gcap = glio_switch<GLIO_SW_GBIN_CAP>();
+        int ge = gcap > 0 ? next_pow2(gcap) : next_pow2(map_n_max > 4096 ? map_n_max : 4096);      // (queried cells of the C2 window: ~10 k against a 70 k-point map)
         if (ge > kb->d.gcap) ge = kb->d.gcap;
         a.kb.glob = 1; a.kb.gcap = ge;
         hipLaunchKernelGGL(k_qbin_tile, dim3((maxn + QT_THREADS - 1) / QT_THREADS, rows), dim3(QT_THREADS), 0, stream, a, ps);
@@ -1798,7 +1796,7 @@ static void enqueue_knn(hipStream_t stream, AssocArgs& a, KnnBinHost* kb, int ro
     // carries four quarter-filled units per wavefront and needs a second launch for what it hands on -- measured equal or slower than the 27-cell
     // tiled search alone (C2 scan 46 vs 40 us, C3 57-63 vs 57, 192 pairs 2.3-2.5 vs 2.33 ms), so mode 0 keeps the tiled search there; mode 3 forces
     // the near-block path row by row (tests: the same bytes).
-    if (g_knn_mode == 3 && map_n_max <= (1 << 24)) {
+    if (glio_switch<GLIO_SW_KNN_MODE>() == 3 && map_n_max <= (1 << 24)) {
         int gn = (maxn + 31) / 32;
         if (gn > 4096) gn = 4096;
         hipLaunchKernelGGL(k_knn5_near<16>, dim3((gn + NK_WPB - 1) / NK_WPB, rows), dim3(64 * NK_WPB), 0, stream, a, map, ent, sub, nn5);
@@ -2367,12 +2365,12 @@ int glio_debug_knn_stats(int enable, unsigned long long* out8) {
 }
 
 // test knob: size of the cell table of the merged-window grouping (0 = sized from the map); a tiny table forces the orphan path
-int glio_debug_set_gbin_cap(int cap) { g_gbin_cap = cap < 0 ? 0 : cap; return GLIO_OK; }
+int glio_debug_set_gbin_cap(int cap) { glio_switch_set<GLIO_SW_GBIN_CAP>(cap < 0 ? 0 : cap); return GLIO_OK; }
 // test knob: 0 = every run hashes its search frames at their poses (the only mode before round 6), 1 = tables in the frames' own frames where the rule allows
-int glio_debug_set_bassoc_local(int on) { g_bassoc_local = on ? 1 : 0; return GLIO_OK; }
+int glio_debug_set_bassoc_local(int on) { glio_switch_set<GLIO_SW_BASSOC_LOCAL_TABLES>(on ? 1 : 0); return GLIO_OK; }
 int glio_debug_set_knn_mode(int mode) {
     if (mode < 0 || mode > 3) return GLIO_E_ARG;
-    g_knn_mode = mode;
+    glio_switch_set<GLIO_SW_KNN_MODE>(mode);
     return GLIO_OK;
 }
 
@@ -2387,8 +2385,7 @@ int glio_bassoc_create(int device, int K, int max_points_per_frame, int64_t max_
     {   // LOW priority: the pair searches are wide, throughput-bound launches that a keyframe call enqueues beside its own latency-bound kernels (marginalization,
         // local map, the solve's one-CU steps on the context's stream) -- those must get their CUs first (GLIO_BASSOC_PRIORITY=0: default priority, for A/B)
         int least = 0, greatest = 0;
-        const char* e = getenv("GLIO_BASSOC_PRIORITY");
-        if ((!e || atoi(e) != 0) && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
+        if (glio_switch_at_create<GLIO_SW_BASSOC_PRIORITY>() && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
             BA_CHECK(hipStreamCreateWithPriority(&b->stream, hipStreamNonBlocking, least));
         else BA_CHECK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
     }
@@ -2574,9 +2571,7 @@ static int bassoc_fb_uploaded(glio_bassoc* b) {
 // re-association -- skips the builds: 48.0 against 50.0 ms).  Same records, bit for bit: the candidates of a query
 // are the 27 cells around its cell in either frame, both cover the ball of the search radius, and distances, ranking and gate read the same global floats.
 static bool bassoc_local_mode(const glio_bassoc* b, const int n_pairs, const int n_need, const double* poses, const std::vector<char>& need) {
-    if (g_bassoc_local < 0) g_bassoc_local = (getenv("GLIO_BASSOC_LOCAL_TABLES") && atoi(getenv("GLIO_BASSOC_LOCAL_TABLES")) == 0) ? 0 : 1;
-    static const int ratio = getenv("GLIO_BASSOC_LOCAL_RATIO") ? atoi(getenv("GLIO_BASSOC_LOCAL_RATIO")) : 16;
-    if (!g_bassoc_local || g_knn_mode != 0 || n_need == 0 || n_pairs >= ratio * n_need) return false;
+    if (!glio_switch<GLIO_SW_BASSOC_LOCAL_TABLES>() || glio_switch<GLIO_SW_KNN_MODE>() != 0 || n_need == 0 || n_pairs >= glio_switch<GLIO_SW_BASSOC_LOCAL_RATIO>() * n_need) return false;
     if (poses)       // (the grouping inverts the pose with the conjugate: unit quaternions only; anything else takes the global mode)
         for (int k = 0; k < b->K; ++k) if (need[k]) {
             const double* q = poses + 7 * k + 3;
@@ -2789,8 +2784,7 @@ static int bassoc_run(glio_bassoc* b, const double* poses, int n_pairs, const in
                 chunk_rows[(size_t)p0 / BA_CHUNK] = nr;
             }
         }
-        static const bool share_env = !(getenv("GLIO_BASSOC_SHARED_BINS") && atoi(getenv("GLIO_BASSOC_SHARED_BINS")) == 0);      // (0: every pair bins for itself -- A/B and tests)
-        const bool share_bins = share_env && !local;       // (local tables: a pair's queries are grouped by their cell in ITS search frame)
+        const bool share_bins = glio_switch<GLIO_SW_BASSOC_SHARED_BINS>() && !local;       // (GLIO_BASSOC_SHARED_BINS=0: every pair bins for itself -- A/B and tests; local tables: a pair's queries are grouped by their cell in ITS search frame)
         if (!local) {
         BA_CHECK(hipMemcpyAsync(b->d_frames, b->h_fd, (size_t)b->K * sizeof(FrameDesc), hipMemcpyHostToDevice, b->stream));
         BA_CHECK(hipMemcpyAsync(b->d_pair_ci, b->h_pairs, (size_t)n_pairs * 4, hipMemcpyHostToDevice, b->stream));

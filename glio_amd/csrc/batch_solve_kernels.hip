@@ -676,7 +676,7 @@ __global__ __launch_bounds__(BcrCfg<M>::THREADS) void k_bcr_elim(const int* skip
 // block AND solve those rows; the trailing part takes its rank-16 update as v_mfma_f64_16x16x4 tiles with operands read from LDS
 // (the scheme of the window solver's packed LDS Cholesky, solver_kernels.hip, extended by the coupling rows).  Two barriers per
 // PANEL instead of one per pivot.  (Another algorithm than k_bcr_elim, not a second writing of it: both stay, chosen by size -- the
-// register steps are the faster ones at M = 36, 15 vs 19 us; see g_bcr_elim_mode.)  LDS: the packed lower triangle of A_pp (rows at i (i + 1) / 2) + M + 1 full rows
+// register steps are the faster ones at M = 36, 15 vs 19 us; see GLIO_BCR_ELIM.)  LDS: the packed lower triangle of A_pp (rows at i (i + 1) / 2) + M + 1 full rows
 // (A_ap, y, A_bp: 2 M + 1 rows; at M = 90 that is 159.3 of the 160 KB).
 #define BCR_E2_THREADS 512
 template <int M> struct BcrE2 {
@@ -1260,15 +1260,14 @@ void glio_bcr_view(void* h, BcrView* v) {
 
 // -1 (default): by size -- the blocked elimination (k_bcr_elim2) for M >= 54, one register step per pivot with a workgroup barrier each
 // (k_bcr_elim) for M = 36, where it is the faster one (15 vs 19 us on MI355X); 1 / 0 force either (GLIO_BCR_ELIM, cross-checks)
-static int g_bcr_elim_mode = getenv("GLIO_BCR_ELIM") ? atoi(getenv("GLIO_BCR_ELIM")) : -1;
-void glio_bcr_debug_set_elim(int mode) { g_bcr_elim_mode = mode; }
+void glio_bcr_debug_set_elim(int mode) { glio_switch_set<GLIO_SW_BCR_ELIM>(mode); }
 template <int M>
 static void bcr_levels(BcrDev* b, const BcrOp& op, int l0, int l1, hipStream_t stream) {
     const size_t lds_up = BcrUp<M>::lds_bytes;
     for (int l = l0; l < l1; ++l) {
         const int ne = b->h_elim_off[l + 1] - b->h_elim_off[l], nk = b->h_kept_off[l + 1] - b->h_kept_off[l];
         if (ne > 0) {
-            if (g_bcr_elim_mode == 0 || (g_bcr_elim_mode < 0 && M < 54)) hipLaunchKernelGGL((k_bcr_elim<M>), dim3(ne), dim3(BcrCfg<M>::THREADS), 0, stream, op.skip, b->elim + b->h_elim_off[l], b->ws, b->L, b->Ua, b->Ub, b->w, b->fail);
+            if (const int mode = glio_switch<GLIO_SW_BCR_ELIM>(); mode == 0 || (mode < 0 && M < 54)) hipLaunchKernelGGL((k_bcr_elim<M>), dim3(ne), dim3(BcrCfg<M>::THREADS), 0, stream, op.skip, b->elim + b->h_elim_off[l], b->ws, b->L, b->Ua, b->Ub, b->w, b->fail);
             else hipLaunchKernelGGL((k_bcr_elim2<M>), dim3(ne), dim3(BCR_E2_THREADS), BcrE2<M>::lds_bytes, stream, op.skip, b->elim + b->h_elim_off[l], b->ws, b->L, b->Ua, b->Ub, b->w, b->fail);
         }
         if (nk > 0) hipLaunchKernelGGL((k_bcr_update<M>), dim3(2 * nk), dim3(BCR_UP_THREADS), lds_up, stream, op.skip, b->kept + b->h_kept_off[l], b->ws, b->Ua, b->Ub, b->w);

@@ -50,7 +50,7 @@ struct CtxExtra {
     hipEvent_t ev_copy = nullptr;          // glio_set_scan: the end of the scan's copy (what the call waits for; the presort behind it is not waited for)
     hipStream_t up_stream = nullptr; hipEvent_t ev_up = nullptr;
     struct UpArena { char* h = nullptr; char* d = nullptr; size_t cap = 0; hipEvent_t ev_free = nullptr; bool pending = false; hipEvent_t ev_copied = nullptr; bool copying = false; } up[2];
-    int up_next = 0, up_cur = -1, up_mode = -1, up_wait = -1, unstage_up = -1;
+    int up_next = 0, up_cur = -1, up_mode = 1, up_wait = 0, unstage_up = 1;       // (the last three: GLIO_EARLY_UPLOAD, GLIO_EARLY_UPLOAD_WAIT, GLIO_UNSTAGE_IN_STREAM at glio_create)
     int* marg_h_ok = nullptr;              // glio_marginalize_keep_async: the pinned "positive definite" flag its finish looks at
     hipEvent_t ev_ahead = nullptr; int ahead_valid = 0, ahead_n = 0;      // glio_set_scan_ahead: the upload + presort of the NEXT keyframe's scan on the upload stream
     char* sv_h = nullptr; char* sv_d = nullptr; size_t sv_cap = 0;
@@ -69,8 +69,7 @@ struct Roctx {
     int (*push)(const char*) = nullptr;
     int (*pop)() = nullptr;
     Roctx() {
-        const char* e = getenv("GLIO_ROCTX");
-        if (!e || atoi(e) == 0) return;
+        if (!glio_switch<GLIO_SW_ROCTX>()) return;
         void* h = dlopen("libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
         if (!h) h = dlopen("/opt/rocm/lib/libroctx64.so", RTLD_NOW | RTLD_GLOBAL);
         if (!h) return;
@@ -114,9 +113,9 @@ void glio_opts_default(glio_opts* o) {
     o->parameter_tolerance = TR_PARAMETER_TOLERANCE;
 }
 
-static int g_fill = getenv("GLIO_DEBUG_FILL") ? atoi(getenv("GLIO_DEBUG_FILL")) : -1;     // development aid: fill every allocation with this byte
+// GLIO_DEBUG_FILL (development aid): fill every allocation with this byte
 #define ALLOC(ptr, bytes) do { GLIO_HIP_CHECK(hipMalloc((void**)&(ptr), (bytes) > 0 ? (size_t)(bytes) : 16)); \
-                               if (g_fill >= 0) GLIO_HIP_CHECK(hipMemset((void*)(ptr), g_fill, (bytes) > 0 ? (size_t)(bytes) : 16)); } while (0)
+                               if (const int fill = glio_switch<GLIO_SW_DEBUG_FILL>(); fill >= 0) GLIO_HIP_CHECK(hipMemset((void*)(ptr), fill, (bytes) > 0 ? (size_t)(bytes) : 16)); } while (0)
 
 static int create_body(int device, const glio_opts* opts, glio_ctx* c);
 int glio_create(int device, const glio_opts* opts, glio_ctx** out) {
@@ -158,8 +157,7 @@ static int create_body(int device, const glio_opts* opts, glio_ctx* c) {
     {   // the window's kernels are short and latency-bound (one-CU trust-region steps, marginalization, local map): highest priority, so that wide launches of
         // other streams (the batch association of the same keyframe) do not sit in front of them
         int least = 0, greatest = 0;
-        const char* e = getenv("GLIO_CTX_PRIORITY");
-        if ((!e || atoi(e) != 0) && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
+        if (glio_switch_at_create<GLIO_SW_CTX_PRIORITY>() && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
             GLIO_HIP_CHECK(hipStreamCreateWithPriority(&c->own_stream, hipStreamNonBlocking, greatest));
         else GLIO_HIP_CHECK(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
     }
@@ -256,6 +254,8 @@ static int create_body(int device, const glio_opts* opts, glio_ctx* c) {
     GLIO_HIP_CHECK(hipEventCreate(&c->ev0)); GLIO_HIP_CHECK(hipEventCreate(&c->ev1));
     CtxExtra* ex = new CtxExtra();          // value-initialised: pointers null, vectors empty
     ex->imu_edge0 = -1;
+    ex->up_mode = glio_switch_at_create<GLIO_SW_EARLY_UPLOAD>(); ex->up_wait = glio_switch_at_create<GLIO_SW_EARLY_UPLOAD_WAIT>();
+    ex->unstage_up = !glio_switch_at_create<GLIO_SW_UNSTAGE_IN_STREAM>();
     ALLOC(ex->gx.d_runs, (size_t)std::max(1, c->n_ddt_max) * sizeof(DopRun));
     ALLOC(ex->gx.d_prior_colblk, npmax * 4);
     ALLOC(ex->d_eval_params, 64 * 8); ALLOC(ex->d_eval_out, (15 + 15 * 32) * 8); ALLOC(ex->d_eval_edge, sizeof(ImuEdgeDev));
@@ -668,7 +668,6 @@ static int stage_reserve(glio_ctx* c, size_t bytes) {
 // searches and every earlier reader of the tables, and waits for the copy through an event.  Two blocks take turns; a block is sent again only
 // after the k_unstage that read its mirror (event ev_free, waited for by the upload stream).  GLIO_EARLY_UPLOAD=0: the in-stream path (A/B).
 static bool stage_early_enabled(CtxExtra* ex) {
-    if (ex->up_mode < 0) { const char* e = getenv("GLIO_EARLY_UPLOAD"); ex->up_mode = (!e || atoi(e) != 0) ? 1 : 0; }
     return ex->up_mode == 1;
 }
 static int stage_begin_early(glio_ctx* c, size_t bytes) {
@@ -752,7 +751,6 @@ static int stage_flush(glio_ctx* c) {
         // a wait; what may still be in flight on the context's stream -- the window's searches, the local map, a presort -- reads none of them), and the next
         // reader on the context's stream waits for the event below.  Behind the searches on the context's stream instead (GLIO_UNSTAGE_IN_STREAM=1) the two
         // installs sat between the searches and the solve: 2 x (4 us + a 10 us cross-stream hand-over) of every keyframe call.
-        if (ex->unstage_up < 0) { const char* w = getenv("GLIO_UNSTAGE_IN_STREAM"); ex->unstage_up = (w && atoi(w) != 0) ? 0 : 1; }
         if (ex->unstage_up) {
             if (e == hipSuccess) {
                 hipLaunchKernelGGL(k_unstage, dim3(n, UNSTAGE_GY), dim3(256), 0, ex->up_stream, reinterpret_cast<const StageSegDev*>(a.d));
@@ -772,7 +770,6 @@ static int stage_flush(glio_ctx* c) {
         }
         // the pinned block is this arena's until its next turn (stage_begin_early waits for the copy then): the call does not wait for the copy
         // (it did, with hipStreamSynchronize on the upload stream: 10-40 us of host time per call while a search kernel fills the chip; GLIO_EARLY_UPLOAD_WAIT=1)
-        if (ex->up_wait < 0) { const char* w = getenv("GLIO_EARLY_UPLOAD_WAIT"); ex->up_wait = (w && atoi(w) != 0) ? 1 : 0; }
         if (e == hipSuccess) {
             if (ex->up_wait) e = hipStreamSynchronize(ex->up_stream);
             else { e = hipEventRecord(a.ev_copied, ex->up_stream); a.copying = true; }
@@ -1174,9 +1171,8 @@ extern __shared__ double poison_lds[];
 __global__ void k_lds_poison(int n) {
     for (int k = threadIdx.x; k < n; k += blockDim.x) poison_lds[k] = __longlong_as_double(0x7ff8dead00000000ll + k);
 }
-static int g_poison = getenv("GLIO_DEBUG_LDS_POISON") ? atoi(getenv("GLIO_DEBUG_LDS_POISON")) : 0;
 extern "C++" void glio_lds_poison_stream(hipStream_t stream) {       // also called by the batch solve (batch_tr_kernels.hip)
-    if (!g_poison) return;
+    if (!glio_switch<GLIO_SW_DEBUG_LDS_POISON>()) return;
     static bool configured = false;
     if (!configured) { hipFuncSetAttribute(reinterpret_cast<const void*>(k_lds_poison), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); configured = true; }
     hipLaunchKernelGGL(k_lds_poison, dim3(1024), dim3(256), 160 * 1024, stream, 160 * 1024 / 8);
@@ -1221,7 +1217,7 @@ static int enqueue_solve(glio_ctx* c, int n_ddt) {
     // (glio_time_solve, the error paths below); the max_solver_time_s stop touches h_progress only.  No tag is compared on the device: the record is the
     // one written two lines up, and the buffer to linearise is fixed by construction (cur = 1, candidate 0 pending), so the ids' wrap has nothing to fool.
     const int dense = glio_chain_kind(c, n_ddt) == 3 ? 2 : glio_solver_needs_dense_H(c, n_ddt);      // (2: the band k_chain_solve<true> reads is enough)
-    const bool first_mapped = (glio_solve_ends_mask() & 2) && c->merged_linearize && dense == 0 && c->n_imu + c->n_groups + (c->prior_n > 0 ? 1 : 0) > 0;
+    const bool first_mapped = (glio_switch<GLIO_SW_SOLVE_ENDS>() & 2) && c->merged_linearize && dense == 0 && c->n_imu + c->n_groups + (c->prior_n > 0 ? 1 : 0) > 0;
     if (!first_mapped)
         hipLaunchKernelGGL(k_stage_in, dim3(1), dim3(1024), 0, c->stream, reinterpret_cast<unsigned long long*>(c->d_status),
                            reinterpret_cast<const unsigned long long*>(c->d_h_status), 64 + nx);                          // status + state

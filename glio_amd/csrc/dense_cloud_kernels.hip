@@ -156,8 +156,7 @@ static int dn_create_body(glio_dense* d) {
     GLIO_HIP_CHECK(hipEventCreateWithFlags(&d->ev_src, hipEventDisableTiming));
     GLIO_HIP_CHECK(hipEventCreateWithFlags(&d->ev_read, hipEventDisableTiming));
     GLIO_HIP_CHECK(hipEventCreateWithFlags(&d->ev_ext_read, hipEventDisableTiming));
-    const char* e = getenv("GLIO_DENSE_TIMING");
-    d->timed = e && atoi(e) != 0;
+    d->timed = glio_switch_at_create<GLIO_SW_DENSE_TIMING>();
     for (int i = 0; i < 4 && d->timed; ++i) GLIO_HIP_CHECK(hipEventCreate(&d->ev_t[i]));
     return GLIO_OK;
 }

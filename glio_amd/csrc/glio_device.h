@@ -13,9 +13,9 @@
 // int) before it is handed out.  Fresh device memory of a process that runs alone is zero, so a kernel that READS a buffer it was never
 // given -- and silently relies on the zero -- passes every single-process test; with several processes on one GPU the pages may come back
 // with another process's data (found in round 3: `contention_repro.py`).  With the poison such a read fails loudly and reproducibly.
-#include <cstdlib>
+#include "glio_switches.h"
 static inline hipError_t glio_dbg_malloc(void** p, size_t bytes) {
-    static const int poison = getenv("GLIO_DEBUG_POISON_ALLOC") ? atoi(getenv("GLIO_DEBUG_POISON_ALLOC")) : 0;
+    const int poison = glio_switch<GLIO_SW_DEBUG_POISON_ALLOC>();
     const hipError_t e = hipMalloc(p, bytes);
     if (e == hipSuccess && poison && bytes > 0) { (void)hipMemset(*p, 0xFF, bytes); (void)hipDeviceSynchronize(); }
     return e;
@@ -501,7 +501,6 @@ void glio_lidar_pack_f32(glio_ctx* c);                      // no-op unless the 
 // factor_kernels.hip
 void glio_launch_small_factors(glio_ctx* c, int use_status_cand, int which, int n_ddt, int marg = 0);
 void glio_launch_linearize_all(glio_ctx* c, int use_status_cand, int which, int n_ddt, int first = 0);   // K3 + small factors, one launch (first: factor_kernels.hip)
-int glio_solve_ends_mask();   // lab switch GLIO_SOLVE_ENDS / glio_debug_solve_ends (solver_kernels.hip)
 void glio_launch_lidar_reduce(glio_ctx* c, int which);      // K3 partials -> d_lidar_blocks (the marginalization's assembly reads the blocks)
 void glio_launch_assemble(glio_ctx* c, int use_status_cand, int which, int n_ddt, int band = 0);      // band: the block-tridiagonal part + epoch columns only
 int glio_chain_kind(const glio_ctx* c, int n_ddt);

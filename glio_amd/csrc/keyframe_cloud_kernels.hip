@@ -221,8 +221,7 @@ int glio_scan_filter_config(glio_ctx* c, int max_input_points) {
     const int max_vox = max_input_points > c->cap ? max_input_points : c->cap;
     int rc = glio_vg_create(1, max_input_points, 1.0f, max_vox, c->stream, &k->vg);
     if (rc != GLIO_OK) { glio_kfcloud_destroy(c); return rc; }
-    const char* e = getenv("GLIO_KFCLOUD_TIMING");
-    k->timed = e && atoi(e) != 0;
+    k->timed = glio_switch_at_create<GLIO_SW_KFCLOUD_TIMING>();
     hipError_t he = hipMalloc(&k->raw.d, (size_t)max_input_points * 32);
     if (he == hipSuccess) { k->raw.cap = (size_t)max_input_points * 32; he = hipEventCreateWithFlags(&k->ev_src, hipEventDisableTiming); }
     if (he == hipSuccess) he = hipEventCreateWithFlags(&k->ev_done, hipEventDisableTiming);

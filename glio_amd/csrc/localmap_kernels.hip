@@ -558,8 +558,7 @@ static int lm_alloc(LocalMap* m, hipStream_t stream) {
     memset(m->h_pub, 0, 64);
     LM_CHECK(hipHostGetDevicePointer((void**)&m->d_h_pub, m->h_pub, 0));
     {   // occupancy bitmap of the bounding box + its running counts (GLIO_LM_SORT=1: the radix sort only)
-        const char* e = getenv("GLIO_LM_SORT");
-        m->force_sort = e && atoi(e) != 0;
+        m->force_sort = glio_switch_at_create<GLIO_SW_LM_SORT>();
         LM_CHECK(hipMalloc((void**)&m->d_bm_over, 4));
         LM_CHECK(hipMemsetAsync(m->d_bm_over, 0, 4, stream));
         if (!m->force_sort) {
@@ -856,8 +855,7 @@ int glio_localmap_rebuild_from_frames(glio_ctx* c, glio_bassoc* frames, int n_fr
     if (!m->h_frames) {
         LM_CHECK(hipHostMalloc((void**)&m->h_frames, (size_t)m->width * sizeof(LmFrame))); LM_CHECK(hipMalloc((void**)&m->d_frames, (size_t)m->width * sizeof(LmFrame)));
         LM_CHECK(hipEventCreateWithFlags(&m->ev_frames, hipEventDisableTiming)); LM_CHECK(hipEventCreateWithFlags(&m->ev_dep, hipEventDisableTiming));
-        const char* e = getenv("GLIO_LM_REBUILD_TIMING");
-        m->time_rebuild = e && atoi(e) != 0;
+        m->time_rebuild = glio_switch_at_create<GLIO_SW_LM_REBUILD_TIMING>();
         if (m->time_rebuild) { LM_CHECK(hipEventCreate(&m->ev_rb0)); LM_CHECK(hipEventCreate(&m->ev_rb1)); }
     }
     if (m->frames_in_flight) { LM_CHECK(hipEventSynchronize(m->ev_frames)); m->frames_in_flight = 0; }      // (the pinned table is rewritten only behind its last upload)

@@ -3847,22 +3847,13 @@ int glio_solver_needs_dense_H(const glio_ctx* c, int n_ddt) { return glio_chain_
 
 // GLIO_CHAIN_FAST (bit 0: tail, bit 1: front of k_chain_step from LDS; default both).  0 = the generic bodies: the A/B switch of
 // scripts/chain_step_time.py and of test_chain_step_fast_paths_are_bit_identical.
-static int g_chain_fast = -1;
-extern "C" int glio_debug_chain_fast(int mask) { const int old = g_chain_fast; g_chain_fast = mask; return old; }
-static int chain_fast_mask() {
-    if (g_chain_fast < 0) { const char* e = getenv("GLIO_CHAIN_FAST"); g_chain_fast = e ? atoi(e) & 3 : 3; }
-    return g_chain_fast;
-}
+// (The setters below return the value they replace and store what they are given: a negative value no longer means "read the environment again".)
+extern "C" int glio_debug_chain_fast(int mask) { return glio_switch_set<GLIO_SW_CHAIN_FAST>(mask); }
 
 // GLIO_SOLVE_ENDS (bit 1: the first group of glio_solve reads status and state from the mapped host copy, no k_stage_in launch; bit 2: a solve that ends
 // in k_chain_step's state machine is published from LDS, finalize_lds; default both).  0 = the staging launch and finalize(): the A/B switch of
 // tests/test_hip_solve_ends.py.  (Bit 0 is not in use.)
-static int g_solve_ends = -1;
-int glio_solve_ends_mask() {
-    if (g_solve_ends < 0) { const char* e = getenv("GLIO_SOLVE_ENDS"); g_solve_ends = e ? atoi(e) & 6 : 6; }
-    return g_solve_ends;
-}
-extern "C" int glio_debug_solve_ends(int mask) { const int old = glio_solve_ends_mask(); g_solve_ends = mask & 6; return old; }
+extern "C" int glio_debug_solve_ends(int mask) { return glio_switch_set<GLIO_SW_SOLVE_ENDS>(mask & 6); }
 
 // test hook (CPU-callable: host arithmetic only): where the four-front panels of k_chain_step would live for a window of W keyframes and nd clock-drift
 // epochs.  out = {regular dynamic LDS bytes, off_dds, bytes available at off_dds (the clock-drift copy), k0 (E slots placed there), off_r1, total bytes,
@@ -3883,12 +3874,7 @@ extern "C" int glio_debug_chain_f4_layout(int W, int nd, int mirrors, long long*
 }
 
 // GLIO_CHAIN_FRONTS = 2: k_chain_step keeps the two-front elimination for every window (A/B switch and cross-check of the four-front order)
-static int g_chain_fronts = -1;
-extern "C" int glio_debug_chain_fronts(int fronts) { const int old = g_chain_fronts; g_chain_fronts = fronts; return old; }
-static int chain_fronts_mode() {
-    if (g_chain_fronts < 0) { const char* e = getenv("GLIO_CHAIN_FRONTS"); g_chain_fronts = e ? atoi(e) : 4; }
-    return g_chain_fronts;
-}
+extern "C" int glio_debug_chain_fronts(int fronts) { return glio_switch_set<GLIO_SW_CHAIN_FRONTS>(fronts); }
 
 void glio_launch_tr_step(glio_ctx* c, int n_ddt) {
     TrArgs a;
@@ -3927,15 +3913,15 @@ void glio_launch_tr_step(glio_ctx* c, int n_ddt) {
     if (chain) {
         ChainArgs r;
         r.W = c->W; r.n = a.n; r.nd = n_ddt; r.ep_slots = c->arrow.d_ep_slots; r.ep_off = c->arrow.d_ep_off; r.ep_list = c->arrow.d_ep_list;
-        r.z = c->arrow.d_z; r.flag = c->arrow.d_flag; r.status = c->d_status; r.dbg = c->arrow.d_dbg; r.force_fail = c->arrow.mode == 2; r.fast = chain_fast_mask(); r.blk = nullptr; r.helpers = 0; r.hseq = 0; r.hsum = nullptr; r.hdone = nullptr; r.hpolls = 0; r.fat = 0; r.fat_blk = nullptr; r.fat_ep = nullptr;
+        r.z = c->arrow.d_z; r.flag = c->arrow.d_flag; r.status = c->d_status; r.dbg = c->arrow.d_dbg; r.force_fail = c->arrow.mode == 2; r.fast = glio_switch<GLIO_SW_CHAIN_FAST>(); r.blk = nullptr; r.helpers = 0; r.hseq = 0; r.hsum = nullptr; r.hdone = nullptr; r.hpolls = 0; r.fat = 0; r.fat_blk = nullptr; r.fat_ep = nullptr;
         if (chain_step_lds_bytes(c->W, n_ddt, a.n, true) + 2 * 1024 > 158 * 1024) r.fast = 0;      // no room for the LDS mirrors: generic bodies
-        if ((r.fast & 2) && (glio_solve_ends_mask() & 4)) r.fast |= 4;                            // (bit 2: finalize_lds)
+        if ((r.fast & 2) && (glio_switch<GLIO_SW_SOLVE_ENDS>() & 4)) r.fast |= 4;                            // (bit 2: finalize_lds)
         size_t lds_step = chain_step_lds_bytes(c->W, n_ddt, a.n, r.fast != 0);
         {   // separator + four fronts when the window is long enough for it to pay and its panels fit (chain_f4_layout)
             const ChainF4Layout L = chain_f4_layout(c->W, n_ddt, a.n, r.fast != 0);
             const size_t with4 = L.total > lds_step ? L.total : lds_step;
             // (158 KB is what hipFuncSetAttribute grants this kernel as dynamic LDS: 160 KB less 2 KB for its 1.4 KB of static LDS)
-            r.fronts4 = (c->W >= KC_F4_MIN_W && chain_fronts_mode() != 2 && with4 + 256 <= 158 * 1024) ? 1 : 0;
+            r.fronts4 = (c->W >= KC_F4_MIN_W && glio_switch<GLIO_SW_CHAIN_FRONTS>() != 2 && with4 + 256 <= 158 * 1024) ? 1 : 0;
             if (r.fronts4) lds_step = with4;
             c->arrow.last_fronts = r.fronts4 ? 4 : 2;
         }
@@ -3951,27 +3937,24 @@ void glio_launch_tr_step(glio_ctx* c, int n_ddt) {
             a.hd0 = c->d_hdiag[0]; a.hd1 = c->d_hdiag[1];
             a.fused_chain = 2;
             // helper workgroups (one per keyframe) pre-sum the candidate's block entries: GLIO_CHAIN_HELPERS=0 switches them off (A/B)
-            static const bool helpers_off = getenv("GLIO_CHAIN_HELPERS") && atoi(getenv("GLIO_CHAIN_HELPERS")) == 0;
             // Workgroup 0 WAITS for the helpers' completion words inside the launch, and every workgroup of this launch reserves the whole dynamic LDS
             // grant, i.e. a CU of its own: the hand-over needs 1 + W CUs that the launch can actually get.  HIP promises no forward progress between
             // workgroups, so the helpers are used only when the device has room to spare (>= 2 (1 + W) CUs) AND the wait is bounded (hpolls below): a
             // deployment that masks CUs or partitions the device cannot hang the step, it only loses the helpers' 4 us (GLIO_CHAIN_HELPERS=0 skips the
             // attempt).  INTEGRATION.md section 5.
             const bool room = c->n_cu >= 2 * (1 + c->W);          // (the context's own device: queried at glio_create, not a process-wide value)
-            r.helpers = (helpers_off || !room) ? 0 : c->W; r.hsum = c->arrow.d_chain_sum; r.hdone = c->arrow.d_chain_done;
+            r.helpers = (glio_switch<GLIO_SW_CHAIN_HELPERS>() && room) ? c->W : 0; r.hsum = c->arrow.d_chain_sum; r.hdone = c->arrow.d_chain_done;
             r.hseq = c->arrow.chain_seq; c->arrow.chain_seq = c->arrow.chain_seq % (1 << 28) + 1;
             // the wait for the helpers is bounded (a poll is a device-scope load + s_sleep: ~0.5-1 us; the helpers report ~5 us into the launch): ~0.2 ms at
             // most, then the step sums the blocks itself.  GLIO_CHAIN_HELPER_POLLS=0 gives them up at once (test: same bits out)
-            static const int hpolls = getenv("GLIO_CHAIN_HELPER_POLLS") ? atoi(getenv("GLIO_CHAIN_HELPER_POLLS")) : 256;
-            r.hpolls = hpolls;
+            r.hpolls = glio_switch<GLIO_SW_CHAIN_HELPER_POLLS>();
             // fat helpers (GLIO_CHAIN_FAT=0: the helpers only sum): the speculative build of every keyframe's block, its rows of t and its epochs' columns
-            static const bool fat_on = !(getenv("GLIO_CHAIN_FAT") && atoi(getenv("GLIO_CHAIN_FAT")) == 0);
-            r.fat = (fat_on && r.helpers && chain_fat_helper_lds_bytes(c->W, n_ddt) <= lds_step) ? 1 : 0; r.fat_blk = c->arrow.d_blk; r.fat_ep = c->arrow.d_fat_ep;
+            r.fat = (glio_switch<GLIO_SW_CHAIN_FAT>() && r.helpers && chain_fat_helper_lds_bytes(c->W, n_ddt) <= lds_step) ? 1 : 0; r.fat_blk = c->arrow.d_blk; r.fat_ep = c->arrow.d_fat_ep;
             hipLaunchKernelGGL(k_chain_step, dim3(1 + r.helpers), dim3(KC_THREADS), lds_step, c->stream, r, a, G);
             return;                                   // the one launch is the whole step
         }
         if (ckind == 3) {
-            r.blk = c->arrow.d_blk; r.fronts4 = chain_fronts_mode() != 2 ? 1 : 0;
+            r.blk = c->arrow.d_blk; r.fronts4 = glio_switch<GLIO_SW_CHAIN_FRONTS>() != 2 ? 1 : 0;
             c->arrow.last_fronts = r.fronts4 ? 4 : 2;
             hipLaunchKernelGGL(k_chain_solve<true>, dim3(1), dim3(KC_THREADS), lds_chain, c->stream, r, a);
         } else hipLaunchKernelGGL(k_chain_solve<false>, dim3(1), dim3(KC_THREADS), lds_chain, c->stream, r, a);
@@ -4494,7 +4477,7 @@ int glio_launch_marginalize(glio_ctx* c, int imu_edge0, double** J0_dev, double*
     hipLaunchKernelGGL(k_marg_assemble, dim3(pos + 1), dim3(256), 0, c->stream, a);
     int* d_ok = reinterpret_cast<int*>(c->d_vec + 9 * (size_t)c->n_max);
     double* Twork = c->d_marg_T;                 // n x 15, n <= 15 (W - 1)
-    static const bool split = !(getenv("GLIO_MARG_SPLIT") && atoi(getenv("GLIO_MARG_SPLIT")) == 0);      // (0: the one-workgroup form, for A/B and tests)
+    const bool split = glio_switch<GLIO_SW_MARG_SPLIT>();      // (0: the one-workgroup form, for A/B and tests)
     // scratch of the split form: Ainv (225), the tolerances (n), the pattern flag -- behind the (n + 1) x n work matrix in d_L, when it fits there
     const size_t lwork = (size_t)(n + 1) * n + 2, need = 226 + (size_t)n + 2 + 1100, have = (size_t)(c->n_max + 1) * c->n_max;
     if (split && lwork + need <= have) {
