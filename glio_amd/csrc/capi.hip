@@ -3,16 +3,10 @@
 // path: IMU sqrt-information, factor sorting), and the solve / linearise / evaluator orchestration.
 // There is NO CPU fallback in here: without a HIP device glio_create fails and every entry point
 // returns GLIO_E_HIP / GLIO_E_STATE.
-#include <algorithm>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <atomic>
 #include <chrono>
 #include <thread>
-#include <vector>
 
 #include "../../include/glio_cov.h"
 #include "glio_device.h"
@@ -50,10 +44,9 @@ struct CtxExtra {
     hipEvent_t ev_copy = nullptr;          // glio_set_scan: the end of the scan's copy (what the call waits for; the presort behind it is not waited for)
     hipStream_t up_stream = nullptr; hipEvent_t ev_up = nullptr;
     struct UpArena { char* h = nullptr; char* d = nullptr; size_t cap = 0; hipEvent_t ev_free = nullptr; bool pending = false; hipEvent_t ev_copied = nullptr; bool copying = false; } up[2];
-    int up_next = 0, up_cur = -1, up_mode = 1, up_wait = 0, unstage_up = 1;       // (the last three: GLIO_EARLY_UPLOAD, GLIO_EARLY_UPLOAD_WAIT, GLIO_UNSTAGE_IN_STREAM at glio_create)
+    int up_next = 0, up_mode = 1, up_wait = 0, unstage_up = 1;       // (the last three: GLIO_EARLY_UPLOAD, GLIO_EARLY_UPLOAD_WAIT, GLIO_UNSTAGE_IN_STREAM at glio_create)
     int* marg_h_ok = nullptr;              // glio_marginalize_keep_async: the pinned "positive definite" flag its finish looks at
     hipEvent_t ev_ahead = nullptr; int ahead_valid = 0, ahead_n = 0;      // glio_set_scan_ahead: the upload + presort of the NEXT keyframe's scan on the upload stream
-    char* sv_h = nullptr; char* sv_d = nullptr; size_t sv_cap = 0;
     GlioCovWs* cov = nullptr;              // glio_covariance_*: the workspace, allocated by the first call
 };
 // the extras hang off the context itself (glio_ctx::extra): no process-global registry, so independent contexts can be
@@ -61,6 +54,24 @@ struct CtxExtra {
 static CtxExtra* extra_of(glio_ctx* c) { return static_cast<CtxExtra*>(c->extra); }
 GnssDevExtra* glio_extra(glio_ctx* c) { return &extra_of(c)->gx; }
 static int marg_pending_done(glio_ctx* c);
+static_assert(TAB_E_ARG == GLIO_E_ARG && TAB_E_STATE == GLIO_E_STATE, "window_tables.h restates the two codes its refusals carry");
+static int refused(const TabError& e) { if (e.msg[0]) glio_set_error("%s", e.msg); return e.code; }
+// the factor tables changed: the solve's gather tables are rebuilt, the dense H buffers are no longer known to be zero outside the band
+static void factor_tables_changed(glio_ctx* c) { c->chain_tabs_dirty = 1; c->h_band_clean = 0; }
+static void prior_clear(glio_ctx* c) {
+    c->prior_n = 0; c->prior_nb = 0; c->arrow.prior_ok = 1; c->arrow.prior_chain = 1; c->prior_ext_coupled = 0;
+    for (int k = 0; k < 15 * c->W; ++k) c->h_prior_index[k] = -1;
+    factor_tables_changed(c);
+}
+// the upload stream (early uploads, scans sent ahead) and its event, made by the first call that needs them
+static int up_stream_make(CtxExtra* ex) {
+    if (ex->up_stream) return GLIO_OK;
+    int least = 0, greatest = 0;
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) GLIO_HIP_CHECK(hipStreamCreateWithPriority(&ex->up_stream, hipStreamNonBlocking, greatest));
+    else GLIO_HIP_CHECK(hipStreamCreateWithFlags(&ex->up_stream, hipStreamNonBlocking));
+    GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_up, hipEventDisableTiming));
+    return GLIO_OK;
+}
 
 // ---- roctx ranges (GLIO_ROCTX=1)
 #include <dlfcn.h>
@@ -209,7 +220,7 @@ static int create_body(int device, const glio_opts* opts, glio_ctx* c) {
     c->h_groups = (GnssGroup*)calloc((size_t)W * W, sizeof(GnssGroup));
     c->h_prior_index = (int*)malloc((size_t)15 * W * sizeof(int));
     for (int k = 0; k < 15 * W; ++k) c->h_prior_index[k] = -1;
-    c->chain_tabs_dirty = 1; c->h_band_clean = 0;
+    factor_tables_changed(c);
     c->k3_bpk = GLIO_K3_BLOCKS_PER_KF; c->last_k3_nb = c->k3_bpk; c->merged_linearize = 2; c->want_pair_H = 1; c->k3_unroll = 22;   /* 2-deep batches, non-temporal loads, next batch issued before the arithmetic of the current one */
     { int per = 768 / W;   /* ~3 workgroups per CU measured best on MI355X (scripts/k3_sweep.py) */
       // the fp32 / MFMA form keeps two chunks (four 16-byte loads per lane) in flight per wavefront and wants ~8x as many of them resident: at the C5
@@ -464,12 +475,7 @@ int glio_localmap_push_scan_ahead_and_build(glio_ctx* c, const float lidar_offse
 int glio_ahead_begin(glio_ctx* c, hipStream_t* up) {
     { const int rp = glio_assoc_finish_pending(c); if (rp != GLIO_OK) return rp; }              // every search that reads slot 0's scan has ended
     CtxExtra* ex = extra_of(c);
-    if (!ex->up_stream) {
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) GLIO_HIP_CHECK(hipStreamCreateWithPriority(&ex->up_stream, hipStreamNonBlocking, greatest));
-        else GLIO_HIP_CHECK(hipStreamCreateWithFlags(&ex->up_stream, hipStreamNonBlocking));
-        GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_up, hipEventDisableTiming));
-    }
+    { const int rs = up_stream_make(ex); if (rs != GLIO_OK) return rs; }
     if (!ex->ev_ahead) GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_ahead, hipEventDisableTiming));
     if (!ex->ev_copy) GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_copy, hipEventDisableTiming));
     // (another object's stream may still be reading a resident scan -- never slot 0's: glio_bassoc_set_frame_from_scan copies the newest -- but the event is cheap)
@@ -565,69 +571,13 @@ int glio_associate(glio_ctx* c, int slot, const float* scan, int n, const double
 }
 
 // ---------------------------------------------------------------------------------------------- IMU
-static bool inv15(const double* A_in, double* Ainv) {
-    double A[225];
-    memcpy(A, A_in, sizeof A);
-    for (int i = 0; i < 15; ++i) for (int j = 0; j < 15; ++j) Ainv[i * 15 + j] = i == j;
-    for (int c = 0; c < 15; ++c) {
-        int piv = c; double best = fabs(A[c * 15 + c]);
-        for (int r = c + 1; r < 15; ++r) if (fabs(A[r * 15 + c]) > best) { best = fabs(A[r * 15 + c]); piv = r; }
-        if (best == 0.0) return false;
-        if (piv != c) for (int j = 0; j < 15; ++j) { std::swap(A[c * 15 + j], A[piv * 15 + j]); std::swap(Ainv[c * 15 + j], Ainv[piv * 15 + j]); }
-        const double d = A[c * 15 + c];
-        for (int j = 0; j < 15; ++j) { A[c * 15 + j] /= d; Ainv[c * 15 + j] /= d; }
-        for (int r = 0; r < 15; ++r) {
-            if (r == c) continue;
-            const double f = A[r * 15 + c];
-            if (f == 0.0) continue;
-            for (int j = 0; j < 15; ++j) { A[r * 15 + j] -= f * A[c * 15 + j]; Ainv[r * 15 + j] -= f * Ainv[c * 15 + j]; }
-        }
-    }
-    return true;
-}
-// sqrt_info = LLT(cov^-1).matrixL().transpose()  (ImuFactor.h:44-45) -- the reference recomputes this on
-// the CPU in every Evaluate; it only depends on the pre-integration, so it is digested once at upload (Q5).
-static bool digest_edge(const glio_preint* p, int slot, ImuEdgeDev* e);
+// (inv15, digest_edge: window_tables.h)
 extern "C++" bool glio_digest_imu_edge(const glio_preint* p, int slot, ImuEdgeDev* e) { return digest_edge(p, slot, e); }
-static bool digest_edge(const glio_preint* p, int slot, ImuEdgeDev* e) {
-    memset(e, 0, sizeof *e);
-    memcpy(e->delta_p, p->delta_p, 24); memcpy(e->delta_q, p->delta_q, 32); memcpy(e->delta_v, p->delta_v, 24);
-    memcpy(e->lin_ba, p->linearized_ba, 24); memcpy(e->lin_bg, p->linearized_bg, 24);
-    e->sum_dt = p->sum_dt; e->slot_i = slot;
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {
-            e->dp_dba[r * 3 + c] = p->jacobian[(0 + r) * 15 + 9 + c];
-            e->dp_dbg[r * 3 + c] = p->jacobian[(0 + r) * 15 + 12 + c];
-            e->dq_dbg[r * 3 + c] = p->jacobian[(3 + r) * 15 + 12 + c];
-            e->dv_dba[r * 3 + c] = p->jacobian[(6 + r) * 15 + 9 + c];
-            e->dv_dbg[r * 3 + c] = p->jacobian[(6 + r) * 15 + 12 + c];
-        }
-    double I[225];
-    if (!inv15(p->covariance, I)) return false;
-    for (int j = 0; j < 15; ++j) {           // lower Cholesky of the (lower triangle of the) inverse
-        double d = I[j * 15 + j];
-        for (int k = 0; k < j; ++k) d -= I[j * 15 + k] * I[j * 15 + k];
-        if (!(d > 0.0)) return false;
-        d = sqrt(d);
-        I[j * 15 + j] = d;
-        for (int i = j + 1; i < 15; ++i) {
-            double s = I[i * 15 + j];
-            for (int k = 0; k < j; ++k) s -= I[i * 15 + k] * I[j * 15 + k];
-            I[i * 15 + j] = s / d;
-        }
-    }
-    for (int i = 0; i < 15; ++i) for (int j = 0; j < 15; ++j) e->sqrt_info[i * 15 + j] = j >= i ? I[j * 15 + i] : 0.0;
-    return true;
-}
 
 // ---------------------------------------------------------------------------------------------- pinned upload arena
-// A set_* call stages every table in ONE pinned block [segment descriptors (1 KB) | payloads, 64-byte aligned]; stage_flush sends the
-// block with ONE asynchronous copy to its device mirror and ONE kernel moves every segment to its destination (device-to-device
-// segments -- results a kernel left in a workspace -- ride along): two operations per call instead of one copy per table (a keyframe
-// cycle issued 25 copies of a few hundred bytes, ~5 us of GPU time and ~4 us of host time each).  The caller synchronises once.
-#define STAGE_HEADER 1024
-#define STAGE_DIRECT_BYTES 16384
-struct StageSegDev { void* dst; const void* src; size_t bytes; };
+// The byte arithmetic of a batch (StageBatch: header, alignment, segments, the tables sent on their own) is in window_tables.h; here are the pinned
+// blocks, the copies into them and what is enqueued.  (A keyframe cycle issued 25 copies of a few hundred bytes, ~5 us of GPU time and ~4 us of
+// host time each; a batch is two operations.)  The caller synchronises once.
 __global__ __launch_bounds__(256) void k_unstage(const StageSegDev* __restrict__ segs) {
     const StageSegDev sg = segs[blockIdx.x];
     const size_t words = sg.bytes >> 2;          // every table is made of 4- or 8-byte items
@@ -645,19 +595,24 @@ __global__ __launch_bounds__(256) void k_unstage(const StageSegDev* __restrict__
     for (size_t i = done + t; i < words; i += nt) dst[i] = src[i];
 }
 #define UNSTAGE_GY 32
-static int stage_reserve(glio_ctx* c, size_t bytes) {
-    c->h_stage_used = STAGE_HEADER; c->n_stage_seg = 0;
-    bytes += STAGE_HEADER + 64 * 34;
-    c->h_stage_top = c->h_stage_cap & ~(size_t)63;
-    if (bytes <= c->h_stage_cap) return GLIO_OK;
-    GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (c->h_stage) hipHostFree(c->h_stage);
-    if (c->d_stage) hipFree(c->d_stage);
-    c->h_stage = nullptr; c->d_stage = nullptr; c->h_stage_cap = 0;
-    const size_t cap = bytes * 2 + 4096;
-    GLIO_HIP_CHECK(hipHostMalloc((void**)&c->h_stage, cap));
-    GLIO_HIP_CHECK(hipMalloc((void**)&c->d_stage, cap));
-    c->h_stage_cap = cap; c->h_stage_top = cap & ~(size_t)63;
+// a batch in the context's own block (grown when the payload does not fit): its copy and its k_unstage go on the context's stream
+static int stage_block_grow(char** h, char** d, size_t* cap, size_t bytes) {          // (nothing reads or writes the old block any more)
+    if (*h) hipHostFree(*h);
+    if (*d) hipFree(*d);
+    *h = nullptr; *d = nullptr; *cap = 0;
+    GLIO_HIP_CHECK(hipHostMalloc((void**)h, bytes * 2 + 4096));
+    GLIO_HIP_CHECK(hipMalloc((void**)d, bytes * 2 + 4096));
+    *cap = bytes * 2 + 4096;
+    return GLIO_OK;
+}
+static int stage_reserve(glio_ctx* c, size_t bytes, StageBatch* b) {
+    bytes = stage_block_bytes(bytes);
+    if (bytes > c->h_stage_cap) {
+        GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
+        const int rg = stage_block_grow(&c->h_stage, &c->d_stage, &c->h_stage_cap, bytes);
+        if (rg != GLIO_OK) return rg;
+    }
+    stage_open(b, c->h_stage, c->d_stage, c->h_stage_cap, -1);
     return GLIO_OK;
 }
 // EARLY uploads.  glio_set_imu / glio_set_gnss are called while the window's searches are still running on the context's stream
@@ -667,152 +622,109 @@ static int stage_reserve(glio_ctx* c, size_t bytes) {
 // k_unstage reads, the host waits for that copy alone, and k_unstage -- the only writer of the tables -- stays on the context's stream, behind the
 // searches and every earlier reader of the tables, and waits for the copy through an event.  Two blocks take turns; a block is sent again only
 // after the k_unstage that read its mirror (event ev_free, waited for by the upload stream).  GLIO_EARLY_UPLOAD=0: the in-stream path (A/B).
-static bool stage_early_enabled(CtxExtra* ex) {
-    return ex->up_mode == 1;
-}
-static int stage_begin_early(glio_ctx* c, size_t bytes) {
+static int stage_begin_early(glio_ctx* c, size_t bytes, StageBatch* b) {
     CtxExtra* ex = extra_of(c);
-    if (!ex->up_stream) {
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) GLIO_HIP_CHECK(hipStreamCreateWithPriority(&ex->up_stream, hipStreamNonBlocking, greatest));
-        else GLIO_HIP_CHECK(hipStreamCreateWithFlags(&ex->up_stream, hipStreamNonBlocking));
-        GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_up, hipEventDisableTiming));
-    }
+    { const int rs = up_stream_make(ex); if (rs != GLIO_OK) return rs; }
     const int k = ex->up_next;
     CtxExtra::UpArena& a = ex->up[k];
-    bytes += STAGE_HEADER + 64 * 34;
+    bytes = stage_block_bytes(bytes);
     // the pinned block is written again: its last copy (two uploads ago) has to be through -- it has been for a long time; nothing else is waited for
     if (a.copying) { GLIO_HIP_CHECK(hipEventSynchronize(a.ev_copied)); a.copying = false; }
     if (!a.ev_copied) GLIO_HIP_CHECK(hipEventCreateWithFlags(&a.ev_copied, hipEventDisableTiming));
     if (bytes > a.cap) {
         if (a.pending) { GLIO_HIP_CHECK(hipEventSynchronize(a.ev_free)); a.pending = false; }
-        if (a.h) hipHostFree(a.h);
-        if (a.d) hipFree(a.d);
-        a.h = nullptr; a.d = nullptr; a.cap = 0;
-        const size_t cap = bytes * 2 + 4096;
-        GLIO_HIP_CHECK(hipHostMalloc((void**)&a.h, cap));
-        GLIO_HIP_CHECK(hipMalloc((void**)&a.d, cap));
-        a.cap = cap;
+        { const int rg = stage_block_grow(&a.h, &a.d, &a.cap, bytes); if (rg != GLIO_OK) return rg; }
         if (!a.ev_free) GLIO_HIP_CHECK(hipEventCreateWithFlags(&a.ev_free, hipEventDisableTiming));
     }
-    // the staging functions work on the context's arena fields: point them at this block until stage_flush
-    ex->sv_h = c->h_stage; ex->sv_d = c->d_stage; ex->sv_cap = c->h_stage_cap;
-    c->h_stage = a.h; c->d_stage = a.d; c->h_stage_cap = a.cap;
-    c->h_stage_used = STAGE_HEADER; c->n_stage_seg = 0; c->h_stage_top = a.cap & ~(size_t)63;
-    ex->up_cur = k; ex->up_next = k ^ 1;
+    stage_open(b, a.h, a.d, a.cap, k);
+    ex->up_next = k ^ 1;
     return GLIO_OK;
 }
-static void stage_end_early(glio_ctx* c) {
-    CtxExtra* ex = extra_of(c);
-    if (ex->up_cur < 0) return;
-    c->h_stage = ex->sv_h; c->d_stage = ex->sv_d; c->h_stage_cap = ex->sv_cap;
-    c->h_stage_used = STAGE_HEADER; c->n_stage_seg = 0; c->h_stage_top = c->h_stage_cap & ~(size_t)63;
-    ex->up_cur = -1;
-}
-static int stage_upload(glio_ctx* c, void* dst, const void* src, size_t bytes) {
+// the batch of a glio_set_imu / glio_set_gnss: an early one unless GLIO_EARLY_UPLOAD=0
+static int stage_begin(glio_ctx* c, size_t bytes, StageBatch* b) { return extra_of(c)->up_mode == 1 ? stage_begin_early(c, bytes, b) : stage_reserve(c, bytes, b); }
+static int stage_upload(glio_ctx* c, StageBatch* b, void* dst, const void* src, size_t bytes) {
     if (bytes == 0) return GLIO_OK;
-    if (bytes > STAGE_DIRECT_BYTES && extra_of(c)->up_cur < 0) {          // a large table goes straight to its destination (the copy engine beats a second pass over it);
-        const size_t need = (bytes + 63) & ~(size_t)63;      // its pinned copy is taken from the TOP of the arena, outside the block stage_flush sends
-        if (c->h_stage_top < need || c->h_stage_top - need < c->h_stage_used) { glio_set_error("upload arena overflow"); return GLIO_E_STATE; }
-        c->h_stage_top -= need;
-        memcpy(c->h_stage + c->h_stage_top, src, bytes);
-        GLIO_HIP_CHECK(hipMemcpyAsync(dst, c->h_stage + c->h_stage_top, bytes, hipMemcpyHostToDevice, c->stream));
-        return GLIO_OK;
-    }
-    const size_t off = (c->h_stage_used + 63) & ~(size_t)63;
-    if (off + bytes > c->h_stage_top || c->n_stage_seg >= 32 || (bytes & 3)) { glio_set_error("upload arena overflow"); return GLIO_E_STATE; }
-    memcpy(c->h_stage + off, src, bytes);
-    c->h_stage_used = off + bytes;
-    c->stage_seg[c->n_stage_seg].dst = dst; c->stage_seg[c->n_stage_seg].src = c->d_stage + off; c->stage_seg[c->n_stage_seg].bytes = bytes;
-    c->n_stage_seg += 1;
+    StagePlace p; TabError e;
+    if (stage_place(b, dst, bytes, &p, &e)) return refused(e);
+    memcpy(p.at, src, bytes);
+    if (p.direct) GLIO_HIP_CHECK(hipMemcpyAsync(dst, p.at, bytes, hipMemcpyHostToDevice, c->stream));
     return GLIO_OK;
 }
-// a device-to-device segment of the same batch
-static int stage_d2d(glio_ctx* c, void* dst, const void* src, size_t bytes) {
-    if (bytes == 0) return GLIO_OK;
-    if (c->n_stage_seg >= 32 || (bytes & 3)) { glio_set_error("upload arena overflow"); return GLIO_E_STATE; }
-    c->stage_seg[c->n_stage_seg].dst = dst; c->stage_seg[c->n_stage_seg].src = src; c->stage_seg[c->n_stage_seg].bytes = bytes;
-    c->n_stage_seg += 1;
-    return GLIO_OK;
+static int stage_d2d(StageBatch* b, void* dst, const void* src, size_t bytes) {
+    TabError e;
+    return bytes == 0 ? GLIO_OK : (stage_place_d2d(b, dst, src, bytes, &e) ? refused(e) : GLIO_OK);
 }
-static int stage_flush(glio_ctx* c) {
-    const int n = c->n_stage_seg;
+static int stage_flush(glio_ctx* c, StageBatch* b) {
+    const int n = b->n_seg;
     CtxExtra* ex = extra_of(c);
-    if (n == 0) { stage_end_early(c); return GLIO_OK; }
-    static_assert(sizeof(StageSegDev) * 32 <= STAGE_HEADER, "descriptor header");
-    memcpy(c->h_stage, c->stage_seg, sizeof(StageSegDev) * (size_t)n);
-    if (ex->up_cur >= 0) {
-        CtxExtra::UpArena& a = ex->up[ex->up_cur];
+    if (n == 0) return GLIO_OK;
+    memcpy(b->h, b->seg, sizeof(StageSegDev) * (size_t)n);
+    if (b->early >= 0) {
+        CtxExtra::UpArena& a = ex->up[b->early];
         hipError_t e = hipSuccess;
         if (a.pending) e = hipStreamWaitEvent(ex->up_stream, a.ev_free, 0);
-        if (e == hipSuccess) e = hipMemcpyAsync(a.d, a.h, c->h_stage_used, hipMemcpyHostToDevice, ex->up_stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(a.d, a.h, b->used, hipMemcpyHostToDevice, ex->up_stream);
         // k_unstage -- the only writer of the factor tables -- ON THE UPLOAD STREAM too, right behind its copy: every reader of those tables is an entry point
         // that has returned by the time glio_set_imu / glio_set_gnss can be called (solve, marginalization, linearisation and the evaluation calls all end with
         // a wait; what may still be in flight on the context's stream -- the window's searches, the local map, a presort -- reads none of them), and the next
         // reader on the context's stream waits for the event below.  Behind the searches on the context's stream instead (GLIO_UNSTAGE_IN_STREAM=1) the two
         // installs sat between the searches and the solve: 2 x (4 us + a 10 us cross-stream hand-over) of every keyframe call.
-        if (ex->unstage_up) {
-            if (e == hipSuccess) {
-                hipLaunchKernelGGL(k_unstage, dim3(n, UNSTAGE_GY), dim3(256), 0, ex->up_stream, reinterpret_cast<const StageSegDev*>(a.d));
-                e = hipEventRecord(a.ev_free, ex->up_stream);
-                a.pending = true;
-            }
-            if (e == hipSuccess) e = hipEventRecord(ex->ev_up, ex->up_stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ex->ev_up, 0);
-        } else {
+        auto unstage_on = [&](hipStream_t s) {
+            if (e != hipSuccess) return;
+            hipLaunchKernelGGL(k_unstage, dim3(n, UNSTAGE_GY), dim3(256), 0, s, reinterpret_cast<const StageSegDev*>(a.d));
+            e = hipEventRecord(a.ev_free, s);
+            a.pending = true;
+        };
+        if (ex->unstage_up) unstage_on(ex->up_stream);
         if (e == hipSuccess) e = hipEventRecord(ex->ev_up, ex->up_stream);
         if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, ex->ev_up, 0);
-        if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_unstage, dim3(n, UNSTAGE_GY), dim3(256), 0, c->stream, reinterpret_cast<const StageSegDev*>(a.d));
-            e = hipEventRecord(a.ev_free, c->stream);
-            a.pending = true;
-        }
-        }
+        if (!ex->unstage_up) unstage_on(c->stream);
         // the pinned block is this arena's until its next turn (stage_begin_early waits for the copy then): the call does not wait for the copy
         // (it did, with hipStreamSynchronize on the upload stream: 10-40 us of host time per call while a search kernel fills the chip; GLIO_EARLY_UPLOAD_WAIT=1)
         if (e == hipSuccess) {
             if (ex->up_wait) e = hipStreamSynchronize(ex->up_stream);
             else { e = hipEventRecord(a.ev_copied, ex->up_stream); a.copying = true; }
         }
-        stage_end_early(c);
         if (e != hipSuccess) { glio_set_error("early upload: %s", hipGetErrorString(e)); return GLIO_E_HIP; }
         return GLIO_OK;
     }
-    GLIO_HIP_CHECK(hipMemcpyAsync(c->d_stage, c->h_stage, c->h_stage_used, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_unstage, dim3(n, UNSTAGE_GY), dim3(256), 0, c->stream, reinterpret_cast<const StageSegDev*>(c->d_stage));
-    c->n_stage_seg = 0;
+    GLIO_HIP_CHECK(hipMemcpyAsync(b->d, b->h, b->used, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_unstage, dim3(n, UNSTAGE_GY), dim3(256), 0, c->stream, reinterpret_cast<const StageSegDev*>(b->d));
     return GLIO_OK;
 }
-#define STAGE(dst, src, bytes) do { const int rc_ = stage_upload(c, (dst), (src), (bytes)); if (rc_ != GLIO_OK) { stage_end_early(c); return rc_; } } while (0)
+#define STAGE(dst, src, bytes) do { const int rc_ = stage_upload(c, &sb, (dst), (src), (bytes)); if (rc_ != GLIO_OK) return rc_; } while (0)
 
+// the tail of an IMU install: the host's picture of the edges now in d_imu
+static void imu_installed(glio_ctx* c, int n_edges, const int32_t* slot_i) {
+    c->n_imu = n_edges;
+    extra_of(c)->imu_edge0 = -1;
+    for (int k = 0; k < n_edges; ++k) { c->h_imu_slot[k] = slot_i[k]; if (slot_i[k] == 0) extra_of(c)->imu_edge0 = k; }
+    factor_tables_changed(c);
+    if (n_edges) c->have_factors = 1;
+}
 int glio_set_imu(glio_ctx* c, int n_edges, const glio_preint* edges, const int32_t* slot_i) {
     if (!c || n_edges < 0 || n_edges > c->W - 1 + (c->W == 1)) { glio_set_error("bad IMU edge count"); return GLIO_E_ARG; }
     { const int rp = marg_pending_done(c); if (rp) return rp; }
     GLIO_HIP_CHECK(hipSetDevice(c->device));
+    CtxExtra* ex = extra_of(c);
     std::vector<ImuEdgeDev> h(std::max(1, n_edges));
     for (int k = 0; k < n_edges; ++k) {
         if (slot_i[k] < 0 || slot_i[k] + 1 >= c->W) { glio_set_error("IMU edge slot out of range"); return GLIO_E_ARG; }
-        CtxExtra* ex = extra_of(c);
         int hit = -1;
         for (int j = k; j <= k + 1 && hit < 0; ++j)
             if (j < (int)ex->imu_raw.size() && memcmp(&ex->imu_raw[j], &edges[k], sizeof(glio_preint)) == 0) hit = j;
         if (hit >= 0) { h[k] = ex->imu_dig[hit]; h[k].slot_i = slot_i[k]; }
         else if (!digest_edge(&edges[k], slot_i[k], &h[k])) { glio_set_error("IMU covariance not invertible / not SPD"); return GLIO_E_NUMERIC; }
     }
-    { CtxExtra* ex = extra_of(c); ex->imu_raw.assign(edges, edges + n_edges); ex->imu_dig.assign(h.begin(), h.begin() + n_edges); }
     if (n_edges) {
-        const bool early = stage_early_enabled(extra_of(c));
-        { const int rc = early ? stage_begin_early(c, n_edges * sizeof(ImuEdgeDev) + 64) : stage_reserve(c, n_edges * sizeof(ImuEdgeDev) + 64); if (rc != GLIO_OK) return rc; }
+        StageBatch sb;
+        { const int rc = stage_begin(c, n_edges * sizeof(ImuEdgeDev) + 64, &sb); if (rc != GLIO_OK) return rc; }
         STAGE(c->d_imu, h.data(), n_edges * sizeof(ImuEdgeDev));
-        { const int rf = stage_flush(c); if (rf != GLIO_OK) return rf; }
-        if (!early) GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
+        { const int rf = stage_flush(c, &sb); if (rf != GLIO_OK) return rf; }
+        if (sb.early < 0) GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
     }
-    c->n_imu = n_edges;
-    for (int k = 0; k < n_edges; ++k) c->h_imu_slot[k] = slot_i[k];
-    c->chain_tabs_dirty = 1; c->h_band_clean = 0;
-    extra_of(c)->imu_edge0 = -1;
-    for (int k = 0; k < n_edges; ++k) if (slot_i[k] == 0) extra_of(c)->imu_edge0 = k;
-    if (n_edges) c->have_factors = 1;
+    ex->imu_raw.assign(edges, edges + n_edges); ex->imu_dig.assign(h.begin(), h.begin() + n_edges);
+    imu_installed(c, n_edges, slot_i);
     return GLIO_OK;
 }
 
@@ -831,13 +743,8 @@ int glio_set_imu_from_store(glio_ctx* c, glio_imu* st, int n_edges, const int32_
     GLIO_HIP_CHECK(hipSetDevice(c->device));
     CtxExtra* ex = extra_of(c);
     if (n_edges) {
-        if (stage_early_enabled(ex)) {
-            if (!ex->up_stream) {          // as stage_begin_early makes it
-                int least = 0, greatest = 0;
-                if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) GLIO_HIP_CHECK(hipStreamCreateWithPriority(&ex->up_stream, hipStreamNonBlocking, greatest));
-                else GLIO_HIP_CHECK(hipStreamCreateWithFlags(&ex->up_stream, hipStreamNonBlocking));
-                GLIO_HIP_CHECK(hipEventCreateWithFlags(&ex->ev_up, hipEventDisableTiming));
-            }
+        if (ex->up_mode == 1) {
+            { const int rs = up_stream_make(ex); if (rs != GLIO_OK) return rs; }
             GLIO_HIP_CHECK(hipStreamWaitEvent(ex->up_stream, st->ev_done, 0));
             glio_imu_launch_gather_list(ex->up_stream, st, n_edges, edge, slot_i, c->d_imu);
             GLIO_HIP_CHECK(hipEventRecord(ex->ev_up, ex->up_stream));
@@ -848,12 +755,7 @@ int glio_set_imu_from_store(glio_ctx* c, glio_imu* st, int n_edges, const int32_
         }
     }
     ex->imu_raw.clear(); ex->imu_dig.clear();          // glio_set_imu's cache of digested edges describes another table now
-    c->n_imu = n_edges;
-    for (int k = 0; k < n_edges; ++k) c->h_imu_slot[k] = slot_i[k];
-    c->chain_tabs_dirty = 1; c->h_band_clean = 0;
-    ex->imu_edge0 = -1;
-    for (int k = 0; k < n_edges; ++k) if (slot_i[k] == 0) ex->imu_edge0 = k;
-    if (n_edges) c->have_factors = 1;
+    imu_installed(c, n_edges, slot_i);
     return GLIO_OK;
 }
 
@@ -862,52 +764,17 @@ int glio_set_prior(glio_ctx* c, const glio_prior* p) {
     if (!c) return GLIO_E_ARG;
     { const int rp = marg_pending_done(c); if (rp) return rp; }
     GLIO_HIP_CHECK(hipSetDevice(c->device));
-    if (!p || p->n <= 0) {
-        c->prior_n = 0; c->prior_nb = 0; c->arrow.prior_ok = 1; c->arrow.prior_chain = 1; c->prior_ext_coupled = 0;
-        for (int k = 0; k < 15 * c->W; ++k) c->h_prior_index[k] = -1;
-        c->chain_tabs_dirty = 1; c->h_band_clean = 0;
-        return GLIO_OK;
-    }
+    if (!p || p->n <= 0) { prior_clear(c); return GLIO_OK; }
     const int np = p->n, nb = p->n_blocks, W = c->W;
     if (nb <= 0 || !p->lin_jac || !p->lin_res || !p->blk_slot || !p->blk_kind || !p->blk_idx || !p->blk_x0) { glio_set_error("prior: null table"); return GLIO_E_ARG; }
     if (np > glio_prior_np_limit(W) || nb > glio_prior_nb_limit(W)) {
         glio_set_error("prior too large for window: n = %d in %d blocks, a window of %d takes n <= %d in <= %d blocks", np, nb, W, glio_prior_np_limit(W), glio_prior_nb_limit(W));
         return GLIO_E_ARG;
     }
-    std::vector<int> index(15 * W, -1), colblk(np, -1);
-    for (int b = 0; b < nb; ++b) {
-        const int s = p->blk_slot[b], k = p->blk_kind[b], idx = p->blk_idx[b];
-        if (k != GLIO_BLK_TRANS && k != GLIO_BLK_QUAT && k != GLIO_BLK_SPEEDBIAS) { glio_set_error("prior block %d: unknown kind %d", b, k); return GLIO_E_ARG; }
-        const int ls = k == GLIO_BLK_SPEEDBIAS ? 9 : 3;
-        if (s < 0 || s >= W || idx < 0 || idx + ls > np) { glio_set_error("prior block out of range"); return GLIO_E_ARG; }
-        const int off = 15 * s + (k == GLIO_BLK_TRANS ? 0 : (k == GLIO_BLK_QUAT ? 3 : 6));
-        for (int j = 0; j < ls; ++j) {
-            if (index[off + j] >= 0) { glio_set_error("prior: two blocks for slot %d kind %d", s, k); return GLIO_E_ARG; }
-            if (colblk[idx + j] >= 0) { glio_set_error("prior: blocks %d and %d overlap at column %d", colblk[idx + j], b, idx + j); return GLIO_E_ARG; }
-            index[off + j] = idx + j; colblk[idx + j] = b;
-        }
-    }
-    for (int j = 0; j < np; ++j) if (colblk[j] < 0) { glio_set_error("prior column %d not covered by a block", j); return GLIO_E_ARG; }
-    { int nsb = 0; for (int b = 0; b < nb; ++b) nsb += p->blk_kind[b] == GLIO_BLK_SPEEDBIAS; c->arrow.prior_ok = nsb <= 1; }   // two speed-bias blocks would couple the chain densely
-    {   // Is J0^T J0 block diagonal by keyframe?  The reference's own marginalization always produces that (its LiDAR factors
-        // constrain every pose absolutely, quirk Q7, so eliminating the oldest keyframe never couples two kept ones); then
-        // the whole window is a keyframe chain and the solver needs no dense pose block.
-        std::vector<double> cn(np, 0.0);
-        for (int i = 0; i < np; ++i) for (int j = 0; j < np; ++j) cn[j] += p->lin_jac[(size_t)i * np + j] * p->lin_jac[(size_t)i * np + j];
-        bool chain = true;
-        for (int a = 0; a < np && chain; ++a)
-            for (int b2 = a + 1; b2 < np; ++b2) {
-                if (p->blk_slot[colblk[a]] == p->blk_slot[colblk[b2]]) continue;
-                double sab = 0;
-                for (int i = 0; i < np; ++i) sab += p->lin_jac[(size_t)i * np + a] * p->lin_jac[(size_t)i * np + b2];
-                if (fabs(sab) > 1e-13 * sqrt(cn[a] * cn[b2])) { chain = false; break; }
-            }
-        c->arrow.prior_chain = chain ? 1 : 0;
-        c->prior_device_made = 0;
-        c->prior_ext_coupled = 0;
-        for (int b = 0; b < nb; ++b) if (p->blk_kind[b] == GLIO_BLK_SPEEDBIAS && p->blk_slot[b] >= 2) c->prior_ext_coupled = 1;
-    }
-    GnssDevExtra* ex = glio_extra(c);
+    std::vector<int> index(15 * W), colblk(np);
+    { TabError e; if (prior_index_tables(W, np, nb, p->blk_slot, p->blk_kind, p->blk_idx, index.data(), colblk.data(), &e)) return refused(e); }
+    const PriorFlags flags = prior_flags(nb, p->blk_slot, p->blk_kind);
+    const bool chain = prior_is_chain(np, p->lin_jac, p->blk_slot, colblk.data());
     GLIO_HIP_CHECK(hipMemcpy(c->d_prior_J0, p->lin_jac, (size_t)np * np * 8, hipMemcpyHostToDevice));
     GLIO_HIP_CHECK(hipMemcpy(c->d_prior_r0, p->lin_res, np * 8, hipMemcpyHostToDevice));
     GLIO_HIP_CHECK(hipMemcpy(c->d_prior_x0, p->blk_x0, (size_t)nb * 9 * 8, hipMemcpyHostToDevice));
@@ -915,10 +782,11 @@ int glio_set_prior(glio_ctx* c, const glio_prior* p) {
     GLIO_HIP_CHECK(hipMemcpy(c->d_prior_kind, p->blk_kind, nb * 4, hipMemcpyHostToDevice));
     GLIO_HIP_CHECK(hipMemcpy(c->d_prior_idx, p->blk_idx, nb * 4, hipMemcpyHostToDevice));
     GLIO_HIP_CHECK(hipMemcpy(c->d_prior_index, index.data(), 15 * W * 4, hipMemcpyHostToDevice));
-    GLIO_HIP_CHECK(hipMemcpy(ex->d_prior_colblk, colblk.data(), np * 4, hipMemcpyHostToDevice));
-    c->prior_n = np; c->prior_nb = nb;
+    GLIO_HIP_CHECK(hipMemcpy(glio_extra(c)->d_prior_colblk, colblk.data(), np * 4, hipMemcpyHostToDevice));
+    c->arrow.prior_ok = flags.prior_ok; c->arrow.prior_chain = chain ? 1 : 0;
+    c->prior_device_made = 0; c->prior_ext_coupled = flags.ext_coupled; c->prior_n = np; c->prior_nb = nb;
     for (int k = 0; k < 15 * W; ++k) c->h_prior_index[k] = index[k];
-    c->chain_tabs_dirty = 1; c->h_band_clean = 0;
+    factor_tables_changed(c);
     glio_launch_gram(c, np);
     GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
     c->have_factors = 1;
@@ -930,13 +798,11 @@ int glio_set_prior(glio_ctx* c, const glio_prior* p) {
 // 0 .. W-2 (Estimator.cpp:2164-2176).  Each is evaluated by the workgroup of the IMU edge that leaves its slot (imu_block) and lands in that edge's block:
 // the keyframe's own diagonal, gradient and cost -- the structure of the problem, and with it the solver's path, stays what it is without them.
 static int marg_layout_fits(glio_ctx* c, int sbp_n) {
-    const int keep = c->sbp_n;
-    c->sbp_n = sbp_n;
-    const int ne = glio_marg_layout(c, nullptr), n = 6 * (c->W - 1) + 9 + 9 * ne, nb = 2 * (c->W - 1) + 1 + ne;
-    c->sbp_n = keep;
-    if (n <= glio_prior_np_limit(c->W) && nb <= glio_prior_nb_limit(c->W)) return 1;
+    const int ne = glio_marg_layout(c->W, sbp_n, c->prior_n, c->h_prior_index, nullptr);
+    const KeptSize k = marg_kept_size(c->W, ne);
+    if (k.n <= glio_prior_np_limit(c->W) && k.nb <= glio_prior_nb_limit(c->W)) return 1;
     glio_set_error("the marginalization of this window would keep n = %d columns in %d blocks (%d speed-bias blocks beyond slot 1): a window of %d holds n <= %d "
-                   "in <= %d blocks (PRIOR_MAX_NP = %d bounds the prior's LDS; windows of up to 27 keyframes hold every such layout)", n, nb, ne, c->W,
+                   "in <= %d blocks (PRIOR_MAX_NP = %d bounds the prior's LDS; windows of up to 27 keyframes hold every such layout)", k.n, k.nb, ne, c->W,
                    glio_prior_np_limit(c->W), glio_prior_nb_limit(c->W), PRIOR_MAX_NP);
     return 0;
 }
@@ -968,174 +834,52 @@ int glio_marginalize_size(glio_ctx* c, int32_t* out_n, int32_t* out_n_blocks) {
     if (!c) return GLIO_E_ARG;
     if (c->W < 2) { glio_set_error("marginalization needs a window of at least 2 keyframes"); return GLIO_E_ARG; }
     { const int rp = marg_pending_done(c); if (rp) return rp; }
-    const int ne = glio_marg_layout(c, nullptr);
-    if (out_n) *out_n = 6 * (c->W - 1) + 9 + 9 * ne;
-    if (out_n_blocks) *out_n_blocks = 2 * (c->W - 1) + 1 + ne;
+    const KeptSize k = marg_kept_size(c->W, glio_marg_layout(c, nullptr));
+    if (out_n) *out_n = k.n;
+    if (out_n_blocks) *out_n_blocks = k.nb;
     return GLIO_OK;
-}
-// the block tables of the next prior (GetParameterBlocks with addr_shift slot s -> s-1, Estimator.cpp:2584-2600) in the layout of glio_marg_layout
-static void marg_block_tables(const glio_ctx* c, const glio_state* s, int32_t* blk_slot, int32_t* blk_kind, int32_t* blk_idx, double* blk_x0, int* n_out, int* nb_out) {
-    const int W = c->W, ns = 6 * (W - 1) + 9;
-    short extra[GLIO_MAX_WINDOW];
-    const int ne = glio_marg_layout(c, extra);
-    int nb = 0;
-    for (int k = 1; k < W; ++k) {
-        const int kinds = k == 1 ? 3 : 2;
-        for (int kind = 0; kind < kinds; ++kind) {
-            blk_slot[nb] = k - 1; blk_kind[nb] = kind;
-            blk_idx[nb] = k == 1 ? (kind == 0 ? 0 : (kind == 1 ? 3 : 6)) : 15 + 6 * (k - 2) + 3 * kind;
-            const double* src = kind == 0 ? s->trans + 3 * k : (kind == 1 ? s->quat + 4 * k : s->speed_bias + 9 * k);
-            const int gs = kind == 0 ? 3 : (kind == 1 ? 4 : 9);
-            for (int j = 0; j < 9; ++j) blk_x0[9 * nb + j] = j < gs ? src[j] : 0.0;
-            ++nb;
-        }
-    }
-    for (int j = 0; j < ne; ++j, ++nb) {
-        blk_slot[nb] = extra[j] - 1; blk_kind[nb] = GLIO_BLK_SPEEDBIAS; blk_idx[nb] = ns + 9 * j;
-        for (int q = 0; q < 9; ++q) blk_x0[9 * nb + q] = s->speed_bias[9 * extra[j] + q];
-    }
-    *n_out = ns + 9 * ne; *nb_out = nb;
 }
 
 // ---------------------------------------------------------------------------------------------- GNSS
-static void ecef2rotation_host(const double xyz[3], double R[9]) {   // gnss_utility.cpp:347-390,738-748
-    const double e2 = 6.69437999014e-3, a = 6378137.0, R2D = 180.0 / M_PI, D2R = M_PI / 180.0;
-    const double a2 = a * a, b2 = a2 * (1 - e2), b = sqrt(b2), ep2 = (a2 - b2) / b2;
-    const double p = sqrt(xyz[0] * xyz[0] + xyz[1] * xyz[1]);
-    double s1 = xyz[2] * a, s2 = p * b, h = sqrt(s1 * s1 + s2 * s2);
-    const double st = s1 / h, ct = s2 / h;
-    s1 = xyz[2] + ep2 * b * pow(st, 3);
-    s2 = p - a * e2 * pow(ct, 3);
-    const double lat = (atan(s1 / s2) * R2D) * D2R, lon = (atan2(xyz[1], xyz[0]) * R2D) * D2R;
-    const double sl = sin(lat), cl = cos(lat), so = sin(lon), co = cos(lon);
-    R[0] = -so; R[1] = -sl * co; R[2] = cl * co;
-    R[3] = co;  R[4] = -sl * so; R[5] = cl * so;
-    R[6] = 0;   R[7] = cl;       R[8] = sl;
-}
-
 int glio_set_gnss(glio_ctx* c, const glio_gnss_frame* frame, int n_dd, const glio_dd_psr* dd, int n_dop, const glio_doppler* dop) {
     if (!c || n_dd < 0 || n_dop < 0) return GLIO_E_ARG;
     GLIO_HIP_CHECK(hipSetDevice(c->device));
     { const int rp = marg_pending_done(c); if (rp) return rp; }
-    const int W = c->W;
-    if (frame) {
-        c->frame = *frame;
-        double Ree[9];
-        ecef2rotation_host(frame->anc_ecef, Ree);
-        const double s = sin(frame->yaw_enu_local), co = cos(frame->yaw_enu_local);
-        const double Rel[9] = {co, -s, 0, s, co, 0, 0, 0, 1};
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
-            double a = 0;
-            for (int k = 0; k < 3; ++k) a += Ree[i * 3 + k] * Rel[k * 3 + j];
-            c->R_ecef_local[i * 3 + j] = a;
-        }
-    } else if (n_dd + n_dop > 0) { glio_set_error("GNSS factors need a frame"); return GLIO_E_ARG; }
-    // sort by (slot_i, slot_j), Doppler additionally by epoch; group = one slot pair.  A caller that builds the factors keyframe pair by
-    // keyframe pair (the reference's loop order, Estimator.cpp:2255-2421) hands them over sorted already: then nothing is copied or
-    // moved on the host, the arrays are staged for upload as they are (0.17 -> 0.06 ms per keyframe at 152 + 1520 factors)
-    struct Span { const glio_dd_psr* p; size_t n; const glio_dd_psr* begin() const { return p; } const glio_dd_psr* end() const { return p + n; }
-                  size_t size() const { return n; } const glio_dd_psr& operator[](size_t k) const { return p[k]; } const glio_dd_psr* data() const { return p; } };
-    struct SpanD { const glio_doppler* p; size_t n; const glio_doppler* begin() const { return p; } const glio_doppler* end() const { return p + n; }
-                   size_t size() const { return n; } const glio_doppler& operator[](size_t k) const { return p[k]; } const glio_doppler* data() const { return p; } };
-    std::vector<glio_dd_psr> dd_copy;
-    std::vector<glio_doppler> dop_copy;
-    Span sdd{dd, (size_t)n_dd};
-    SpanD sdop{dop, (size_t)n_dop};
-    for (auto& f : sdd) if (f.slot_i < 0 || f.slot_i >= W || f.slot_j < 0 || f.slot_j >= W || f.slot_i == f.slot_j || f.n_sat < 2 || f.n_sat > GLIO_DD_MAX_SAT || f.master < 0 || f.master >= f.n_sat) { glio_set_error("bad DD factor"); return GLIO_E_ARG; }
-    for (auto& f : sdop) if (f.slot_i < 0 || f.slot_i >= W || f.slot_j < 0 || f.slot_j >= W || f.slot_i == f.slot_j || f.epoch < 0 || f.epoch >= c->n_ddt_max) { glio_set_error("bad Doppler factor (epoch %d, max_ddt_epochs %d)", f.epoch, c->n_ddt_max); return GLIO_E_ARG; }
-    auto key = [W](int i, int j) { return i * W + j; };
-    auto dd_less = [&](const glio_dd_psr& a, const glio_dd_psr& b) { return key(a.slot_i, a.slot_j) < key(b.slot_i, b.slot_j); };
-    auto dop_less = [&](const glio_doppler& a, const glio_doppler& b) {
-        const int ka = key(a.slot_i, a.slot_j), kb = key(b.slot_i, b.slot_j);
-        return ka != kb ? ka < kb : a.epoch < b.epoch; };
-    if (!std::is_sorted(sdd.begin(), sdd.end(), dd_less)) {
-        dd_copy.assign(dd, dd + n_dd);
-        std::stable_sort(dd_copy.begin(), dd_copy.end(), dd_less);
-        sdd.p = dd_copy.data();
-    }
-    if (!std::is_sorted(sdop.begin(), sdop.end(), dop_less)) {
-        dop_copy.assign(dop, dop + n_dop);
-        std::stable_sort(dop_copy.begin(), dop_copy.end(), dop_less);
-        sdop.p = dop_copy.data();
-    }
-    std::vector<GnssGroup> groups;
-    std::vector<DopRun> runs;
-    size_t a = 0, b = 0;
-    while (a < sdd.size() || b < sdop.size()) {
-        int k = 1 << 30;
-        if (a < sdd.size()) k = std::min(k, key(sdd[a].slot_i, sdd[a].slot_j));
-        if (b < sdop.size()) k = std::min(k, key(sdop[b].slot_i, sdop[b].slot_j));
-        GnssGroup g;
-        g.slot_i = k / W; g.slot_j = k % W;
-        g.dd_begin = (int)a;
-        while (a < sdd.size() && key(sdd[a].slot_i, sdd[a].slot_j) == k) ++a;
-        g.dd_end = (int)a;
-        g.dop_begin = (int)b;
-        g.run_begin = (int)runs.size();
-        while (b < sdop.size() && key(sdop[b].slot_i, sdop[b].slot_j) == k) {
-            DopRun r;
-            r.begin = (int)b; r.epoch = sdop[b].epoch; r.group = (int)groups.size();
-            while (b < sdop.size() && key(sdop[b].slot_i, sdop[b].slot_j) == k && sdop[b].epoch == r.epoch) ++b;
-            r.end = (int)b;
-            runs.push_back(r);
-        }
-        g.dop_end = (int)b;
-        g.run_end = (int)runs.size();
-        groups.push_back(g);
-    }
-    // an epoch must belong to exactly one group (one clock-drift unknown per epoch, one bracketing pair)
-    { std::vector<int> seen(std::max(1, c->n_ddt_max), 0); for (auto& r : runs) if (seen[r.epoch]++) { glio_set_error("epoch %d appears under two keyframe pairs", r.epoch); return GLIO_E_ARG; } }
-    if ((int)groups.size() > W * W) return GLIO_E_ARG;
-    if (sdd.size() > c->dd_cap || !c->d_dd) {
+    const int W = c->W, ne = std::max(1, c->n_ddt_max);
+    if (!frame && n_dd + n_dop > 0) { glio_set_error("GNSS factors need a frame"); return GLIO_E_ARG; }
+    GnssTables t;
+    { TabError e; if (gnss_build_tables(W, c->n_ddt_max, n_dd, dd, n_dop, dop, &t, &e)) return refused(e); }
+    auto grow = [c](auto*& d, size_t& cap, size_t n) -> int {          // the grow-only device arrays of the factors
+        if (n <= cap && d) return GLIO_OK;
         GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (c->d_dd) { hipFree(c->d_dd); c->d_dd = nullptr; }
-        c->dd_cap = sdd.size() + sdd.size() / 2 + 16;
-        ALLOC(c->d_dd, c->dd_cap * sizeof(glio_dd_psr));
-    }
-    if (sdop.size() > c->dop_cap || !c->d_dop) {
-        GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (c->d_dop) { hipFree(c->d_dop); c->d_dop = nullptr; }
-        c->dop_cap = sdop.size() + sdop.size() / 2 + 16;
-        ALLOC(c->d_dop, c->dop_cap * sizeof(glio_doppler));
-    }
-    // structure tables of the arrow solver: which keyframe slots each clock-drift epoch couples
-    const int ne = std::max(1, c->n_ddt_max);
-    std::vector<int2> es(ne, make_int2(-1, -1));
-    std::vector<std::vector<int>> per(W);
-    c->arrow.gnss_ok = 1; c->arrow.max_epoch = -1; c->arrow.gnss_chain = 1;
-    for (auto& g : groups) if (g.slot_j - g.slot_i != 1) c->arrow.gnss_chain = 0;       // a pair that skips a keyframe (or is listed upper keyframe first) breaks the chain
-    for (size_t k = 0; k < groups.size(); ++k) c->h_groups[k] = groups[k];
-    c->chain_tabs_dirty = 1; c->h_band_clean = 0;
-    for (auto& r : runs) {
-        c->arrow.max_epoch = std::max(c->arrow.max_epoch, r.epoch);
-        const GnssGroup& g = groups[r.group];
-        const int lo = std::min(g.slot_i, g.slot_j), hi = std::max(g.slot_i, g.slot_j);
-        es[r.epoch] = make_int2(lo, hi);
-        per[lo].push_back(r.epoch); per[hi].push_back(r.epoch);
-        if (hi - lo != 1) c->arrow.gnss_ok = 0;       // velocity coupling between non-adjacent keyframes: chain is not tridiagonal
-    }
-    std::vector<int> off(W + 1, 0), list;
-    for (int i = 0; i < W; ++i) { off[i + 1] = off[i] + (int)per[i].size(); list.insert(list.end(), per[i].begin(), per[i].end()); }
+        if (d) { hipFree(d); d = nullptr; }
+        cap = n + n / 2 + 16;
+        ALLOC(d, cap * sizeof *d);
+        return GLIO_OK;
+    };
+    { int rg = grow(c->d_dd, c->dd_cap, t.n_dd); if (rg == GLIO_OK) rg = grow(c->d_dop, c->dop_cap, t.n_dop); if (rg != GLIO_OK) return rg; }
     GnssDevExtra* ex = glio_extra(c);
-    const bool early = stage_early_enabled(extra_of(c));
-    {
-        const size_t total = sdd.size() * sizeof(glio_dd_psr) + sdop.size() * sizeof(glio_doppler) + groups.size() * sizeof(GnssGroup) +
-                             (size_t)ne * sizeof(int2) + (W + 1) * 4 + list.size() * 4 + runs.size() * sizeof(DopRun) + 8 * 64;
-        const int rc = early ? stage_begin_early(c, total) : stage_reserve(c, total);
-        if (rc != GLIO_OK) return rc;
-    }
-    STAGE(c->d_dd, sdd.data(), sdd.size() * sizeof(glio_dd_psr));
-    STAGE(c->d_dop, sdop.data(), sdop.size() * sizeof(glio_doppler));
-    STAGE(c->d_groups, groups.data(), groups.size() * sizeof(GnssGroup));
-    STAGE(c->arrow.d_ep_slots, es.data(), (size_t)ne * sizeof(int2));
-    STAGE(c->arrow.d_ep_off, off.data(), (size_t)(W + 1) * 4);
-    STAGE(c->arrow.d_ep_list, list.data(), list.size() * 4);
-    STAGE(ex->d_runs, runs.data(), runs.size() * sizeof(DopRun));
-    ex->n_runs = (int)runs.size();
-    { const int rf = stage_flush(c); if (rf != GLIO_OK) return rf; }
-    GLIO_HIP_CHECK(hipMemsetAsync(c->d_ddt_blocks, 0, 2 * (size_t)std::max(1, c->n_ddt_max) * sizeof(DdtBlock), c->stream));
-    if (!early) GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
-    c->n_dd = (int)sdd.size(); c->n_dop = (int)sdop.size(); c->n_groups = (int)groups.size();
+    StageBatch sb;
+    const size_t total = t.n_dd * sizeof(glio_dd_psr) + t.n_dop * sizeof(glio_doppler) + t.groups.size() * sizeof(GnssGroup) +
+                         (size_t)ne * sizeof(int2) + (W + 1) * 4 + t.list.size() * 4 + t.runs.size() * sizeof(DopRun) + 8 * 64;
+    { const int rc = stage_begin(c, total, &sb); if (rc != GLIO_OK) return rc; }
+    static_assert(sizeof(EpochSlots) == sizeof(int2) && alignof(EpochSlots) == alignof(int2), "d_ep_slots");
+    STAGE(c->d_dd, t.dd, t.n_dd * sizeof(glio_dd_psr));
+    STAGE(c->d_dop, t.dop, t.n_dop * sizeof(glio_doppler));
+    STAGE(c->d_groups, t.groups.data(), t.groups.size() * sizeof(GnssGroup));
+    STAGE(c->arrow.d_ep_slots, t.es.data(), (size_t)ne * sizeof(int2));
+    STAGE(c->arrow.d_ep_off, t.off.data(), (size_t)(W + 1) * 4);
+    STAGE(c->arrow.d_ep_list, t.list.data(), t.list.size() * 4);
+    STAGE(ex->d_runs, t.runs.data(), t.runs.size() * sizeof(DopRun));
+    { const int rf = stage_flush(c, &sb); if (rf != GLIO_OK) return rf; }
+    GLIO_HIP_CHECK(hipMemsetAsync(c->d_ddt_blocks, 0, 2 * (size_t)ne * sizeof(DdtBlock), c->stream));
+    if (sb.early < 0) GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (frame) { c->frame = *frame; ecef_local_rotation(frame->anc_ecef, frame->yaw_enu_local, c->R_ecef_local); }
+    c->arrow.gnss_ok = t.gnss_ok; c->arrow.max_epoch = t.max_epoch; c->arrow.gnss_chain = t.gnss_chain;
+    for (size_t k = 0; k < t.groups.size(); ++k) c->h_groups[k] = t.groups[k];
+    factor_tables_changed(c);
+    ex->n_runs = (int)t.runs.size();
+    c->n_dd = (int)t.n_dd; c->n_dop = (int)t.n_dop; c->n_groups = (int)t.groups.size();
     if (c->n_groups) c->have_factors = 1;
     return GLIO_OK;
 }
@@ -1419,6 +1163,20 @@ int glio_debug_covariance_of(glio_ctx* c, int n, const double* H, int m, const i
 }
 
 // ---------------------------------------------------------------------------------------------- marginalization
+// the state to the device and the marginalization's kernels behind it; *dJ, *dr, *dok: where they leave the root, the residual and the "positive definite" flag
+static int enqueue_marginalize(glio_ctx* c, const glio_state* s, double** dJ, double** dr, int** dok) {
+    const int n_ddt = s->n_ddt, nx = glio_x_size(c->W, n_ddt);
+    pack_state(c, s, c->h_xbuf);
+    GLIO_HIP_CHECK(hipMemcpyAsync(c->d_x[0], c->h_xbuf, (size_t)nx * 8, hipMemcpyHostToDevice, c->stream));
+    lds_poison(c);
+    glio_launch_lidar_linearize(c, 0, 0, 1); glio_launch_lidar_reduce(c, 0);
+    lds_poison(c);
+    glio_launch_small_factors(c, 0, 0, n_ddt, 1);
+    lds_poison(c);
+    glio_launch_marginalize(c, extra_of(c)->imu_edge0, dJ, dr, dok);
+    GLIO_HIP_CHECK(hipGetLastError());
+    return GLIO_OK;
+}
 int glio_marginalize(glio_ctx* c, const glio_state* s, double* lin_jac, double* lin_res, int32_t* blk_slot, int32_t* blk_kind,
                      int32_t* blk_idx, double* blk_x0, int32_t* out_n, int32_t* out_n_blocks) {
     GLIO_TRACE("glio_marginalize");
@@ -1428,31 +1186,21 @@ int glio_marginalize(glio_ctx* c, const glio_state* s, double* lin_jac, double* 
     rc = glio_assoc_finish_pending(c);
     if (rc) return rc;
     if (!lin_jac || !lin_res || !blk_slot || !blk_kind || !blk_idx || !blk_x0) { glio_set_error("null output"); return GLIO_E_ARG; }
-    const int W = c->W;
-    if (W < 2) { glio_set_error("marginalization needs a window of at least 2 keyframes"); return GLIO_E_ARG; }
+    if (c->W < 2) { glio_set_error("marginalization needs a window of at least 2 keyframes"); return GLIO_E_ARG; }
     GLIO_HIP_CHECK(hipSetDevice(c->device));
     if (!marg_layout_fits(c, c->sbp_n)) return GLIO_E_ARG;
-    int n = 0, nb = 0;
-    marg_block_tables(c, s, blk_slot, blk_kind, blk_idx, blk_x0, &n, &nb);
-    const int n_ddt = s->n_ddt, nx = glio_x_size(W, n_ddt);
-    pack_state(c, s, c->h_xbuf);
-    GLIO_HIP_CHECK(hipMemcpyAsync(c->d_x[0], c->h_xbuf, (size_t)nx * 8, hipMemcpyHostToDevice, c->stream));
-    lds_poison(c);
-    glio_launch_lidar_linearize(c, 0, 0, 1); glio_launch_lidar_reduce(c, 0);
-    lds_poison(c);
-    glio_launch_small_factors(c, 0, 0, n_ddt, 1);
-    lds_poison(c);
+    const KeptSize k = marg_block_tables(c->W, c->sbp_n, c->prior_n, c->h_prior_index, s, blk_slot, blk_kind, blk_idx, blk_x0);
     double *dJ, *dr; int* dok;
-    glio_launch_marginalize(c, extra_of(c)->imu_edge0, &dJ, &dr, &dok);
-    GLIO_HIP_CHECK(hipGetLastError());
+    rc = enqueue_marginalize(c, s, &dJ, &dr, &dok);
+    if (rc) return rc;
     int ok = 0;
-    GLIO_HIP_CHECK(hipMemcpyAsync(lin_jac, dJ, (size_t)n * n * 8, hipMemcpyDeviceToHost, c->stream));
-    GLIO_HIP_CHECK(hipMemcpyAsync(lin_res, dr, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
+    GLIO_HIP_CHECK(hipMemcpyAsync(lin_jac, dJ, (size_t)k.n * k.n * 8, hipMemcpyDeviceToHost, c->stream));
+    GLIO_HIP_CHECK(hipMemcpyAsync(lin_res, dr, (size_t)k.n * 8, hipMemcpyDeviceToHost, c->stream));
     GLIO_HIP_CHECK(hipMemcpyAsync(&ok, dok, 4, hipMemcpyDeviceToHost, c->stream));
     GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
     if (!ok) { glio_set_error("marginalization: Schur complement is not positive definite (rank-deficient kept block)"); return GLIO_E_NUMERIC; }
-    if (out_n) *out_n = n;
-    if (out_n_blocks) *out_n_blocks = nb;
+    if (out_n) *out_n = k.n;
+    if (out_n_blocks) *out_n_blocks = k.nb;
     return GLIO_OK;
 }
 
@@ -1484,47 +1232,39 @@ int glio_marginalize_keep_async(glio_ctx* c, const glio_state* s) {
     if (W < 2) { glio_set_error("marginalization needs a window of at least 2 keyframes"); return GLIO_E_ARG; }
     GLIO_HIP_CHECK(hipSetDevice(c->device));
     if (!marg_layout_fits(c, c->sbp_n)) return GLIO_E_ARG;
-    const int n_ddt = s->n_ddt, nx = glio_x_size(W, n_ddt), nbmax = glio_prior_nb_limit(W);
+    // the new prior's tables (slots already shifted s -> s-1, Estimator.cpp:2584-2600), held to the checks of a caller's prior
+    const int nbmax = glio_prior_nb_limit(W);
     std::vector<int> slot(nbmax), kind(nbmax), idx(nbmax);
     std::vector<double> x0((size_t)nbmax * 9, 0.0);
-    int n = 0, nb = 0;
-    marg_block_tables(c, s, slot.data(), kind.data(), idx.data(), x0.data(), &n, &nb);
-    const int n_extra = nb - (2 * (W - 1) + 1);
-    pack_state(c, s, c->h_xbuf);
-    GLIO_HIP_CHECK(hipMemcpyAsync(c->d_x[0], c->h_xbuf, (size_t)nx * 8, hipMemcpyHostToDevice, c->stream));
-    lds_poison(c);
-    glio_launch_lidar_linearize(c, 0, 0, 1); glio_launch_lidar_reduce(c, 0);
-    lds_poison(c);
-    glio_launch_small_factors(c, 0, 0, n_ddt, 1);
-    lds_poison(c);
+    const KeptSize k = marg_block_tables(W, c->sbp_n, c->prior_n, c->h_prior_index, s, slot.data(), kind.data(), idx.data(), x0.data());
+    const int n = k.n, nb = k.nb, n_extra = nb - marg_kept_size(W, 0).nb;
+    std::vector<int> index(15 * W), colblk(n);
+    { TabError e; if (prior_index_tables(W, n, nb, slot.data(), kind.data(), idx.data(), index.data(), colblk.data(), &e)) return refused(e); }
     double *dJ, *dr; int* dok;
-    glio_launch_marginalize(c, extra_of(c)->imu_edge0, &dJ, &dr, &dok);
-    GLIO_HIP_CHECK(hipGetLastError());
-    // the new prior's block tables (slots already shifted s -> s-1, Estimator.cpp:2584-2600).  Everything below is enqueued behind the
-    // marginalization kernels without waiting for them: the tables go through the pinned arena, the "positive definite" flag is
-    // read back last, ONE synchronisation ends the call (two synchronisations and eight pageable copies cost ~0.1 ms of the 0.33 ms)
-    std::vector<int> index(15 * W, -1), colblk(n, -1);
-    for (int b = 0; b < nb; ++b) {
-        const int kd = kind[b], ls = kd == GLIO_BLK_SPEEDBIAS ? 9 : 3;
-        const int off = 15 * slot[b] + (kd == GLIO_BLK_TRANS ? 0 : (kd == GLIO_BLK_QUAT ? 3 : 6));
-        for (int j = 0; j < ls; ++j) { index[off + j] = idx[b] + j; colblk[idx[b] + j] = b; }
-    }
+    rc = enqueue_marginalize(c, s, &dJ, &dr, &dok);
+    if (rc) return rc;
+    // Everything below is enqueued behind the marginalization kernels without waiting for them: the tables go through the pinned arena, the
+    // "positive definite" flag is read back last, ONE synchronisation ends the call (two synchronisations and eight pageable copies cost ~0.1 ms
+    // of the 0.33 ms)
     GnssDevExtra* ex = glio_extra(c);
-    { const int rs = stage_reserve(c, (size_t)nb * 9 * 8 + 3 * (size_t)nb * 4 + 15 * (size_t)W * 4 + (size_t)n * 4 + 8 * 64 + 64); if (rs != GLIO_OK) return rs; }
-    { int rd = stage_d2d(c, c->d_prior_J0, dJ, (size_t)n * n * 8); if (rd == GLIO_OK) rd = stage_d2d(c, c->d_prior_r0, dr, (size_t)n * 8); if (rd != GLIO_OK) return rd; }
+    StageBatch sb;
+    { const int rs = stage_reserve(c, (size_t)nb * 9 * 8 + 3 * (size_t)nb * 4 + 15 * (size_t)W * 4 + (size_t)n * 4 + 8 * 64 + 64, &sb); if (rs != GLIO_OK) return rs; }
+    { int rd = stage_d2d(&sb, c->d_prior_J0, dJ, (size_t)n * n * 8); if (rd == GLIO_OK) rd = stage_d2d(&sb, c->d_prior_r0, dr, (size_t)n * 8); if (rd != GLIO_OK) return rd; }
     STAGE(c->d_prior_x0, x0.data(), (size_t)nb * 9 * 8);
     STAGE(c->d_prior_slot, slot.data(), (size_t)nb * 4);
     STAGE(c->d_prior_kind, kind.data(), (size_t)nb * 4);
     STAGE(c->d_prior_idx, idx.data(), (size_t)nb * 4);
     STAGE(c->d_prior_index, index.data(), (size_t)15 * W * 4);
     STAGE(ex->d_prior_colblk, colblk.data(), (size_t)n * 4);
-    { const int rf = stage_flush(c); if (rf != GLIO_OK) return rf; }
+    { const int rf = stage_flush(c, &sb); if (rf != GLIO_OK) return rf; }
+    int* h_ok = reinterpret_cast<int*>(stage_result_word(&sb));      // (pinned: the 64 bytes reserved above, behind what the flush has sent)
+    if (!h_ok) { glio_set_error("upload arena overflow"); return GLIO_E_STATE; }
     // a Schur complement of block-diagonal pieces (LiDAR blocks, the IMU edge of the dropped keyframe, a block-diagonal old
     // prior) is block diagonal, and so is its Cholesky root: the chain property is inherited
     const int chain = c->prior_n > 0 ? c->arrow.prior_chain : 1;
     c->prior_n = n; c->prior_nb = nb;
-    for (int k = 0; k < 15 * W; ++k) c->h_prior_index[k] = index[k];
-    c->chain_tabs_dirty = 1; c->h_band_clean = 0;
+    for (int j = 0; j < 15 * W; ++j) c->h_prior_index[j] = index[j];
+    factor_tables_changed(c);
     // (several speed-bias blocks: block diagonal by keyframe like the rest, so the keyframe chain takes them as they are -- its slices and its prior index
     //  are per (keyframe, local column); the arrow factorisation, which keeps one speed-bias chain, does not)
     c->arrow.prior_ok = n_extra == 0; c->arrow.prior_chain = chain;
@@ -1532,20 +1272,16 @@ int glio_marginalize_keep_async(glio_ctx* c, const glio_state* s) {
     if (n_extra == 0) c->prior_ext_coupled = 0;
     c->sbp_n = 0;          // the reference's marg = true (Estimator.cpp:2517): the next window carries them in its prior
     glio_launch_gram(c, n);
-    int* h_ok = reinterpret_cast<int*>(c->h_stage + ((c->h_stage_used + 63) & ~(size_t)63));      // (pinned; reserved above)
     GLIO_HIP_CHECK(hipMemcpyAsync(h_ok, dok, 4, hipMemcpyDeviceToHost, c->stream));
     extra_of(c)->marg_h_ok = h_ok;                         // glio_marginalize_keep_finish (or the entry points that use the prior) waits and looks at it
     return GLIO_OK;
 }
 static int marginalize_keep_wait(glio_ctx* c) {
-    const int W = c->W;
     int* h_ok = extra_of(c)->marg_h_ok;
     extra_of(c)->marg_h_ok = nullptr;
     GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
     if (!*h_ok) {          // the installed tables describe a factor that does not exist: the context is left WITHOUT a prior
-        c->prior_n = 0; c->prior_nb = 0; c->arrow.prior_ok = 1; c->arrow.prior_chain = 1; c->prior_ext_coupled = 0;
-        for (int k = 0; k < 15 * W; ++k) c->h_prior_index[k] = -1;
-        c->chain_tabs_dirty = 1; c->h_band_clean = 0;
+        prior_clear(c);
         glio_set_error("marginalization: Schur complement is not positive definite (the context now has no prior)");
         return GLIO_E_NUMERIC;
     }
@@ -1553,18 +1289,8 @@ static int marginalize_keep_wait(glio_ctx* c) {
 }
 
 }  // extern "C"
-// R_ecef_local = R_ecef_enu(anchor) * Rz(yaw)  (dd_psr_factor.hpp:33-45) -- shared with eval_kernels.hip
-void glio_host_ecef_local(const double anc[3], double yaw, double R[9]) {
-    double Ree[9];
-    ecef2rotation_host(anc, Ree);
-    const double s = sin(yaw), co = cos(yaw);
-    const double Rel[9] = {co, -s, 0, s, co, 0, 0, 0, 1};
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) {
-        double a = 0;
-        for (int k = 0; k < 3; ++k) a += Ree[i * 3 + k] * Rel[k * 3 + j];
-        R[i * 3 + j] = a;
-    }
-}
+// R_ecef_local = R_ecef_enu(anchor) * Rz(yaw) -- for eval_kernels.hip and batch_tr_kernels.hip
+void glio_host_ecef_local(const double anc[3], double yaw, double R[9]) { ecef_local_rotation(anc, yaw, R); }
 extern "C" {
 // ---------------------------------------------------------------------------------------------- evaluators
 int glio_eval_lidar_plane(glio_ctx* c, const float cp[4], const float plane[4], double score,

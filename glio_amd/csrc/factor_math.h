@@ -61,7 +61,7 @@ __device__ __forceinline__ void fm_dd_whiten(const double* W, const int i, const
 // ------------------------------------------------------------------------------------------------
 // The frame the DD rows live in (include/glio_align.h): R_ecef_enu at an anchor, and the DD row with its derivatives wrt the frame
 // ------------------------------------------------------------------------------------------------
-// the device twin of capi.hip's ecef2rotation_host (gnss_utility.cpp:347-390, 738-748, closed form): the same expressions in the same order
+// the device twin of window_tables.h's ecef2rotation_host (gnss_utility.cpp:347-390, 738-748, closed form): the same expressions in the same order
 __device__ __forceinline__ void fm_ecef2rotation(const double xyz[3], double R[9]) {
 #pragma clang fp contract(off)
     const double PI = 3.14159265358979323846;

@@ -14,6 +14,7 @@
 // given -- and silently relies on the zero -- passes every single-process test; with several processes on one GPU the pages may come back
 // with another process's data (found in round 3: `contention_repro.py`).  With the poison such a read fails loudly and reproducibly.
 #include "glio_switches.h"
+#include "window_tables.h"      // ImuEdgeDev, GnssGroup, DopRun, the prior's limits, glio_marg_layout: host-only definitions
 static inline hipError_t glio_dbg_malloc(void** p, size_t bytes) {
     const int poison = glio_switch<GLIO_SW_DEBUG_POISON_ALLOC>();
     const hipError_t e = hipMalloc(p, bytes);
@@ -45,15 +46,6 @@ static inline hipError_t glio_memset_done(void* p, int value, size_t bytes) {
 #define GLIO_K3_BLOCKS_PER_KF 32       /* default; ctx->k3_bpk is the live value */
 #define GLIO_K3_MAX_BLOCKS_PER_KF 256
 
-// IMU edge, device form (pre-digested on upload: sqrt_info is LLT(cov^-1).L^T, ImuFactor.h:44-45)
-struct ImuEdgeDev {
-    double delta_p[3], delta_q[4], delta_v[3], lin_ba[3], lin_bg[3];
-    double sum_dt;
-    double dp_dba[9], dp_dbg[9], dq_dbg[9], dv_dba[9], dv_dbg[9];
-    double sqrt_info[225];
-    int slot_i;
-    int pad_;
-};
 // dense local block of one IMU edge / GNSS group over [slot_a(15) | slot_b(15)]
 #define GLIO_PAIR_DIM 30
 struct PairBlock {
@@ -62,15 +54,6 @@ struct PairBlock {
     double cost;
     int slot_a, slot_b;
 };
-// GNSS group = all DD / Doppler factors that share one (slot_i, slot_j) pair
-struct GnssGroup {
-    int slot_i, slot_j;
-    int dd_begin, dd_end;      // range in the sorted glio_dd_psr array
-    int dop_begin, dop_end;    // range in the sorted glio_doppler array (sorted by epoch inside)
-    int run_begin, run_end;    // range in the DopRun array
-};
-// Doppler rows of one epoch inside a group (contiguous in the sorted glio_doppler array)
-struct DopRun { int begin, end, epoch, group; };
 struct GnssDevExtra { DopRun* d_runs; int n_runs; int* d_prior_colblk; };
 // per-epoch Doppler coupling with the 12 pose variables (t_i v_i t_j v_j) of its group
 struct DdtBlock {
@@ -184,8 +167,8 @@ struct glio_ctx {
     glio_dd_psr* d_dd; int n_dd;
     glio_doppler* d_dop; int n_dop;
     size_t dd_cap, dop_cap;       // grow-only capacities (elements) of d_dd / d_dop
-    char* h_stage; size_t h_stage_cap, h_stage_used; char* d_stage; size_t h_stage_top; int n_stage_seg; struct { void* dst; const void* src; size_t bytes; } stage_seg[32];   // pinned upload arena of the factor tables: every table of a set_* call
-                                                       // goes through it with asynchronous copies and ONE synchronisation
+    char* h_stage; size_t h_stage_cap; char* d_stage;   // pinned upload arena of the factor tables (and its device mirror): every table of a set_* call
+                                                       // goes through it with asynchronous copies and ONE synchronisation (StageBatch, window_tables.h)
     GnssGroup* d_groups; int n_groups;
     PairBlock* d_gnss_blocks;     // [2][W*W] (n_groups used)
     DdtBlock* d_ddt_blocks;       // [2][n_ddt_max]
@@ -264,21 +247,7 @@ struct glio_ctx {
     double* d_marg_T;                         // [15 (W - 1)][15] T = Arm Amm^+ of the marginalization (the kept part has up to 15 (W - 1) columns)
 };
 
-// Limits of a prior: the LDS arrays of the prior's workgroups (factor_kernels.hip, PriorLds) are sized by them.  A standard prior has 6 W + 9 columns in
-// 2 W + 1 blocks; the layouts of the windows after a loop closure (speed-bias blocks of several keyframes) up to 15 (W - 1) in 3 (W - 1): W <= 27.
-#define PRIOR_MAX_NP (6 * GLIO_MAX_WINDOW + 9)
-#define PRIOR_MAX_NB (2 * GLIO_MAX_WINDOW + 1)
-static inline int glio_prior_np_limit(int W) { const int a = 6 * W + 9, b = 15 * (W - 1), m = a > b ? a : b; return m < PRIOR_MAX_NP ? m : PRIOR_MAX_NP; }
-static inline int glio_prior_nb_limit(int W) { const int a = 2 * W + 1, b = 3 * (W - 1), m = a > b ? a : b; return m < PRIOR_MAX_NB ? m : PRIOR_MAX_NB; }
-// Kept layout of the next marginalization: the poses of slots 1 .. W-1 and the speed/bias of slot 1 as ever ([T1 Q1 SB1 | T2 Q2 | ...], 6 (W - 1) + 9
-// columns), then the speed/bias of every slot s >= 2 that carries a speed-bias prior or has a speed-bias block in the installed prior, ascending, 9
-// columns each.  Returns their number; extra_slot[j] = s.
-static inline int glio_marg_layout(const glio_ctx* c, short* extra_slot) {
-    int ne = 0;
-    for (int s = 2; s < c->W; ++s)
-        if (s < c->sbp_n || (c->prior_n > 0 && c->h_prior_index[15 * s + 6] >= 0)) { if (extra_slot) extra_slot[ne] = (short)s; ++ne; }
-    return ne;
-}
+static inline int glio_marg_layout(const glio_ctx* c, short* extra_slot) { return glio_marg_layout(c->W, c->sbp_n, c->prior_n, c->h_prior_index, extra_slot); }
 
 static inline int glio_x_size(int W, int n_ddt) { return 16 * W + n_ddt; }
 static inline size_t glio_partials_stride(const glio_ctx* c) { return (size_t)c->W * GLIO_K3_MAX_BLOCKS_PER_KF * GLIO_LIDAR_ACC; }

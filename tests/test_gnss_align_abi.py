@@ -98,7 +98,8 @@ def test_the_formula_has_one_definition():
     assert "fm_align_row(" in k and "fm_dd_whiten(" in k and "fm_ecef2rotation(" in k
     assert "0.05" not in k and "atan2" not in k and "6378137" not in k
     cap = open(os.path.join(ROOT, "glio_amd", "csrc", "capi.hip")).read()
-    assert "static void ecef2rotation_host(" in cap                    # the host function stays
+    tab = open(os.path.join(ROOT, "glio_amd", "csrc", "window_tables.h")).read()
+    assert "static inline void ecef2rotation_host(" in tab and "ecef_local_rotation(" in cap          # the host function stays (capi.hip's host arithmetic: window_tables.h)
 
 
 def test_the_restatement_and_the_kernel_do_not_know_each_other():

@@ -188,3 +188,60 @@ def test_scan_sent_ahead_and_asynchronous_marginalization_change_nothing():
         if j % 2:
             b.marginalize_keep_finish()          # (else: the next solve finishes it by itself)
     a.close(); b.close()
+
+
+def refused_gnss_then_valid():
+    """[(state arrays and summary fields)] of a context whose first glio_set_gnss was refused, and of a fresh context given only the valid calls"""
+    import copy
+    import ctypes as C
+    from glio_amd import capi
+    from glio_amd import ctypes_types as T
+    win = synth.make_window(W=4, pts_per_scan=64, seed=synth.SEED_BASE + 32, with_gnss=True)
+    o = win.opts
+    o.max_ddt_epochs = win.init.n_ddt + 4
+    bad = copy.copy(win.dd[0])
+    bad.master = bad.n_sat                         # out of range: the whole call is refused
+    out = []
+    for refuse_first in (True, False):
+        c = capi.Context(o)
+        c.set_map(win.map_pts)
+        c.set_prior(None)
+        for s in range(win.W):
+            c.set_scan(s, win.scans[s])
+        poses = [capi.lidar_pose(o, win.init.quat[s], win.init.trans[s]) for s in range(win.W)]
+        c.associate_window_async(np.array([p[0] for p in poses]), np.array([p[1] for p in poses]))
+        if refuse_first:
+            frame, ndd, dd_arr, ndop, dop_arr = c.marshal_gnss(win.frame, [bad] + list(win.dd), win.dop)
+            assert capi.load().glio_set_gnss(c._h, C.byref(frame), ndd, dd_arr, ndop, dop_arr) == capi.E_ARG
+            assert capi.load().glio_last_error() == b"bad DD factor"
+        c.set_imu(win.preints); c.set_gnss(win.frame, win.dd, win.dop)
+        sol, summ = c.solve(win.init)
+        out.append([sol.trans.tobytes(), sol.quat.tobytes(), sol.speed_bias.tobytes(), np.asarray(sol.rcv_ddt).tobytes()] +
+                   [getattr(summ, name) for name, _ in T.GlioSummary._fields_])
+        c.close()
+    return out
+
+
+REFUSED_CHILD = """
+import os, sys
+sys.path[:0] = [sys.argv[1], os.path.join(sys.argv[1], "tests")]
+import test_hip_streaming as t
+a, b = t.refused_gnss_then_valid()
+assert a == b and a[4] > 0, (a[4:], b[4:])
+print("same")
+"""
+
+
+def test_refused_set_gnss_leaves_no_trace():
+    """A glio_set_gnss that fails validation (one DD factor whose master is out of range) returns GLIO_E_ARG; the valid glio_set_imu / glio_set_gnss and
+    the solve behind it on the same context give, bit for bit, the state and summary of a fresh context that saw only the valid calls -- with the early
+    uploads (default) and, in a child process, with GLIO_EARLY_UPLOAD=0."""
+    import os
+    import subprocess
+    import sys
+    a, b = refused_gnss_then_valid()
+    assert a == b, (a[4:], b[4:])
+    assert a[4] > 0          # iterations: the solve ran
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", REFUSED_CHILD, root], env=dict(os.environ, GLIO_EARLY_UPLOAD="0"), capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.strip().endswith("same"), out.stderr[-2000:]
