@@ -33,6 +33,14 @@
 //   k_pg_lin_nodes / k_pg_lin_loops at the candidate
 //   k_pg_lm_decide    one workgroup: the candidate's error and the model decrease in k_pg_error's fixed order, the gain, the radius, the history, the termination
 //   k_pg_lm_commit    the accepted candidate becomes x
+//
+// The covariance of every node (glio_pgraph_covariance_all, include/glio_pgraph_cov.h): one factorisation with the plan of a solve and no right-hand side, then
+// the Takahashi recurrence over that factor's own pattern:
+//   k_pg_segments<true>   the segment kernel's second instantiation: beside Y it keeps D~_i^-1 (six more lanes solve for the unit vectors), the segment's
+//                     smallest and largest squared pivot and the node of a failed one
+//   k_pg_sep_inverse  ONE workgroup, behind k_pg_sep_factor: Z = (L L^T)^-1 on L's pattern, columns n - 1 .. 0 over pg_rowset's row sets
+//   k_pg_cov_sweep    one wavefront per separator: its diagonal block of Z, then down the segment to its right from the blocks of Z at both ends:
+//                     Sigma_{i,N} = -Y' Sigma_{N,N}, Sigma_ii = D~_i^-1 - Sigma_{i,N} Y'^T with N(i) = {i + 1, the left separator}
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -40,11 +48,13 @@
 #include <vector>
 
 #include "glio_device.h"
+#include "../../include/glio_pgraph_cov.h"
 #include "tr_math.h"
 #include "tr_math_device.h"
 
 #define PG_MAX_LOOPS 1024
 #define PG_SEP_THREADS 1024
+#define PG_COV_LDS 512          /* k_pg_sep_inverse: the longest column (rows below the diagonal) it keeps in LDS */
 #define PG_AHEAD 12               /* iterations enqueued before the first wait of a solve */
 #define PG_YS 78                /* per interior node: D^-1 C (36), D^-1 E (36), D^-1 g (6) */
 #define PG_SEGS 120             /* per segment: S_LL (36), S_LR (36), S_RR (36), g_L (6), g_R (6) */
@@ -62,6 +72,9 @@ struct PgCtl {
     // k_pg_lm_commit copies into x
     double radius, decrease_factor;
     int accepted, rejected, invalid, lin_fresh, commit_trial, pad_;
+    // glio_pgraph_covariance_all (k_pg_sep_inverse): the squared diagonal of the factor, the node of the first pivot that failed
+    double min_pivot, max_pivot;
+    int bad_node, pad2_;
 };
 // glio_pgraph_lm_opts as the decision kernel takes it
 struct PgLm { double max_radius, min_radius, min_relative_decrease, min_diagonal, max_diagonal; int max_trials; };
@@ -222,6 +235,13 @@ struct PgPlan {
     double* ldiag;              // [n]
     double* delta;              // [N][6]
     const double* dr;           // [N][6] the damping d_i / rho of a damped trial (k_pg_damping), null for an undamped solve
+};
+
+// what the covariance of every node keeps of the forward pass (k_pg_segments<true>)
+struct PgCovSeg {
+    double* dinv;               // [N][36] D~_i^-1 of every interior node
+    double* piv;                // [S - 1][2] the smallest and the largest squared pivot of the segment's 6x6 factors
+    int* bad;                   // [S - 1] the node whose pivot was not positive and finite, or -1 (set by the host before the launch)
 };
 
 __device__ static inline double* pg_A(const PgPlan& p, int r, int c) {
@@ -407,8 +427,12 @@ __device__ static inline void pg_chol6_solve(const double* Lm, double* b) {
     }
 }
 
-__global__ void __launch_bounds__(64) k_pg_segments(PgPlan P, PgLin lin, PgCtl* ctl) {
-    if (ctl->done || ctl->pivot_fail) return;
+// COV: the instantiation of glio_pgraph_covariance_all, which also fills cv; the solves' instantiation never touches cv
+// (COV: a segment does not leave because ANOTHER one failed -- each runs to its own first failure, so that the node named afterwards, the first segment's,
+// does not depend on which wavefront ran first)
+template <bool COV>
+__global__ void __launch_bounds__(64) k_pg_segments(PgPlan P, PgLin lin, PgCtl* ctl, PgCovSeg cv) {
+    if (ctl->done || (!COV && ctl->pivot_fail)) return;
     const int k = blockIdx.x;                 // segment between separators k and k + 1
     const int lane = threadIdx.x;
     const int sL = P.sep_node[k], sR = P.sep_node[k + 1];
@@ -417,6 +441,7 @@ __global__ void __launch_bounds__(64) k_pg_segments(PgPlan P, PgLin lin, PgCtl* 
     if (b < a) {                                // no interior node: the chain edge couples the two separators directly
         if (lane < 36) { so[lane] = 0; so[36 + lane] = lin.C[(size_t)36 * sL + lane]; so[72 + lane] = 0; }
         else if (lane < 48) so[108 + lane - 36] = 0;
+        if (COV && lane == 48) { cv.piv[2 * k] = DBL_MAX; cv.piv[2 * k + 1] = 0.0; }       // no pivot: neutral for the minimum and the maximum
         return;
     }
     __shared__ double sD[36], sE[36], sg[6], sC[36], sY[PG_YS];
@@ -429,6 +454,7 @@ __global__ void __launch_bounds__(64) k_pg_segments(PgPlan P, PgLin lin, PgCtl* 
     }
     else if (lane < 42) sg[lane - 36] = lin.g[(size_t)6 * a + lane - 36];
     double acc = 0;                             // lanes < 36: S_LL entry; lanes 36 .. 41: g_L entry
+    double pmin = DBL_MAX, pmax = 0.0;          // COV: over the squared diagonal of the 6x6 factors (the same in every lane)
     for (int i = a; i <= b; ++i) {
         if (lane < 36) sC[lane] = lin.C[(size_t)36 * i + lane];
         __syncthreads();
@@ -437,10 +463,22 @@ __global__ void __launch_bounds__(64) k_pg_segments(PgPlan P, PgLin lin, PgCtl* 
             double A[36], Lm[36], col[6];
 #pragma unroll
             for (int q = 0; q < 36; ++q) A[q] = sD[q];
-            const bool ok = pg_chol6(A, Lm);
+            bool ok = pg_chol6(A, Lm);
+            if (COV) {
+#pragma unroll
+                for (int q = 0; q < 6; ++q) { const double d2 = Lm[7 * q] * Lm[7 * q]; pmin = fmin(pmin, d2); pmax = fmax(pmax, d2); }
+                ok = ok && pmax <= DBL_MAX;
+            }
             if (!ok) {                          // every lane sees the same block: the whole wavefront leaves
-                if (lane == 0) ctl->pivot_fail = 1;
+                if (lane == 0) { ctl->pivot_fail = 1; if (COV) cv.bad[k] = i; }
                 return;
+            }
+            if (COV && lane >= 13 && lane < 19) {       // column lane - 13 of D~_i^-1
+#pragma unroll
+                for (int q = 0; q < 6; ++q) col[q] = q == lane - 13 ? 1.0 : 0.0;
+                pg_chol6_solve(Lm, col);
+#pragma unroll
+                for (int q = 0; q < 6; ++q) cv.dinv[(size_t)36 * i + 6 * q + lane - 13] = col[q];
             }
             if (lane < 13) {
 #pragma unroll
@@ -491,6 +529,7 @@ __global__ void __launch_bounds__(64) k_pg_segments(PgPlan P, PgLin lin, PgCtl* 
             else if (lane < 42) sg[lane - 36] = nD;
         }
     }
+    if (COV && lane == 0) { cv.piv[2 * k] = pmin; cv.piv[2 * k + 1] = pmax; }
 }
 
 __global__ void __launch_bounds__(64) k_pg_backsub(PgPlan P, const PgCtl* ctl) {
@@ -555,7 +594,7 @@ __global__ void __launch_bounds__(64) k_pg_sep_assemble(PgPlan P, PgLin lin, con
             const int l = P.sl_idx[q] >> 1, end = P.sl_idx[q] & 1;
             v += lin.lp_out[(size_t)PG_LOOP_OUT * l + (end ? 114 : 108) + r];
         }
-        if (P.cov_sep < 0) *pg_A(P, P.n, 6 * k + r) = -v;
+        if (P.cov_sep < 0) { if (P.nrhs) *pg_A(P, P.n, 6 * k + r) = -v; }       // (no right-hand side: the covariance of every node)
         else if (k == P.cov_sep) *pg_A(P, P.n + r, 6 * k + r) = 1.0;
     }
 }
@@ -629,6 +668,7 @@ __global__ void __launch_bounds__(PG_SEP_THREADS) k_pg_sep_factor(PgPlan P, PgCt
         }
         __syncthreads();
     }
+    if (P.nrhs == 0) return;
     if (P.cov_sep < 0) {
         const double* x = P.wide + (size_t)(6 * P.nW) * P.n;
         for (int q = t; q < P.n; q += PG_SEP_THREADS) P.delta[(size_t)6 * P.sep_node[q / 6] + q % 6] = x[q];
@@ -636,6 +676,144 @@ __global__ void __launch_bounds__(PG_SEP_THREADS) k_pg_sep_factor(PgPlan P, PgCt
         const int r = t / 6, c = t % 6, hi = r > c ? r : c, lo = r > c ? c : r;      // the lower triangle, mirrored: symmetric to the bit
         ctl->cov[t] = P.wide[(size_t)(6 * P.nW + lo) * P.n + 6 * P.cov_sep + hi];
     }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------------------ every node's covariance
+// ONE workgroup, behind k_pg_sep_factor with no right-hand side: Z = (L L^T)^-1 on L's own pattern (Zp: the plan with Z's band and wide buffer, laid out as
+// L's are).  Columns k = n - 1 .. 0; with I the rows below k of pg_rowset's set:  Z[I, k] = -Z[I, I] L[I, k] / L_kk,  Z_kk = 1 / L_kk^2 - L[I, k]^T Z[I, k] / L_kk.
+// The pattern is closed under fill, so every Z[r, c] with r, c in I was written by a later column.  One thread per entry, one sum in ascending row order.
+// Per block the rows' places in the storage are worked out once (code[]: where pg_A would look, without its load of sep_w per access): in both systems the
+// wide buffer follows the band, so entry (r, c) is at band[pg_cov_at(code of r, c)].
+// Before that: the factor's squared diagonal (min, max) over the separators and the segments, and -- after a failed pivot -- the node it belongs to.
+__device__ static inline size_t pg_cov_at(int code, int c, int n) {
+    return code >= 0 ? (size_t)n * 12 + (size_t)code * n + c : (size_t)(-1 - code) + c;
+}
+__global__ void __launch_bounds__(PG_SEP_THREADS) k_pg_sep_inverse(PgPlan P, PgPlan Zp, PgCovSeg cv, PgCtl* ctl) {
+    __shared__ int rows[12 + 6 * PG_MAX_LOOPS + 6], code[12 + 6 * PG_MAX_LOOPS + 6];
+    __shared__ int wtot[PG_SEP_THREADS / 64];
+    __shared__ double smin[PG_SEP_THREADS / 64], smax[PG_SEP_THREADS / 64], sd[6];
+    __shared__ double lk[2][PG_COV_LDS], zk[PG_COV_LDS];
+    const int t = threadIdx.x;
+    if (!ctl->pivot_fail) {
+        double lo = DBL_MAX, hi = 0.0;
+        for (int k = t; k < P.n; k += PG_SEP_THREADS) { const double d = P.ldiag[k], d2 = d * d; lo = fmin(lo, d2); hi = fmax(hi, d2); }
+        for (int k = t; k < P.S - 1; k += PG_SEP_THREADS) { lo = fmin(lo, cv.piv[2 * k]); hi = fmax(hi, cv.piv[2 * k + 1]); }
+        for (int h = 32; h > 0; h >>= 1) { lo = fmin(lo, __shfl_xor(lo, h)); hi = fmax(hi, __shfl_xor(hi, h)); }
+        if ((t & 63) == 0) { smin[t >> 6] = lo; smax[t >> 6] = hi; }
+        __syncthreads();
+        for (int w = 0; w < PG_SEP_THREADS / 64; ++w) { lo = fmin(lo, smin[w]); hi = fmax(hi, smax[w]); }
+        if (t == 0) { ctl->min_pivot = lo; ctl->max_pivot = hi; ctl->bad_node = -1; }
+        if (hi <= DBL_MAX) {                    // uniform: every thread holds the same two numbers
+            const double* Ls = P.band;
+            double* Zs = Zp.band;
+            const int n = P.n;
+            for (int b = P.S - 1; b >= 0; --b) {
+                const int m = pg_rowset(P, b, rows, wtot);
+                for (int q = t; q < m; q += PG_SEP_THREADS) {
+                    const int r = rows[q], rb = r / 6, w = P.sep_w[rb];
+                    code[q] = w >= 0 ? 6 * w + (r - 6 * rb) : -1 - (r * 12 - 6 * (rb - 1));
+                }
+                if (t < 6) sd[t] = P.ldiag[6 * b + t];
+                __syncthreads();
+                // a block whose longest column fits keeps the column of L and the new column of Z in LDS (lk is double-buffered: the next column's L is
+                // fetched beside the diagonal entry's sum); a longer one reads both from memory.  The same sums in the same order either way.
+                const bool fits = m - 1 <= PG_COV_LDS;
+                int cur = 0;
+                if (fits) for (int q = t; q < m - 6; q += PG_SEP_THREADS) lk[0][q] = Ls[pg_cov_at(code[6 + q], 6 * b + 5, n)];
+                __syncthreads();
+                for (int k = 6 * b + 5; k >= 6 * b; --k) {
+                    const int start = k - 6 * b + 1, mm = m - start, kc = code[start - 1];
+                    const double d = sd[k - 6 * b];
+                    for (int q = t; q < mm; q += PG_SEP_THREADS) {
+                        const int r = rows[start + q], rc = code[start + q];
+                        double s = 0;
+#pragma unroll 8
+                        for (int p = 0; p < mm; ++p) {          // (unrolled: the loads of eight terms are in flight together; the sum keeps its order)
+                            const int c = rows[start + p], cc = code[start + p];
+                            s += Zs[r > c ? pg_cov_at(rc, c, n) : pg_cov_at(cc, r, n)] * (fits ? lk[cur][p] : Ls[pg_cov_at(cc, k, n)]);
+                        }
+                        const double v = -s / d;
+                        Zs[pg_cov_at(rc, k, n)] = v;
+                        if (fits) zk[q] = v;
+                    }
+                    __syncthreads();
+                    if (t == 0) {
+                        double s = 0;
+                        if (fits) {
+                            for (int p = 0; p < mm; ++p) s += lk[cur][p] * zk[p];
+                        } else {
+#pragma unroll 8
+                            for (int p = 0; p < mm; ++p) { const size_t at = pg_cov_at(code[start + p], k, n); s += Ls[at] * Zs[at]; }
+                        }
+                        Zs[pg_cov_at(kc, k, n)] = 1.0 / (d * d) - s / d;
+                    } else if (fits && t >= 64 && k > 6 * b) {
+                        for (int q = t - 64; q < mm + 1; q += PG_SEP_THREADS - 64) lk[cur ^ 1][q] = Ls[pg_cov_at(code[start - 1 + q], k - 1, n)];
+                    }
+                    __syncthreads();
+                    cur ^= 1;
+                }
+            }
+            return;
+        }
+    }
+    // a pivot failed (the segments' kernel named its node; the separator factor left at its column: ldiag, zeroed by the host, ends there) or is not finite
+    if (t != 0) return;
+    int bad = -1;
+    for (int k = 0; k < P.S - 1 && bad < 0; ++k) bad = cv.bad[k];
+    for (int k = 0; k < P.n && bad < 0; ++k) { const double d2 = P.ldiag[k] * P.ldiag[k]; if (!(d2 > 0.0) || !(d2 <= DBL_MAX)) bad = P.sep_node[k / 6]; }
+    ctl->pivot_fail = 1; ctl->bad_node = bad;
+}
+
+// One wavefront per separator k, lanes = the entries of a 6x6 block.  The separator's own block of Z is its covariance.  Then the segment to its right, from
+// node sR - 1 down to sL + 1, with n the node behind i (sR at the start), L the left separator and Y_C = D~^-1 C, Y_E = D~^-1 E as k_pg_segments left them:
+//   Sigma_in = -Y_C Sigma_nn - Y_E Sigma_nL^T      Sigma_iL = -Y_C Sigma_nL - Y_E Sigma_LL      Sigma_ii = D~_i^-1 - Sigma_in Y_C^T - Sigma_iL Y_E^T
+// Sigma_nn, Sigma_nL, Sigma_LL are carried in LDS; they start as blocks (k+1, k+1), (k+1, k), (k, k) of Z -- adjacent separators, inside the band.  next[i] is
+// Sigma_in; next[sL] is the spike Sigma_aL^T at the segment's first node a, or Z's sub-diagonal block when the segment has no interior.  Every diagonal block:
+// the lower triangle, mirrored.
+__global__ void __launch_bounds__(64) k_pg_cov_sweep(PgPlan P, PgPlan Zp, PgCovSeg cv, double* diag, double* next, const PgCtl* ctl) {
+    if (ctl->pivot_fail) return;
+    __shared__ double sNN[36], sNL[36], sLL[36], sY[72], sDi[36], sIN[36], sIL[36];
+    const int k = blockIdx.x, lane = threadIdx.x;
+    const bool on = lane < 36;
+    const int r = on ? lane / 6 : 0, c = on ? lane % 6 : 0, hi = r > c ? r : c, lo = r > c ? c : r;
+    const int sL = P.sep_node[k];
+    if (on) {
+        const double v = *pg_A(Zp, 6 * k + hi, 6 * k + lo);
+        diag[(size_t)36 * sL + lane] = v; sLL[lane] = v;
+    }
+    if (k + 1 >= P.S) return;
+    const int sR = P.sep_node[k + 1];
+    if (on) { sNN[lane] = *pg_A(Zp, 6 * (k + 1) + hi, 6 * (k + 1) + lo); sNL[lane] = *pg_A(Zp, 6 * (k + 1) + r, 6 * k + c); }
+    double y0 = 0, y1 = 0, d0 = 0;              // the next node's Y_C, Y_E, D~^-1 entries, loaded one node ahead
+    if (on && sR - 1 > sL) { const double* Y = P.Y + (size_t)PG_YS * (sR - 1); y0 = Y[lane]; y1 = Y[36 + lane]; d0 = cv.dinv[(size_t)36 * (sR - 1) + lane]; }
+    for (int i = sR - 1; i > sL; --i) {
+        if (on) { sY[lane] = y0; sY[36 + lane] = y1; sDi[lane] = d0; }
+        if (on && i - 1 > sL) { const double* Y = P.Y + (size_t)PG_YS * (i - 1); y0 = Y[lane]; y1 = Y[36 + lane]; d0 = cv.dinv[(size_t)36 * (i - 1) + lane]; }
+        __syncthreads();
+        if (on) {
+            double a = 0, b = 0;
+#pragma unroll
+            for (int q = 0; q < 6; ++q) { a += sY[6 * r + q] * sNN[6 * q + c]; b += sY[6 * r + q] * sNL[6 * q + c]; }
+#pragma unroll
+            for (int q = 0; q < 6; ++q) { a += sY[36 + 6 * r + q] * sNL[6 * c + q]; b += sY[36 + 6 * r + q] * sLL[6 * q + c]; }
+            sIN[lane] = -a; sIL[lane] = -b;
+            next[(size_t)36 * i + lane] = -a;
+        }
+        __syncthreads();
+        double s = 0;
+        if (on) {
+            s = sDi[6 * hi + lo];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) s -= sIN[6 * hi + q] * sY[6 * lo + q];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) s -= sIL[6 * hi + q] * sY[36 + 6 * lo + q];
+            diag[(size_t)36 * i + lane] = s;
+        }
+        __syncthreads();
+        if (on) { sNN[lane] = s; sNL[lane] = sIL[lane]; }
+    }
+    __syncthreads();
+    if (on) next[(size_t)36 * sL + lane] = sNL[6 * c + r];
 }
 
 // xo = x [+] delta per node (xo may be x).  A damped trial (dr not null) retracts into the candidate table and leaves the node's share of the model decrease,
@@ -775,6 +953,11 @@ struct glio_pgraph {
     double* d_xc; double* d_dr; double* d_gf; double* d_nm; double* d_hist; size_t hist_cap;
     std::vector<double> lm_hist;                // [trials][4] of the last damped solve that returned GLIO_OK
     std::vector<double> lm_hist_in;             // where a running solve's rows arrive
+    // the covariance of every node (allocated by the first glio_pgraph_covariance_all*, for cov_cap nodes): Z on the factor's pattern (band, wide), the
+    // segments' record, the result on the device (diag [N][36], then next [N - 1][36]) and in pinned memory, the last call's times (five stages, the whole)
+    double* d_zsys; size_t zsys_cap;
+    double* d_dinv; double* d_segpiv; int* d_segbad; double* d_cov; double* h_cov; size_t cov_cap;
+    float cov_ms[6]; int cov_timed;
 };
 
 #define PG_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { glio_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); return GLIO_E_HIP; } } while (0)
@@ -863,8 +1046,8 @@ static int pg_segment_nodes(const glio_pgraph* pg) {
     return std::min(255, std::max(4, m));
 }
 // the separators (node 0, the last node, every loop endpoint, the node whose covariance is asked, and a node after every segment_nodes interior nodes), the
-// full-row separators, the loops per separator: computed on the host, one upload
-static int pg_make_plan(glio_pgraph* pg, int cov_node, PgPlan* P) {
+// full-row separators, the loops per separator: computed on the host, one upload.  rhs false: no right-hand side (the covariance of every node)
+static int pg_make_plan(glio_pgraph* pg, int cov_node, PgPlan* P, bool rhs = true) {
     const int N = pg->N, L = (int)pg->lp_i.size(), seg = pg_segment_nodes(pg);
     std::vector<int> forced;
     forced.push_back(0); forced.push_back(N - 1);
@@ -905,7 +1088,7 @@ static int pg_make_plan(glio_pgraph* pg, int cov_node, PgPlan* P) {
         pg->plan_cap = cap;
     }
     PG_CHECK(hipMemcpy(pg->d_plan, blk.data(), blk.size() * 4, hipMemcpyHostToDevice));
-    const int nrhs = cov_node >= 0 ? 6 : 1, n = 6 * S;
+    const int nrhs = cov_node >= 0 ? 6 : (rhs ? 1 : 0), n = 6 * S;
     const size_t need = (size_t)n * 12 + (size_t)(6 * nW + nrhs) * n + n;
     if (need > pg->sys_cap) {
         if (pg->d_sys) { hipFree(pg->d_sys); pg->d_sys = nullptr; pg->sys_cap = 0; }
@@ -935,10 +1118,14 @@ static void pg_enqueue_linearise(glio_pgraph* pg, int phase, int max_iter) {
     hipLaunchKernelGGL(k_pg_error, dim3(1), dim3(1024), 0, pg->stream, pg->N, (int)pg->lp_i.size(), pg->d_nerr, pg->d_lp_out, pg->d_ctl, phase, max_iter,
                        pg->o.relative_error_tol, pg->o.absolute_error_tol);
 }
-// segments, separator system, back-substitution of one linear solve; ev (may be null): events after the segments and after the separator system
-static void pg_enqueue_linear_solve(glio_pgraph* pg, const PgPlan& P, hipEvent_t* ev) {
+// segments, separator system, back-substitution of one linear solve; ev (may be null): events after the segments and after the separator system;
+// cv (may be null): the segments' record for the covariance of every node
+static void pg_enqueue_linear_solve(glio_pgraph* pg, const PgPlan& P, hipEvent_t* ev, const PgCovSeg* cv = nullptr) {
     const PgLin lin = pg_lin(pg);
-    if (P.S > 1) hipLaunchKernelGGL(k_pg_segments, dim3(P.S - 1), dim3(64), 0, pg->stream, P, lin, pg->d_ctl);
+    if (P.S > 1) {
+        if (cv) hipLaunchKernelGGL(k_pg_segments<true>, dim3(P.S - 1), dim3(64), 0, pg->stream, P, lin, pg->d_ctl, *cv);
+        else hipLaunchKernelGGL(k_pg_segments<false>, dim3(P.S - 1), dim3(64), 0, pg->stream, P, lin, pg->d_ctl, PgCovSeg{nullptr, nullptr, nullptr});
+    }
     if (ev) hipEventRecord(ev[0], pg->stream);
     const size_t cells = (size_t)P.n * 12 + (size_t)(6 * P.nW + P.nrhs) * P.n;
     hipLaunchKernelGGL(k_pg_sep_zero, dim3((unsigned)std::min<size_t>(1024, (cells + 255) / 256)), dim3(256), 0, pg->stream, P, pg->d_ctl);
@@ -969,9 +1156,11 @@ void glio_pgraph_destroy(glio_pgraph* pg) {
     (void)hipSetDevice(pg->device);
     if (pg->stream) (void)hipStreamSynchronize(pg->stream);
     void* p[] = {pg->d_x, pg->d_x0, pg->d_cm, pg->d_cw, pg->d_un_node, pg->d_un_type, pg->d_un_m, pg->d_un_w, pg->d_lp_i, pg->d_lp_j, pg->d_lp_m, pg->d_lp_w,
-                 pg->d_D, pg->d_C, pg->d_g, pg->d_nerr, pg->d_lp_out, pg->d_Y, pg->d_seg, pg->d_delta, pg->d_plan, pg->d_sys, pg->d_ctl, pg->d_xc, pg->d_dr, pg->d_gf, pg->d_nm, pg->d_hist};
+                 pg->d_D, pg->d_C, pg->d_g, pg->d_nerr, pg->d_lp_out, pg->d_Y, pg->d_seg, pg->d_delta, pg->d_plan, pg->d_sys, pg->d_ctl, pg->d_xc, pg->d_dr, pg->d_gf, pg->d_nm, pg->d_hist,
+                 pg->d_zsys, pg->d_dinv, pg->d_segpiv, pg->d_segbad, pg->d_cov};
     for (void* q : p) if (q) (void)hipFree(q);
     if (pg->h_ctl) (void)hipHostFree(pg->h_ctl);
+    if (pg->h_cov) (void)hipHostFree(pg->h_cov);
     if (pg->ev_done) (void)hipEventDestroy(pg->ev_done);
     for (hipEvent_t e : pg->ev_t) if (e) (void)hipEventDestroy(e);
     if (pg->stream) (void)hipStreamDestroy(pg->stream);
@@ -1329,6 +1518,104 @@ int glio_pgraph_marginal_covariance(glio_pgraph* pg, int node, double* out) {
     PG_CHECK(hipGetLastError());
     if (pg->h_ctl->pivot_fail) { glio_set_error("glio_pgraph_marginal_covariance: a non-positive pivot"); return GLIO_E_NUMERIC; }
     memcpy(out, pg->h_ctl->cov, 36 * 8);
+    return GLIO_OK;
+}
+
+int glio_pgraph_cov_struct_sizes(int32_t* out, int n) {
+    if (out && n > 0) out[0] = (int32_t)sizeof(glio_pgraph_cov_info);
+    return 1;
+}
+
+// One factorisation with the plan of a solve and no right-hand side, the selected inversion, one wait.  to_host: diag (and next, unless null) go through pinned
+// memory into the caller's arrays; otherwise the result stays on the device.
+static int pg_covariance_all(glio_pgraph* pg, const char* who, bool to_host, double* diag, double* next, glio_pgraph_cov_info* info) {
+    { const int rc = pg_ready(pg, who); if (rc != GLIO_OK) return rc; }
+    PgPlan P;
+    { const int rc = pg_make_plan(pg, -1, &P, false); if (rc != GLIO_OK) return rc; }
+    const int N = pg->N;
+    if ((size_t)N > pg->cov_cap) {              // everything that scales with the nodes, for twice as many as asked now (at most max_nodes)
+        void* old[] = {pg->d_dinv, pg->d_segpiv, pg->d_segbad, pg->d_cov};
+        for (void* q : old) if (q) (void)hipFree(q);
+        if (pg->h_cov) (void)hipHostFree(pg->h_cov);
+        pg->d_dinv = pg->d_segpiv = pg->d_cov = pg->h_cov = nullptr; pg->d_segbad = nullptr; pg->cov_cap = 0;
+        const size_t cap = std::min<size_t>((size_t)pg->o.max_nodes, std::max<size_t>(2 * (size_t)N, 64));
+        PG_CHECK(hipMalloc((void**)&pg->d_dinv, cap * 288)); PG_CHECK(hipMalloc((void**)&pg->d_segpiv, cap * 16)); PG_CHECK(hipMalloc((void**)&pg->d_segbad, cap * 4));
+        PG_CHECK(hipMalloc((void**)&pg->d_cov, cap * 576)); PG_CHECK(hipHostMalloc((void**)&pg->h_cov, cap * 576));
+        pg->cov_cap = cap;
+    }
+    const size_t zneed = (size_t)P.n * 12 + (size_t)6 * P.nW * P.n;
+    if (zneed > pg->zsys_cap) {
+        if (pg->d_zsys) { hipFree(pg->d_zsys); pg->d_zsys = nullptr; pg->zsys_cap = 0; }
+        PG_CHECK(hipMalloc((void**)&pg->d_zsys, (zneed + zneed / 2) * 8));
+        pg->zsys_cap = zneed + zneed / 2;
+    }
+    PgPlan Zp = P;
+    Zp.band = pg->d_zsys; Zp.wide = pg->d_zsys + (size_t)P.n * 12;
+    const PgCovSeg cv = {pg->d_dinv, pg->d_segpiv, pg->d_segbad};
+    double* d_diag = pg->d_cov;
+    double* d_next = pg->d_cov + (size_t)36 * N;
+    PG_CHECK(hipMemsetAsync(pg->d_ctl, 0, sizeof(PgCtl), pg->stream));
+    PG_CHECK(hipMemsetAsync(pg->d_segbad, 0xff, (size_t)std::max(P.S - 1, 1) * 4, pg->stream));
+    PG_CHECK(hipMemsetAsync(P.ldiag, 0, (size_t)P.n * 8, pg->stream));
+    PG_CHECK(hipEventRecord(pg->ev_t[0], pg->stream));
+    pg_enqueue_lin_at(pg, pg->d_x, 0);
+    PG_CHECK(hipEventRecord(pg->ev_t[1], pg->stream));
+    pg_enqueue_linear_solve(pg, P, nullptr, &cv);
+    PG_CHECK(hipEventRecord(pg->ev_t[2], pg->stream));
+    hipLaunchKernelGGL(k_pg_sep_inverse, dim3(1), dim3(PG_SEP_THREADS), 0, pg->stream, P, Zp, cv, pg->d_ctl);
+    PG_CHECK(hipEventRecord(pg->ev_t[3], pg->stream));
+    hipLaunchKernelGGL(k_pg_cov_sweep, dim3(P.S), dim3(64), 0, pg->stream, P, Zp, cv, d_diag, d_next, pg->d_ctl);
+    PG_CHECK(hipEventRecord(pg->ev_t[4], pg->stream));
+    const size_t words = (size_t)36 * N + (next ? (size_t)36 * (N - 1) : 0);
+    if (to_host) PG_CHECK(hipMemcpyAsync(pg->h_cov, pg->d_cov, words * 8, hipMemcpyDeviceToHost, pg->stream));
+    { const int rc = pg_wait_ctl(pg, 0); if (rc != GLIO_OK) return rc; }
+    PG_CHECK(hipGetLastError());
+    const PgCtl& c = *pg->h_ctl;
+    for (int k = 0; k < 5; ++k) (void)hipEventElapsedTime(&pg->cov_ms[k], pg->ev_t[k], pg->ev_t[k + 1]);
+    (void)hipEventElapsedTime(&pg->cov_ms[5], pg->ev_t[0], pg->ev_t[5]);
+    pg->cov_timed = 1;
+    if (info) {
+        memset(info, 0, sizeof *info);
+        info->n_nodes = N; info->separators = P.S; info->full_row_separators = P.nW; info->segment_nodes = pg_segment_nodes(pg);
+        info->bad_node = c.pivot_fail ? c.bad_node : -1;
+        if (!c.pivot_fail) { info->min_pivot = c.min_pivot; info->max_pivot = c.max_pivot; }
+    }
+    if (c.pivot_fail) { glio_set_error("%s: the pivot of node %d is not positive and finite", who, c.bad_node); return GLIO_E_NUMERIC; }
+    if (to_host) {
+        memcpy(diag, pg->h_cov, (size_t)N * 288);
+        if (next && N > 1) memcpy(next, pg->h_cov + (size_t)36 * N, (size_t)(N - 1) * 288);
+    }
+    return GLIO_OK;
+}
+
+int glio_pgraph_covariance_all(glio_pgraph* pg, double* diag, double* next, glio_pgraph_cov_info* info) {
+    GLIO_TRACE("glio_pgraph_covariance_all");
+    if (!pg || !diag) { glio_set_error("glio_pgraph_covariance_all: null argument"); return GLIO_E_ARG; }
+    return pg_covariance_all(pg, "glio_pgraph_covariance_all", true, diag, next, info);
+}
+
+int glio_pgraph_covariance_all_dev(glio_pgraph* pg, const double** diag_dev, const double** next_dev, int* n_nodes) {
+    GLIO_TRACE("glio_pgraph_covariance_all_dev");
+    if (!pg || !diag_dev) { glio_set_error("glio_pgraph_covariance_all_dev: null argument"); return GLIO_E_ARG; }
+    const int rc = pg_covariance_all(pg, "glio_pgraph_covariance_all_dev", false, nullptr, nullptr, nullptr);
+    if (rc != GLIO_OK) return rc;
+    *diag_dev = pg->d_cov;
+    if (next_dev) *next_dev = pg->d_cov + (size_t)36 * pg->N;
+    if (n_nodes) *n_nodes = pg->N;
+    return GLIO_OK;
+}
+
+int glio_pgraph_covariance_all_last_device_ms(glio_pgraph* pg, float* ms) {
+    if (!pg || !ms) return GLIO_E_ARG;
+    if (!pg->cov_timed) { glio_set_error("glio_pgraph_covariance_all_last_device_ms: no call yet"); return GLIO_E_STATE; }
+    *ms = pg->cov_ms[5];
+    return GLIO_OK;
+}
+
+int glio_pgraph_covariance_all_last_stage_ms(glio_pgraph* pg, float* ms5) {
+    if (!pg || !ms5) return GLIO_E_ARG;
+    if (!pg->cov_timed) { glio_set_error("glio_pgraph_covariance_all_last_stage_ms: no call yet"); return GLIO_E_STATE; }
+    memcpy(ms5, pg->cov_ms, 5 * sizeof(float));
     return GLIO_OK;
 }
 

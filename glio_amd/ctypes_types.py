@@ -200,6 +200,15 @@ class GlioPgraphLmInfo(C.Structure):
     _fields_ = [("final_radius", C.c_double), ("accepted", C.c_int32), ("rejected", C.c_int32), ("invalid", C.c_int32), ("trials", C.c_int32)]
 
 
+class GlioPgraphCovInfo(C.Structure):
+    """glio_pgraph_cov_info (include/glio_pgraph_cov.h): the plan glio_pgraph_covariance_all used, the factor's squared diagonal, the node of a failed pivot"""
+    _fields_ = [("n_nodes", C.c_int32), ("separators", C.c_int32), ("full_row_separators", C.c_int32), ("segment_nodes", C.c_int32),
+                ("bad_node", C.c_int32), ("pad_", C.c_int32), ("min_pivot", C.c_double), ("max_pivot", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "pad_"}
+
+
 LOOP_SOURCE, LOOP_TARGET = 0, 1
 LOOP_NOT_CONVERGED, LOOP_ITERATIONS, LOOP_TRANSFORM, LOOP_ABS_MSE, LOOP_REL_MSE, LOOP_NO_CORRESPONDENCES = range(6)
 LOOP_STATE_NAMES = ("NOT_CONVERGED", "ITERATIONS", "TRANSFORM", "ABS_MSE", "REL_MSE", "NO_CORRESPONDENCES")
@@ -317,8 +326,18 @@ ALIGN_PROTOTYPES = {
 }
 
 
+# include/glio_pgraph_cov.h
+PGRAPH_COV_PROTOTYPES = {
+    "glio_pgraph_cov_struct_sizes": [c_int32_p, C.c_int],
+    "glio_pgraph_covariance_all": [C.c_void_p, c_double_p, c_double_p, C.POINTER(GlioPgraphCovInfo)],
+    "glio_pgraph_covariance_all_dev": [C.c_void_p, c_void_pp, c_void_pp, c_int_p],
+    "glio_pgraph_covariance_all_last_device_ms": [C.c_void_p, c_float_p],
+    "glio_pgraph_covariance_all_last_stage_ms": [C.c_void_p, c_float_p],
+}
+
+
 def apply_prototypes(lib):
-    for name, args in list(KEYFRAME_CLOUD_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()):
+    for name, args in list(KEYFRAME_CLOUD_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(PGRAPH_COV_PROTOTYPES.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise AttributeError(f"{name} is missing from the library: it is stale, rebuild it with `python -m glio_amd.build`")

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "glio_hip.h"
+#include "glio_pgraph_cov.h"
 
 namespace glio {
 
@@ -83,6 +84,17 @@ public:
         std::vector<double> out(36);
         check(glio_pgraph_marginal_covariance(h_, node, out.data()), "glio_pgraph_marginal_covariance");
         return out;
+    }
+    // glio_pgraph_covariance_all (glio_pgraph_cov.h): block (i, i) of (J^T J)^-1 of EVERY node from one factorisation, [N][36] row major, rotation first;
+    // next (may be null): the blocks (i, i + 1), [N - 1][36]; info (may be null): the plan used, the factor's squared diagonal, the node of a failed pivot
+    std::vector<double> marginalCovariances(std::vector<double>* next = nullptr, glio_pgraph_cov_info* info = nullptr) {
+        const int n = size();
+        std::vector<double> diag((size_t)36 * (n > 0 ? n : 1));
+        if (next) next->assign((size_t)36 * (n > 1 ? n - 1 : 1), 0.0);
+        check(glio_pgraph_covariance_all(h_, diag.data(), next ? next->data() : nullptr, info), "glio_pgraph_covariance_all");
+        diag.resize((size_t)36 * n);
+        if (next) next->resize((size_t)36 * (n > 1 ? n - 1 : 0));
+        return diag;
     }
     double error() { double e = 0; check(glio_pgraph_error(h_, &e), "glio_pgraph_error"); return e; }
     const double* posesDev(int* n = nullptr) { const double* p = nullptr; check(glio_pgraph_poses_dev(h_, &p, n), "glio_pgraph_poses_dev"); return p; }

@@ -661,6 +661,46 @@ def run_demo_batch_cov(path, device=0, env=None):
     return out
 
 
+DEMO_POSE_GRAPH_COV = os.path.join(HERE, "host_demo_pose_graph_cov")
+
+
+def build_demo_pose_graph_cov(force=False):
+    """The C++ covariance of every pose-graph node (host_demo_pose_graph_cov.cpp over glio::PoseGraph::marginalCovariances)."""
+    src = [os.path.join(HERE, "host_demo_pose_graph_cov.cpp"), os.path.join(HERE, "glio_posegraph_backend.hpp"),
+           os.path.join(HERE, "..", "..", "include", "glio_pgraph_cov.h")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_POSE_GRAPH_COV) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_POSE_GRAPH_COV) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_POSE_GRAPH_COV])
+    return DEMO_POSE_GRAPH_COV
+
+
+def write_pose_graph_cov_case(path, poses, loops, gps, segment_nodes, prior=True, solve=True):
+    """the case file of host_demo_pose_graph_cov.cpp (layout in its header); loops: (i, j, rel [7], var [6]); gps: (node, xyz [3], var [3])"""
+    P = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+    with open(path, "wb") as f:
+        f.write(np.array([len(P), len(loops), len(gps), segment_nodes, 1 if prior else 0, 1 if solve else 0, 0, 0], np.int32).tobytes())
+        f.write(P.tobytes())
+        for i, j, rel, var in loops:
+            f.write(np.array([float(i), float(j), *rel, *var], np.float64).tobytes())
+        for node, xyz, v in gps:
+            f.write(np.array([float(node), *xyz, *v], np.float64).tobytes())
+
+
+def run_demo_pose_graph_cov(path, device=0, env=None):
+    """-> dict(diag, next, info: the result's bytes; nodes, separators, full_row_separators, bad_node)"""
+    r = subprocess.run([build_demo_pose_graph_cov(), path, str(device)], capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError("host_demo_pose_graph_cov failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
+    out = {}
+    for ln in r.stdout.splitlines():
+        w = ln.split()
+        if w[:1] == ["nodes"]:
+            out.update({w[i]: int(w[i + 1]) for i in range(0, len(w) - 1, 2)})
+        elif w and w[0] in ("diag", "next", "info"):
+            out[w[0]] = bytes.fromhex(w[1]) if len(w) > 1 else b""
+    return out
+
+
 DEMO_ALIGN = os.path.join(HERE, "host_demo_align")
 
 

@@ -159,6 +159,36 @@ class PoseGraph:
         capi._check(capi.load().glio_pgraph_marginal_covariance(self._h, int(node), T.dptr(out)))
         return out
 
+    def marginal_covariances(self, next=False, with_info=False):
+        """glio_pgraph_covariance_all (include/glio_pgraph_cov.h): block (i, i) of (J^T J)^-1 for EVERY node from one factorisation, [N][6][6] in the tangent
+        frame of the retraction (rotation first); next=True: also the blocks (i, i + 1), [N - 1][6][6]; with_info: also the glio_pgraph_cov_info as a dict.
+        A pivot that is not positive and finite raises GlioError with code E_NUMERIC and `info` (bad_node names the node)."""
+        n = self.size()
+        diag = np.zeros((max(n, 1), 6, 6))[:n]           # (an empty graph still hands over an address: the refusal is the library's)
+        nxt = np.zeros((max(n, 2) - 1, 6, 6))[:max(n - 1, 0)] if next else None
+        info = T.GlioPgraphCovInfo()
+        rc = capi.load().glio_pgraph_covariance_all(self._h, T.dptr(diag), T.dptr(nxt) if next else None, C.byref(info))
+        if rc != 0:
+            e = capi.GlioError(f"libglio_hip error {rc}: {capi.load().glio_last_error().decode()}")
+            e.code, e.info = rc, info.as_dict()
+            raise e
+        out = (diag, nxt) if next else (diag,)
+        out = out + (info.as_dict(),) if with_info else out
+        return out[0] if len(out) == 1 else out
+
+    def marginal_covariances_dev(self):
+        """(device address of diag [n][36], device address of next [n - 1][36], n): valid until the next call that changes the graph or asks again"""
+        d, x, n = C.c_void_p(), C.c_void_p(), C.c_int(0)
+        capi._check(capi.load().glio_pgraph_covariance_all_dev(self._h, C.byref(d), C.byref(x), C.byref(n)))
+        return d.value, x.value, n.value
+
+    def marginal_covariances_ms(self):
+        """(device ms of the last marginal_covariances call, its five stages: linearise, segments + separator factor, separator inversion, down-sweep, copy)"""
+        ms, st = C.c_float(0), (C.c_float * 5)()
+        capi._check(capi.load().glio_pgraph_covariance_all_last_device_ms(self._h, C.byref(ms)))
+        capi._check(capi.load().glio_pgraph_covariance_all_last_stage_ms(self._h, st))
+        return float(ms.value), [float(v) for v in st]
+
     def error(self):
         e = C.c_double(0)
         capi._check(capi.load().glio_pgraph_error(self._h, C.byref(e)))
