@@ -80,6 +80,23 @@ def align_opts(**kw):
     return o
 
 
+def place_opts(**kw):
+    """glio_place_opts_default with fields replaced"""
+    o = T.GlioPlaceOpts()
+    load().glio_place_opts_default(C.byref(o))
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
+def place_tables(max_radius):
+    """glio_place_tables: (rb2 [21], dir [60][2]) float32; needs no device"""
+    rb2, dirs = np.zeros(T.PLACE_RINGS + 1, np.float32), np.zeros((T.PLACE_SECTORS, 2), np.float32)
+    _check(load().glio_place_tables(float(max_radius), T.fptr(rb2), T.fptr(dirs)))
+    return rb2, dirs
+
+
 def device_count():
     return load().glio_device_count()
 

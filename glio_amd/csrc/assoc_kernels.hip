@@ -2480,6 +2480,7 @@ int glio_bassoc_view(glio_bassoc* b, GlioBassocView* out) {
 }
 int glio_bassoc_external_read(glio_bassoc* b, hipStream_t reader) {
     if (!b->ev_ext_read) BA_CHECK(hipEventCreateWithFlags(&b->ev_ext_read, hipEventDisableTiming));
+    if (b->ext_read_pending) BA_CHECK(hipStreamWaitEvent(reader, b->ev_ext_read, 0));       // (another object's read: the new record covers it)
     BA_CHECK(hipEventRecord(b->ev_ext_read, reader));
     b->ext_read_pending = 1;
     return GLIO_OK;

@@ -49,6 +49,7 @@ int glio_dense_view(glio_dense* d, GlioBassocView* out) {
     return GLIO_OK;
 }
 int glio_dense_external_read(glio_dense* d, hipStream_t reader) {
+    if (d->ext_read_pending) GLIO_HIP_CHECK(hipStreamWaitEvent(reader, d->ev_ext_read, 0));       // (another object's read: the new record covers it)
     GLIO_HIP_CHECK(hipEventRecord(d->ev_ext_read, reader));
     d->ext_read_pending = 1;
     return GLIO_OK;

@@ -336,8 +336,39 @@ PGRAPH_COV_PROTOTYPES = {
 }
 
 
+# ---- place recognition (include/glio_place.h)
+PLACE_RINGS, PLACE_SECTORS, PLACE_TOP_K_MAX = 20, 60, 8
+
+
+class GlioPlaceOpts(C.Structure):
+    """glio_place_opts"""
+    _fields_ = [("max_places", C.c_int32), ("top_k_max", C.c_int32), ("max_radius", C.c_float), ("lidar_height", C.c_float)]
+
+
+class GlioPlaceMatch(C.Structure):
+    """glio_place_match"""
+    _fields_ = [("place", C.c_int32), ("shift", C.c_int32), ("distance", C.c_float), ("yaw", C.c_float)]
+
+
+c_uint64_p = C.POINTER(C.c_uint64)
+PLACE_PROTOTYPES = {
+    "glio_place_struct_sizes": [c_int32_p, C.c_int],
+    "glio_place_tables": [C.c_float, c_float_p, c_float_p],
+    "glio_place_create": [C.c_void_p, C.POINTER(GlioPlaceOpts), c_void_pp],
+    "glio_place_create_on_dense": [C.c_void_p, C.POINTER(GlioPlaceOpts), c_void_pp],
+    "glio_place_add_frames": [C.c_void_p, C.c_int, c_int32_p, c_int32_p, c_double_p, c_double_p],
+    "glio_place_read_descriptor": [C.c_void_p, C.c_int, c_float_p, c_uint64_p, c_double_p, c_int32_p],
+    "glio_place_set_descriptor": [C.c_void_p, C.c_int, c_float_p, C.c_uint64, C.c_double],
+    "glio_place_clear": [C.c_void_p],
+    "glio_place_query": [C.c_void_p, C.c_int, C.c_double, C.c_int, C.POINTER(GlioPlaceMatch), c_int32_p],
+    "glio_place_query_many": [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(GlioPlaceMatch), c_int32_p],
+    "glio_place_last_device_ms": [C.c_void_p, c_float_p],
+}
+
+
 def apply_prototypes(lib):
-    for name, args in list(KEYFRAME_CLOUD_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(PGRAPH_COV_PROTOTYPES.items()):
+    for name, args in list(KEYFRAME_CLOUD_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(PGRAPH_COV_PROTOTYPES.items()) + \
+            list(PLACE_PROTOTYPES.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise AttributeError(f"{name} is missing from the library: it is stale, rebuild it with `python -m glio_amd.build`")
@@ -349,3 +380,7 @@ def apply_prototypes(lib):
     lib.glio_align_destroy.restype = None
     lib.glio_align_opts_default.argtypes = [C.POINTER(GlioAlignOpts)]
     lib.glio_align_opts_default.restype = None
+    lib.glio_place_destroy.argtypes = [C.c_void_p]
+    lib.glio_place_destroy.restype = None
+    lib.glio_place_opts_default.argtypes = [C.POINTER(GlioPlaceOpts)]
+    lib.glio_place_opts_default.restype = None

@@ -738,3 +738,48 @@ def run_demo_align(path, device=0, env=None):
         elif w and w[0] == "status":
             out.update(status=int(w[1]), rows=int(w[3]), downweighted=int(w[5]))
     return out
+
+
+DEMO_PLACE = os.path.join(HERE, "host_demo_place")
+
+
+def build_demo_place(force=False):
+    """The C++ place recognition (host_demo_place.cpp over glio::PlaceRecognition, glio_place_backend.hpp)."""
+    src = [os.path.join(HERE, "host_demo_place.cpp"), os.path.join(HERE, "glio_place_backend.hpp"), os.path.join(HERE, "..", "..", "include", "glio_place.h")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_PLACE) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_PLACE) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_PLACE])
+    return DEMO_PLACE
+
+
+def write_place_case(path, opts, cap, top_k, min_time_gap, clouds, times, attitudes, pose_closest):
+    """int32 K cap top_k 0 | glio_place_opts | double min_time_gap | K x (n, cloud) | double times[K] | double attitude[K][4] | double pose_closest[7]"""
+    K = len(clouds)
+    times, att = np.ascontiguousarray(times, np.float64), np.ascontiguousarray(attitudes, np.float64)
+    assert times.shape == (K,) and att.shape == (K, 4)
+    with open(path, "wb") as f:
+        f.write(np.array([K, cap, top_k, 0], np.int32).tobytes())
+        f.write(bytes(opts)); f.write(np.array([min_time_gap], np.float64).tobytes())
+        for c in clouds:
+            c = np.ascontiguousarray(c, np.float32).reshape(-1, 4)
+            f.write(np.array([len(c)], np.int32).tobytes()); f.write(c.tobytes())
+        f.write(times.tobytes()); f.write(att.tobytes()); f.write(np.ascontiguousarray(pose_closest, np.float64).reshape(7).tobytes())
+
+
+def run_demo_place(path, device=0, env=None):
+    """-> dict(name: the bytes host_demo_place printed under that name; candidate: int; mask<k>: int)"""
+    r = subprocess.run([build_demo_place(), path, str(device)], capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError("host_demo_place failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
+    out = {}
+    for ln in r.stdout.splitlines():
+        w = ln.split()
+        if not w:
+            continue
+        if w[0] == "candidate":
+            out["candidate"] = int(w[1])
+        elif w[0].startswith("mask"):
+            out[w[0]] = int(w[1], 16)
+        else:
+            out[w[0]] = bytes.fromhex(w[1]) if len(w) > 1 else b""
+    return out
