@@ -2130,6 +2130,7 @@ int glio_assoc_run_window_async(glio_ctx* c, const double* quats, const double* 
     w->counts_pending = 1;
     return GLIO_OK;
 }
+int glio_assoc_counts_pending(const glio_ctx* c) { return c->assoc && c->assoc->counts_pending ? 1 : 0; }
 int glio_assoc_finish_pending(glio_ctx* c) {
     AssocWork* w = c->assoc;
     if (!w || !w->counts_pending) return GLIO_OK;

@@ -59,7 +59,7 @@ static int refused(const TabError& e) { if (e.msg[0]) glio_set_error("%s", e.msg
 // the factor tables changed: the solve's gather tables are rebuilt, the dense H buffers are no longer known to be zero outside the band
 static void factor_tables_changed(glio_ctx* c) { c->chain_tabs_dirty = 1; c->h_band_clean = 0; }
 static void prior_clear(glio_ctx* c) {
-    c->prior_n = 0; c->prior_nb = 0; c->arrow.prior_ok = 1; c->arrow.prior_chain = 1; c->prior_ext_coupled = 0;
+    c->prior_n = 0; c->prior_nb = 0; c->arrow.prior_ok = 1; c->arrow.prior_chain = 1; c->prior_ext_coupled = 0; c->prior_span_ok = 0; c->prior_jac_exact = 0;
     for (int k = 0; k < 15 * c->W; ++k) c->h_prior_index[k] = -1;
     factor_tables_changed(c);
 }
@@ -268,7 +268,7 @@ static int create_body(int device, const glio_opts* opts, glio_ctx* c) {
     ex->up_mode = glio_switch_at_create<GLIO_SW_EARLY_UPLOAD>(); ex->up_wait = glio_switch_at_create<GLIO_SW_EARLY_UPLOAD_WAIT>();
     ex->unstage_up = !glio_switch_at_create<GLIO_SW_UNSTAGE_IN_STREAM>();
     ALLOC(ex->gx.d_runs, (size_t)std::max(1, c->n_ddt_max) * sizeof(DopRun));
-    ALLOC(ex->gx.d_prior_colblk, npmax * 4);
+    ALLOC(ex->gx.d_prior_colblk, ((size_t)npmax * 5 + 4) * 4);          // column -> block, then the four spans of every column (glio_prior_span_dev)
     ALLOC(ex->d_eval_params, 64 * 8); ALLOC(ex->d_eval_out, (15 + 15 * 32) * 8); ALLOC(ex->d_eval_edge, sizeof(ImuEdgeDev));
     GLIO_HIP_CHECK(hipHostMalloc((void**)&ex->h_eval, (15 + 15 * 32) * 8));
     c->extra = ex;
@@ -775,6 +775,8 @@ int glio_set_prior(glio_ctx* c, const glio_prior* p) {
     { TabError e; if (prior_index_tables(W, np, nb, p->blk_slot, p->blk_kind, p->blk_idx, index.data(), colblk.data(), &e)) return refused(e); }
     const PriorFlags flags = prior_flags(nb, p->blk_slot, p->blk_kind);
     const bool chain = prior_is_chain(np, p->lin_jac, p->blk_slot, colblk.data());
+    std::vector<int> span(4 * (size_t)np);
+    const int span_ok = prior_span_tables(W, np, nb, p->blk_slot, p->blk_kind, p->blk_idx, colblk.data(), span.data());
     GLIO_HIP_CHECK(hipMemcpy(c->d_prior_J0, p->lin_jac, (size_t)np * np * 8, hipMemcpyHostToDevice));
     GLIO_HIP_CHECK(hipMemcpy(c->d_prior_r0, p->lin_res, np * 8, hipMemcpyHostToDevice));
     GLIO_HIP_CHECK(hipMemcpy(c->d_prior_x0, p->blk_x0, (size_t)nb * 9 * 8, hipMemcpyHostToDevice));
@@ -783,6 +785,9 @@ int glio_set_prior(glio_ctx* c, const glio_prior* p) {
     GLIO_HIP_CHECK(hipMemcpy(c->d_prior_idx, p->blk_idx, nb * 4, hipMemcpyHostToDevice));
     GLIO_HIP_CHECK(hipMemcpy(c->d_prior_index, index.data(), 15 * W * 4, hipMemcpyHostToDevice));
     GLIO_HIP_CHECK(hipMemcpy(glio_extra(c)->d_prior_colblk, colblk.data(), np * 4, hipMemcpyHostToDevice));
+    GLIO_HIP_CHECK(hipMemcpy(const_cast<int*>(glio_prior_span_dev(c, glio_extra(c)->d_prior_colblk)), span.data(), (size_t)np * 16, hipMemcpyHostToDevice));
+    // (a caller's prior: the host has the Jacobian in hand, so whether its zeros are exact is looked at, not assumed)
+    c->prior_span_ok = span_ok; c->prior_jac_exact = span_ok && chain && prior_jac_is_block_exact(np, p->lin_jac, p->blk_slot, colblk.data());
     c->arrow.prior_ok = flags.prior_ok; c->arrow.prior_chain = chain ? 1 : 0;
     c->prior_device_made = 0; c->prior_ext_coupled = flags.ext_coupled; c->prior_n = np; c->prior_nb = nb;
     for (int k = 0; k < 15 * W; ++k) c->h_prior_index[k] = index[k];
@@ -1238,8 +1243,9 @@ int glio_marginalize_keep_async(glio_ctx* c, const glio_state* s) {
     std::vector<double> x0((size_t)nbmax * 9, 0.0);
     const KeptSize k = marg_block_tables(W, c->sbp_n, c->prior_n, c->h_prior_index, s, slot.data(), kind.data(), idx.data(), x0.data());
     const int n = k.n, nb = k.nb, n_extra = nb - marg_kept_size(W, 0).nb;
-    std::vector<int> index(15 * W), colblk(n);
+    std::vector<int> index(15 * W), colblk(n), span(4 * (size_t)n);
     { TabError e; if (prior_index_tables(W, n, nb, slot.data(), kind.data(), idx.data(), index.data(), colblk.data(), &e)) return refused(e); }
+    const int span_ok = prior_span_tables(W, n, nb, slot.data(), kind.data(), idx.data(), colblk.data(), span.data());
     double *dJ, *dr; int* dok;
     rc = enqueue_marginalize(c, s, &dJ, &dr, &dok);
     if (rc) return rc;
@@ -1248,7 +1254,7 @@ int glio_marginalize_keep_async(glio_ctx* c, const glio_state* s) {
     // of the 0.33 ms)
     GnssDevExtra* ex = glio_extra(c);
     StageBatch sb;
-    { const int rs = stage_reserve(c, (size_t)nb * 9 * 8 + 3 * (size_t)nb * 4 + 15 * (size_t)W * 4 + (size_t)n * 4 + 8 * 64 + 64, &sb); if (rs != GLIO_OK) return rs; }
+    { const int rs = stage_reserve(c, (size_t)nb * 9 * 8 + 3 * (size_t)nb * 4 + 15 * (size_t)W * 4 + (size_t)n * 4 + (size_t)n * 16 + 9 * 64 + 64, &sb); if (rs != GLIO_OK) return rs; }
     { int rd = stage_d2d(&sb, c->d_prior_J0, dJ, (size_t)n * n * 8); if (rd == GLIO_OK) rd = stage_d2d(&sb, c->d_prior_r0, dr, (size_t)n * 8); if (rd != GLIO_OK) return rd; }
     STAGE(c->d_prior_x0, x0.data(), (size_t)nb * 9 * 8);
     STAGE(c->d_prior_slot, slot.data(), (size_t)nb * 4);
@@ -1256,6 +1262,7 @@ int glio_marginalize_keep_async(glio_ctx* c, const glio_state* s) {
     STAGE(c->d_prior_idx, idx.data(), (size_t)nb * 4);
     STAGE(c->d_prior_index, index.data(), (size_t)15 * W * 4);
     STAGE(ex->d_prior_colblk, colblk.data(), (size_t)n * 4);
+    STAGE(const_cast<int*>(glio_prior_span_dev(c, ex->d_prior_colblk)), span.data(), (size_t)n * 16);
     { const int rf = stage_flush(c, &sb); if (rf != GLIO_OK) return rf; }
     int* h_ok = reinterpret_cast<int*>(stage_result_word(&sb));      // (pinned: the 64 bytes reserved above, behind what the flush has sent)
     if (!h_ok) { glio_set_error("upload arena overflow"); return GLIO_E_STATE; }
@@ -1269,6 +1276,8 @@ int glio_marginalize_keep_async(glio_ctx* c, const glio_state* s) {
     //  are per (keyframe, local column); the arrow factorisation, which keeps one speed-bias chain, does not)
     c->arrow.prior_ok = n_extra == 0; c->arrow.prior_chain = chain;
     c->prior_device_made = 1;
+    // (the Jacobian never visits the host here: whether the root left exact zeros depends on the route the marginalization took, so the full rows stay)
+    c->prior_span_ok = span_ok; c->prior_jac_exact = 0;
     if (n_extra == 0) c->prior_ext_coupled = 0;
     c->sbp_n = 0;          // the reference's marg = true (Estimator.cpp:2517): the next window carries them in its prior
     glio_launch_gram(c, n);
@@ -1368,6 +1377,82 @@ int glio_debug_set_solve_id(glio_ctx* c, int id) {
     return GLIO_OK;
 }
 int glio_debug_solver_path(glio_ctx* c) { return c ? c->arrow.last_path : -1; }
+// ---- test hooks of the linearisation launch (tests/test_hip_linearize_entry.py; the switch itself: glio_debug_linearize_entry, factor_kernels.hip)
+// K3 workgroups per keyframe of the merged launch pinned to `nb` (0: the launch's own rule), so that two forms can be compared partial by partial
+int glio_debug_linearize_pin_nb(glio_ctx* c, int nb) {
+    if (!c || nb < 0 || nb > GLIO_K3_MAX_BLOCKS_PER_KF) return GLIO_E_ARG;
+    c->k3_bpk_pin = nb;
+    return GLIO_OK;
+}
+// One linearisation launch exactly as glio_solve queues it for this window (the chain path's launch where the window takes that path), from state `s` in
+// buffer `which`.  use_status = 0: the buffer is fixed by the caller.  use_status = 1: behind a status record {done, cand_pending, cur = 1 - which}, as
+// the launches of a solve's later groups run.  Returns the K3 workgroups per keyframe of the launch, or a negative error.
+// It rewrites the context's status record and state buffer: no solve may be in flight, and the next glio_solve starts from its own record as ever.
+int glio_debug_linearize_launch(glio_ctx* c, const glio_state* s, int which, int use_status, int done, int cand_pending) {
+    int rc = check_state(c, s);
+    if (rc) return rc;
+    if (which < 0 || which > 1) return GLIO_E_ARG;
+    rc = marg_pending_done(c);
+    if (rc) return rc;
+    rc = glio_assoc_finish_pending(c);
+    if (rc) return rc;
+    GLIO_HIP_CHECK(hipSetDevice(c->device));
+    const int n_ddt = s->n_ddt, nx = glio_x_size(c->W, n_ddt);
+    pack_state(c, s, c->h_xbuf);
+    SolverStatus st;
+    memset(&st, 0, sizeof st);
+    st.done = done; st.cand_pending = cand_pending; st.cur = 1 - which; st.n_ddt = n_ddt; st.radius = c->opts.initial_trust_region_radius; st.mu = TR_MIN_MU;
+    *c->h_status = st;
+    GLIO_HIP_CHECK(hipMemcpyAsync(c->d_status, c->h_status, sizeof st, hipMemcpyHostToDevice, c->stream));
+    GLIO_HIP_CHECK(hipMemcpyAsync(c->d_x[which], c->h_xbuf, (size_t)nx * 8, hipMemcpyHostToDevice, c->stream));
+    const int dense = glio_chain_kind(c, n_ddt) == 3 ? 2 : glio_solver_needs_dense_H(c, n_ddt);
+    enqueue_linearize(c, use_status, which, n_ddt, dense, 0);
+    GLIO_HIP_CHECK(hipGetLastError());
+    GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->last_n_ddt = n_ddt;
+    return c->last_k3_nb;
+}
+// The buffers a linearisation launch writes, for `which` = 0 / 1.  what: 0 K3 partials (W x nb x 28 doubles), 1 IMU pair blocks, 2 GNSS pair blocks,
+// 3 clock-drift blocks, 4 chain slices, 5 prior g, 6 prior cost, 7 prior H.  out = null: the size in bytes is returned.  fill >= 0: the buffer is
+// filled with that byte instead of being read.
+long long glio_debug_linearize_buffer(glio_ctx* c, int what, int which, void* out, long long cap, int fill) {
+    if (!c || which < 0 || which > 1) return GLIO_E_ARG;
+    if (hipSetDevice(c->device) != hipSuccess) return GLIO_E_HIP;
+    const size_t np = (size_t)c->prior_n, ne = (size_t)std::max(1, c->n_ddt_max);
+    unsigned char* base = nullptr;
+    size_t bytes = 0;
+    switch (what) {
+        case 0: bytes = (size_t)c->W * c->last_k3_nb * GLIO_LIDAR_ACC * 8; base = reinterpret_cast<unsigned char*>(c->d_lidar_partials + (size_t)which * glio_partials_stride(c)); break;
+        case 1: bytes = (size_t)c->W * sizeof(PairBlock); base = reinterpret_cast<unsigned char*>(c->d_imu_blocks + (size_t)which * c->W); break;
+        case 2: bytes = (size_t)c->W * c->W * sizeof(PairBlock); base = reinterpret_cast<unsigned char*>(c->d_gnss_blocks + (size_t)which * c->W * c->W); break;
+        case 3: bytes = ne * sizeof(DdtBlock); base = reinterpret_cast<unsigned char*>(c->d_ddt_blocks + (size_t)which * ne); break;
+        case 4: bytes = (size_t)c->W * GLIO_CS_SOURCES * GLIO_CS_STRIDE * 8; base = reinterpret_cast<unsigned char*>(c->d_chain_src + (size_t)which * c->W * GLIO_CS_SOURCES * GLIO_CS_STRIDE); break;
+        case 5: bytes = np * 8; base = reinterpret_cast<unsigned char*>(c->d_prior_g + (size_t)which * np); break;
+        case 6: bytes = 8; base = reinterpret_cast<unsigned char*>(c->d_prior_cost + which); break;
+        case 7: bytes = np * np * 8; base = reinterpret_cast<unsigned char*>(c->d_prior_H + (size_t)which * np * np); break;
+        default: return GLIO_E_ARG;
+    }
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return GLIO_E_HIP;
+    if (fill >= 0) { if (bytes && hipMemset(base, fill & 0xff, bytes) != hipSuccess) return GLIO_E_HIP; return (long long)bytes; }
+    if (!out) return (long long)bytes;
+    if (cap < (long long)bytes) return GLIO_E_ARG;
+    if (bytes && hipMemcpy(out, base, bytes, hipMemcpyDeviceToHost) != hipSuccess) return GLIO_E_HIP;
+    return (long long)bytes;
+}
+// What the installed prior's launch would be: out = {prior columns, spans walkable (prior_span_tables), J0 found exactly block diagonal, device made}
+int glio_debug_prior_form(glio_ctx* c, int32_t* out4) {
+    if (!c || !out4) return GLIO_E_ARG;
+    out4[0] = c->prior_n; out4[1] = c->prior_span_ok; out4[2] = c->prior_jac_exact; out4[3] = c->prior_device_made;
+    return GLIO_OK;
+}
+// CPU-callable (host arithmetic only): window_tables.h's span tables of a prior layout; returns prior_span_tables' verdict, or a negative error
+int glio_debug_prior_spans(int W, int np, int nb, const int32_t* blk_slot, const int32_t* blk_kind, const int32_t* blk_idx, int32_t* span_out) {
+    if (W < 1 || W > GLIO_MAX_WINDOW || np < 1 || nb < 1 || !blk_slot || !blk_kind || !blk_idx || !span_out) return GLIO_E_ARG;
+    std::vector<int> index(15 * (size_t)W), colblk(np);
+    TabError e;
+    if (prior_index_tables(W, np, nb, blk_slot, blk_kind, blk_idx, index.data(), colblk.data(), &e)) return GLIO_E_ARG;
+    return prior_span_tables(W, np, nb, blk_slot, blk_kind, blk_idx, colblk.data(), span_out);
+}
 int glio_debug_chain_fronts_used(glio_ctx* c) { return c ? c->arrow.last_fronts : -1; }
 int glio_debug_set_k3(glio_ctx* c, int bpk, int unroll) {
     if (!c || bpk < 1 || bpk > GLIO_K3_MAX_BLOCKS_PER_KF || (unroll != 1 && unroll != 2 && unroll != 4 && unroll != 8 && unroll != 12 && unroll != 14 && unroll != 18 && unroll != 21 && unroll != 22 && unroll != 24 && unroll != 32 && unroll != 33 && unroll != 34 && unroll != 35)) return GLIO_E_ARG;

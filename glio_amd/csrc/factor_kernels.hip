@@ -42,7 +42,46 @@ struct SmallArgs {
     double* chain_src; const short* chain_tabs; int pair_H;
     // speed-bias priors of the window after a loop closure (glio_set_speed_bias_priors): slots 0 .. sbp_n - 1, targets [sbp_n][9]
     int sbp_n; const double* sbp_target;
+    // the launch's entry form (glio_switches.h, LINEARIZE_ENTRY; glio_launch_linearize_all fills these, every other launcher leaves them 0)
+    int entry;                 // bit 0: the status record, and what a role can address from the arguments and its index, asked for in ONE first round
+    int prior_form;            // 1: the prior by keyframe -- 1 + PRIOR_CHAIN_H_BLOCKS workgroups, only the entries the chain slices hold, no pH
+    int prior_sparse;          // 1: J0 is exactly zero outside the keyframes' diagonal blocks (glio_set_prior looked): r and v walk a row's / column's span only
+    const int* pspan;          // [np][4] the spans of every prior column (window_tables.h, prior_span_tables)
+    int imu_slot[GLIO_MAX_WINDOW];                // slot_i of every IMU edge as the host knows it (h_imu_slot): the state is addressed without the record
 };
+// The status record as a launch sees it.  `deferred`: the record was asked for at entry, behind the role's other first-round loads, and is looked at by
+// entry_resolve; otherwise `which` was settled before anything else was read (the launch as it was, and every launch without a record).
+struct EntryStatus { int done, pend, cur; bool deferred; };
+// The three words of the record a linearisation launch looks at, by scalar loads issued HERE and waited for here.  The statement is a compiler barrier
+// for memory: every load the source has ahead of it is issued ahead of it (the optimiser otherwise sinks a load into the one branch that uses it, i.e.
+// back behind the record's round trip), and nothing behind it starts before the record is there.  So a role writes its first-round loads, then this
+// call: one round trip for all of them.
+// To re-verify after a compiler change (it costs time, never a result): hipcc --save-temps on this file, and in k_linearize_all<false> the s_load / global_load
+// instructions of a role's first round must stand between the last kernel-argument wait and the s_waitcnt of this statement, with no wait among them.
+// (Asked for whether or not the launch has a record to follow -- the context's record is always there to be read --, so that the record's address arrives
+//  with the role's other arguments and not behind a branch of its own, which would be a wait for everything asked for so far.)
+__device__ __forceinline__ void entry_status_load(const SolverStatus* st, const int use_status, EntryStatus& e) {
+    static_assert(offsetof(SolverStatus, done) == 0 && offsetof(SolverStatus, cur) == 16 && offsetof(SolverStatus, cand_pending) == 36, "the offsets below");
+    asm volatile("s_load_dword %0, %3, 0x0\n\ts_load_dword %1, %3, 0x24\n\ts_load_dword %2, %3, 0x10\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(e.done), "=&s"(e.pend), "=&s"(e.cur) : "s"(st) : "memory");
+    e.deferred = use_status != 0;
+}
+// ... and a GNSS group's record (32 bytes) in the same round: the compiler's own load of it is followed by its move into scalar registers, i.e. by a wait
+// of its own ahead of the record's loads
+typedef int entry_v8i __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void entry_status_load_group(const SolverStatus* st, const int use_status, EntryStatus& e, const GnssGroup* g, GnssGroup& gr) {
+    static_assert(sizeof(GnssGroup) == 32 && offsetof(GnssGroup, run_end) == 28, "eight words");
+    entry_v8i w;
+    asm volatile("s_load_dwordx8 %3, %5, 0x0\n\ts_load_dword %0, %4, 0x0\n\ts_load_dword %1, %4, 0x24\n\ts_load_dword %2, %4, 0x10\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&s"(e.done), "=&s"(e.pend), "=&s"(e.cur), "=&s"(w) : "s"(st), "s"(g) : "memory");
+    gr.slot_i = w[0]; gr.slot_j = w[1]; gr.dd_begin = w[2]; gr.dd_end = w[3]; gr.dop_begin = w[4]; gr.dop_end = w[5]; gr.run_begin = w[6]; gr.run_end = w[7];
+    e.deferred = use_status != 0;
+}
+// true: the launch runs behind a finished solve, or no candidate is pending -- it leaves every buffer alone
+__device__ __forceinline__ bool entry_resolve(const EntryStatus& e, int& which) {
+    if (e.deferred) { if (e.done || !e.pend) return true; which = 1 - e.cur; }
+    return false;
+}
 __device__ __forceinline__ double* chain_slice(const SmallArgs& a, const int which, const int slot, const int source) {
     return a.chain_src + (((size_t)which * a.W + slot) * GLIO_CS_SOURCES + source) * GLIO_CS_STRIDE;
 }
@@ -567,43 +606,121 @@ __device__ void gnss_block(const SmallArgs& a, const double* __restrict__ x, con
 //   r = r0 + J0 dx ; local Jacobian = J0 * blockdiag(M_b), M_b = I or 2 s Qleft(q0^-1)[1:4,:] P(q)
 //   H = M^T (J0^T J0) M, g = M^T J0^T r, cost = |r|^2/2
 // ------------------------------------------------------------------------------------------------
-#define PRIOR_H_BLOCKS 24     // workgroups that share the H = M^T A0 M entries; one more does r, g, cost
+#define PRIOR_H_BLOCKS 24     // dense form: workgroups that share the H = M^T A0 M entries; one more does r, g, cost
+#define PRIOR_CHAIN_H_BLOCKS 4     // the form by keyframe: workgroups that share the entries of the chain slices (32 lanes per row of H, four rows each at the
+                                   // benchmark's 123 columns); any number up to 8 leaves K3 the same 21 workgroups per keyframe there
 
+// one block's part of dx and its M_b from the block's table entries, its linearisation point x0 and its part xv of the state (3, 4 or 9 values)
+__device__ __forceinline__ void prior_dx_M_block(const int marg, const int b, const int kind, const int idx, const double* x0, const double* xv, double* dx, double* Mb) {
+    if (kind == GLIO_BLK_TRANS) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) dx[idx + k] = xv[k] - x0[k];
+    } else if (kind == GLIO_BLK_SPEEDBIAS) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) dx[idx + k] = xv[k] - x0[k];
+    } else {
+        double q[4], L[16], P[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = xv[k];
+        const double sg = fm_prior_quat(x0, q, dx + idx, L);
+        d_plus_jac(q, P);
+        for (int p = 0; p < 3; ++p)
+            for (int c = 0; c < 3; ++c) {
+                double acc = 0;
+                for (int k = 0; k < 4; ++k) acc += L[(1 + p) * 4 + k] * P[k * 3 + c];
+                Mb[9 * b + p * 3 + c] = marg ? sg * L[(1 + p) * 4 + 1 + c] : sg * acc;
+            }
+    }
+}
+// where a block's part of the state starts in x
+__device__ __forceinline__ int prior_x_offset(const int W, const int s, const int kind) {
+    return kind == GLIO_BLK_TRANS ? 3 * s : (kind == GLIO_BLK_SPEEDBIAS ? 7 * W + 9 * s : 3 * W + 4 * s);
+}
 // dx [np] and the 3x3 blocks M_b of the quaternion blocks, into LDS (every prior workgroup recomputes them)
 __device__ __forceinline__ void prior_dx_M(const SmallArgs& a, const double* __restrict__ x, double* dx, double* Mb) {
     const int tid = threadIdx.x, nb = a.npb, W = a.W;
     for (int b = tid; b < nb; b += SF_THREADS) {
         const int s = a.pslot[b], kind = a.pkind[b], idx = a.pidx[b];
-        const double* x0 = a.px0 + 9 * b;
-        if (kind == GLIO_BLK_TRANS) {
-            for (int k = 0; k < 3; ++k) dx[idx + k] = x[3 * s + k] - x0[k];
-        } else if (kind == GLIO_BLK_SPEEDBIAS) {
-            for (int k = 0; k < 9; ++k) dx[idx + k] = x[7 * W + 9 * s + k] - x0[k];
-        } else {
-            double q[4], L[16], P[12];
-            for (int k = 0; k < 4; ++k) q[k] = x[3 * W + 4 * s + k];
-            const double sg = fm_prior_quat(x0, q, dx + idx, L);
-            d_plus_jac(q, P);
-            for (int p = 0; p < 3; ++p)
-                for (int c = 0; c < 3; ++c) {
-                    double acc = 0;
-                    for (int k = 0; k < 4; ++k) acc += L[(1 + p) * 4 + k] * P[k * 3 + c];
-                    Mb[9 * b + p * 3 + c] = a.marg ? sg * L[(1 + p) * 4 + 1 + c] : sg * acc;
-                }
-        }
+        const double* xs = x + prior_x_offset(W, s, kind);
+        double x0[9], xv[9];
+        const int len = kind == GLIO_BLK_TRANS ? 3 : (kind == GLIO_BLK_SPEEDBIAS ? 9 : 4);
+#pragma unroll
+        for (int k = 0; k < 9; ++k) { x0[k] = k < len ? a.px0[9 * b + k] : 0.0; xv[k] = k < len ? xs[k] : 0.0; }
+        prior_dx_M_block(a.marg, b, kind, idx, x0, xv, dx, Mb);
     }
     __syncthreads();
 }
 
 // (PRIOR_MAX_NP, PRIOR_MAX_NB: glio_device.h -- glio_set_prior and the marginalization hold every layout to them)
 
+// entry j of g = M^T v (column j lies in block b, a quaternion block or not, whose first column is idx)
+__device__ __forceinline__ double prior_g_entry(const int j, const int b, const bool quat, const int idx, const double* Mb, const double* v) {
+    if (quat) { const int c = j - idx; return Mb[9 * b + 0 * 3 + c] * v[idx] + Mb[9 * b + 1 * 3 + c] * v[idx + 1] + Mb[9 * b + 2 * 3 + c] * v[idx + 2]; }
+    return v[j];
+}
+// cost = |r|^2 / 2, by the first wavefront
+__device__ __forceinline__ void prior_cost(const double* r, const int np, double* cost) {
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        double s = 0;
+        for (int i = tid; i < np; i += 64) s += r[i] * r[i];
+        s = wave_sum(s);
+        if (tid == 0) *cost = 0.5 * s;
+    }
+}
+// Entry (i, j) of H = M^T A0 M: the up to nine entries of A0 it is made of, and the entry from them.  (qi / qj: i / j is a column of a quaternion block, whose
+// first column is ii / jj; ci / cj: the column inside its block)
+__device__ __forceinline__ void prior_H_load(const double* __restrict__ A0, const int np, const int i, const int j, const bool qi, const int ii, const bool qj, const int jj, double (&av)[9]) {
+    if (!qi && !qj) av[0] = A0[(size_t)i * np + j];
+    else if (qi && !qj) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) av[k] = A0[(size_t)(ii + k) * np + j];
+    } else if (!qi && qj) {
+#pragma unroll
+        for (int l = 0; l < 3; ++l) av[l] = A0[(size_t)i * np + jj + l];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int l = 0; l < 3; ++l) av[3 * k + l] = A0[(size_t)(ii + k) * np + jj + l];
+    }
+}
+__device__ __forceinline__ double prior_H_value(const double (&av)[9], const double* Mb, const bool qi, const int bi, const int ci, const bool qj, const int bj, const int cj) {
+    double s;
+    if (!qi && !qj) s = av[0];
+    else if (qi && !qj) {
+        s = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s += Mb[9 * bi + k * 3 + ci] * av[k];
+    } else if (!qi && qj) {
+        s = 0;
+#pragma unroll
+        for (int l = 0; l < 3; ++l) s += av[l] * Mb[9 * bj + l * 3 + cj];
+    } else {
+        s = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            double t = 0;
+#pragma unroll
+            for (int l = 0; l < 3; ++l) t += av[3 * k + l] * Mb[9 * bj + l * 3 + cj];
+            s += Mb[9 * bi + k * 3 + ci] * t;
+        }
+    }
+    return s;
+}
+// row / column of a prior column inside its keyframe's 15 (T 0-2, Q 3-5, SB 6-14)
+__device__ __forceinline__ int prior_local(const int kind, const int c) { return (kind == GLIO_BLK_TRANS ? 0 : (kind == GLIO_BLK_QUAT ? 3 : 6)) + c; }
+
 // workgroup 0 of the prior: r = r0 + J0 dx (one wavefront per row, coalesced), v = J0^T r, g = M^T v, cost
 struct PriorLds { double dx[PRIOR_MAX_NP], r[PRIOR_MAX_NP], v[PRIOR_MAX_NP], Mb[9 * PRIOR_MAX_NB]; };
-union SmallLds { ImuLds imu; GnssLds gn; PriorLds pr; };
+// ... and of the form by keyframe (np <= SF_THREADS there: one lane per column), with the tables the workgroup walks by
+struct PriorKfLds { double dx[SF_THREADS], r[SF_THREADS], v[SF_THREADS], Mb[9 * PRIOR_MAX_NB]; int4 span[SF_THREADS]; int colblk[SF_THREADS], bkind[PRIOR_MAX_NB], bidx[PRIOR_MAX_NB], bslot[PRIOR_MAX_NB]; };
+static_assert(PRIOR_MAX_NB <= SF_THREADS, "one lane per block of the prior");
+union SmallLds { ImuLds imu; GnssLds gn; PriorLds pr; PriorKfLds pk; };
 __device__ void prior_rg_block(const SmallArgs& a, const double* __restrict__ x, double* gout, double* cost, unsigned char* pool) {
     PriorLds& lds_ = *reinterpret_cast<PriorLds*>(pool);
     double (&dx)[PRIOR_MAX_NP] = lds_.dx; double (&r)[PRIOR_MAX_NP] = lds_.r; double (&v)[PRIOR_MAX_NP] = lds_.v; double (&Mb)[9 * PRIOR_MAX_NB] = lds_.Mb;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, np = a.np;
+    const int tid = threadIdx.x, np = a.np;
     prior_dx_M(a, x, dx, Mb);
     // r = r0 + J0 dx: one lane per row, four independent accumulators -- the loads of a row do not depend on each other, so
     // the whole product costs a few latency rounds instead of one wave-reduction round trip per row
@@ -615,7 +732,6 @@ __device__ void prior_rg_block(const SmallArgs& a, const double* __restrict__ x,
         for (; k < np; ++k) s0 += row[k] * dx[k];
         r[i] = a.pr0[i] + ((s0 + s1) + (s2 + s3));
     }
-    (void)lane; (void)wv;
     __syncthreads();
     for (int j = tid; j < np; j += SF_THREADS) {
         double s0 = 0, s1 = 0, s2 = 0, s3 = 0;
@@ -630,19 +746,9 @@ __device__ void prior_rg_block(const SmallArgs& a, const double* __restrict__ x,
     __syncthreads();
     for (int j = tid; j < np; j += SF_THREADS) {
         const int b = a.pcolblk[j];
-        double s;
-        if (a.pkind[b] == GLIO_BLK_QUAT) {
-            const int idx = a.pidx[b], c = j - idx;
-            s = Mb[9 * b + 0 * 3 + c] * v[idx] + Mb[9 * b + 1 * 3 + c] * v[idx + 1] + Mb[9 * b + 2 * 3 + c] * v[idx + 2];
-        } else s = v[j];
-        gout[j] = s;
+        gout[j] = prior_g_entry(j, b, a.pkind[b] == GLIO_BLK_QUAT, a.pidx[b], Mb, v);
     }
-    if (tid < 64) {
-        double s = 0;
-        for (int i = tid; i < np; i += 64) s += r[i] * r[i];
-        s = wave_sum(s);
-        if (tid == 0) *cost = 0.5 * s;
-    }
+    prior_cost(r, np, cost);
 }
 
 // workgroups 1..PRIOR_H_BLOCKS: rows i = part, part + PRIOR_H_BLOCKS, ... of H = M^T A0 M
@@ -660,32 +766,183 @@ __device__ void prior_H_block(const SmallArgs& a, const double* __restrict__ x, 
             const int bj = a.pcolblk[j];
             const bool qj = a.pkind[bj] == GLIO_BLK_QUAT;
             const int jj = a.pidx[bj], cj = j - jj;
-            double s;
-            if (!qi && !qj) s = a.pA0[(size_t)i * np + j];
-            else if (qi && !qj) {
-                s = 0;
-                for (int k = 0; k < 3; ++k) s += Mb[9 * bi + k * 3 + ci] * a.pA0[(size_t)(ii + k) * np + j];
-            } else if (!qi && qj) {
-                s = 0;
-                for (int l = 0; l < 3; ++l) s += a.pA0[(size_t)i * np + jj + l] * Mb[9 * bj + l * 3 + cj];
-            } else {
-                s = 0;
-                for (int k = 0; k < 3; ++k) {
-                    double t = 0;
-                    for (int l = 0; l < 3; ++l) t += a.pA0[(size_t)(ii + k) * np + jj + l] * Mb[9 * bj + l * 3 + cj];
-                    s += Mb[9 * bi + k * 3 + ci] * t;
-                }
-            }
+            double av[9];
+            prior_H_load(a.pA0, np, i, j, qi, ii, qj, jj, av);
+            const double s = prior_H_value(av, Mb, qi, bi, ci, qj, bj, cj);
             H[(size_t)i * np + j] = s;
             if (a.chain_src && !a.marg) {        // chain layout: same-keyframe entries (lower triangle) and entries towards the keyframe below
                 const int sr = slot_i, sc = a.pslot[bj];
-                const int lr = (a.pkind[bi] == GLIO_BLK_TRANS ? 0 : (a.pkind[bi] == GLIO_BLK_QUAT ? 3 : 6)) + ci;
-                const int lc = (a.pkind[bj] == GLIO_BLK_TRANS ? 0 : (a.pkind[bj] == GLIO_BLK_QUAT ? 3 : 6)) + cj;
+                const int lr = prior_local(a.pkind[bi], ci), lc = prior_local(a.pkind[bj], cj);
                 if (sr == sc) { if (lc <= lr) chain_slice(a, which, sr, 4)[lr * (lr + 1) / 2 + lc] = s; }
                 else if (sr == sc + 1) chain_slice(a, which, sc, 4)[120 + lr * 15 + lc] = s;
             }
         }
     }
+}
+
+// ---- the prior by keyframe (SmallArgs::prior_form: the keyframe-chain path, whose step reads the chain slices, g and the cost and nothing else) ----
+// First round of every workgroup of this form: the table entries and the linearisation point of the lane's block, the block and the spans of the lane's
+// column -- addresses that follow from the arguments and the lane alone, so they travel with the status record.
+struct PriorPre { int s, kind, idx, cb; int4 sp; double x0[9]; };
+__device__ __forceinline__ void prior_pre_load(const SmallArgs& a, PriorPre& p) {
+    const int tid = threadIdx.x, b = tid < a.npb ? tid : 0, j = tid < a.np ? tid : 0;
+    p.s = a.pslot[b]; p.kind = a.pkind[b]; p.idx = a.pidx[b];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) p.x0[k] = a.px0[9 * b + k];
+    p.cb = a.pcolblk[j];
+    p.sp = reinterpret_cast<const int4*>(a.pspan)[j];
+}
+// Second round, first half: the lane's block asks for its part of the state (nine values from the block's offset: x is 16 W + n_ddt long, a block's part
+// starts at most at 7 W + 9 (W - 1), and what lies behind its 3 or 4 values is not used)
+__device__ __forceinline__ void prior_state_load(const SmallArgs& a, const double* __restrict__ x, const PriorPre& p, double (&xv)[9]) {
+    const double* xs = x + prior_x_offset(a.W, p.s, p.kind);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) xv[k] = xs[k];
+}
+__device__ __forceinline__ void prior_tables_to_lds(const SmallArgs& a, const PriorPre& p, PriorKfLds& L) {
+    const int tid = threadIdx.x;
+    if (tid < a.npb) { L.bkind[tid] = p.kind; L.bidx[tid] = p.idx; L.bslot[tid] = p.s; }
+    if (tid < a.np) { L.colblk[tid] = p.cb; L.span[tid] = p.sp; }
+}
+
+// r, g and the cost.  With prior_sparse a row of J0 (and a column, for v = J0^T r) is walked over its keyframe's span only: the products left out are
+// (exact zero) x dx, which add +-0 to sums that start at +0 -- no bit of r, v, g or the cost changes for a finite state.  The walk starts at the
+// multiple of four below the span and keeps the full walk's assignment of terms to its four accumulators (term k goes to accumulator k & 3, the np & 3
+// terms at the end of a row to the first), each accumulator adding its terms in ascending order as before.
+#define PRIOR_WALK (PRIOR_SPAN_MAX + 4)
+__device__ void prior_rg_block_kf(const SmallArgs& a, EntryStatus es, int which, unsigned char* pool) {
+    PriorKfLds& L = *reinterpret_cast<PriorKfLds*>(pool);
+    const int tid = threadIdx.x, np = a.np, np4 = np & ~3;
+    const bool row = tid < np;
+    PriorPre p;
+    prior_pre_load(a, p);
+    const double r0 = a.pr0[row ? tid : 0];
+    if (a.entry & 1) entry_status_load(a.st, a.use_status, es);
+    if (entry_resolve(es, which)) return;
+    const double* x = which ? a.x1 : a.x0;
+    double xv[9];
+    prior_state_load(a, x, p, xv);
+    const bool sparse = a.prior_sparse != 0;
+    const int k0 = p.sp.x & ~3;
+    double jr[PRIOR_WALK], jc[PRIOR_WALK];
+    if (sparse && row) {
+#pragma unroll
+        for (int q = 0; q < PRIOR_WALK; ++q) {
+            const int k = k0 + q;
+            const bool in = k < p.sp.y;
+            jr[q] = in ? a.pJ0[(size_t)tid * np + k] : 0.0;
+            jc[q] = in ? a.pJ0[(size_t)k * np + tid] : 0.0;
+        }
+    }
+    prior_tables_to_lds(a, p, L);
+    if (tid < a.npb) prior_dx_M_block(a.marg, tid, p.kind, p.idx, p.x0, xv, L.dx, L.Mb);
+    __syncthreads();
+    if (row) {
+        double s[4] = {0, 0, 0, 0};
+        if (sparse) {
+#pragma unroll
+            for (int q = 0; q < PRIOR_WALK; ++q) {
+                const int k = k0 + q;
+                // (one fused multiply-add per term, as the full walk's `s += row[k] * dx[k]` compiles to under hipcc's default -ffp-contract=fast: written out,
+                //  because a product shared by the two targets below would be rounded on its own.  Should a compiler stop fusing the full walk, the "handed"
+                //  cases of tests/test_hip_linearize_entry.py::test_every_mask_leaves_the_same_buffers fail on `prior g`: that is the check of this pairing.)
+                if (k < p.sp.y && k < np4) s[q & 3] = __builtin_fma(jr[q], L.dx[k], s[q & 3]);
+                if (k < p.sp.y && k >= np4) s[0] = __builtin_fma(jr[q], L.dx[k], s[0]);
+            }
+        } else {
+            const double* rowp = a.pJ0 + (size_t)tid * np;
+            int k = 0;
+            for (; k + 4 <= np; k += 4) { s[0] += rowp[k] * L.dx[k]; s[1] += rowp[k + 1] * L.dx[k + 1]; s[2] += rowp[k + 2] * L.dx[k + 2]; s[3] += rowp[k + 3] * L.dx[k + 3]; }
+            for (; k < np; ++k) s[0] += rowp[k] * L.dx[k];
+        }
+        L.r[tid] = r0 + ((s[0] + s[1]) + (s[2] + s[3]));
+    }
+    __syncthreads();
+    if (row) {
+        double s[4] = {0, 0, 0, 0};
+        if (sparse) {
+#pragma unroll
+            for (int q = 0; q < PRIOR_WALK; ++q) {
+                const int i = k0 + q;
+                if (i < p.sp.y && i < np4) s[q & 3] = __builtin_fma(jc[q], L.r[i], s[q & 3]);
+                if (i < p.sp.y && i >= np4) s[0] = __builtin_fma(jc[q], L.r[i], s[0]);
+            }
+        } else {
+            int i = 0;
+            for (; i + 4 <= np; i += 4) {
+                s[0] += a.pJ0[(size_t)i * np + tid] * L.r[i]; s[1] += a.pJ0[(size_t)(i + 1) * np + tid] * L.r[i + 1];
+                s[2] += a.pJ0[(size_t)(i + 2) * np + tid] * L.r[i + 2]; s[3] += a.pJ0[(size_t)(i + 3) * np + tid] * L.r[i + 3];
+            }
+            for (; i < np; ++i) s[0] += a.pJ0[(size_t)i * np + tid] * L.r[i];
+        }
+        L.v[tid] = (s[0] + s[1]) + (s[2] + s[3]);
+    }
+    __syncthreads();
+    if (row) {
+        const int b = p.cb;
+        a.pg[(size_t)which * np + tid] = prior_g_entry(tid, b, L.bkind[b] == GLIO_BLK_QUAT, L.bidx[b], L.Mb, L.v);
+    }
+    prior_cost(L.r, np, a.pcost + which);
+}
+
+// The entries of H = M^T A0 M that a chain slice holds: for row i the columns of i's own keyframe up to the diagonal (in the keyframe's own order)
+// and the columns of the keyframe below.  32 lanes per row -- 16 for either span -- and rows 32-lane group by 32-lane group over the
+// PRIOR_CHAIN_H_BLOCKS workgroups; a lane asks for the A0 entries of four rows before it uses the first.  The dense form computes these same entries by
+// the same expressions (prior_H_load / prior_H_value) and every other entry of H besides, into pH, which no kernel of the chain path reads.
+struct PriorEnt { bool on, qi, qj; int i, j, bi, bj, ii, jj, ci, cj, off, slot; };
+__device__ __forceinline__ PriorEnt prior_chain_entry(const PriorKfLds& L, const int np, const int i, const int l) {
+    PriorEnt e;
+    e.on = false; e.i = i;
+    if (i >= np) return e;
+    const int4 sp = L.span[i];
+    const bool own = l < 16;
+    e.j = own ? sp.x + l : sp.z + (l - 16);
+    if (e.j >= (own ? sp.y : sp.w)) return e;
+    e.bi = L.colblk[i]; e.bj = L.colblk[e.j];
+    const int ki = L.bkind[e.bi], kj = L.bkind[e.bj];
+    e.qi = ki == GLIO_BLK_QUAT; e.qj = kj == GLIO_BLK_QUAT;
+    e.ii = L.bidx[e.bi]; e.jj = L.bidx[e.bj]; e.ci = i - e.ii; e.cj = e.j - e.jj;
+    const int lr = prior_local(ki, e.ci), lc = prior_local(kj, e.cj);
+    if (own && lc > lr) return e;
+    e.slot = L.bslot[e.bj];          // (own: the row's keyframe; below: the keyframe whose slice holds the coupling)
+    e.off = own ? lr * (lr + 1) / 2 + lc : 120 + lr * 15 + lc;
+    e.on = true;
+    return e;
+}
+__device__ void prior_chain_H_block(const SmallArgs& a, EntryStatus es, int which, const int part, unsigned char* pool) {
+    PriorKfLds& L = *reinterpret_cast<PriorKfLds*>(pool);
+    const int tid = threadIdx.x, np = a.np;
+    PriorPre p;
+    prior_pre_load(a, p);
+    if (a.entry & 1) entry_status_load(a.st, a.use_status, es);
+    if (entry_resolve(es, which)) return;
+    const double* x = which ? a.x1 : a.x0;
+    double xv[9];
+    prior_state_load(a, x, p, xv);
+    prior_tables_to_lds(a, p, L);
+    __syncthreads();
+    constexpr int G = (SF_THREADS / 32) * PRIOR_CHAIN_H_BLOCKS;
+    const int g32 = part * (SF_THREADS / 32) + (tid >> 5), l = tid & 31;
+    double av[4][9];
+    auto load = [&](const int i0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const PriorEnt e = prior_chain_entry(L, np, i0 + q * G, l);
+            if (e.on) prior_H_load(a.pA0, np, e.i, e.j, e.qi, e.ii, e.qj, e.jj, av[q]);
+        }
+    };
+    auto finish = [&](const int i0) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const PriorEnt e = prior_chain_entry(L, np, i0 + q * G, l);
+            if (e.on) chain_slice(a, which, e.slot, 4)[e.off] = prior_H_value(av[q], L.Mb, e.qi, e.bi, e.ci, e.qj, e.bj, e.cj);
+        }
+    };
+    load(g32);          // (in flight while the blocks' M_b are worked out)
+    if (tid < a.npb) prior_dx_M_block(a.marg, tid, p.kind, p.idx, p.x0, xv, L.dx, L.Mb);
+    __syncthreads();
+    finish(g32);
+    for (int i0 = g32 + 4 * G; i0 < np; i0 += 4 * G) { load(i0); finish(i0); }
 }
 
 __device__ void small_factors_body(const SmallArgs& a, int role);
@@ -703,14 +960,22 @@ __global__ __launch_bounds__(SF_THREADS) void k_small_factors(const SmallArgs a)
 __device__ void small_factors_body(const SmallArgs& a, const int role) {
     __shared__ __attribute__((aligned(16))) unsigned char pool[sizeof(SmallLds)];
     int which = a.fixed_which;
-    if (a.use_status) {
+    // Entry form (SmallArgs::entry bit 0): the record is asked for by entry_status_load once the role has asked for everything else it can address
+    // without it -- one round trip for both.  A launch behind a finished solve returns at entry_resolve, before its first store.
+    EntryStatus es = {0, 1, 0, false};
+    const bool early = (a.entry & 1) != 0;
+    if (a.use_status && !early) {
         if (a.st->done || !a.st->cand_pending) return;
         which = 1 - a.st->cur;
     }
-    const double* x = which ? a.x1 : a.x0;
     int b = role;                // (the K3 partials are summed by their consumers, k_assemble / k_lidar_reduce: this kernel does not depend on K3)
     if (b < a.n_imu) {
-        const int si = a.imu[b].slot_i, sj = si + 1, W = a.W;
+        // slot_i from the arguments (the host's h_imu_slot, what glio_set_imu* installed the records with) instead of the record: the state is addressed
+        // as soon as the status record is there, not a round trip later.  (Both buffers' 32 doubles ahead of the record would be 128 scalar registers.)
+        const int si = (a.entry & 1) ? a.imu_slot[b] : a.imu[b].slot_i, sj = si + 1, W = a.W;
+        if (early) entry_status_load(a.st, a.use_status, es);
+        if (entry_resolve(es, which)) return;
+        const double* x = which ? a.x1 : a.x0;
         imu_block(a.gravity, x + 3 * si, x + 3 * W + 4 * si, x + 7 * W + 9 * si, x + 3 * sj, x + 3 * W + 4 * sj, x + 7 * W + 9 * sj,
                   a.imu[b], a.imu_blocks + (size_t)which * a.W + b, nullptr, a.marg, pool,
                   a.marg ? nullptr : chain_slice(a, which, si, 0), a.marg ? nullptr : chain_slice(a, which, sj, 1), (b == 0 && a.dbg) ? a.dbg + 190 : nullptr, a.pair_H != 0,
@@ -720,11 +985,25 @@ __device__ void small_factors_body(const SmallArgs& a, const int role) {
     }
     b -= a.n_imu;
     if (b < a.n_groups) {
-        gnss_block(a, x, a.groups[b], b, a.gnss_blocks + (size_t)which * a.gnss_stride + b, a.ddt_blocks + (size_t)which * a.ddt_stride, pool, which);
+        // the group's record (its slots and the ranges of its factors) beside the status record: what it addresses -- the state, the factors -- is one round behind both
+        GnssGroup gr;
+        if (early) entry_status_load_group(a.st, a.use_status, es, a.groups + b, gr);
+        else gr = a.groups[b];
+        if (entry_resolve(es, which)) return;
+        const double* x = which ? a.x1 : a.x0;
+        gnss_block(a, x, gr, b, a.gnss_blocks + (size_t)which * a.gnss_stride + b, a.ddt_blocks + (size_t)which * a.ddt_stride, pool, which);
         return;
     }
     b -= a.n_groups;
     if (a.has_prior) {
+        if (a.prior_form) {
+            if (b == 0) prior_rg_block_kf(a, es, which, pool);
+            else prior_chain_H_block(a, es, which, b - 1, pool);
+            return;
+        }
+        if (early) entry_status_load(a.st, a.use_status, es);
+        if (entry_resolve(es, which)) return;
+        const double* x = which ? a.x1 : a.x0;
         if (b == 0) prior_rg_block(a, x, a.pg + (size_t)which * a.np, a.pcost + which, pool);
         else prior_H_block(a, x, a.pH + (size_t)which * a.np * a.np, b - 1, pool, which);
     }
@@ -743,6 +1022,8 @@ struct K3Args {
     // the first group of a solve (first_words > 0): every workgroup reads the state from the mapped host copy (SmallArgs::x0 points there, no status
     // check), and workgroup first_wg -- an idle one where there is one -- leaves [status | state] in device memory for the launches that follow
     const unsigned long long* first_src; unsigned long long* first_dst; int first_words, first_wg;
+    // entry form: the residual count of every keyframe as the host holds it (h_count), so that no K3 workgroup waits for count[kf] before its first data load
+    int count_in_args; int count_h[GLIO_MAX_WINDOW];
 };
 template <bool F32>
 __global__ __launch_bounds__(SF_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_linearize_all(const SmallArgs a, const K3Args k) {
@@ -767,24 +1048,56 @@ __global__ __launch_bounds__(SF_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2
     if (role >= 0) { small_factors_body(a, role); return; }
 #endif
     int which = a.fixed_which;
-    if (a.use_status) {
-        if (a.st->done || !a.st->cand_pending) return;
-        which = 1 - a.st->cur;
-    }
-    if (k.first_words > 0 && b == k.first_wg) {      // (what k_stage_in did in a launch of its own; nobody in THIS launch reads the destination)
-        for (int w = threadIdx.x; w < k.first_words; w += SF_THREADS) k.first_dst[w] = __builtin_nontemporal_load(k.first_src + w);
-    }
     // workgroups [skip_lo, skip_hi) stay idle: in dispatch order they would land in the second slot of the CUs that run the
     // small-factor workgroups and slow those (the launch's long pole) down
     // (the small-factor workgroups two to a CU, [0, n/2) and [256, 256 + n/2), and every other slot for K3 -- 22 instead of 19 workgroups per keyframe:
     //  16.2 us against 12.9; with K3 workgroups in those slots 15.7.  A small-factor workgroup wants its CU alone.)
-    if (b >= k.skip_lo && b < k.skip_hi) return;
-    b -= k.n_small + (b >= k.skip_hi ? k.skip_hi - k.skip_lo : 0);
-    if (b >= k.n_k3) return;
-    const int kf = b / k.nb, bx = b - kf * k.nb;
+    const bool idle = b >= k.skip_lo && b < k.skip_hi;
+    const int bk = b - k.n_small - (b >= k.skip_hi ? k.skip_hi - k.skip_lo : 0);
+    const bool work = !idle && bk < k.n_k3;
+    const int kf = work ? bk / k.nb : 0, bx = bk - kf * k.nb;
+    const bool early = !F32 && (a.entry & 1);
+    int n = 0;
+    double t[3] = {0, 0, 0}, q[4] = {1, 0, 0, 0};
+    if (early) {
+        // Entry form: which workgroup this is follows from its index alone, so the status record, the keyframe's count (an argument) and its pose out of BOTH
+        // state buffers (14 doubles) are asked for in one round; the record then picks the pose and the output buffer, or ends the workgroup before its first
+        // store.  The other form waits for the record, then for count[kf], and only then for the pose and the first correspondences.
+        EntryStatus es = {0, 1, 0, false};
+        n = k.count_in_args ? k.count_h[kf] : k.count[kf];
+        double t0[3], q0[4], t1[3], q1[4];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { t0[c] = a.x0[3 * kf + c]; t1[c] = a.x1[3 * kf + c]; }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { q0[c] = a.x0[3 * a.W + 4 * kf + c]; q1[c] = a.x1[3 * a.W + 4 * kf + c]; }
+        entry_status_load(a.st, a.use_status, es);
+        if (entry_resolve(es, which)) return;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) t[c] = which ? t1[c] : t0[c];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) q[c] = which ? q1[c] : q0[c];
+    } else if (a.use_status) {
+        if (a.st->done || !a.st->cand_pending) return;
+        which = 1 - a.st->cur;
+    }
+    // (what k_stage_in did in a launch of its own.  Nobody in THIS launch USES the destination: in the entry form every workgroup's entry_status_load reads the
+    //  record's three words there while this copy writes them, but a first launch has no record to follow -- use_status is 0, `deferred` false -- and the
+    //  words are dropped unread; aligned 4-byte loads beside aligned 8-byte stores, no result depends on which value they saw)
+    if (k.first_words > 0 && b == k.first_wg) {
+        for (int w = threadIdx.x; w < k.first_words; w += SF_THREADS) k.first_dst[w] = __builtin_nontemporal_load(k.first_src + w);
+    }
+    if (!work) return;
     double* part = k.partials + (size_t)which * k.pstride;
-    if (F32) k3_body_f32<true>(k.pts, k.planes, k.count, k.cap, which ? a.x1 : a.x0, a.W, k.lc, part, kf, bx, k.nb, k3f_tile, k3f_red);
-    else k3_body<2, false, true, true>(k.pts, k.planes, k.scores, k.count, k.cap, which ? a.x1 : a.x0, a.W, k.lc, part, kf, bx, k.nb);
+    const double* x = which ? a.x1 : a.x0;
+    if (F32) { k3_body_f32<true>(k.pts, k.planes, k.count, k.cap, x, a.W, k.lc, part, kf, bx, k.nb, k3f_tile, k3f_red); return; }
+    if (!early) {
+        n = k.count[kf];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) t[c] = x[3 * kf + c];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) q[c] = x[3 * a.W + 4 * kf + c];
+    }
+    k3_body_at<2, false, true, true>(k.pts, k.planes, k.scores, n, k.cap, t, q, k.lc, part, kf, bx, k.nb);
 }
 
 // fixed-order sum of the K3 partials of keyframe blockIdx.x into its 28-double block (consumers that want the blocks
@@ -1111,7 +1424,16 @@ void glio_launch_gram(glio_ctx* c, int np) {
 // ------------------------------------------------------------------------------------------------
 GnssDevExtra* glio_extra(glio_ctx* c);   // defined in capi.hip
 
-static int fill_small_args(glio_ctx* c, int use_status_cand, int which, int n_ddt, int marg, SmallArgs& a) {
+// how many workgroups the prior takes in either form (the dense one: 1 + PRIOR_H_BLOCKS; by keyframe: 1 + PRIOR_CHAIN_H_BLOCKS)
+static int prior_workgroups(int has_prior, int by_keyframe) { return has_prior ? 1 + (by_keyframe ? PRIOR_CHAIN_H_BLOCKS : PRIOR_H_BLOCKS) : 0; }
+// May this launch take the prior by keyframe?  Only where nothing reads pH: a linearisation for the keyframe-chain step (no dense assembly behind it, no
+// marginalization), chain slices in place; the prior itself block diagonal by keyframe (arrow.prior_chain, as the chain path requires anyway) in a layout
+// that can be walked by span, one lane per column.
+static bool prior_by_keyframe(const glio_ctx* c, int marg) {
+    return c->prior_n > 0 && !marg && c->d_chain_src && c->want_pair_H == 0 && c->arrow.prior_chain && c->prior_span_ok && c->prior_n <= SF_THREADS;
+}
+// `entry`: the LINEARIZE_ENTRY bits this launch works with (glio_launch_linearize_all; every other launcher passes 0: the forms as they were)
+static int fill_small_args(glio_ctx* c, int use_status_cand, int which, int n_ddt, int marg, SmallArgs& a, int entry = 0) {
     a.marg = marg;
     a.dbg = c->arrow.d_dbg + 64;
     GnssDevExtra* ex = glio_extra(c);
@@ -1130,8 +1452,15 @@ static int fill_small_args(glio_ctx* c, int use_status_cand, int which, int n_dd
     a.pH = c->d_prior_H; a.pg = c->d_prior_g; a.pcost = c->d_prior_cost; a.pwork = c->d_prior_work;
     a.chain_src = c->d_chain_src; a.chain_tabs = c->d_chain_tabs; a.pair_H = (marg || !c->d_chain_src) ? 1 : c->want_pair_H;
     a.sbp_n = c->sbp_n; a.sbp_target = c->d_sbp_target;
-    return c->n_imu + c->n_groups + (a.has_prior ? 1 + PRIOR_H_BLOCKS : 0);
+    a.entry = entry & 1;
+    a.prior_form = (entry & 2) && prior_by_keyframe(c, marg) ? 1 : 0;
+    // (a caller's prior: glio_set_prior has looked at J0; the library's own: the full rows, see glio_marginalize_keep_async)
+    a.prior_sparse = a.prior_form && c->prior_jac_exact ? 1 : 0;
+    a.pspan = glio_prior_span_dev(c, ex->d_prior_colblk);
+    for (int k = 0; k < GLIO_MAX_WINDOW; ++k) a.imu_slot[k] = k < c->n_imu ? c->h_imu_slot[k] : 0;
+    return c->n_imu + c->n_groups + prior_workgroups(a.has_prior, a.prior_form);
 }
+extern "C" int glio_debug_linearize_entry(int mask) { return glio_switch_set<GLIO_SW_LINEARIZE_ENTRY>(mask & 7); }
 void glio_launch_small_factors(glio_ctx* c, int use_status_cand, int which, int n_ddt, int marg) {
     SmallArgs a;
     const int blocks = fill_small_args(c, use_status_cand, which, n_ddt, marg, a);
@@ -1144,14 +1473,17 @@ void glio_launch_small_factors(glio_ctx* c, int use_status_cand, int which, int 
 // what the host has just written (candidate buffer 0 pending), so the buffer is fixed and the state is read from the host copy.  Needs n_small > 0.
 void glio_launch_linearize_all(glio_ctx* c, int use_status_cand, int which, int n_ddt, int first) {
     SmallArgs a;
-    const int n_small = fill_small_args(c, first ? 0 : use_status_cand, first ? 0 : which, n_ddt, 0, a);
+    const int entry = glio_switch<GLIO_SW_LINEARIZE_ENTRY>();
+    const int n_small = fill_small_args(c, first ? 0 : use_status_cand, first ? 0 : which, n_ddt, 0, a, entry);
     if (n_small == 0) { glio_launch_lidar_linearize(c, use_status_cand, which); return; }
     if (first) a.x0 = reinterpret_cast<const double*>(static_cast<const unsigned char*>(c->d_h_status) + 512);
     K3Args k;
     k.pts = c->d_pts; k.planes = c->d_planes; k.scores = c->d_scores; k.count = c->d_count; k.cap = c->cap;
     k.lc = glio_lidar_const(c); k.partials = c->d_lidar_partials; k.pstride = glio_partials_stride(c); k.n_small = n_small;
     const bool skip = c->merged_linearize == 2 && n_small <= 128;
-    int nb = (512 - (skip ? 2 : 1) * n_small) / c->W;
+    // (LINEARIZE_ENTRY bit 2 off: K3 keeps the share it had beside the dense prior's 25 workgroups, whatever the prior takes now)
+    const int n_reserve = (entry & 4) ? n_small : c->n_imu + c->n_groups + prior_workgroups(a.has_prior, 0);
+    int nb = (512 - (skip ? 2 : 1) * n_reserve) / c->W;
     if (nb < 4) nb = 4;
     if (nb > c->k3_bpk) nb = c->k3_bpk;
     {   // large keyframes (C5: 262 144 residuals each) get more workgroups than fit at once -- about 4 k residuals per
@@ -1162,10 +1494,18 @@ void glio_launch_linearize_all(glio_ctx* c, int use_status_cand, int which, int 
         if (want > GLIO_K3_MAX_BLOCKS_PER_KF) want = GLIO_K3_MAX_BLOCKS_PER_KF;
         if (want > nb) nb = want;
     }
+    // (With the prior by keyframe the roles of the benchmark's window are 43 workgroups, K3 has 213 CUs and 21 workgroups per keyframe: 11.9-12.1 us against
+    //  12.6-13.1 with 63 roles and 19, K3's last end 10.3-10.5 us into the launch -- profiles/linearize_entry_ab.txt.  The figures below are the 63-role
+    //  launch's, where a 20th workgroup per keyframe had no free slot.)
     // (the launch now lasts as long as K3 on the CUs the small-factor workgroups leave it -- 193 of 256: with the small-factor roles left out altogether it
     //  takes the same 12.5 us, and K3 alone on the whole chip 9.8.  More K3 workgroups than free slots do not help: from 20 per keyframe on the late ones land
     //  beside the small-factor workgroups and the launch takes 15.3-15.9 us; 17 per keyframe 13.5.)
+    if (c->k3_bpk_pin > 0) nb = c->k3_bpk_pin;
     k.nb = nb; k.n_k3 = c->W * nb;
+    // the counts as the host holds them, unless an asynchronous association has not handed them over yet (glio_time_solve and glio_time_kernel do not wait
+    // for one as the other entry points do): then the workgroups read count[kf] as before
+    k.count_in_args = (entry & 1) && !glio_assoc_counts_pending(c) ? 1 : 0;
+    for (int s2 = 0; s2 < GLIO_MAX_WINDOW; ++s2) k.count_h[s2] = s2 < c->W ? c->h_count[s2] : 0;
     k.skip_lo = skip ? 256 : 0; k.skip_hi = skip ? 256 + n_small : 0;
     c->last_k3_nb = nb;
     const int grid = n_small + k.n_k3 + (k.skip_hi - k.skip_lo);

@@ -245,7 +245,12 @@ struct glio_ctx {
     int prior_ext_coupled;                    // the installed prior descends from a CALLER's prior with speed-bias blocks beyond slot 1: those may couple to the
                                               // poses of their keyframe, so the marginalization takes the general root (the per-block root wants them alone)
     double* d_marg_T;                         // [15 (W - 1)][15] T = Arm Amm^+ of the marginalization (the kept part has up to 15 (W - 1) columns)
+    // ---- the prior by keyframe (window_tables.h, prior_span_tables; the table itself sits behind the column -> block table, glio_prior_span_dev)
+    int prior_span_ok;                        // the installed prior's columns are one run per keyframe: its workgroups may walk them by span
+    int prior_jac_exact;                      // ... and glio_set_prior found every entry of J0 outside the keyframes' diagonal blocks to be an exact zero
+    int k3_bpk_pin;                           // test knob (glio_debug_linearize_pin_nb): K3 workgroups per keyframe of the merged launch, 0 = the launch's own rule
 };
+static inline const int* glio_prior_span_dev(const glio_ctx* c, const int* d_prior_colblk) { return d_prior_colblk + ((glio_prior_np_limit(c->W) + 3) & ~3); }      // (16-byte aligned: one int4 per column)
 
 static inline int glio_marg_layout(const glio_ctx* c, short* extra_slot) { return glio_marg_layout(c->W, c->sbp_n, c->prior_n, c->h_prior_index, extra_slot); }
 
@@ -480,6 +485,7 @@ int glio_assoc_select_window(glio_ctx* c, const int32_t* offsets, const int32_t*
 int glio_assoc_run_window(glio_ctx* c, const double* quats, const double* trans, int32_t* out_counts);
 int glio_assoc_run_window_async(glio_ctx* c, const double* quats, const double* trans);
 int glio_assoc_finish_pending(glio_ctx* c);
+int glio_assoc_counts_pending(const glio_ctx* c);   // 1: an asynchronous window association has not handed its counts to h_count yet (only d_count is current)
 void glio_localmap_destroy(glio_ctx* c);
 void glio_features_destroy(glio_ctx* c);          // feature_kernels.hip
 // feature_kernels.hip: the surf features of the last glio_features_extract* where they lie (GLIO_E_STATE before the first extraction)

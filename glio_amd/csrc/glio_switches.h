@@ -9,7 +9,7 @@
 //            snapshot, and the environment is not looked at again.  The glio_debug_* setters write the snapshot.
 //   CREATE   read when the object it configures is created or configured (glio_switch_at_create): glio_create, glio_bassoc_create,
 //            glio_dense_create, glio_scan_filter_config, a local map's or voxel grid's creation, a ring's first rebuild.
-// The last row has no environment name: a test knob that only its setter writes.
+// The last rows have no environment name: knobs that only their setters write (tests and A/B scripts).
 #pragma once
 #include <cstdlib>
 #include <cstring>
@@ -42,7 +42,8 @@
     X(LM_REBUILD_TIMING,   "GLIO_LM_REBUILD_TIMING",   0,   BOOL,  0, CREATE,  "a ring's first rebuild: 1 rebuilds are timed with events") \
     X(KFCLOUD_TIMING,      "GLIO_KFCLOUD_TIMING",      0,   BOOL,  0, CREATE,  "glio_scan_filter_config: 1 the keyframe cloud's stages are timed with events") \
     X(DENSE_TIMING,        "GLIO_DENSE_TIMING",        0,   BOOL,  0, CREATE,  "glio_dense_create: 1 the dense store's stages are timed with events") \
-    X(GBIN_CAP,            nullptr,                    0,   RAW,   0, PROCESS, "glio_debug_set_gbin_cap: cell-table size of the merged-window grouping, 0 = from the map")
+    X(GBIN_CAP,            nullptr,                    0,   RAW,   0, PROCESS, "glio_debug_set_gbin_cap: cell-table size of the merged-window grouping, 0 = from the map") \
+    X(LINEARIZE_ENTRY,     nullptr,                    7,   MASK,  7, PROCESS, "glio_debug_linearize_entry: the merged linearisation launch: bit 0 status, counts and records asked for at entry, bit 1 the prior by keyframe on the chain path, bit 2 K3 workgroups from the roles' own count; 0 the launch as it was")
 
 enum GlioSwitchId {
 #define GLIO_SWITCH_ID(id, name, dflt, norm, arg, scope, doc) GLIO_SW_##id,

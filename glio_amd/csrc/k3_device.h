@@ -135,15 +135,35 @@ template <int UNROLL, bool MARG, bool NT = false, bool PIPE = false>
 __device__ __forceinline__ void k3_body(
     const float4* __restrict__ pts, const float4* __restrict__ planes, const double* __restrict__ scores,
     const int* __restrict__ count, const int cap, const double* __restrict__ x, const int W,
+    const LidarConst& lc, double* __restrict__ partials, const int kf, const int bx, const int nb);
+// ... the same from the keyframe's count and pose in registers: k_linearize_all asks for the status record, the count (a kernel argument) and the pose out
+// of BOTH state buffers in one round of loads and selects, where the form above reads count[kf] and then the chosen buffer
+template <int UNROLL, bool MARG, bool NT = false, bool PIPE = false>
+__device__ __forceinline__ void k3_body_at(
+    const float4* __restrict__ pts, const float4* __restrict__ planes, const double* __restrict__ scores,
+    const int n, const int cap, const double (&t)[3], const double (&q)[4],
+    const LidarConst& lc, double* __restrict__ partials, const int kf, const int bx, const int nb);
+
+template <int UNROLL, bool MARG, bool NT, bool PIPE>
+__device__ __forceinline__ void k3_body(
+    const float4* __restrict__ pts, const float4* __restrict__ planes, const double* __restrict__ scores,
+    const int* __restrict__ count, const int cap, const double* __restrict__ x, const int W,
     const LidarConst& lc, double* __restrict__ partials, const int kf, const int bx, const int nb) {
     const int n = count[kf];
-
-    // per-keyframe constants: M = R(q) R_lb^T, t
-    double q[4], R[9], M[9], t[3];
+    double q[4], t[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) t[k] = x[3 * kf + k];
 #pragma unroll
     for (int k = 0; k < 4; ++k) q[k] = x[3 * W + 4 * kf + k];
+    k3_body_at<UNROLL, MARG, NT, PIPE>(pts, planes, scores, n, cap, t, q, lc, partials, kf, bx, nb);
+}
+template <int UNROLL, bool MARG, bool NT, bool PIPE>
+__device__ __forceinline__ void k3_body_at(
+    const float4* __restrict__ pts, const float4* __restrict__ planes, const double* __restrict__ scores,
+    const int n, const int cap, const double (&t)[3], const double (&q)[4],
+    const LidarConst& lc, double* __restrict__ partials, const int kf, const int bx, const int nb) {
+    // per-keyframe constants: M = R(q) R_lb^T, t
+    double R[9], M[9];
     d_q2R(q, R);
 #pragma unroll
     for (int i = 0; i < 3; ++i)

@@ -96,6 +96,40 @@ static inline PriorFlags prior_flags(int nb, const int32_t* blk_slot, const int3
     return {nsb <= 1, ext};
 }
 
+// ---------------------------------------------------------------------------------------------- the prior by keyframe
+// Column spans for the prior's workgroups on the keyframe-chain path (factor_kernels.hip, prior_chain_H_block / prior_rg_block): span[4 np], per prior
+// column j four numbers -- [lo, hi) the columns of j's own keyframe, [plo, phi) those of the keyframe below it (0, 0 where the prior has none).
+// Returns 1 when the layout can be walked by span: the columns of every keyframe are ONE run of at most PRIOR_SPAN_MAX (a pose and a speed/bias block
+// side by side are 15).  The layouts after a loop closure, whose extra speed-bias blocks sit behind the poses, return 0: they keep the dense form.
+#define PRIOR_SPAN_MAX 16
+static inline int prior_span_tables(int W, int np, int nb, const int32_t* blk_slot, const int32_t* blk_kind, const int32_t* blk_idx, const int* colblk, int* span) {
+    std::vector<int> lo(W, np), hi(W, 0), cols(W, 0);
+    for (int b = 0; b < nb; ++b) {
+        const int s = blk_slot[b], ls = blk_kind[b] == GLIO_BLK_SPEEDBIAS ? 9 : 3;
+        if (s < 0 || s >= W) return 0;
+        lo[s] = std::min(lo[s], blk_idx[b]); hi[s] = std::max(hi[s], blk_idx[b] + ls); cols[s] += ls;
+    }
+    int ok = 1;
+    for (int s = 0; s < W; ++s) if (cols[s] > 0 && (hi[s] - lo[s] != cols[s] || cols[s] > PRIOR_SPAN_MAX)) ok = 0;
+    for (int j = 0; j < np; ++j) {
+        const int s = colblk[j] >= 0 && colblk[j] < nb ? blk_slot[colblk[j]] : -1;
+        if (s < 0) { span[4 * j] = span[4 * j + 1] = span[4 * j + 2] = span[4 * j + 3] = 0; ok = 0; continue; }
+        span[4 * j] = lo[s]; span[4 * j + 1] = hi[s];
+        const bool below = s > 0 && cols[s - 1] > 0;
+        span[4 * j + 2] = below ? lo[s - 1] : 0; span[4 * j + 3] = below ? hi[s - 1] : 0;
+    }
+    return ok;
+}
+// Is every entry of the prior's Jacobian outside its keyframe's diagonal block an EXACT zero (of either sign)?  Then r = r0 + J0 dx and v = J0^T r
+// can skip those products: they add +-0 to sums that start at +0, which changes no bit for a finite state.  (prior_is_chain above holds J0^T J0 to a
+// tolerance only, which is enough for the solver's path and not for this.)
+static inline int prior_jac_is_block_exact(int np, const double* lin_jac, const int32_t* blk_slot, const int* colblk) {
+    for (int i = 0; i < np; ++i)
+        for (int j = 0; j < np; ++j)
+            if (lin_jac[(size_t)i * np + j] != 0.0 && blk_slot[colblk[i]] != blk_slot[colblk[j]]) return 0;
+    return 1;
+}
+
 // ---------------------------------------------------------------------------------------------- kept layout of the next marginalization
 // The poses of slots 1 .. W-1 and the speed/bias of slot 1 as ever ([T1 Q1 SB1 | T2 Q2 | ...], 6 (W - 1) + 9 columns), then the speed/bias of every
 // slot s >= 2 that carries a speed-bias prior or has a speed-bias block in the installed prior, ascending, 9 columns each.  Returns their number;
