@@ -5,8 +5,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libglio_hip.so")
-SOURCES = ["lidar_kernels.hip", "factor_kernels.hip", "solver_kernels.hip", "assoc_kernels.hip", "batch_kernels.hip", "batch_solve_kernels.hip", "batch_tr_kernels.hip", "batch_cov_kernels.hip", "localmap_kernels.hip", "eval_kernels.hip", "feature_kernels.hip", "imu_kernels.hip", "loop_kernels.hip", "globalmap_kernels.hip", "posegraph_kernels.hip", "keyframe_cloud_kernels.hip", "dense_cloud_kernels.hip", "trajectory_kernels.hip", "covariance_kernels.hip", "align_kernels.hip", "place_kernels.hip", "capi.hip", "switches.hip"]
-HEADERS = [os.path.join(CSRC, "glio_device.h"), os.path.join(CSRC, "glio_switches.h"), os.path.join(CSRC, "window_tables.h"),os.path.join(CSRC, "k3_device.h"), os.path.join(CSRC, "batch_device.h"), os.path.join(CSRC, "factor_math.h"), os.path.join(CSRC, "tr_math.h"), os.path.join(CSRC, "tr_math_device.h"), os.path.join(CSRC, "cloud_device.h"), os.path.join(HERE, "..", "include", "glio_hip.h"), os.path.join(HERE, "..", "include", "glio_types.h"), os.path.join(HERE, "..", "include", "glio_pgraph_lm.h"), os.path.join(HERE, "..", "include", "glio_traj.h"), os.path.join(HERE, "..", "include", "glio_cov.h"), os.path.join(HERE, "..", "include", "glio_dense.h"), os.path.join(HERE, "..", "include", "glio_align.h"), os.path.join(HERE, "..", "include", "glio_batch_cov.h"), os.path.join(HERE, "..", "include", "glio_pgraph_cov.h"), os.path.join(HERE, "..", "include", "glio_place.h")]
+SOURCES = ["lidar_kernels.hip", "factor_kernels.hip", "solver_kernels.hip", "assoc_kernels.hip", "batch_kernels.hip", "batch_solve_kernels.hip", "batch_tr_kernels.hip", "batch_cov_kernels.hip", "localmap_kernels.hip", "eval_kernels.hip", "feature_kernels.hip", "imu_kernels.hip", "loop_kernels.hip", "globalmap_kernels.hip", "posegraph_kernels.hip", "keyframe_cloud_kernels.hip", "dense_cloud_kernels.hip", "trajectory_kernels.hip", "covariance_kernels.hip", "align_kernels.hip", "place_kernels.hip", "static_kernels.hip", "capi.hip", "switches.hip"]
+HEADERS = [os.path.join(CSRC, "glio_device.h"), os.path.join(CSRC, "glio_switches.h"), os.path.join(CSRC, "window_tables.h"),os.path.join(CSRC, "k3_device.h"), os.path.join(CSRC, "batch_device.h"), os.path.join(CSRC, "factor_math.h"), os.path.join(CSRC, "tr_math.h"), os.path.join(CSRC, "tr_math_device.h"), os.path.join(CSRC, "cloud_device.h"), os.path.join(HERE, "..", "include", "glio_hip.h"), os.path.join(HERE, "..", "include", "glio_types.h"), os.path.join(HERE, "..", "include", "glio_pgraph_lm.h"), os.path.join(HERE, "..", "include", "glio_traj.h"), os.path.join(HERE, "..", "include", "glio_cov.h"), os.path.join(HERE, "..", "include", "glio_dense.h"), os.path.join(HERE, "..", "include", "glio_align.h"), os.path.join(HERE, "..", "include", "glio_batch_cov.h"), os.path.join(HERE, "..", "include", "glio_pgraph_cov.h"), os.path.join(HERE, "..", "include", "glio_place.h"), os.path.join(HERE, "..", "include", "glio_static.h")]
 
 
 def _stale():

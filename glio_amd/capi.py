@@ -97,6 +97,31 @@ def place_tables(max_radius):
     return rb2, dirs
 
 
+def static_opts(**kw):
+    """glio_static_opts_default with fields replaced"""
+    o = T.GlioStaticOpts()
+    load().glio_static_opts_default(C.byref(o))
+    for k, v in kw.items():
+        assert hasattr(o, k), k
+        setattr(o, k, v)
+    return o
+
+
+def static_tables(opts):
+    """glio_static_tables: (s2 [rows + 1], dir [4 cols_per_quadrant][2]) float32; needs no device"""
+    s2, dirs = np.zeros(max(opts.rows, 0) + 1, np.float32), np.zeros((4 * max(opts.cols_per_quadrant, 1), 2), np.float32)
+    _check(load().glio_static_tables(C.byref(opts), T.fptr(s2), T.fptr(dirs)))
+    return s2, dirs
+
+
+def static_relative_pose(pose_v, pose_f):
+    """glio_static_relative_pose: T(v, f) = pose_v^-1 o pose_f as a float32 [3][4]; poses are t[3], q[4] (w first); needs no device"""
+    pv, pf = np.ascontiguousarray(pose_v, np.float64).reshape(7), np.ascontiguousarray(pose_f, np.float64).reshape(7)
+    out = np.zeros((3, 4), np.float32)
+    _check(load().glio_static_relative_pose(T.dptr(pv), T.dptr(pf), T.fptr(out)))
+    return out
+
+
 def device_count():
     return load().glio_device_count()
 

@@ -550,6 +550,11 @@ int glio_bassoc_external_read(glio_bassoc* b, hipStream_t reader);
 struct glio_dense;
 int glio_dense_view(glio_dense* d, GlioBassocView* out);
 int glio_dense_external_read(glio_dense* d, hipStream_t reader);
+// static_kernels.hip: the same view of a static store (glio_static_*: [K][cap] frames without the points that were seen through; a frame never classified has
+// size 0), and the same hook: the next glio_static_classify comes behind the reader
+struct glio_static;
+int glio_static_view(glio_static* st, GlioBassocView* out);
+int glio_static_external_read(glio_static* st, hipStream_t reader);
 // capi.hip: a scan / map sent ahead on the upload stream (glio_set_scan_ahead, glio_localmap_push_scan_ahead_and_build) is still pending -> the context's
 // stream waits for it (the next glio_slide_window still takes the scan over)
 int glio_order_behind_ahead(glio_ctx* c);

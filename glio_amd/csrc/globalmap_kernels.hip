@@ -30,7 +30,7 @@
 
 #include "glio_device.h"
 #include "cloud_device.h"
-#include "../../include/glio_dense.h"
+#include "../../include/glio_static.h"
 
 // transformCloud and the voxel sums must round like scalar float / double code: no FMA contraction in this file
 #pragma clang fp contract(off)
@@ -61,6 +61,7 @@ struct GmVox { gm_u64* key; float4* sum; int* cnt; float4* out; };      // sorte
 struct glio_gmap {
     GlioBassocView v;                   // the resident clouds: a batch association's keyframes, or a dense store's frames (glio_gmap_create_on_dense)
     glio_dense* dense;                  // the dense store the view is of (null: a batch association)
+    glio_static* stat;                  // the static store the view is of (glio_gmap_create_on_static), or null
     glio_gmap_opts o;
     float inv_leaf;
     hipStream_t stream;
@@ -363,8 +364,8 @@ static int gm_create_body(glio_gmap* gm) {
     return GLIO_OK;
 }
 // b or d: the source of the clouds
-static int gm_create(glio_bassoc* b, glio_dense* d, const glio_gmap_opts* opts, glio_gmap** out) {
-    if ((!b && !d) || !opts || !out) return GLIO_E_ARG;
+static int gm_create(glio_bassoc* b, glio_dense* d, glio_static* st, const glio_gmap_opts* opts, glio_gmap** out) {
+    if ((!b && !d && !st) || !opts || !out) return GLIO_E_ARG;
     const glio_gmap_opts& o = *opts;
     if (!(o.leaf > 0.f) || !(o.leaf <= FLT_MAX) || o.max_voxels < 1 || o.max_points_per_add < 1) {
         glio_set_error("bad glio_gmap_opts (leaf %g, max_voxels %d, max_points_per_add %d)", (double)o.leaf, o.max_voxels, o.max_points_per_add);
@@ -375,15 +376,16 @@ static int gm_create(glio_bassoc* b, glio_dense* d, const glio_gmap_opts* opts, 
     gm->o = o;
     gm->inv_leaf = 1.0f / o.leaf;
     gm_reset(gm);
-    gm->dense = d;
-    { const int rv = d ? glio_dense_view(d, &gm->v) : glio_bassoc_view(b, &gm->v); if (rv != GLIO_OK) { delete gm; return rv; } }
+    gm->dense = d; gm->stat = st;
+    { const int rv = st ? glio_static_view(st, &gm->v) : d ? glio_dense_view(d, &gm->v) : glio_bassoc_view(b, &gm->v); if (rv != GLIO_OK) { delete gm; return rv; } }
     const int rc = gm_create_body(gm);
     if (rc != GLIO_OK) { glio_gmap_destroy(gm); return rc; }
     *out = gm;
     return GLIO_OK;
 }
-int glio_gmap_create(glio_bassoc* b, const glio_gmap_opts* opts, glio_gmap** out) { return gm_create(b, nullptr, opts, out); }
-int glio_gmap_create_on_dense(glio_dense* d, const glio_gmap_opts* opts, glio_gmap** out) { return gm_create(nullptr, d, opts, out); }
+int glio_gmap_create(glio_bassoc* b, const glio_gmap_opts* opts, glio_gmap** out) { return gm_create(b, nullptr, nullptr, opts, out); }
+int glio_gmap_create_on_dense(glio_dense* d, const glio_gmap_opts* opts, glio_gmap** out) { return gm_create(nullptr, d, nullptr, opts, out); }
+int glio_gmap_create_on_static(glio_static* st, const glio_gmap_opts* opts, glio_gmap** out) { return gm_create(nullptr, nullptr, st, opts, out); }
 
 int glio_gmap_clear(glio_gmap* gm) {
     if (!gm) return GLIO_E_ARG;
@@ -445,6 +447,7 @@ int glio_gmap_add_frames(glio_gmap* gm, int n_frames, const int32_t* frame_idx, 
     GM_CHECK(hipGetLastError());
     // (a dense store writes its frames without waiting for the host: its next write comes behind this read)
     if (gm->dense) { const int re = glio_dense_external_read(gm->dense, s); if (re != GLIO_OK) return re; }
+    if (gm->stat) { const int re = glio_static_external_read(gm->stat, s); if (re != GLIO_OK) return re; }
     GM_CHECK(hipEventRecord(gm->ev_t[4], s));
     GM_CHECK(hipMemcpyAsync(gm->h_ctl, gm->d_ctl, sizeof(GmCtl), hipMemcpyDeviceToHost, s));
     GM_CHECK(hipEventRecord(gm->ev_done, s));

@@ -366,9 +366,45 @@ PLACE_PROTOTYPES = {
 }
 
 
+# ---- the static map (include/glio_static.h)
+STATIC_MAX_VIEWS, STATIC_PATH_AUTO, STATIC_PATH_GLOBAL, STATIC_LDS_LIMIT = 32, 0, 1, 163840
+
+
+class GlioStaticOpts(C.Structure):
+    """glio_static_opts"""
+    _fields_ = [("rows", C.c_int32), ("cols_per_quadrant", C.c_int32), ("neighbourhood", C.c_int32), ("min_votes", C.c_int32), ("max_views", C.c_int32),
+                ("image_path", C.c_int32), ("elev_min_deg", C.c_float), ("elev_max_deg", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float),
+                ("range_gain", C.c_float), ("range_margin", C.c_float)]
+
+
+class GlioStaticInfo(C.Structure):
+    """glio_static_info"""
+    _fields_ = [("n_points", C.c_int64), ("n_tested", C.c_int64), ("n_dynamic", C.c_int64), ("n_frames", C.c_int32), ("lds_path", C.c_int32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+c_uint8_p = C.POINTER(C.c_uint8)
+STATIC_PROTOTYPES = {
+    "glio_static_struct_sizes": [c_int32_p, C.c_int],
+    "glio_static_tables": [C.POINTER(GlioStaticOpts), c_float_p, c_float_p],
+    "glio_static_relative_pose": [c_double_p, c_double_p, c_float_p],
+    "glio_static_create": [C.c_void_p, C.POINTER(GlioStaticOpts), c_void_pp],
+    "glio_static_create_on_dense": [C.c_void_p, C.POINTER(GlioStaticOpts), c_void_pp],
+    "glio_static_classify": [C.c_void_p, C.c_int, c_int32_p, c_double_p, c_int32_p, c_int32_p, C.POINTER(GlioStaticInfo)],
+    "glio_static_read_frame": [C.c_void_p, C.c_int, c_float_p, C.c_int, c_int_p],
+    "glio_static_frame_count": [C.c_void_p, C.c_int, c_int_p],
+    "glio_static_read_votes": [C.c_void_p, C.c_int, c_uint8_p, c_uint8_p, C.c_int, c_int_p],
+    "glio_static_read_image": [C.c_void_p, C.c_int, c_float_p, c_float_p],
+    "glio_static_last_device_ms": [C.c_void_p, c_float_p],
+    "glio_gmap_create_on_static": [C.c_void_p, C.c_void_p, c_void_pp],
+}
+
+
 def apply_prototypes(lib):
     for name, args in list(KEYFRAME_CLOUD_PROTOTYPES.items()) + list(DENSE_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(PGRAPH_COV_PROTOTYPES.items()) + \
-            list(PLACE_PROTOTYPES.items()):
+            list(PLACE_PROTOTYPES.items()) + list(STATIC_PROTOTYPES.items()):
         fn = getattr(lib, name, None)
         if fn is None:
             raise AttributeError(f"{name} is missing from the library: it is stale, rebuild it with `python -m glio_amd.build`")
@@ -384,3 +420,7 @@ def apply_prototypes(lib):
     lib.glio_place_destroy.restype = None
     lib.glio_place_opts_default.argtypes = [C.POINTER(GlioPlaceOpts)]
     lib.glio_place_opts_default.restype = None
+    lib.glio_static_destroy.argtypes = [C.c_void_p]
+    lib.glio_static_destroy.restype = None
+    lib.glio_static_opts_default.argtypes = [C.POINTER(GlioStaticOpts)]
+    lib.glio_static_opts_default.restype = None

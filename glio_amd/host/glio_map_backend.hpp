@@ -17,6 +17,7 @@
 
 #include "glio_hip.h"
 #include "glio_dense.h"
+#include "glio_static.h"
 
 namespace glio {
 
@@ -88,6 +89,11 @@ public:
     explicit GlobalMap(DenseClouds& dense, const glio_gmap_opts* opts = nullptr) {
         if (opts) o_ = *opts; else glio_gmap_opts_default(&o_);
         check(glio_gmap_create_on_dense(dense.handle(), &o_, &h_), "glio_gmap_create_on_dense");
+    }
+    // ... or a static store (glio::StaticClouds::handle(), glio_static_backend.hpp): its frames without the points that were seen through -- the static map
+    explicit GlobalMap(glio_static* st, const glio_gmap_opts* opts = nullptr) {
+        if (opts) o_ = *opts; else glio_gmap_opts_default(&o_);
+        check(glio_gmap_create_on_static(st, &o_, &h_), "glio_gmap_create_on_static");
     }
     ~GlobalMap() { glio_gmap_destroy(h_); }
     GlobalMap(const GlobalMap&) = delete;

@@ -783,3 +783,43 @@ def run_demo_place(path, device=0, env=None):
         else:
             out[w[0]] = bytes.fromhex(w[1]) if len(w) > 1 else b""
     return out
+
+
+DEMO_STATIC_MAP = os.path.join(HERE, "host_demo_static_map")
+
+
+def build_demo_static_map(force=False):
+    """The C++ static map (host_demo_static_map.cpp over glio::StaticClouds, glio_static_backend.hpp, and glio::GlobalMap on it)."""
+    src = [os.path.join(HERE, "host_demo_static_map.cpp"), os.path.join(HERE, "glio_static_backend.hpp"), os.path.join(HERE, "glio_map_backend.hpp"),
+           os.path.join(HERE, "..", "..", "include", "glio_static.h"), os.path.join(HERE, "..", "..", "include", "glio_dense.h")] + _ABI_HEADERS
+    if force or not os.path.exists(DEMO_STATIC_MAP) or any(os.path.getmtime(s) > os.path.getmtime(DEMO_STATIC_MAP) for s in src):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", src[0], "-I" + os.path.join(HERE, "..", "..", "include"),
+                               "-L" + os.path.join(HERE, "..", "lib"), "-lglio_hip", "-Wl,-rpath,$ORIGIN/../lib", "-o", DEMO_STATIC_MAP])
+    return DEMO_STATIC_MAP
+
+
+def write_static_map_case(path, opts, gmap_opts, cap, half_window, min_baseline, clouds, poses):
+    """int32 K cap half_window 0 | glio_static_opts | glio_gmap_opts | double min_baseline | K x (n, cloud) | double poses[K][7]"""
+    K = len(clouds)
+    poses = np.ascontiguousarray(poses, np.float64)
+    assert poses.shape == (K, 7)
+    with open(path, "wb") as f:
+        f.write(np.array([K, cap, half_window, 0], np.int32).tobytes())
+        f.write(bytes(opts)); f.write(bytes(gmap_opts)); f.write(np.array([min_baseline], np.float64).tobytes())
+        for c in clouds:
+            c = np.ascontiguousarray(c, np.float32).reshape(-1, 4)
+            f.write(np.array([len(c)], np.int32).tobytes()); f.write(c.tobytes())
+        f.write(poses.tobytes())
+
+
+def run_demo_static_map(path, device=0, env=None):
+    """-> dict(name: the bytes host_demo_static_map printed under that name)"""
+    r = subprocess.run([build_demo_static_map(), path, str(device)], capture_output=True, text=True, env=env)
+    if r.returncode != 0:
+        raise RuntimeError("host_demo_static_map failed (%d): %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
+    out = {}
+    for ln in r.stdout.splitlines():
+        w = ln.split()
+        if w:
+            out[w[0]] = bytes.fromhex(w[1]) if len(w) > 1 else b""
+    return out

@@ -111,7 +111,8 @@ class DenseClouds:
 
 
 class GlobalMap:
-    """One glio_gmap on a batch.BatchAssociation (which owns the resident keyframe clouds), or on a DenseClouds (whose frames it then reads: the dense map)."""
+    """One glio_gmap on a batch.BatchAssociation (which owns the resident keyframe clouds), or on a DenseClouds (whose frames it then reads: the dense map), or on a
+    static_map.StaticClouds (the frames without the points that were seen through: the static map)."""
 
     def __init__(self, assoc, opts=None):
         lib = capi.load()
@@ -119,7 +120,10 @@ class GlobalMap:
         self.opts = default_opts() if opts is None else opts
         self._assoc = assoc             # (the association / dense store must outlive the map object)
         self._h = C.c_void_p()
-        if isinstance(assoc, DenseClouds):
+        from .static_map import StaticClouds
+        if isinstance(assoc, StaticClouds):
+            capi._check(lib.glio_gmap_create_on_static(assoc._h, C.byref(self.opts), C.byref(self._h)))
+        elif isinstance(assoc, DenseClouds):
             capi._check(lib.glio_gmap_create_on_dense(assoc._h, C.byref(self.opts), C.byref(self._h)))
         else:
             capi._check(lib.glio_gmap_create(assoc._h, C.byref(self.opts), C.byref(self._h)))

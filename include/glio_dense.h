@@ -19,7 +19,8 @@
  * non-finite motion, a front end on another device, more outputs than max_points_per_frame (*n_out still tells the count).  GLIO_E_STATE: a front end without an
  * extraction; glio_dense_world_cloud before any glio_dense_set_frame*.  n == 0 gives an empty frame and GLIO_OK.
  *
- * Not built: writing .pcd files, pub_map, the de-skew of edge_features, removal of frames from a map. */
+ * Not built: writing .pcd files, pub_map, the de-skew of edge_features, removal of frames from a map (the points of moving objects are dropped frame by frame
+ * by a static store on top of this one, include/glio_static.h, and the map is built again from it). */
 #ifndef GLIO_DENSE_H
 #define GLIO_DENSE_H
 
