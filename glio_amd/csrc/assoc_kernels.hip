@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "glio_device.h"
+#include "cloud_device.h"
 
 // Bit-exact contract with the reference arithmetic: no fused multiply-add anywhere in this file (the
 // float distances of FLANN and the double transform / plane fit of the reference are separate IEEE
@@ -78,21 +79,77 @@ struct AssocWork {
 
 #define KEY_EMPTY (~0ull)
 
-__device__ __forceinline__ unsigned long long pack_key(int ix, int iy, int iz) {
-    // 21 bits per axis, biased
-    return ((unsigned long long)(unsigned)(ix + (1 << 20)) << 42) | ((unsigned long long)(unsigned)(iy + (1 << 20)) << 21) |
-           (unsigned long long)(unsigned)(iz + (1 << 20));
-}
-__device__ __forceinline__ unsigned hash_key(unsigned long long k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned)k;
-}
+// (the key of a cell, its inverse, its (lo, hi) halves and its hash: cloud_cell_key .. cloud_key_hash of cloud_device.h)
 __device__ __forceinline__ int cell_of(float v, float inv_cell) { return (int)floorf(v * inv_cell); }
+__device__ __forceinline__ unsigned long long cell_key_of(const float x, const float y, const float z, const float inv_cell) {
+    return cloud_cell_key(cell_of(x, inv_cell), cell_of(y, inv_cell), cell_of(z, inv_cell));
+}
 // Home slot: the eight cells of a 2x2x2 block sit in eight consecutive 16 B entries (one 128 B line), so the 27 probes
 // of a query touch at most 8 lines of the table instead of 27; collisions continue linearly.
 __device__ __forceinline__ unsigned home_slot(int cx, int cy, int cz, int cap) {
-    const unsigned h = hash_key(pack_key(cx >> 1, cy >> 1, cz >> 1));
+    const unsigned h = cloud_key_hash(cloud_cell_key(cx >> 1, cy >> 1, cz >> 1));
     return ((h << 3) | (unsigned)((cx & 1) | ((cy & 1) << 1) | ((cz & 1) << 2))) & (unsigned)(cap - 1);
+}
+__device__ __forceinline__ unsigned home_slot_of_key(const unsigned long long key, const int cap) {
+    int cx, cy, cz;
+    cloud_cell_of_key(key, cx, cy, cz);
+    return home_slot(cx, cy, cz, cap);
+}
+// "find this key's slot or claim an empty one" by linear probing from slot s of a table of cap (a power of two) slots that is never full (load factor
+// <= 0.5): the slot that holds the key afterwards.  Global tables read before they CAS: a stale EMPTY only costs the CAS; a key, once seen, stays.
+// (gbin_segment's probe is BOUNDED -- a table sized for fewer cells than arrive -- and stays apart.)
+__device__ __forceinline__ unsigned table_claim(unsigned long long* keys, unsigned s, const int cap, const unsigned long long key) {
+    for (;;) {
+        unsigned long long prev = keys[s];
+        if (prev != key) prev = atomicCAS(&keys[s], KEY_EMPTY, key);
+        if (prev == KEY_EMPTY || prev == key) return s;
+        s = (s + 1) & (cap - 1);
+    }
+}
+// The LDS table that groups the points of a tile by cell (hash_insert_tile, k_qbin_count, k_qbin_tile): SLOTS keys (at least twice the tile's points) and
+// SUB counters per slot.  clear, a barrier, insert (the point's slot and its arrival rank in counter `sub`), a barrier, then the slots are walked.
+template <int SLOTS, int SUB, class C> struct TileCells {
+    unsigned long long key[SLOTS];
+    C cnt[SLOTS][SUB];
+    template <int THREADS> __device__ __forceinline__ void clear() {
+        for (int q = threadIdx.x; q < SLOTS; q += THREADS) {
+            key[q] = KEY_EMPTY;
+#pragma unroll
+            for (int o = 0; o < SUB; ++o) cnt[q][o] = 0;
+        }
+    }
+    __device__ __forceinline__ int insert(const unsigned long long k, const int sub, C& rank) {
+        unsigned q = cloud_key_hash(k) & (SLOTS - 1);
+        for (;;) {
+            const unsigned long long prev = atomicCAS(&key[q], KEY_EMPTY, k);
+            if (prev == KEY_EMPTY || prev == k) break;
+            q = (q + 1) & (SLOTS - 1);
+        }
+        rank = atomicAdd(&cnt[q][sub], (C)1);
+        return (int)q;
+    }
+};
+// the entry of neighbour c (0 .. 26, x fastest) of cell (cx, cy, cz) in a table the queries read (ent: {key lo, key hi, first point, points}; the walk ends
+// on the key or on EMPTY): first point and points of the cell, untouched when it is not there; SUB: its octant prefix too (that load is issued with the
+// entry's: one round trip per probe step).  Returns the entries read.
+template <bool SUB> __device__ __forceinline__ int cell_lookup(const int4* __restrict__ ent, const uint4* __restrict__ sub, const int table_cap, const int cx, const int cy,
+                                                               const int cz, const int c, int& first, int& count, uint4& pre) {
+    const int x = cx + (c % 3 - 1), y = cy + ((c / 3) % 3 - 1), z = cz + (c / 9 - 1);
+    const unsigned long long key = cloud_cell_key(x, y, z);
+    const int klo = cloud_key_lo(key), khi = cloud_key_hi(key);
+    unsigned s = home_slot(x, y, z, table_cap);
+    for (int probes = 1;; ++probes) {
+        const int4 e = ent[s];
+        uint4 sv;
+        if (SUB) sv = sub[s];
+        if (e.x == klo && e.y == khi) { first = e.z; count = e.w; if (SUB) pre = sv; return probes; }
+        if ((e.x & e.y) == -1) return probes;                 // KEY_EMPTY
+        s = (s + 1) & (table_cap - 1);
+    }
+}
+__device__ __forceinline__ int cell_lookup(const int4* __restrict__ ent, const int table_cap, const int cx, const int cy, const int cz, const int c, int& first, int& count) {
+    uint4 none;
+    return cell_lookup<false>(ent, nullptr, table_cap, cx, cy, cz, c, first, count, none);
 }
 
 // K1 orders the points of a cell by OCTANT (which half of the cell along x, y, z): oct = (hx & 1) | (hy & 1) << 1 | (hz & 1) << 2 with
@@ -114,77 +171,72 @@ __device__ __forceinline__ void hash_clear_slot(const int i, const int cap, unsi
     }
     if (i == 0) *total = 0;
 }
-__device__ __forceinline__ void hash_insert_point(const float4 p, const int i, const float inv_cell, unsigned long long* keys, unsigned* cnt8, int* pt_slot, int* pt_rank,
-                                                  const int cap) {
-    const int cx = cell_of(p.x, inv_cell), cy = cell_of(p.y, inv_cell), cz = cell_of(p.z, inv_cell);
-    const unsigned long long key = pack_key(cx, cy, cz);
-    unsigned s = home_slot(cx, cy, cz, cap);
-    for (;;) {
-        unsigned long long prev = keys[s];                         // a stale EMPTY only costs the CAS; a key, once seen, stays
-        if (prev != key) prev = atomicCAS(&keys[s], KEY_EMPTY, key);
-        if (prev == KEY_EMPTY || prev == key) break;
-        s = (s + 1) & (cap - 1);
-    }
-    const int so = (int)(s * 8u) + oct_of(p, inv_cell);
-    pt_rank[i] = (int)atomicAdd(&cnt8[so], 1u);
-    pt_slot[i] = so;
-}
-// The same per TILE of HI_THREADS consecutive points, aggregated in LDS first (round 5).  Every returning device-scope atomic is a round trip to the memory side and
-// they pass at ~4 per ns whatever the launch: the per-point form spent 187 us inserting the 12 x 64 k points of one keyframe's batch association.  A tile groups
+// K1's insert per TILE of HI_THREADS consecutive points, aggregated in LDS first (round 5; the per-point form is gone).  Every returning device-scope atomic is a round trip
+// to the memory side and they pass at ~4 per ns whatever the launch: the per-point form spent 187 us inserting the 12 x 64 k points of one keyframe's batch association.  A tile groups
 // its points by cell in an LDS table (LDS atomics), then issues ONE global key insertion per distinct cell and ONE counting atomic per distinct (cell, octant);
 // the points take their ranks from the LDS counts.  Clouds that arrive spatially ordered (the presorted keyframe clouds, the voxel-sorted local map) put ~10-25
 // points into a cell of a tile; a cloud in random order gains nothing and loses nothing.
 #define HI_THREADS 512
 #define HI_SLOTS 1024
-struct HashInsertLds { unsigned long long key[HI_SLOTS]; unsigned cnt[HI_SLOTS][8]; unsigned base[HI_SLOTS][8]; int gslot[HI_SLOTS]; };
+struct HashInsertLds { TileCells<HI_SLOTS, 8, unsigned> cells; unsigned base[HI_SLOTS][8]; int gslot[HI_SLOTS]; };
 __device__ __forceinline__ void hash_insert_tile(HashInsertLds& L, const float4* __restrict__ pts, const int n, const int tile0, const float inv_cell, unsigned long long* keys,
                                                  unsigned* cnt8, int* pt_slot, int* pt_rank, const int cap) {
     const int tid = threadIdx.x;
-    for (int q = tid; q < HI_SLOTS; q += HI_THREADS) {
-        L.key[q] = KEY_EMPTY;
-#pragma unroll
-        for (int o = 0; o < 8; ++o) L.cnt[q][o] = 0;
-    }
+    L.cells.clear<HI_THREADS>();
     __syncthreads();
     const int i = tile0 + tid;
     int ls = 0, oc = 0;
     unsigned lrank = 0;
     if (i < n) {
         const float4 p = pts[i];
-        const unsigned long long key = pack_key(cell_of(p.x, inv_cell), cell_of(p.y, inv_cell), cell_of(p.z, inv_cell));
-        unsigned q = hash_key(key) & (HI_SLOTS - 1);
-        for (;;) {
-            const unsigned long long prev = atomicCAS(&L.key[q], KEY_EMPTY, key);
-            if (prev == KEY_EMPTY || prev == key) break;
-            q = (q + 1) & (HI_SLOTS - 1);
-        }
-        ls = (int)q; oc = oct_of(p, inv_cell);
-        lrank = atomicAdd(&L.cnt[q][oc], 1u);
+        oc = oct_of(p, inv_cell);
+        ls = L.cells.insert(cell_key_of(p.x, p.y, p.z, inv_cell), oc, lrank);
     }
     __syncthreads();
     for (int q = tid; q < HI_SLOTS; q += HI_THREADS) {
-        const unsigned long long key = L.key[q];
+        const unsigned long long key = L.cells.key[q];
         if (key == KEY_EMPTY) continue;
-        const int cx = (int)((key >> 42) & 0x1fffffu) - (1 << 20), cy = (int)((key >> 21) & 0x1fffffu) - (1 << 20), cz = (int)(key & 0x1fffffu) - (1 << 20);
-        unsigned g = home_slot(cx, cy, cz, cap);
-        for (;;) {
-            unsigned long long prev = keys[g];                         // a stale EMPTY only costs the CAS; a key, once seen, stays
-            if (prev != key) prev = atomicCAS(&keys[g], KEY_EMPTY, key);
-            if (prev == KEY_EMPTY || prev == key) break;
-            g = (g + 1) & (cap - 1);
-        }
+        const unsigned g = table_claim(keys, home_slot_of_key(key, cap), cap, key);
         L.gslot[q] = (int)g;
 #pragma unroll
-        for (int o = 0; o < 8; ++o) { const unsigned c = L.cnt[q][o]; if (c) L.base[q][o] = atomicAdd(&cnt8[g * 8u + o], c); }
+        for (int o = 0; o < 8; ++o) { const unsigned c = L.cells.cnt[q][o]; if (c) L.base[q][o] = atomicAdd(&cnt8[g * 8u + o], c); }
     }
     __syncthreads();
     if (i < n) { pt_slot[i] = L.gslot[ls] * 8 + oc; pt_rank[i] = (int)(L.base[ls][oc] + lrank); }
 }
-// range allocation: one atomic per 1024-slot workgroup (block-wide exclusive scan of the cell counts; same-address atomics
-// execute one after the other at the memory side, a wavefront-granular version spent 14 us on 2048 of them)
+// The range a 1024-thread workgroup takes from running counters.  The NQ quantities v[k] of every thread are scanned in thread order (the 16 wavefront totals
+// turned into offsets by thread 0), and thread 0 adds the workgroup's total of quantity k to *target[k]: ONE atomic per workgroup and counter (same-address
+// atomics execute one after the other at the memory side; a wavefront-granular version spent 14 us on 2048 of them), in the order of k, none for a null target
+// or a total of 0.  excl[k] = what the atomic returned (0 without one) + the sum of v[k] over the threads before this one.  s_w: 16 ints of LDS per
+// quantity; s_base: one per quantity up to the last one that has a target.
+template <int NQ> __device__ __forceinline__ void wg1024_claim(const int (&v)[NQ], int* const (&target)[NQ], int* s_w, int* s_base, int (&excl)[NQ]) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int incl[NQ];
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) incl[k] = cloud_wave_incl_scan(v[k]);
+    if (lane == 63) {
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) s_w[16 * k + wv] = incl[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t[NQ];
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) t[k] = 0;
+        for (int w = 0; w < 16; ++w) {
+#pragma unroll
+            for (int k = 0; k < NQ; ++k) { const int x = s_w[16 * k + w]; s_w[16 * k + w] = t[k]; t[k] += x; }
+        }
+#pragma unroll
+        for (int k = 0; k < NQ; ++k) if (target[k]) s_base[k] = t[k] > 0 ? atomicAdd(target[k], t[k]) : 0;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) excl[k] = (target[k] ? s_base[k] : 0) + s_w[16 * k + wv] + incl[k] - v[k];
+}
+// range allocation: the cells' counts through wg1024_claim, one atomic per 1024-slot workgroup
 __device__ __forceinline__ void cell_alloc_slot(const int i, const int cap, const unsigned* __restrict__ cnt8, int* total, const unsigned long long* __restrict__ keys,
                                                 int4* __restrict__ ent, uint4* __restrict__ sub, int* s_w, int* s_base) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     unsigned o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (i < cap) {
         const uint4 a = reinterpret_cast<const uint4*>(cnt8)[2 * (size_t)i], b = reinterpret_cast<const uint4*>(cnt8)[2 * (size_t)i + 1];
@@ -194,26 +246,14 @@ __device__ __forceinline__ void cell_alloc_slot(const int i, const int cap, cons
     unsigned cs = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) { pre[k] = cs; cs += o[k]; }
-    const int c = (int)cs;
-    int incl = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
-    if (lane == 63) s_w[wv] = incl;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int k = 0; k < 16; ++k) { const int v = s_w[k]; s_w[k] = t; t += v; }
-        *s_base = t > 0 ? atomicAdd(total, t) : 0;
-    }
-    __syncthreads();
-    const int st = *s_base + s_w[wv] + incl - c;
+    const int c[1] = {(int)cs};
+    int* const target[1] = {total};
+    int st[1];
+    wg1024_claim<1>(c, target, s_w, s_base, st);
     if (i < cap) {
         const unsigned long long k = keys[i];
-        ent[i] = make_int4((int)(unsigned)(k & 0xffffffffull), (int)(unsigned)(k >> 32), st, c);
-        sub[i] = c > SUB_MAX ? make_uint4(~0u, ~0u, ~0u, ~0u)
+        ent[i] = make_int4(cloud_key_lo(k), cloud_key_hi(k), st[0], c[0]);
+        sub[i] = c[0] > SUB_MAX ? make_uint4(~0u, ~0u, ~0u, ~0u)
                              : make_uint4(pre[0] | (pre[1] << 16), pre[2] | (pre[3] << 16), pre[4] | (pre[5] << 16), pre[6] | (pre[7] << 16));
     }
 }
@@ -537,12 +577,8 @@ __device__ __forceinline__ void knn5_group_body(const AssocArgs& a, const float4
         px = qp.x; py = qp.y; pz = qp.z;
         i = glob ? (size_t)((unsigned)qw >> NK_ROW_SHIFT) * a.w_stride + (qw & ((1 << NK_ROW_SHIFT) - 1)) : (size_t)qw;
     } else {
-        const float4 pl = scan[qlive ? i : 0];
-        // transformPoint: double math, float store
-        const double pin[3] = {(double)pl.x, (double)pl.y, (double)pl.z};
-        double po[3];
-        d_qrot_nc(sl.q, pin, po);
-        px = (float)(po[0] + sl.t[0]); py = (float)(po[1] + sl.t[1]); pz = (float)(po[2] + sl.t[2]);
+        const float4 pw = cloud_transform(sl.q, sl.t, scan[qlive ? i : 0]);       // transformPoint: double math, float store
+        px = pw.x; py = pw.y; pz = pw.z;
     }
     const int cx = cell_of(px, a.inv_cell), cy = cell_of(py, a.inv_cell), cz = cell_of(pz, a.inv_cell);
     // ---- probe: lane j looks up cells j and j + AQ_LANES of the 27-neighbourhood (one 16 B entry per probe)
@@ -551,30 +587,14 @@ __device__ __forceinline__ void knn5_group_body(const AssocArgs& a, const float4
     for (int h = 0; h < AQ_ROUNDS; ++h) {
         cs[h] = 0; cc[h] = 0;
         const int c = j + AQ_LANES * h;
-        if (c < 27 && qlive) {
-            const int dx = c % 3 - 1, dy = (c / 3) % 3 - 1, dz = c / 9 - 1;
-            const unsigned long long key = pack_key(cx + dx, cy + dy, cz + dz);
-            const int klo = (int)(unsigned)(key & 0xffffffffull), khi = (int)(unsigned)(key >> 32);
-            unsigned s = home_slot(cx + dx, cy + dy, cz + dz, table_cap);
-            for (;;) {
-                const int4 e = ent[s];
-                if (e.x == klo && e.y == khi) { cs[h] = e.z; cc[h] = e.w; break; }
-                if ((e.x & e.y) == -1) break;                 // KEY_EMPTY
-                s = (s + 1) & (table_cap - 1);
-            }
-        }
+        if (c < 27 && qlive) cell_lookup(ent, table_cap, cx, cy, cz, c, cs[h], cc[h]);
     }
     // ---- flatten: exclusive prefix of the counts in cell order (round 0 lanes 0..15, then round 1), so that the group
     // walks ONE list of `tot` candidates with all its lanes busy instead of 27 mostly empty cells one after the other
     int tot = 0;
 #pragma unroll
     for (int h = 0; h < AQ_ROUNDS; ++h) {
-        int incl = cc[h];
-#pragma unroll
-        for (int off = 1; off < AQ_LANES; off <<= 1) {
-            const int t0 = __shfl_up(incl, off, AQ_LANES);
-            if (j >= off) incl += t0;
-        }
+        const int incl = cloud_wave_incl_scan<AQ_LANES>(cc[h]);
         s_tab[g][h * AQ_LANES + j] = make_int2(tot + incl - cc[h], cs[h]);      // cells >= 27 are empty: their prefix is the total
         tot += __shfl(incl, gbase + AQ_LANES - 1, 64);
     }
@@ -680,78 +700,48 @@ __global__ __launch_bounds__(256) void k_knn5(const AssocArgs a, const float4* _
 #define QC_THREADS 512
 #define QC_SLOTS 1024
 __global__ __launch_bounds__(QC_THREADS) void k_qbin_count(const AssocArgs a, const float4* __restrict__ scan) {
-    __shared__ unsigned long long s_key[QC_SLOTS];
-    __shared__ int s_cnt[QC_SLOTS], s_base[QC_SLOTS], s_g[QC_SLOTS];
+    __shared__ TileCells<QC_SLOTS, 1, int> s_cells;
+    __shared__ int s_base[QC_SLOTS], s_g[QC_SLOTS];
     const AssocSlot sl = assoc_slot(a);
     const int tid = threadIdx.x, i = blockIdx.x * QC_THREADS + tid;
     if ((int)(blockIdx.x * QC_THREADS) >= sl.n) return;
-    for (int q = tid; q < QC_SLOTS; q += QC_THREADS) { s_key[q] = KEY_EMPTY; s_cnt[q] = 0; }
+    s_cells.clear<QC_THREADS>();
     __syncthreads();
     const int capq = a.kb.capq;
     unsigned long long* keys = a.kb.keys + (size_t)blockIdx.y * capq;
-    float px = 0, py = 0, pz = 0;
+    float4 pw = make_float4(0, 0, 0, 0);
     int ls = 0, lrank = 0;
     if (i < sl.n) {
-        const float4 pl = scan[sl.qoff + i];
-        const double pin[3] = {(double)pl.x, (double)pl.y, (double)pl.z};
-        double po[3];
-        d_qrot_nc(sl.q, pin, po);
-        px = (float)(po[0] + sl.t[0]); py = (float)(po[1] + sl.t[1]); pz = (float)(po[2] + sl.t[2]);
-        const unsigned long long key = pack_key(cell_of(px, a.inv_cell), cell_of(py, a.inv_cell), cell_of(pz, a.inv_cell));
-        unsigned q = hash_key(key) & (QC_SLOTS - 1);
-        for (;;) {
-            const unsigned long long prev = atomicCAS(&s_key[q], KEY_EMPTY, key);
-            if (prev == KEY_EMPTY || prev == key) break;
-            q = (q + 1) & (QC_SLOTS - 1);
-        }
-        ls = (int)q;
-        lrank = atomicAdd(&s_cnt[q], 1);
+        pw = cloud_transform(sl.q, sl.t, scan[sl.qoff + i]);
+        ls = s_cells.insert(cell_key_of(pw.x, pw.y, pw.z, a.inv_cell), 0, lrank);
     }
     __syncthreads();
     for (int q = tid; q < QC_SLOTS; q += QC_THREADS) {
-        const unsigned long long key = s_key[q];
+        const unsigned long long key = s_cells.key[q];
         if (key == KEY_EMPTY) continue;
-        const int cx = (int)((key >> 42) & 0x1fffffu) - (1 << 20), cy = (int)((key >> 21) & 0x1fffffu) - (1 << 20), cz = (int)(key & 0x1fffffu) - (1 << 20);
-        unsigned s = home_slot(cx, cy, cz, capq);
-        for (;;) {
-            unsigned long long prev = keys[s];                         // a stale EMPTY only costs the CAS; a key, once seen, stays
-            if (prev != key) prev = atomicCAS(&keys[s], KEY_EMPTY, key);
-            if (prev == KEY_EMPTY || prev == key) break;
-            s = (s + 1) & (capq - 1);
-        }
+        const unsigned s = table_claim(keys, home_slot_of_key(key, capq), capq, key);
         s_g[q] = (int)s;
-        s_base[q] = atomicAdd(&a.kb.cnt[(size_t)blockIdx.y * capq + s], s_cnt[q]);
+        s_base[q] = atomicAdd(&a.kb.cnt[(size_t)blockIdx.y * capq + s], s_cells.cnt[q][0]);
     }
     __syncthreads();
     if (i < sl.n) {
         a.kb.qslot[sl.woff + i] = s_g[ls];
         a.kb.qrank[sl.woff + i] = s_base[ls] + lrank;
-        a.kb.qtmp[sl.woff + i] = make_float4(px, py, pz, __int_as_float(i));
+        a.kb.qtmp[sl.woff + i] = make_float4(pw.x, pw.y, pw.z, __int_as_float(i));
     }
 }
 
 __global__ __launch_bounds__(1024) void k_qbin_alloc(const AssocArgs a) {
     __shared__ int s_w[16], s_base;
     const int capq = a.kb.capq;
-    const int s = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int s = blockIdx.x * 1024 + threadIdx.x;
     const size_t row = (size_t)blockIdx.y * capq;
-    const int c = s < capq ? a.kb.cnt[row + s] : 0;
-    int ic = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(ic, off, 64);
-        if (lane >= off) ic += v;
-    }
-    if (lane == 63) s_w[wv] = ic;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int k = 0; k < 16; ++k) { const int v = s_w[k]; s_w[k] = t; t += v; }
-        s_base = t > 0 ? atomicAdd(&a.kb.counters[4 * blockIdx.y], t) : 0;
-    }
-    __syncthreads();
-    if (c > 0) {
-        a.kb.cstart[row + s] = s_base + s_w[wv] + ic - c;
+    const int c[1] = {s < capq ? a.kb.cnt[row + s] : 0};
+    int* const target[1] = {&a.kb.counters[4 * blockIdx.y]};
+    int st[1];
+    wg1024_claim<1>(c, target, s_w, &s_base, st);
+    if (c[0] > 0) {
+        a.kb.cstart[row + s] = st[0];
         a.kb.keys[row + s] = KEY_EMPTY;
         a.kb.cnt[row + s] = 0;
     }
@@ -768,13 +758,19 @@ __global__ __launch_bounds__(256) void k_qbin_scatter(const AssocArgs a) {
 
 // ---- merged-window grouping (KnnBin::glob): the (tile, cell) segments k_qbin_tile found, counted per cell in a global table.
 #define GB_UNIT 64         /* queries per unit of the merged window (k_knn5_near<64>) */
+// the unit records of `count` grouped queries of cell `key` that start at position `pos`: units of <= U queries from units[ub] on
+template <int U> __device__ __forceinline__ void units_emit(int4* units, const int ub, const int pos, const int count, const unsigned long long key) {
+    const int nu = (count + U - 1) / U;
+    for (int u = 0; u < nu; ++u) units[ub + u] = make_int4(pos + U * u, min(U, count - U * u), cloud_key_lo(key), cloud_key_hi(key));
+}
 // One segment = `count` queries of cell `key` at qs[qs_pos ..].  The cell gets a table slot (bounded probe: 32 steps) and the segment an offset inside the
 // cell's run; a segment that finds no slot (more distinct cells than the table was sized for) is laid out by itself from the END of qs2 downwards and
 // becomes its own unit(s) -- slower, never wrong.  (No fill counter: every same-address atomic is executed one after the other at the memory side,
-// ~5 ns each -- a counter bumped per cell and read per segment made this kernel 284 us instead of 25.)
+// ~5 ns each -- a counter bumped per cell and read per segment made this kernel 284 us instead of 25.)  The probe is not table_claim: this table may be
+// FULL (it is sized for the cells expected, not for the queries), so the walk is bounded and may end without a slot.
 __device__ __forceinline__ void gbin_segment(const KnnBin& kb, const int seg, const unsigned long long key, const int count, const int qs_pos) {
     const unsigned mask = (unsigned)(kb.gcap - 1);
-    unsigned s = hash_key(key) & mask;
+    unsigned s = cloud_key_hash(key) & mask;
     int slot = -1;
     for (int tries = 0; tries < 32; ++tries) {
         unsigned long long prev = kb.gkeys[s];
@@ -789,38 +785,22 @@ __device__ __forceinline__ void gbin_segment(const KnnBin& kb, const int seg, co
     if (slot >= 0) off = atomicAdd(&kb.gcnt[slot], count);
     else {
         off = kb.qcap_total - atomicAdd(&kb.gctr[6], count) - count;
-        const int nu = (count + GB_UNIT - 1) / GB_UNIT, ub = atomicAdd(&kb.gctr[1], nu);
-        for (int u = 0; u < nu; ++u)
-            kb.units[ub + u] = make_int4(off + GB_UNIT * u, min(GB_UNIT, count - GB_UNIT * u), (int)(unsigned)(key & 0xffffffffull), (int)(unsigned)(key >> 32));
+        units_emit<GB_UNIT>(kb.units, atomicAdd(&kb.gctr[1], (count + GB_UNIT - 1) / GB_UNIT), off, count, key);
     }
     kb.segs[seg] = make_int4(slot, off, qs_pos, count);
 }
 // the cells in table order: first position in qs2 (exclusive scan of the counts), units of <= 64 queries; the table is left EMPTY / 0 for the next call
 __global__ __launch_bounds__(1024) void k_gbin_alloc(const KnnBin kb) {
-    __shared__ int s_wc[16], s_wu[16], s_pb, s_ub;
-    const int s = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int c = s < kb.gcap ? kb.gcnt[s] : 0, nu = (c + GB_UNIT - 1) / GB_UNIT;
-    int ic = c, iu = nu;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(ic, off, 64), u = __shfl_up(iu, off, 64);
-        if (lane >= off) { ic += v; iu += u; }
-    }
-    if (lane == 63) { s_wc[wv] = ic; s_wu[wv] = iu; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tc = 0, tu = 0;
-        for (int k = 0; k < 16; ++k) { const int v = s_wc[k], u = s_wu[k]; s_wc[k] = tc; s_wu[k] = tu; tc += v; tu += u; }
-        s_pb = tc > 0 ? atomicAdd(&kb.gctr[0], tc) : 0;
-        s_ub = tu > 0 ? atomicAdd(&kb.gctr[1], tu) : 0;
-    }
-    __syncthreads();
+    __shared__ int s_w[2 * 16], s_base[2];
+    const int s = blockIdx.x * 1024 + threadIdx.x;
+    const int c = s < kb.gcap ? kb.gcnt[s] : 0;
+    const int v[2] = {c, (c + GB_UNIT - 1) / GB_UNIT};
+    int* const target[2] = {&kb.gctr[0], &kb.gctr[1]};
+    int st[2];
+    wg1024_claim<2>(v, target, s_w, s_base, st);
     if (c > 0) {
-        const int pb = s_pb + s_wc[wv] + ic - c, ub = s_ub + s_wu[wv] + iu - nu;
-        const unsigned long long key = kb.gkeys[s];
-        kb.gstart[s] = pb;
-        for (int u = 0; u < nu; ++u)
-            kb.units[ub + u] = make_int4(pb + GB_UNIT * u, min(GB_UNIT, c - GB_UNIT * u), (int)(unsigned)(key & 0xffffffffull), (int)(unsigned)(key >> 32));
+        kb.gstart[s] = st[0];
+        units_emit<GB_UNIT>(kb.units, st[1], st[0], c, kb.gkeys[s]);
         kb.gkeys[s] = KEY_EMPTY; kb.gcnt[s] = 0;
     }
 }
@@ -836,13 +816,12 @@ __global__ __launch_bounds__(256) void k_gbin_scatter(const KnnBin kb) {
 
 // per launch row y and tile of 1024 consecutive presorted points: units + grouped world-frame queries (w = original index)
 __global__ __launch_bounds__(QT_THREADS) void k_qbin_tile(const AssocArgs a, const float4* __restrict__ ps) {
-    __shared__ unsigned long long s_key[QT_SLOTS];
-    __shared__ int s_cnt[QT_SLOTS];
-    __shared__ int s_wc[16], s_wu[16], s_ubase;
+    __shared__ TileCells<QT_SLOTS, 1, int> s_cells;
+    __shared__ int s_w[2 * 16], s_ubase;
     const AssocSlot sl = assoc_slot(a);
-    const int tile0 = blockIdx.x * QT_THREADS, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tile0 = blockIdx.x * QT_THREADS, tid = threadIdx.x;
     if (tile0 >= sl.n) return;
-    for (int s = tid; s < QT_SLOTS; s += QT_THREADS) { s_key[s] = KEY_EMPTY; s_cnt[s] = 0; }
+    s_cells.clear<QT_THREADS>();
     __syncthreads();
     const int i = tile0 + tid;
     const bool live = i < sl.n;
@@ -850,72 +829,53 @@ __global__ __launch_bounds__(QT_THREADS) void k_qbin_tile(const AssocArgs a, con
     int slot = 0, rank = 0;
     if (live) {
         const float4 pl = ps[sl.qoff + i];
-        const double pin[3] = {(double)pl.x, (double)pl.y, (double)pl.z};
         double po[3];
-        d_qrot_nc(sl.q, pin, po);
-        px = (float)(po[0] + sl.t[0]); py = (float)(po[1] + sl.t[1]); pz = (float)(po[2] + sl.t[2]); pw = pl.w;
+        cloud_transform_d(sl.q, sl.t, pl, po);
+        px = (float)po[0]; py = (float)po[1]; pz = (float)po[2]; pw = pl.w;
         float kx = px, ky = py, kz = pz;            // the position the query is grouped by
         if (sl.local) {
             // in the search frame's own frame (its table was built there): R_j^T (p_world - t_j).  Only the grouping depends on it -- a cell edge exceeds
             // the search radius by 2.5 cm, rounding here is ~1e-6 m
-            const double dw[3] = {(po[0] + sl.t[0]) - sl.lt[0], (po[1] + sl.t[1]) - sl.lt[1], (po[2] + sl.t[2]) - sl.lt[2]};
+            const double dw[3] = {po[0] - sl.lt[0], po[1] - sl.lt[1], po[2] - sl.lt[2]};
             const double qc[4] = {sl.lq[0], -sl.lq[1], -sl.lq[2], -sl.lq[3]};
             double pl2[3];
             d_qrot_nc(qc, dw, pl2);
             kx = (float)pl2[0]; ky = (float)pl2[1]; kz = (float)pl2[2];
         }
-        const unsigned long long key = pack_key(cell_of(kx, a.inv_cell), cell_of(ky, a.inv_cell), cell_of(kz, a.inv_cell));
-        unsigned s = hash_key(key) & (QT_SLOTS - 1);
-        for (;;) {
-            const unsigned long long prev = atomicCAS(&s_key[s], KEY_EMPTY, key);
-            if (prev == KEY_EMPTY || prev == key) break;
-            s = (s + 1) & (QT_SLOTS - 1);
-        }
-        rank = atomicAdd(&s_cnt[s], 1);
-        slot = (int)s;
+        slot = s_cells.insert(cell_key_of(kx, ky, kz, a.inv_cell), 0, rank);
     }
     __syncthreads();
-    // exclusive scan of (queries, units) over the 2048 slots, two slots per thread
+    // exclusive scan of (units, queries) over the 2048 slots, two slots per thread; the units take their range of the row's list (the segments: of the merged window's)
     const bool glob = a.kb.glob != 0;
-    const int c0 = s_cnt[2 * tid], c1 = s_cnt[2 * tid + 1];
+    const int c0 = s_cells.cnt[2 * tid][0], c1 = s_cells.cnt[2 * tid + 1][0];
     const int u0 = glob ? (c0 > 0) : (c0 + TK_Q - 1) / TK_Q, u1 = glob ? (c1 > 0) : (c1 + TK_Q - 1) / TK_Q;      // units of this row, or segments of the merged window
-    int ic = c0 + c1, iu = u0 + u1;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const int v = __shfl_up(ic, off, 64), u = __shfl_up(iu, off, 64);
-        if (lane >= off) { ic += v; iu += u; }
-    }
-    if (lane == 63) { s_wc[wv] = ic; s_wu[wv] = iu; }
-    __syncthreads();
-    if (tid == 0) {
-        int tc = 0, tu = 0;
-        for (int k = 0; k < 16; ++k) { const int v = s_wc[k], u = s_wu[k]; s_wc[k] = tc; s_wu[k] = tu; tc += v; tu += u; }
-        s_ubase = glob ? atomicAdd(&a.kb.gctr[4], tu) : atomicAdd(&a.kb.counters[4 * blockIdx.y + 1], tu);
-    }
-    __syncthreads();
-    const int st0 = s_wc[wv] + ic - (c0 + c1), ut0 = s_ubase + s_wu[wv] + iu - (u0 + u1);
-    s_cnt[2 * tid] = st0; s_cnt[2 * tid + 1] = st0 + c0;
+    const int v[2] = {u0 + u1, c0 + c1};
+    int* const target[2] = {glob ? &a.kb.gctr[4] : &a.kb.counters[4 * blockIdx.y + 1], nullptr};
+    int st[2];
+    wg1024_claim<2>(v, target, s_w, &s_ubase, st);
+    const int ut0 = st[0], st0 = st[1];
+    s_cells.cnt[2 * tid][0] = st0; s_cells.cnt[2 * tid + 1][0] = st0 + c0;
     int4* un = a.kb.units + (size_t)blockIdx.y * a.kb.unit_stride;
-    const unsigned long long k0 = s_key[2 * tid], k1 = s_key[2 * tid + 1];
+    const unsigned long long k0 = s_cells.key[2 * tid], k1 = s_cells.key[2 * tid + 1];
     if (glob) {
         if (c0 > 0) gbin_segment(a.kb, ut0, k0, c0, (int)(sl.woff + tile0 + st0));
         if (c1 > 0) gbin_segment(a.kb, ut0 + u0, k1, c1, (int)(sl.woff + tile0 + st0 + c0));
         pw = __int_as_float((int)((unsigned)blockIdx.y << NK_ROW_SHIFT) | __float_as_int(pw));      // the row travels with the query
     } else {
-        for (int u = 0; u < u0; ++u) un[ut0 + u] = make_int4(tile0 + st0 + TK_Q * u, min(TK_Q, c0 - TK_Q * u), (int)(unsigned)(k0 & 0xffffffffull), (int)(unsigned)(k0 >> 32));
-        for (int u = 0; u < u1; ++u) un[ut0 + u0 + u] = make_int4(tile0 + st0 + c0 + TK_Q * u, min(TK_Q, c1 - TK_Q * u), (int)(unsigned)(k1 & 0xffffffffull), (int)(unsigned)(k1 >> 32));
+        units_emit<TK_Q>(un, ut0, tile0 + st0, c0, k0);
+        units_emit<TK_Q>(un, ut0 + u0, tile0 + st0 + c0, c1, k1);
     }
     __syncthreads();
-    if (live) a.kb.qs[sl.woff + tile0 + s_cnt[slot] + rank] = make_float4(px, py, pz, pw);
+    if (live) a.kb.qs[sl.woff + tile0 + s_cells.cnt[slot][0] + rank] = make_float4(px, py, pz, pw);
 }
 
-// sorted insertion of `key` into t[0] <= ... <= t[6]: new t[k] = med3(t[k-1], key, t[k]) (from the OLD values), new t[0] = min
+// sorted insertion of `key` into t[0] <= ... <= t[N - 1] (the last one drops out): new t[k] = med3(t[k-1], key, t[k]) (from the OLD values), new t[0] = min
 __device__ __forceinline__ unsigned tk_med3(const unsigned a, const unsigned b, const unsigned c) {
     return max(min(a, b), min(max(a, b), c));
 }
-__device__ __forceinline__ void tk_insert(unsigned t[TK_SEL], const unsigned key) {
+template <int N> __device__ __forceinline__ void tk_insert(unsigned (&t)[N], const unsigned key) {
 #pragma unroll
-    for (int k = TK_SEL - 1; k > 0; --k) t[k] = tk_med3(t[k - 1], key, t[k]);
+    for (int k = N - 1; k > 0; --k) t[k] = tk_med3(t[k - 1], key, t[k]);
     t[0] = min(t[0], key);
 }
 
@@ -981,31 +941,19 @@ __device__ __forceinline__ void knn5_tile_body(const AssocArgs& a, const float4*
         const int qw = __float_as_int(qp.w);
         const size_t qi = glob ? (size_t)((unsigned)qw >> NK_ROW_SHIFT) * a.w_stride + (qw & ((1 << NK_ROW_SHIFT) - 1)) : (size_t)qw;
         // the unit's cell from its record (not from the query: the probe below then does not wait for the query's load)
-        const unsigned long long ukey = ((unsigned long long)(unsigned)un.w << 32) | (unsigned)un.z;
-        const int cx = (int)((ukey >> 42) & 0x1fffffu) - (1 << 20), cy = (int)((ukey >> 21) & 0x1fffffu) - (1 << 20), cz = (int)(ukey & 0x1fffffu) - (1 << 20);
+        int cx, cy, cz;
+        cloud_cell_of_key(cloud_key_join(un.z, un.w), cx, cy, cz);
         // ---- probe the 27 cells once per unit: lane c < 27 takes cell c
         int cs = 0, cc = 0;
         if (l32 < 27 && ulive) {
-            const int dx = l32 % 3 - 1, dy = (l32 / 3) % 3 - 1, dz = l32 / 9 - 1;
-            const unsigned long long key = pack_key(cx + dx, cy + dy, cz + dz);
-            const int klo = (int)(unsigned)(key & 0xffffffffull), khi = (int)(unsigned)(key >> 32);
-            unsigned s = home_slot(cx + dx, cy + dy, cz + dz, table_cap);
-            for (;;) {
-                const int4 e = ent[s];
+            const int probes = cell_lookup(ent, table_cap, cx, cy, cz, l32, cs, cc);
 #ifdef GLIO_DEV_STAMPS
-                ++wg_probe;
+            wg_probe += probes;
+#else
+            (void)probes;
 #endif
-                if (e.x == klo && e.y == khi) { cs = e.z; cc = e.w; break; }
-                if ((e.x & e.y) == -1) break;
-                s = (s + 1) & (table_cap - 1);
-            }
         }
-        int incl = cc;
-#pragma unroll
-        for (int off = 1; off < TK_LANES; off <<= 1) {
-            const int t0 = __shfl_up(incl, off, TK_LANES);
-            if (l32 >= off) incl += t0;
-        }
+        const int incl = cloud_wave_incl_scan<TK_LANES>(cc);
         s_tab[g][l32] = make_int2(incl - cc, cs);
         const int tot = __shfl(incl, gbase + TK_LANES - 1, 64);
         if (l32 == 0) s_tab[g][32] = make_int2(tot, 0);
@@ -1213,11 +1161,6 @@ __global__ __launch_bounds__(64) void k_knn5_rest(const AssocArgs a, const int g
 #ifndef NK_UNIT_FAILS
 #define NK_UNIT_FAILS 6    /* uncertified queries (of 16) from which they are re-searched together by the tiled kernel */
 #endif
-__device__ __forceinline__ void nk_insert(unsigned t[6], const unsigned key) {
-#pragma unroll
-    for (int k = 5; k > 0; --k) t[k] = tk_med3(t[k - 1], key, t[k]);
-    t[0] = min(t[0], key);
-}
 __device__ __forceinline__ void nk_cex(unsigned long long& x, unsigned long long& y) {
     const bool sw = y < x;
     const unsigned long long lo = sw ? y : x, hi = sw ? x : y;
@@ -1293,8 +1236,8 @@ __global__ __launch_bounds__(64 * NK_WPB) NK_ATTR void k_knn5_near(const AssocAr
         const float px = qp.x, py = qp.y, pz = qp.z;
         const int qw = __float_as_int(qp.w);
         const size_t qi = glob ? (size_t)((unsigned)qw >> NK_ROW_SHIFT) * a.w_stride + (qw & ((1 << NK_ROW_SHIFT) - 1)) : (size_t)qw;
-        const unsigned long long ukey = ((unsigned long long)(unsigned)un.w << 32) | (unsigned)un.z;
-        const int cx = (int)((ukey >> 42) & 0x1fffffu) - (1 << 20), cy = (int)((ukey >> 21) & 0x1fffffu) - (1 << 20), cz = (int)(ukey & 0x1fffffu) - (1 << 20);
+        int cx, cy, cz;
+        cloud_cell_of_key(cloud_key_join(un.z, un.w), cx, cy, cz);
         // ---- probe the 27 cells once per unit; the record of a cell = (first point, points, octant prefix)
         int* cellw = reinterpret_cast<int*>(&s_q4[g][0][0]);      // [27][6], dead before the staging writes the quads
 #pragma unroll
@@ -1303,19 +1246,7 @@ __global__ __launch_bounds__(64 * NK_WPB) NK_ATTR void k_knn5_near(const AssocAr
             if (c < 27) {
                 int cs = 0, cc = 0;
                 uint4 sb = make_uint4(0, 0, 0, 0);
-                if (ulive) {
-                    const int dx = c % 3 - 1, dy = (c / 3) % 3 - 1, dz = c / 9 - 1;
-                    const unsigned long long key = pack_key(cx + dx, cy + dy, cz + dz);
-                    const int klo = (int)(unsigned)(key & 0xffffffffull), khi = (int)(unsigned)(key >> 32);
-                    unsigned s = home_slot(cx + dx, cy + dy, cz + dz, table_cap);
-                    for (;;) {
-                        const int4 e = ent[s];
-                        const uint4 sv = sub[s];                  // (issued with the entry: one round trip per probe step)
-                        if (e.x == klo && e.y == khi) { cs = e.z; cc = e.w; sb = sv; break; }
-                        if ((e.x & e.y) == -1) break;
-                        s = (s + 1) & (table_cap - 1);
-                    }
-                }
+                if (ulive) cell_lookup<true>(ent, sub, table_cap, cx, cy, cz, c, cs, cc, sb);
                 int2* cw = reinterpret_cast<int2*>(cellw + 6 * c);
                 cw[0] = make_int2(cs, cc); cw[1] = make_int2((int)sb.x, (int)sb.y); cw[2] = make_int2((int)sb.z, (int)sb.w);
             }
@@ -1346,12 +1277,7 @@ __global__ __launch_bounds__(64 * NK_WPB) NK_ATTR void k_knn5_near(const AssocAr
             }
         }
         const int mine = rcn[0] + rcn[1] + rcn[2];
-        int incl = mine;
-#pragma unroll
-        for (int off = 1; off < NK_Q; off <<= 1) {
-            const int t0 = __shfl_up(incl, off, NK_Q);
-            if ((j & (NK_Q - 1)) >= off) incl += t0;
-        }
+        const int incl = cloud_wave_incl_scan<NK_Q>(mine);
         const int tot = __shfl(incl, gbase + NK_Q - 1, 64);
         const unsigned long long bigb = __ballot(big);
         const bool over = tot > CAP || ((bigb >> gbase) & (UL == 64 ? ~0ull : 0xffffull)) != 0;
@@ -1430,10 +1356,10 @@ __global__ __launch_bounds__(64 * NK_WPB) NK_ATTR void k_knn5_near(const AssocAr
             da = __builtin_elementwise_fma(eya, eya, da); db = __builtin_elementwise_fma(eyb, eyb, db);
             da = __builtin_elementwise_fma(eza, eza, da); db = __builtin_elementwise_fma(ezb, ezb, db);
             const unsigned f0 = (unsigned)(4 * qd);
-            nk_insert(tk, (__float_as_uint(da.x) & ~MASK) | f0);
-            nk_insert(tk, (__float_as_uint(da.y) & ~MASK) | (f0 + 1u));
-            nk_insert(tk, (__float_as_uint(db.x) & ~MASK) | (f0 + 2u));
-            nk_insert(tk, (__float_as_uint(db.y) & ~MASK) | (f0 + 3u));
+            tk_insert(tk, (__float_as_uint(da.x) & ~MASK) | f0);
+            tk_insert(tk, (__float_as_uint(da.y) & ~MASK) | (f0 + 1u));
+            tk_insert(tk, (__float_as_uint(db.x) & ~MASK) | (f0 + 2u));
+            tk_insert(tk, (__float_as_uint(db.y) & ~MASK) | (f0 + 3u));
         }
         NK_T(nt4); NK_ACC(3, nt4, nt3);
         // ---- exact re-ranking of the six selected: unfused float distance (FLANN's L2), then original index; the slot rides in the low byte (indices
@@ -1544,10 +1470,8 @@ __global__ __launch_bounds__(PF_BLOCK) void k_plane_fit(const AssocArgs a, const
     if (sl.map) { map = sl.map; loc += sl.locoff; o_nc += 6 * sl.woff; }
     const bool qlive = i < sl.n;
     const float4 pl = scan[qlive ? i : 0];
-    const double pin[3] = {(double)pl.x, (double)pl.y, (double)pl.z};
-    double po[3];
-    d_qrot_nc(sl.q, pin, po);
-    const float px = (float)(po[0] + sl.t[0]), py = (float)(po[1] + sl.t[1]), pz = (float)(po[2] + sl.t[2]);
+    const float4 pw = cloud_transform(sl.q, sl.t, pl);
+    const float px = pw.x, py = pw.y, pz = pw.z;
     int mp5[5], mi[5];
     float md4 = FLT_MAX;
     float4 nbp[5];
@@ -1654,7 +1578,6 @@ __global__ __launch_bounds__(PF_BLOCK) void k_plane_fit(const AssocArgs a, const
     if (threadIdx.x == 0) { int tot = 0; for (int w2 = 0; w2 < PF_BLOCK / 64; ++w2) tot += wcount[w2]; o_bcount[blockIdx.x] = tot; }
 }
 
-// order-preserving compaction: single-workgroup exclusive scan of the flags, then scatter
 // order-preserving compaction: k_plane_fit left, per workgroup of PF_BLOCK queries, the kept count (bcount) and every kept
 // query's position inside the workgroup (lpos).  Each workgroup here sums the counts of the workgroups before it (a few
 // hundred integers) instead of waiting for a separate scan kernel; the last one writes the slot's total.
@@ -1693,6 +1616,12 @@ __global__ __launch_bounds__(PF_BLOCK) void k_compact(const int* __restrict__ fl
 // ------------------------------------------------------------------------------------------------
 
 struct KnnBinHost { KnnBin d; int rows, cap, capq_max; };
+// the capacity of an open-addressing table for n points: 2 n slots (load factor <= 0.5: table_claim and cell_lookup need an empty slot), at least 1024 -- a
+// table sized for THIS cloud stays in L2 -- and never more than what was allocated
+static int table_cap_for(const int n, const int cap_max) {
+    const int cap = next_pow2(2 * (n > 512 ? n : 512));
+    return cap > cap_max ? cap_max : cap;
+}
 static unsigned long long* g_knn_dbg = nullptr;      // statistics of the near-block search (glio_debug_knn_stats)
 // GLIO_KNN_MODE / glio_debug_set_knn_mode (A/B of whole programs, e.g. host_demo_stream):
 // 0 = window calls: the queries of all slots grouped by cell together, near block first (k_knn5_near<64>), the rest by
@@ -1741,8 +1670,7 @@ static void enqueue_presort(hipStream_t stream, KnnBinHost* kb, const float4* cl
     memset(&a, 0, sizeof a);
     a.q[0] = 1.0; a.inv_cell = 1.0f / PRESORT_CELL; a.n = n;
     a.kb = kb->d; a.kb.qs = ps;
-    a.kb.capq = next_pow2(2 * (n > 512 ? n : 512));
-    if (a.kb.capq > kb->capq_max) a.kb.capq = kb->capq_max;
+    a.kb.capq = table_cap_for(n, kb->capq_max);
     hipLaunchKernelGGL(k_qbin_count, dim3((n + QC_THREADS - 1) / QC_THREADS), dim3(QC_THREADS), 0, stream, a, cloud);
     hipLaunchKernelGGL(k_qbin_alloc, dim3(a.kb.capq / 1024), dim3(1024), 0, stream, a);
     hipLaunchKernelGGL(k_qbin_scatter, dim3((n + 255) / 256), dim3(256), 0, stream, a);
@@ -1821,7 +1749,7 @@ int glio_assoc_create(glio_ctx* c) {
     const int mm = c->opts.max_map_points > 0 ? c->opts.max_map_points : 1;
     w->table_cap = next_pow2(2 * mm);
     const int cap = c->cap;
-#define AALLOC(ptr, bytes) do { if (hipMalloc((void**)&(ptr), (size_t)(bytes)) != hipSuccess) { glio_set_error("hipMalloc failed in assoc_create"); return GLIO_E_HIP; } } while (0)
+#define AALLOC(ptr, bytes) GLIO_HIP_CHECK(hipMalloc((void**)&(ptr), (size_t)(bytes)))
     w->cap_eff = w->table_cap;
     AALLOC(w->d_keys, (size_t)w->table_cap * 8); AALLOC(w->d_ent, (size_t)w->table_cap * 16); AALLOC(w->d_cnt8, (size_t)w->table_cap * 32);
     AALLOC(w->d_sub, (size_t)w->table_cap * 16);
@@ -1877,9 +1805,7 @@ static void enqueue_build(glio_ctx* c, int n, const float4* src = nullptr) {
     AssocWork* w = c->assoc;
     if (!src) src = w->d_map_raw;                          // (src: the map's points as they lie on the device -- the local map's output needs no copy into d_map_raw)
     w->last_src = src;                                     // (what a re-build of the same map -- the timing hook -- reads)
-    int cap = next_pow2(2 * (n > 512 ? n : 512));          // sized for THIS map: a smaller table stays in L2
-    if (cap > w->table_cap) cap = w->table_cap;
-    w->cap_eff = cap;
+    const int cap = w->cap_eff = table_cap_for(n, w->table_cap);
     hipLaunchKernelGGL(k_hash_clear, dim3((cap + 255) / 256), dim3(256), 0, c->stream, w->d_keys, w->d_cnt8, cap, w->d_total, w->d_ent, w->d_sub, n == 0 ? 1 : 0);
     if (n == 0) return;
     hipLaunchKernelGGL(k_hash_insert, dim3((n + HI_THREADS - 1) / HI_THREADS), dim3(HI_THREADS), 0, c->stream, src, n, w->inv_cell, w->d_keys, w->d_cnt8, w->d_pt_slot, w->d_pt_rank, cap);
@@ -1909,16 +1835,28 @@ int glio_assoc_build_map_dev(glio_ctx* c, const float4* d_pts, int n) {
     return GLIO_OK;
 }
 
-static void enqueue_assoc(glio_ctx* c, int slot, const double q[4], const double t[3], int n, int want_nn) {
-    AssocWork* w = c->assoc;
+// the record every launch of an association starts from: the cell, the gates and the score rule; everything else zero (a single scan at the identity)
+static AssocArgs assoc_args_base(const float cell, const float inv_cell, const double kd_max_radius, const double weight_gate, const double surf_dist_thres,
+                                 const double lidar_const, const int unit_scores) {
     AssocArgs a;
     memset(&a, 0, sizeof a);
+    a.cell = cell; a.inv_cell = inv_cell; a.kd_max_radius = kd_max_radius; a.weight_gate = weight_gate;
+    a.surf_dist_thres = surf_dist_thres; a.lidar_const = lidar_const; a.unit_scores = unit_scores;
+    return a;
+}
+// ... of a context: its options, the table of its current map
+static AssocArgs assoc_args_ctx(const glio_ctx* c) {
+    const AssocWork* w = c->assoc;
+    AssocArgs a = assoc_args_base(w->cell, w->inv_cell, c->opts.kd_max_radius, c->opts.weight_gate, c->opts.surf_dist_thres, c->opts.lidar_const, c->opts.unit_scores);
+    a.table_cap = w->cap_eff;
+    return a;
+}
+static void enqueue_assoc(glio_ctx* c, int slot, const double q[4], const double t[3], int n, int want_nn) {
+    AssocWork* w = c->assoc;
+    AssocArgs a = assoc_args_ctx(c);
     for (int k = 0; k < 4; ++k) a.q[k] = q[k];
     for (int k = 0; k < 3; ++k) a.t[k] = t[k];
-    a.inv_cell = w->inv_cell; a.cell = w->cell; a.kd_max_radius = c->opts.kd_max_radius; a.weight_gate = c->opts.weight_gate;
-    a.surf_dist_thres = c->opts.surf_dist_thres; a.lidar_const = c->opts.lidar_const;
-    a.n = n; a.table_cap = w->cap_eff; a.unit_scores = c->opts.unit_scores;
-    a.win_poses = nullptr; a.win_counts = nullptr; a.q_stride = a.w_stride = a.b_stride = 0;
+    a.n = n;
     const size_t off = (size_t)slot * c->cap, row = (size_t)glio_scan_row(c, slot) * c->cap;      // correspondences by window slot, scans by ring row
     const int nblk = (n + PF_BLOCK - 1) / PF_BLOCK;
     if (n > 0) {
@@ -1947,11 +1885,7 @@ static int enqueue_assoc_window(glio_ctx* c, const double* quats, const double* 
         if (c->h_scan_count[s] > maxn) maxn = c->h_scan_count[s];
     }
     GLIO_HIP_CHECK(hipMemcpyAsync(w->d_win, w->h_win, (size_t)W * 60, hipMemcpyHostToDevice, c->stream));
-    AssocArgs a;
-    memset(&a, 0, sizeof a);
-    a.inv_cell = w->inv_cell; a.cell = w->cell; a.kd_max_radius = c->opts.kd_max_radius; a.weight_gate = c->opts.weight_gate;
-    a.surf_dist_thres = c->opts.surf_dist_thres; a.lidar_const = c->opts.lidar_const;
-    a.n = 0; a.table_cap = w->cap_eff; a.unit_scores = c->opts.unit_scores;
+    AssocArgs a = assoc_args_ctx(c);
     a.win_poses = w->d_win; a.win_counts = reinterpret_cast<const int*>(w->d_win + 7 * W);
     a.q_stride = c->cap; a.w_stride = c->cap; a.b_stride = c->cap / AQ_PER_BLOCK + 2;
     a.ring_base = c->scan_base; a.ring_W = W;
@@ -1966,7 +1900,7 @@ static int enqueue_assoc_window(glio_ctx* c, const double* quats, const double* 
     return GLIO_OK;
 }
 
-int glio_assoc_finish_pending(glio_ctx* c);
+int glio_assoc_finish_pending(glio_ctx* c);      // (defined behind the asynchronous window call it completes)
 // A map that was built but holds no point (a local map whose ring holds only empty keyframes: enqueue_build's n == 0) is not "no map": nothing can be
 // associated against it, so slots [slot0, slot0 + ns) keep 0 correspondences and no search is launched.  (w->last_src: set by every build.)
 static bool assoc_map_is_empty(const glio_ctx* c) { return c->map_n == 0 && c->assoc->last_src != nullptr; }
@@ -2091,7 +2025,6 @@ int glio_assoc_select_window(glio_ctx* c, const int32_t* offsets, const int32_t*
 
 // all W slots back to back on the stream, ONE host synchronisation: the per-slot sync of glio_assoc_run (count
 // read-back) costs as much as half a K2 launch
-int glio_assoc_finish_pending(glio_ctx* c);
 int glio_assoc_run_window(glio_ctx* c, const double* quats, const double* trans, int32_t* out_counts) {
     AssocWork* w = c->assoc;
     if (!w) return GLIO_E_STATE;
@@ -2146,6 +2079,19 @@ int glio_assoc_finish_pending(glio_ctx* c) {
 extern "C" int glio_debug_last_nn(glio_ctx* c, int32_t* out, int n) {
     if (!c || !c->assoc) return GLIO_E_STATE;
     GLIO_HIP_CHECK(hipMemcpy(out, c->assoc->d_nn, (size_t)n * 5 * 4, hipMemcpyDeviceToHost));
+    return GLIO_OK;
+}
+
+// test hook: K1's tables as the searches read them -- *cap_out = slots of the current map's table, ent [cap][4] (key lo, key hi, first point, points), sub [cap][4],
+// sorted [map_n][4] (w = the bits of the original index); null pointers are skipped (a first call with only cap_out sizes the buffers)
+extern "C" int glio_debug_read_map_table(glio_ctx* c, int32_t* cap_out, int32_t* ent, uint32_t* sub, float* sorted) {
+    if (!c || !c->assoc) return GLIO_E_STATE;
+    const AssocWork* w = c->assoc;
+    GLIO_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (cap_out) *cap_out = w->cap_eff;
+    if (ent) GLIO_HIP_CHECK(hipMemcpy(ent, w->d_ent, (size_t)w->cap_eff * 16, hipMemcpyDeviceToHost));
+    if (sub) GLIO_HIP_CHECK(hipMemcpy(sub, w->d_sub, (size_t)w->cap_eff * 16, hipMemcpyDeviceToHost));
+    if (sorted && c->map_n > 0) GLIO_HIP_CHECK(hipMemcpy(sorted, c->d_map_sorted, (size_t)c->map_n * 16, hipMemcpyDeviceToHost));
     return GLIO_OK;
 }
 
@@ -2245,11 +2191,7 @@ __global__ void k_transform_cloud(const float4* __restrict__ in, int n, const do
     const int i = blockIdx.x * blockDim.x + threadIdx.x;          // transformCloud, Estimator.cpp:1517-1546
     if (i >= n) return;
     const double t[3] = {pose[0], pose[1], pose[2]}, q[4] = {pose[3], pose[4], pose[5], pose[6]};
-    const float4 p = in[i];
-    const double pin[3] = {(double)p.x, (double)p.y, (double)p.z};
-    double po[3];
-    d_qrot_nc(q, pin, po);
-    out[i] = make_float4((float)(po[0] + t[0]), (float)(po[1] + t[1]), (float)(po[2] + t[2]), p.w);
+    out[i] = cloud_transform(q, t, in[i]);
 }
 
 // ---- the per-keyframe voxel hashes of the batch association, BA_FB keyframes per launch (blockIdx.y = keyframe of the batch).  One keyframe at a time
@@ -2269,11 +2211,9 @@ __global__ void k_transform_cloud_multi(const FrameBuild* __restrict__ fb) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;          // transformCloud, Estimator.cpp:1517-1546
     if (i >= f.n) return;
     const double t[3] = {f.pose[0], f.pose[1], f.pose[2]}, q[4] = {f.pose[3], f.pose[4], f.pose[5], f.pose[6]};
-    const float4 p = f.local[i];                                  // (the PRESORTED copy of the keyframe cloud: w = index in the cloud; consecutive points are neighbours,
-    const double pin[3] = {(double)p.x, (double)p.y, (double)p.z};    //  which is what lets the tile insert below aggregate its atomics)
-    double po[3];
-    d_qrot_nc(q, pin, po);
-    f.global[i] = make_float4((float)(po[0] + t[0]), (float)(po[1] + t[1]), (float)(po[2] + t[2]), p.w);
+    // (f.local: the PRESORTED copy of the keyframe cloud, w = index in the cloud; consecutive points are neighbours, which is what lets the tile insert below
+    //  aggregate its atomics)
+    f.global[i] = cloud_transform(q, t, f.local[i]);
 }
 __global__ __launch_bounds__(HI_THREADS) void k_hash_insert_multi(const FrameBuild* __restrict__ fb, const float inv_cell) {
     __shared__ HashInsertLds L;
@@ -2310,9 +2250,7 @@ __global__ __launch_bounds__(1024) void k_scan_pairs(const int* __restrict__ bco
         for (int i0 = 0; i0 < nblk; i0 += 64) {
             const int i = i0 + lane;
             const int v = i < nblk ? bcount[(size_t)q * b_stride + i] : 0;
-            int incl = v;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off, 64); if (lane >= off) incl += t; }
+            const int incl = cloud_wave_incl_scan(v);
             if (i < nblk) boff[(size_t)q * b_stride + i] = carry + incl - v;
             carry += __shfl(incl, 63, 64);
         }
@@ -2348,8 +2286,6 @@ __global__ void k_compact_pairs(const int* __restrict__ flag, const int* __restr
     for (int k = 0; k < 6; ++k) o_nc[6 * p + k] = q_nc[6 * w + k];
 }
 
-#define BA_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { glio_set_error("%s failed: %s", #expr, hipGetErrorString(e_)); return GLIO_E_HIP; } } while (0)
-
 extern "C" {
 
 // statistics of the near-block search since the last call (test / profiling hook): out[8] = units, units whose block did not fit, units handed on as units,
@@ -2379,7 +2315,7 @@ int glio_bassoc_create(int device, int K, int max_points_per_frame, int64_t max_
     if (!out || K < 2 || max_points_per_frame < 1 || max_constraints < 1) return GLIO_E_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { glio_set_error("no HIP device %d", device); return GLIO_E_HIP; }
-    BA_CHECK(hipSetDevice(device));
+    GLIO_HIP_CHECK(hipSetDevice(device));
     glio_bassoc* b = new glio_bassoc();
     memset(b, 0, sizeof *b);
     b->device = device; b->K = K; b->cap = max_points_per_frame; b->max_con = max_constraints;
@@ -2387,17 +2323,17 @@ int glio_bassoc_create(int device, int K, int max_points_per_frame, int64_t max_
         // local map, the solve's one-CU steps on the context's stream) -- those must get their CUs first (GLIO_BASSOC_PRIORITY=0: default priority, for A/B)
         int least = 0, greatest = 0;
         if (glio_switch_at_create<GLIO_SW_BASSOC_PRIORITY>() && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-            BA_CHECK(hipStreamCreateWithPriority(&b->stream, hipStreamNonBlocking, least));
-        else BA_CHECK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
+            GLIO_HIP_CHECK(hipStreamCreateWithPriority(&b->stream, hipStreamNonBlocking, least));
+        else GLIO_HIP_CHECK(hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking));
     }
     b->cell = fmaxf(1.25f, sqrtf(1.5f) * 1.0001f);
     b->inv_cell = 1.0f / b->cell;
     const size_t cap = (size_t)b->cap;
-    BA_CHECK(hipMalloc((void**)&b->d_local, (size_t)K * cap * 16)); BA_CHECK(hipMalloc((void**)&b->d_global, (size_t)BA_FB * cap * 16));
-    BA_CHECK(hipMalloc((void**)&b->d_local_ps, (size_t)K * cap * 16));
-    BA_CHECK(hipMalloc((void**)&b->d_sorted_local, (size_t)K * cap * 16));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_local, (size_t)K * cap * 16)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_global, (size_t)BA_FB * cap * 16));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_local_ps, (size_t)K * cap * 16));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_sorted_local, (size_t)K * cap * 16));
     b->inbox_bytes = (size_t)K * (7 * 8 + sizeof(FrameBuild) + sizeof(FrameDesc)) + (size_t)2 * 4 * 16 * K + 64;      // (pair arrays: 2 x up to 16 K pairs)
-    BA_CHECK(hipMalloc((void**)&b->d_inbox, b->inbox_bytes)); BA_CHECK(hipHostMalloc((void**)&b->h_inbox, b->inbox_bytes));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_inbox, b->inbox_bytes)); GLIO_HIP_CHECK(hipHostMalloc((void**)&b->h_inbox, b->inbox_bytes));
     b->h_n = new int[K]();
     b->frames = new FrameHash[K]();
     const int tc = next_pow2(2 * b->cap);
@@ -2405,31 +2341,31 @@ int glio_bassoc_create(int device, int K, int max_points_per_frame, int64_t max_
         FrameHash& f = b->frames[k];
         f.table_cap = tc;
         f.d_sorted_local = b->d_sorted_local + (size_t)k * cap; f.local_valid = 0;
-        BA_CHECK(hipMalloc((void**)&f.d_ent, (size_t)tc * 16)); BA_CHECK(hipMalloc((void**)&f.d_sub, (size_t)tc * 16)); BA_CHECK(hipMalloc((void**)&f.d_sorted, cap * 16));
+        GLIO_HIP_CHECK(hipMalloc((void**)&f.d_ent, (size_t)tc * 16)); GLIO_HIP_CHECK(hipMalloc((void**)&f.d_sub, (size_t)tc * 16)); GLIO_HIP_CHECK(hipMalloc((void**)&f.d_sorted, cap * 16));
         // (a keyframe that never serves as a search frame keeps an EMPTY table: the probes of a stray pair end at once)
-        BA_CHECK(hipMemsetAsync(f.d_ent, 0xff, (size_t)tc * 16, b->stream));
+        GLIO_HIP_CHECK(hipMemsetAsync(f.d_ent, 0xff, (size_t)tc * 16, b->stream));
     }
-    BA_CHECK(hipMalloc((void**)&b->d_total, (size_t)BA_FB * 4));
-    BA_CHECK(hipMalloc((void**)&b->d_bkeys, (size_t)BA_FB * tc * 8)); BA_CHECK(hipMalloc((void**)&b->d_bcnt8, (size_t)BA_FB * tc * 32));
-    BA_CHECK(hipMalloc((void**)&b->d_bslot, (size_t)BA_FB * cap * 4)); BA_CHECK(hipMalloc((void**)&b->d_brank, (size_t)BA_FB * cap * 4));
-    BA_CHECK(hipMalloc((void**)&b->d_fb, (size_t)2 * K * sizeof(FrameBuild))); BA_CHECK(hipHostMalloc((void**)&b->h_fb, (size_t)2 * K * sizeof(FrameBuild)));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_total, (size_t)BA_FB * 4));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_bkeys, (size_t)BA_FB * tc * 8)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_bcnt8, (size_t)BA_FB * tc * 32));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_bslot, (size_t)BA_FB * cap * 4)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_brank, (size_t)BA_FB * cap * 4));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_fb, (size_t)2 * K * sizeof(FrameBuild))); GLIO_HIP_CHECK(hipHostMalloc((void**)&b->h_fb, (size_t)2 * K * sizeof(FrameBuild)));
     // dense per-query work arrays for a chunk of BA_CHUNK pairs (104 B per query and pair)
     const size_t wc = cap * BA_CHUNK;
     b->b_stride = (int)(cap / PF_BLOCK + 2);
-    BA_CHECK(hipMalloc((void**)&b->d_q_cp, wc * 16)); BA_CHECK(hipMalloc((void**)&b->d_q_nc, wc * 48)); BA_CHECK(hipMalloc((void**)&b->d_q_score, wc * 8));
-    BA_CHECK(hipMalloc((void**)&b->d_q_flag, wc * 4)); BA_CHECK(hipMalloc((void**)&b->d_q_pos, wc * 4));
-    BA_CHECK(hipMalloc((void**)&b->d_nn5, wc * 32));
-    BA_CHECK(hipMalloc((void**)&b->d_bcount, (size_t)b->b_stride * BA_CHUNK * 4)); BA_CHECK(hipMalloc((void**)&b->d_boff, (size_t)b->b_stride * BA_CHUNK * 4));
-    BA_CHECK(hipMalloc((void**)&b->d_frames, (size_t)K * sizeof(FrameDesc)));
-    BA_CHECK(hipMalloc((void**)&b->d_cp, (size_t)max_constraints * 16)); BA_CHECK(hipMalloc((void**)&b->d_nc, (size_t)max_constraints * 48));
-    BA_CHECK(hipMalloc((void**)&b->d_score, (size_t)max_constraints * 8));
-    BA_CHECK(hipMalloc((void**)&b->d_run, 16)); BA_CHECK(hipMalloc((void**)&b->d_poses, (size_t)K * 7 * 8));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_q_cp, wc * 16)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_q_nc, wc * 48)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_q_score, wc * 8));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_q_flag, wc * 4)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_q_pos, wc * 4));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_nn5, wc * 32));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_bcount, (size_t)b->b_stride * BA_CHUNK * 4)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_boff, (size_t)b->b_stride * BA_CHUNK * 4));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_frames, (size_t)K * sizeof(FrameDesc)));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_cp, (size_t)max_constraints * 16)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_nc, (size_t)max_constraints * 48));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_score, (size_t)max_constraints * 8));
+    GLIO_HIP_CHECK(hipMalloc((void**)&b->d_run, 16)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_poses, (size_t)K * 7 * 8));
     b->kb = knn_bin_create(BA_CHUNK, b->cap);
     if (!b->kb) return GLIO_E_HIP;
-    BA_CHECK(hipHostMalloc((void**)&b->h_tail, 16)); BA_CHECK(hipHostMalloc((void**)&b->h_poses, (size_t)K * 7 * 8)); BA_CHECK(hipHostMalloc((void**)&b->h_fd, (size_t)K * sizeof(FrameDesc)));
+    GLIO_HIP_CHECK(hipHostMalloc((void**)&b->h_tail, 16)); GLIO_HIP_CHECK(hipHostMalloc((void**)&b->h_poses, (size_t)K * 7 * 8)); GLIO_HIP_CHECK(hipHostMalloc((void**)&b->h_fd, (size_t)K * sizeof(FrameDesc)));
     b->h_tail[0] = b->h_tail[1] = 0; b->pending_pairs = -1; b->done_pairs = -1; b->done_overflow = 0;
-    BA_CHECK(hipMemsetAsync(b->d_run, 0, 16, b->stream));
-    BA_CHECK(hipStreamSynchronize(b->stream));
+    GLIO_HIP_CHECK(hipMemsetAsync(b->d_run, 0, 16, b->stream));
+    GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
     *out = b;
     return GLIO_OK;
 }
@@ -2480,15 +2416,15 @@ int glio_bassoc_view(glio_bassoc* b, GlioBassocView* out) {
     return GLIO_OK;
 }
 int glio_bassoc_external_read(glio_bassoc* b, hipStream_t reader) {
-    if (!b->ev_ext_read) BA_CHECK(hipEventCreateWithFlags(&b->ev_ext_read, hipEventDisableTiming));
-    if (b->ext_read_pending) BA_CHECK(hipStreamWaitEvent(reader, b->ev_ext_read, 0));       // (another object's read: the new record covers it)
-    BA_CHECK(hipEventRecord(b->ev_ext_read, reader));
+    if (!b->ev_ext_read) GLIO_HIP_CHECK(hipEventCreateWithFlags(&b->ev_ext_read, hipEventDisableTiming));
+    if (b->ext_read_pending) GLIO_HIP_CHECK(hipStreamWaitEvent(reader, b->ev_ext_read, 0));       // (another object's read: the new record covers it)
+    GLIO_HIP_CHECK(hipEventRecord(b->ev_ext_read, reader));
     b->ext_read_pending = 1;
     return GLIO_OK;
 }
 // (before a resident cloud is overwritten on the object's stream)
 static int bassoc_behind_external_read(glio_bassoc* b) {
-    if (b->ext_read_pending) { BA_CHECK(hipStreamWaitEvent(b->stream, b->ev_ext_read, 0)); b->ext_read_pending = 0; }
+    if (b->ext_read_pending) { GLIO_HIP_CHECK(hipStreamWaitEvent(b->stream, b->ev_ext_read, 0)); b->ext_read_pending = 0; }
     return GLIO_OK;
 }
 extern "C" {
@@ -2496,13 +2432,13 @@ int glio_bassoc_set_frame(glio_bassoc* b, int k, const float* scan_xyzi, int n) 
 int glio_bassoc_set_frame_strided(glio_bassoc* b, int k, const void* scan, int n, int stride_bytes, int intensity_offset) {
     if (!b || k < 0 || k >= b->K || n < 0 || n > b->cap || (n > 0 && !scan)) { glio_set_error("bad keyframe cloud (k %d, n %d)", k, n); return GLIO_E_ARG; }
     if (!glio_point_layout_ok(stride_bytes, intensity_offset)) { glio_set_error("bad point layout (stride %d, intensity at %d)", stride_bytes, intensity_offset); return GLIO_E_ARG; }
-    BA_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rf = bassoc_drain(b); if (rf != GLIO_OK) return rf; }      // (an asynchronous run may still read the clouds)
     { const int re = bassoc_behind_external_read(b); if (re != GLIO_OK) return re; }
     { const int ru = glio_upload_points(b->stream, &b->raw_stage, scan, n, stride_bytes, intensity_offset, b->d_local + (size_t)k * b->cap); if (ru != GLIO_OK) return ru; }
     enqueue_presort(b->stream, b->kb, b->d_local + (size_t)k * b->cap, n, b->d_local_ps + (size_t)k * b->cap);
-    BA_CHECK(hipGetLastError());
-    BA_CHECK(hipStreamSynchronize(b->stream));
+    GLIO_HIP_CHECK(hipGetLastError());
+    GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
     b->h_n[k] = n;
     b->frames[k].local_valid = 0;
     return GLIO_OK;
@@ -2517,7 +2453,7 @@ int glio_bassoc_set_frame_strided(glio_bassoc* b, int k, const void* scan, int n
 // is reported there too (advisor finding of round 5: side calls used to consume both).
 static int bassoc_drain(glio_bassoc* b) {
     if (b->pending_pairs < 0) return GLIO_OK;
-    BA_CHECK(hipStreamSynchronize(b->stream));
+    GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
     b->done_pairs = b->pending_pairs;
     b->done_overflow = *reinterpret_cast<int*>(&b->h_tail[1]) != 0;
     b->pending_pairs = -1;
@@ -2534,20 +2470,21 @@ static int bassoc_finish(glio_bassoc* b, int64_t* pair_count_out, int64_t* total
     return GLIO_OK;
 }
 // build descriptors of one batch of search frames (keyframes todo[0 .. nb), descriptor slots t0 ..): where the keyframe's hash goes, its build scratch
-static void bassoc_fill_batch(glio_bassoc* b, const int* todo, const size_t t0, const int nb, int* max_tc_out, int* max_n_out) {
+// (local: the table of the keyframe's LOCAL cloud -- what is hashed is the presorted local cloud itself, nothing is transformed, the sorted points go to d_sorted_local)
+static void bassoc_fill_batch(glio_bassoc* b, const int* todo, const size_t t0, const int nb, const bool local, int* max_tc_out, int* max_n_out) {
     int max_tc = 0, max_n = 0;
     for (int q = 0; q < nb; ++q) {
         const int k = todo[q];
         FrameHash& f = b->frames[k];
         const int n = b->h_n[k];
-        int tc = next_pow2(2 * (n > 512 ? n : 512));
-        if (tc > f.table_cap) tc = f.table_cap;
+        const int tc = table_cap_for(n, f.table_cap);
         f.n = n; f.cap_eff = tc;
         FrameBuild& d = b->h_fb[t0 + q];
         d.keys = b->d_bkeys + (size_t)q * f.table_cap; d.cnt8 = b->d_bcnt8 + (size_t)q * f.table_cap * 8;
         d.pt_slot = b->d_bslot + (size_t)q * b->cap; d.pt_rank = b->d_brank + (size_t)q * b->cap;
         d.ent = f.d_ent; d.sub = f.d_sub; d.sorted = f.d_sorted;
         d.local = b->d_local_ps + (size_t)k * b->cap; d.global = b->d_global + (size_t)q * b->cap; d.pose = b->d_poses + 7 * k; d.total = b->d_total + q; d.n = n; d.tc = tc;
+        if (local) { d.global = b->d_local_ps + (size_t)k * b->cap; d.sorted = f.d_sorted_local; }
         if (tc > max_tc) max_tc = tc;
         if (n > max_n) max_n = n;
     }
@@ -2555,12 +2492,12 @@ static void bassoc_fill_batch(glio_bassoc* b, const int* todo, const size_t t0, 
 }
 // the pinned descriptor block h_fb is the source of asynchronous copies: it is rewritten only after the last of them has left it
 static int bassoc_fb_reusable(glio_bassoc* b) {
-    if (b->fb_in_flight) { BA_CHECK(hipEventSynchronize(b->ev_fb)); b->fb_in_flight = 0; }
+    if (b->fb_in_flight) { GLIO_HIP_CHECK(hipEventSynchronize(b->ev_fb)); b->fb_in_flight = 0; }
     return GLIO_OK;
 }
 static int bassoc_fb_uploaded(glio_bassoc* b) {
-    if (!b->ev_fb) BA_CHECK(hipEventCreateWithFlags(&b->ev_fb, hipEventDisableTiming));
-    BA_CHECK(hipEventRecord(b->ev_fb, b->stream));
+    if (!b->ev_fb) GLIO_HIP_CHECK(hipEventCreateWithFlags(&b->ev_fb, hipEventDisableTiming));
+    GLIO_HIP_CHECK(hipEventRecord(b->ev_fb, b->stream));
     b->fb_in_flight = 1;
     return GLIO_OK;
 }
@@ -2582,32 +2519,53 @@ static bool bassoc_local_mode(const glio_bassoc* b, const int n_pairs, const int
         }
     return true;
 }
-// the local tables that are missing among `need`: descriptors h_fb[K + ..] (the caller has made the pinned block reusable), upload, build.  *wrote: the block was written
-static int bassoc_build_local(glio_bassoc* b, const std::vector<char>& need, bool* wrote) {
-    std::vector<int> todo;
-    for (int k = 0; k < b->K; ++k) if (need[k] && !b->frames[k].local_valid) todo.push_back(k);
+// the voxel hashes of a batch of nb keyframes (descriptors dfb on the device) in one launch per step: clear (unless glio_bassoc_prepare_async did it), the clouds into
+// the global frame (unless the tables are the local ones), tile insert, cell allocation, scatter
+static void bassoc_enqueue_build(glio_bassoc* b, const FrameBuild* dfb, const int nb, const int max_tc, const int max_n, const bool clear, const bool transform) {
+    if (clear) hipLaunchKernelGGL(k_hash_clear_multi, dim3((max_tc + 255) / 256, nb), dim3(256), 0, b->stream, dfb);
+    if (max_n == 0) return;
+    if (transform) hipLaunchKernelGGL(k_transform_cloud_multi, dim3((max_n + 255) / 256, nb), dim3(256), 0, b->stream, dfb);
+    hipLaunchKernelGGL(k_hash_insert_multi, dim3((max_n + HI_THREADS - 1) / HI_THREADS, nb), dim3(HI_THREADS), 0, b->stream, dfb, b->inv_cell);
+    hipLaunchKernelGGL(k_cell_alloc_multi, dim3((max_tc + 1023) / 1024, nb), dim3(1024), 0, b->stream, dfb);
+    hipLaunchKernelGGL(k_scatter_multi, dim3((max_n + 255) / 256, nb), dim3(256), 0, b->stream, dfb);
+}
+// The tables of the keyframes `todo`, BA_FB per batch: descriptors filled in the pinned h_fb (made reusable first), uploaded, built.  local: the keyframes' LOCAL
+// tables (descriptor slots [K, 2 K); valid from now on); else their tables at the run's poses (slots [0, K); whoever calls has invalidated the local ones).
+// A first batch that glio_bassoc_prepare_async has sent and cleared already (same keyframes, same sizes, nothing run since) is neither filled nor cleared
+// again: the answer follows from what was prepared alone -- never from how long ago (advisor finding of round 5: a wall-clock test made the kernel sequence
+// depend on host timing) -- and its descriptors are on the device as the preparation wrote them.
+static int bassoc_build_tables(glio_bassoc* b, const std::vector<int>& todo, const bool local) {
+    const size_t slot0 = local ? (size_t)b->K : 0;
+    bool fb_checked = false, fb_written = false;
     for (size_t t0 = 0; t0 < todo.size(); t0 += BA_FB) {
         const int nb = (int)std::min<size_t>(BA_FB, todo.size() - t0);
         int max_tc = 0, max_n = 0;
-        bassoc_fill_batch(b, todo.data() + t0, (size_t)b->K + t0, nb, &max_tc, &max_n);
-        for (int q = 0; q < nb; ++q) {
-            FrameBuild& d = b->h_fb[(size_t)b->K + t0 + q];
-            const int k = todo[t0 + q];
-            d.global = b->d_local_ps + (size_t)k * b->cap;            // (what is hashed: the presorted LOCAL cloud itself; nothing is transformed)
-            d.sorted = b->frames[k].d_sorted_local;
+        bool prepared = !local && t0 == 0 && b->prep_nb == nb;
+        for (int q = 0; prepared && q < nb; ++q) {
+            const int k = todo[q], n = b->h_n[k];
+            prepared = b->prep_todo[q] == k && b->prep_n[q] == n && b->prep_tc[q] == table_cap_for(n, b->frames[k].table_cap);
         }
-        const FrameBuild* dfb = b->d_fb + b->K + t0;
-        BA_CHECK(hipMemcpyAsync(b->d_fb + b->K + t0, b->h_fb + b->K + t0, (size_t)nb * sizeof(FrameBuild), hipMemcpyHostToDevice, b->stream));
-        *wrote = true;
-        hipLaunchKernelGGL(k_hash_clear_multi, dim3((max_tc + 255) / 256, nb), dim3(256), 0, b->stream, dfb);
-        if (max_n > 0) {
-            hipLaunchKernelGGL(k_hash_insert_multi, dim3((max_n + HI_THREADS - 1) / HI_THREADS, nb), dim3(HI_THREADS), 0, b->stream, dfb, b->inv_cell);
-            hipLaunchKernelGGL(k_cell_alloc_multi, dim3((max_tc + 1023) / 1024, nb), dim3(1024), 0, b->stream, dfb);
-            hipLaunchKernelGGL(k_scatter_multi, dim3((max_n + 255) / 256, nb), dim3(256), 0, b->stream, dfb);
+        b->prep_nb = 0;
+        const FrameBuild* dfb = b->d_fb + slot0 + t0;
+        if (prepared) {
+            for (int q = 0; q < nb; ++q) { if (b->prep_tc[q] > max_tc) max_tc = b->prep_tc[q]; if (b->prep_n[q] > max_n) max_n = b->prep_n[q]; }
+        } else {
+            if (!fb_checked) { const int rw = bassoc_fb_reusable(b); if (rw != GLIO_OK) return rw; fb_checked = true; }   // (once per call: its batches write distinct parts of h_fb)
+            bassoc_fill_batch(b, todo.data() + t0, slot0 + t0, nb, local, &max_tc, &max_n);
+            GLIO_HIP_CHECK(hipMemcpyAsync(b->d_fb + slot0 + t0, b->h_fb + slot0 + t0, (size_t)nb * sizeof(FrameBuild), hipMemcpyHostToDevice, b->stream));
+            fb_written = true;
         }
-        for (int q = 0; q < nb; ++q) b->frames[todo[t0 + q]].local_valid = 1;
+        bassoc_enqueue_build(b, dfb, nb, max_tc, max_n, !prepared, !local);
+        if (local) for (int q = 0; q < nb; ++q) b->frames[todo[t0 + q]].local_valid = 1;
     }
+    if (fb_written) { const int rw = bassoc_fb_uploaded(b); if (rw != GLIO_OK) return rw; }
     return GLIO_OK;
+}
+// the local tables that are missing among `need`
+static int bassoc_build_local(glio_bassoc* b, const std::vector<char>& need) {
+    std::vector<int> todo;
+    for (int k = 0; k < b->K; ++k) if (need[k] && !b->frames[k].local_valid) todo.push_back(k);
+    return bassoc_build_tables(b, todo, true);
 }
 // What a run does before it needs the poses: the build descriptors of its (first batch of) search frames go to the device and their hash tables are
 // cleared.  A caller that knows its pairs before it knows its poses (batchFeatureAssociation of a keyframe call: the pairs follow from the keyframe
@@ -2615,7 +2573,7 @@ static int bassoc_build_local(glio_bassoc* b, const std::vector<char>& need, boo
 // searches).  Anything else in between just makes the run do them itself.
 extern "C" int glio_bassoc_prepare_async(glio_bassoc* b, int n_pairs, const int32_t* pair_ci, const int32_t* pair_cj) {
     if (!b || n_pairs < 0 || (n_pairs > 0 && (!pair_ci || !pair_cj))) return GLIO_E_ARG;
-    BA_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rf = bassoc_drain(b); if (rf != GLIO_OK) return rf; }          // (an earlier asynchronous run still uses the build scratch)
     b->prep_nb = 0;
     std::vector<char> need(b->K, 0);
@@ -2627,27 +2585,82 @@ extern "C" int glio_bassoc_prepare_async(glio_bassoc* b, int n_pairs, const int3
     { const int rw = bassoc_fb_reusable(b); if (rw != GLIO_OK) return rw; }
     if (bassoc_local_mode(b, n_pairs, n_need, nullptr, need)) {
         // local mode: nothing of a run's tables depends on the poses -- the missing ones (the newest keyframe's) are BUILT now, the run only re-poses
-        bool wrote = false;
-        { const int rb = bassoc_build_local(b, need, &wrote); if (rb != GLIO_OK) return rb; }
-        if (wrote) { const int rw = bassoc_fb_uploaded(b); if (rw != GLIO_OK) return rw; }
-        BA_CHECK(hipGetLastError());
+        { const int rb = bassoc_build_local(b, need); if (rb != GLIO_OK) return rb; }
+        GLIO_HIP_CHECK(hipGetLastError());
         return GLIO_OK;
     }
-    bassoc_fill_batch(b, todo, 0, nb, &max_tc, &max_n);
-    BA_CHECK(hipMemcpyAsync(b->d_fb, b->h_fb, (size_t)nb * sizeof(FrameBuild), hipMemcpyHostToDevice, b->stream));
+    bassoc_fill_batch(b, todo, 0, nb, false, &max_tc, &max_n);
+    GLIO_HIP_CHECK(hipMemcpyAsync(b->d_fb, b->h_fb, (size_t)nb * sizeof(FrameBuild), hipMemcpyHostToDevice, b->stream));
     { const int rw = bassoc_fb_uploaded(b); if (rw != GLIO_OK) return rw; }
     hipLaunchKernelGGL(k_hash_clear_multi, dim3((max_tc + 255) / 256, nb), dim3(256), 0, b->stream, static_cast<const FrameBuild*>(b->d_fb));
-    BA_CHECK(hipGetLastError());
+    GLIO_HIP_CHECK(hipGetLastError());
     for (int q = 0; q < nb; ++q) { b->prep_todo[q] = todo[q]; b->prep_n[q] = b->h_n[todo[q]]; b->prep_tc[q] = b->h_fb[q].tc; b->frames[todo[q]].local_valid = 0; }
     b->prep_nb = nb;
     return GLIO_OK;
 }
 
+// what the kernels of a run index: the object's tables, or (local mode) the run's one block
+struct BassocRunTables { const double* poses; const FrameDesc* frames; const int* ci; const int* cj; };
+// what a pair search reads of keyframe k (searched: its table was sized for its cloud by this run or by the build of its local table; else it is the EMPTY one)
+static FrameDesc bassoc_frame_desc(const glio_bassoc* b, const int k, const bool searched) {
+    const FrameHash& f = b->frames[k];
+    FrameDesc fd;
+    fd.ent = f.d_ent; fd.sub = f.d_sub; fd.sorted = f.d_sorted; fd.n = b->h_n[k];
+    fd.cap_eff = searched ? f.cap_eff : f.table_cap;
+    return fd;
+}
+// stage (1) of a run: every keyframe that occurs as a search frame (`need`) gets its voxel hash at the run's poses -- cloud -> global frame -> hash, or (local) the
+// missing local tables and the re-posing of every table's points -- behind the upload of the poses and the reset of the run's counters
+static int bassoc_run_tables(glio_bassoc* b, const double* poses, const int n_pairs, const int32_t* pair_ci, const int32_t* pair_cj, const std::vector<char>& need,
+                             const bool local, const bool append, BassocRunTables* t) {
+    t->poses = b->d_poses; t->frames = b->d_frames; t->ci = b->d_pair_ci; t->cj = b->d_pair_cj;
+    if (local) {
+        // [poses K x 7 | re-posing descriptors K | frame descriptors K | pair_ci | pair_cj]: filled, sent once (the previous run was drained above: the pinned
+        // block is free)
+        const size_t o_fb = (size_t)b->K * 56, o_fd = o_fb + (size_t)b->K * sizeof(FrameBuild), o_ci = o_fd + (size_t)b->K * sizeof(FrameDesc), o_cj = o_ci + (size_t)n_pairs * 4;
+        const size_t used = o_cj + (size_t)n_pairs * 4;
+        if (used > b->inbox_bytes) { glio_set_error("batch association: run block too small"); return GLIO_E_STATE; }
+        double* hp = reinterpret_cast<double*>(b->h_inbox);
+        FrameBuild* hfb = reinterpret_cast<FrameBuild*>(b->h_inbox + o_fb);
+        FrameDesc* hfd = reinterpret_cast<FrameDesc*>(b->h_inbox + o_fd);
+        int32_t* hci = reinterpret_cast<int32_t*>(b->h_inbox + o_ci); int32_t* hcj = reinterpret_cast<int32_t*>(b->h_inbox + o_cj);
+        t->poses = reinterpret_cast<const double*>(b->d_inbox);
+        t->frames = reinterpret_cast<const FrameDesc*>(b->d_inbox + o_fd);
+        t->ci = reinterpret_cast<const int*>(b->d_inbox + o_ci); t->cj = reinterpret_cast<const int*>(b->d_inbox + o_cj);
+        b->prep_nb = 0;
+        { const int rb = bassoc_build_local(b, need); if (rb != GLIO_OK) return rb; }      // (only what glio_bassoc_prepare_async has not built already)
+        memcpy(hp, poses, (size_t)b->K * 56);
+        // every search frame's points at its pose of this run, in its table's order: one launch (k_transform_cloud_multi reads .local, writes .global)
+        int nt = 0, max_n = 0;
+        for (int k = 0; k < b->K; ++k) {
+            hfd[k] = bassoc_frame_desc(b, k, need[k] != 0);
+            if (!need[k]) continue;
+            FrameBuild& d = hfb[nt++];
+            memset(&d, 0, sizeof d);
+            d.local = b->frames[k].d_sorted_local; d.global = b->frames[k].d_sorted; d.pose = t->poses + 7 * k; d.n = b->h_n[k];
+            if (d.n > max_n) max_n = d.n;
+        }
+        for (int p = 0; p < n_pairs; ++p) { hci[p] = pair_ci[p]; hcj[p] = pair_cj[p]; }
+        GLIO_HIP_CHECK(hipMemcpyAsync(b->d_inbox, b->h_inbox, used, hipMemcpyHostToDevice, b->stream));
+        if (append) GLIO_HIP_CHECK(hipMemsetAsync(b->d_run + 1, 0, 8, b->stream));
+        else GLIO_HIP_CHECK(hipMemsetAsync(b->d_run, 0, 16, b->stream));
+        if (max_n > 0) hipLaunchKernelGGL(k_transform_cloud_multi, dim3((max_n + 255) / 256, nt), dim3(256), 0, b->stream, reinterpret_cast<const FrameBuild*>(b->d_inbox + o_fb));
+    } else {
+        memcpy(b->h_poses, poses, (size_t)b->K * 7 * 8);
+        GLIO_HIP_CHECK(hipMemcpyAsync(b->d_poses, b->h_poses, (size_t)b->K * 7 * 8, hipMemcpyHostToDevice, b->stream));
+        if (append) GLIO_HIP_CHECK(hipMemsetAsync(b->d_run + 1, 0, 8, b->stream));
+        else GLIO_HIP_CHECK(hipMemsetAsync(b->d_run, 0, 16, b->stream));
+        std::vector<int> todo;
+        for (int k = 0; k < b->K; ++k) if (need[k]) { todo.push_back(k); b->frames[k].local_valid = 0; }      // (the global build overwrites the table)
+        { const int rb = bassoc_build_tables(b, todo, false); if (rb != GLIO_OK) return rb; }
+    }
+    return GLIO_OK;
+}
 static int bassoc_run(glio_bassoc* b, const double* poses, int n_pairs, const int32_t* pair_ci, const int32_t* pair_cj, bool append, bool wait,
                       int64_t* pair_count_out, int64_t* total_out) {
     GLIO_TRACE("K2 glio_bassoc_run (batch association)");
     if (!b || !poses || n_pairs < 0 || (n_pairs > 0 && (!pair_ci || !pair_cj))) return GLIO_E_ARG;
-    BA_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rf = bassoc_drain(b); if (rf != GLIO_OK) return rf; }          // (an earlier asynchronous run still reads the staging buffers)
     // a drained run nobody collected: this run replaces its counts in the pinned buffers -- but its overflow must not get lost with them
     if (b->done_pairs >= 0) {
@@ -2661,11 +2674,11 @@ static int bassoc_run(glio_bassoc* b, const double* poses, int n_pairs, const in
         if (b->d_pair_off) { hipFree(b->d_pair_off); hipHostFree(b->h_pair_off); hipFree(b->d_pair_ci); hipFree(b->d_pair_cj); hipFree(b->d_pair_row); hipFree(b->d_row_pair); hipHostFree(b->h_pairs);
                              b->d_pair_off = nullptr; b->h_pair_off = nullptr; b->h_pairs = nullptr; b->d_pair_ci = b->d_pair_cj = b->d_pair_row = b->d_row_pair = nullptr; }
         b->max_pairs = n_pairs + 64;
-        BA_CHECK(hipMalloc((void**)&b->d_pair_off, (size_t)(b->max_pairs + 2) * 8));
-        BA_CHECK(hipMalloc((void**)&b->d_pair_ci, (size_t)b->max_pairs * 4)); BA_CHECK(hipMalloc((void**)&b->d_pair_cj, (size_t)b->max_pairs * 4));
-        BA_CHECK(hipMalloc((void**)&b->d_pair_row, (size_t)b->max_pairs * 4)); BA_CHECK(hipMalloc((void**)&b->d_row_pair, (size_t)b->max_pairs * 4));
-        BA_CHECK(hipHostMalloc((void**)&b->h_pair_off, (size_t)(b->max_pairs + 2) * 8));
-        BA_CHECK(hipHostMalloc((void**)&b->h_pairs, (size_t)b->max_pairs * 16));
+        GLIO_HIP_CHECK(hipMalloc((void**)&b->d_pair_off, (size_t)(b->max_pairs + 2) * 8));
+        GLIO_HIP_CHECK(hipMalloc((void**)&b->d_pair_ci, (size_t)b->max_pairs * 4)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_pair_cj, (size_t)b->max_pairs * 4));
+        GLIO_HIP_CHECK(hipMalloc((void**)&b->d_pair_row, (size_t)b->max_pairs * 4)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_row_pair, (size_t)b->max_pairs * 4));
+        GLIO_HIP_CHECK(hipHostMalloc((void**)&b->h_pair_off, (size_t)(b->max_pairs + 2) * 8));
+        GLIO_HIP_CHECK(hipHostMalloc((void**)&b->h_pairs, (size_t)b->max_pairs * 16));
     }
     const long long first_before = append ? b->h_tail[0] : 0;      // the records held before this run (every earlier run was drained above: h_tail is settled)
     // (1) every keyframe that occurs as a search frame: cloud -> global frame -> voxel hash
@@ -2674,97 +2687,18 @@ static int bassoc_run(glio_bassoc* b, const double* poses, int n_pairs, const in
     int n_need = 0;
     for (int k = 0; k < b->K; ++k) n_need += need[k] ? 1 : 0;
     const bool local = bassoc_local_mode(b, n_pairs, n_need, poses, need);
-    // what the kernels of this run index: the object's tables, or (local mode) the run's one block
-    const double* d_poses_run = b->d_poses;
-    const FrameDesc* d_frames_run = b->d_frames;
-    const int* d_ci_run = b->d_pair_ci; const int* d_cj_run = b->d_pair_cj;
-    if (local) {
-        // [poses K x 7 | re-posing descriptors K | frame descriptors K | pair_ci | pair_cj]: filled, sent once (the previous run was drained above: the pinned
-        // block is free)
-        const size_t o_fb = (size_t)b->K * 56, o_fd = o_fb + (size_t)b->K * sizeof(FrameBuild), o_ci = o_fd + (size_t)b->K * sizeof(FrameDesc), o_cj = o_ci + (size_t)n_pairs * 4;
-        const size_t used = o_cj + (size_t)n_pairs * 4;
-        if (used > b->inbox_bytes) { glio_set_error("batch association: run block too small"); return GLIO_E_STATE; }
-        double* hp = reinterpret_cast<double*>(b->h_inbox);
-        FrameBuild* hfb = reinterpret_cast<FrameBuild*>(b->h_inbox + o_fb);
-        FrameDesc* hfd = reinterpret_cast<FrameDesc*>(b->h_inbox + o_fd);
-        int32_t* hci = reinterpret_cast<int32_t*>(b->h_inbox + o_ci); int32_t* hcj = reinterpret_cast<int32_t*>(b->h_inbox + o_cj);
-        d_poses_run = reinterpret_cast<const double*>(b->d_inbox);
-        d_frames_run = reinterpret_cast<const FrameDesc*>(b->d_inbox + o_fd);
-        d_ci_run = reinterpret_cast<const int*>(b->d_inbox + o_ci); d_cj_run = reinterpret_cast<const int*>(b->d_inbox + o_cj);
-        b->prep_nb = 0;
-        { const int rw = bassoc_fb_reusable(b); if (rw != GLIO_OK) return rw; }
-        bool wrote = false;
-        { const int rb = bassoc_build_local(b, need, &wrote); if (rb != GLIO_OK) return rb; }      // (only what glio_bassoc_prepare_async has not built already)
-        if (wrote) { const int rw = bassoc_fb_uploaded(b); if (rw != GLIO_OK) return rw; }
-        memcpy(hp, poses, (size_t)b->K * 56);
-        // every search frame's points at its pose of this run, in its table's order: one launch (k_transform_cloud_multi reads .local, writes .global)
-        int nt = 0, max_n = 0;
-        for (int k = 0; k < b->K; ++k) {
-            FrameDesc& fd = hfd[k];
-            fd.ent = b->frames[k].d_ent; fd.sub = b->frames[k].d_sub; fd.sorted = b->frames[k].d_sorted; fd.n = b->h_n[k];
-            fd.cap_eff = need[k] ? b->frames[k].cap_eff : b->frames[k].table_cap;
-            if (!need[k]) continue;
-            FrameBuild& d = hfb[nt++];
-            memset(&d, 0, sizeof d);
-            d.local = b->frames[k].d_sorted_local; d.global = b->frames[k].d_sorted; d.pose = d_poses_run + 7 * k; d.n = b->h_n[k];
-            if (d.n > max_n) max_n = d.n;
-        }
-        for (int p = 0; p < n_pairs; ++p) { hci[p] = pair_ci[p]; hcj[p] = pair_cj[p]; }
-        BA_CHECK(hipMemcpyAsync(b->d_inbox, b->h_inbox, used, hipMemcpyHostToDevice, b->stream));
-        if (append) BA_CHECK(hipMemsetAsync(b->d_run + 1, 0, 8, b->stream));
-        else BA_CHECK(hipMemsetAsync(b->d_run, 0, 16, b->stream));
-        if (max_n > 0) hipLaunchKernelGGL(k_transform_cloud_multi, dim3((max_n + 255) / 256, nt), dim3(256), 0, b->stream, reinterpret_cast<const FrameBuild*>(b->d_inbox + o_fb));
-    } else {
-        memcpy(b->h_poses, poses, (size_t)b->K * 7 * 8);
-        BA_CHECK(hipMemcpyAsync(b->d_poses, b->h_poses, (size_t)b->K * 7 * 8, hipMemcpyHostToDevice, b->stream));
-        if (append) BA_CHECK(hipMemsetAsync(b->d_run + 1, 0, 8, b->stream));
-        else BA_CHECK(hipMemsetAsync(b->d_run, 0, 16, b->stream));
-        std::vector<int> todo;
-        for (int k = 0; k < b->K; ++k) if (need[k]) { todo.push_back(k); b->frames[k].local_valid = 0; }      // (the global build overwrites the table)
-        bool fb_checked = false, fb_written = false;
-        for (size_t t0 = 0; t0 < todo.size(); t0 += BA_FB) {
-            const int nb = (int)std::min<size_t>(BA_FB, todo.size() - t0);
-            int max_tc = 0, max_n = 0;
-            // glio_bassoc_prepare_async has sent this batch's descriptors and cleared its tables already (same keyframes, same sizes, nothing run since)?  The
-            // answer follows from what was prepared alone -- never from how long ago (advisor finding of round 5: a wall-clock test made the kernel sequence
-            // depend on host timing).  A prepared batch's descriptors are NOT rebuilt: they are on the device as the preparation wrote them.
-            bool prepared = t0 == 0 && b->prep_nb == nb;
-            for (int q = 0; prepared && q < nb; ++q) {
-                const int k = todo[q], n = b->h_n[k];
-                int tc = next_pow2(2 * (n > 512 ? n : 512));
-                if (tc > b->frames[k].table_cap) tc = b->frames[k].table_cap;
-                prepared = b->prep_todo[q] == k && b->prep_n[q] == n && b->prep_tc[q] == tc;
-            }
-            b->prep_nb = 0;
-            const FrameBuild* dfb = b->d_fb + t0;
-            if (prepared) {
-                for (int q = 0; q < nb; ++q) { if (b->prep_tc[q] > max_tc) max_tc = b->prep_tc[q]; if (b->prep_n[q] > max_n) max_n = b->prep_n[q]; }
-            } else {
-                if (!fb_checked) { const int rw = bassoc_fb_reusable(b); if (rw != GLIO_OK) return rw; fb_checked = true; }   // (once per run: its batches write distinct parts of h_fb)
-                bassoc_fill_batch(b, todo.data() + t0, t0, nb, &max_tc, &max_n);
-                BA_CHECK(hipMemcpyAsync(b->d_fb + t0, b->h_fb + t0, (size_t)nb * sizeof(FrameBuild), hipMemcpyHostToDevice, b->stream));
-                fb_written = true;
-                hipLaunchKernelGGL(k_hash_clear_multi, dim3((max_tc + 255) / 256, nb), dim3(256), 0, b->stream, dfb);
-            }
-            if (max_n == 0) continue;
-            hipLaunchKernelGGL(k_transform_cloud_multi, dim3((max_n + 255) / 256, nb), dim3(256), 0, b->stream, dfb);
-            hipLaunchKernelGGL(k_hash_insert_multi, dim3((max_n + HI_THREADS - 1) / HI_THREADS, nb), dim3(HI_THREADS), 0, b->stream, dfb, b->inv_cell);
-            hipLaunchKernelGGL(k_cell_alloc_multi, dim3((max_tc + 1023) / 1024, nb), dim3(1024), 0, b->stream, dfb);
-            hipLaunchKernelGGL(k_scatter_multi, dim3((max_n + 255) / 256, nb), dim3(256), 0, b->stream, dfb);
-        }
-        if (fb_written) { const int rw = bassoc_fb_uploaded(b); if (rw != GLIO_OK) return rw; }
-    }
+    BassocRunTables rt;
+    { const int rs = bassoc_run_tables(b, poses, n_pairs, pair_ci, pair_cj, need, local, append, &rt); if (rs != GLIO_OK) return rs; }
+    const double* d_poses_run = rt.poses;
+    const FrameDesc* d_frames_run = rt.frames;
+    const int* d_ci_run = rt.ci; const int* d_cj_run = rt.cj;
     // (2) the pairs, in the caller's (ci, cj) order, BA_CHUNK pairs per launch (blockIdx.y = pair of the chunk)
     int* d_overflow = reinterpret_cast<int*>(b->d_run + 1);
     if (n_pairs > 0) {
         int maxn = 0;
         for (int p = 0; p < n_pairs; ++p) if (b->h_n[pair_ci[p]] > maxn) maxn = b->h_n[pair_ci[p]];
         if (!local) {
-        for (int k = 0; k < b->K; ++k) {
-            FrameDesc& fd = b->h_fd[k];
-            fd.ent = b->frames[k].d_ent; fd.sub = b->frames[k].d_sub; fd.sorted = b->frames[k].d_sorted; fd.n = b->h_n[k];
-            fd.cap_eff = need[k] ? b->frames[k].cap_eff : b->frames[k].table_cap;
-        }
+        for (int k = 0; k < b->K; ++k) b->h_fd[k] = bassoc_frame_desc(b, k, need[k] != 0);
         for (int p = 0; p < n_pairs; ++p) { b->h_pairs[p] = pair_ci[p]; b->h_pairs[b->max_pairs + p] = pair_cj[p]; }
         }
         // shared query binning: per chunk, the distinct source keyframes in order of first appearance (their pairs usually follow each other: a linear look-back
@@ -2788,16 +2722,13 @@ static int bassoc_run(glio_bassoc* b, const double* poses, int n_pairs, const in
         }
         const bool share_bins = glio_switch<GLIO_SW_BASSOC_SHARED_BINS>() && !local;       // (GLIO_BASSOC_SHARED_BINS=0: every pair bins for itself -- A/B and tests; local tables: a pair's queries are grouped by their cell in ITS search frame)
         if (!local) {
-        BA_CHECK(hipMemcpyAsync(b->d_frames, b->h_fd, (size_t)b->K * sizeof(FrameDesc), hipMemcpyHostToDevice, b->stream));
-        BA_CHECK(hipMemcpyAsync(b->d_pair_ci, b->h_pairs, (size_t)n_pairs * 4, hipMemcpyHostToDevice, b->stream));
-        BA_CHECK(hipMemcpyAsync(b->d_pair_cj, b->h_pairs + b->max_pairs, (size_t)n_pairs * 4, hipMemcpyHostToDevice, b->stream));
-        BA_CHECK(hipMemcpyAsync(b->d_pair_row, b->h_pairs + 2 * (size_t)b->max_pairs, (size_t)n_pairs * 4, hipMemcpyHostToDevice, b->stream));
-        BA_CHECK(hipMemcpyAsync(b->d_row_pair, b->h_pairs + 3 * (size_t)b->max_pairs, (size_t)n_pairs * 4, hipMemcpyHostToDevice, b->stream));
+        GLIO_HIP_CHECK(hipMemcpyAsync(b->d_frames, b->h_fd, (size_t)b->K * sizeof(FrameDesc), hipMemcpyHostToDevice, b->stream));
+        GLIO_HIP_CHECK(hipMemcpyAsync(b->d_pair_ci, b->h_pairs, (size_t)n_pairs * 4, hipMemcpyHostToDevice, b->stream));
+        GLIO_HIP_CHECK(hipMemcpyAsync(b->d_pair_cj, b->h_pairs + b->max_pairs, (size_t)n_pairs * 4, hipMemcpyHostToDevice, b->stream));
+        GLIO_HIP_CHECK(hipMemcpyAsync(b->d_pair_row, b->h_pairs + 2 * (size_t)b->max_pairs, (size_t)n_pairs * 4, hipMemcpyHostToDevice, b->stream));
+        GLIO_HIP_CHECK(hipMemcpyAsync(b->d_row_pair, b->h_pairs + 3 * (size_t)b->max_pairs, (size_t)n_pairs * 4, hipMemcpyHostToDevice, b->stream));
         }
-        AssocArgs a;
-        memset(&a, 0, sizeof a);
-        a.inv_cell = b->inv_cell; a.cell = b->cell; a.kd_max_radius = 1.5; a.weight_gate = 0.3; a.surf_dist_thres = 0.18; a.lidar_const = 2.5;   // :3839,3874,3863,3885
-        a.unit_scores = 0;
+        AssocArgs a = assoc_args_base(b->cell, b->inv_cell, 1.5, 0.3, 0.18, 2.5, 0);      // kd_max_radius, weight gate, surf_dist_thres, score factor: :3839,3874,3863,3885
         a.q_stride = b->cap; a.w_stride = b->cap; a.b_stride = b->b_stride;
         a.frames = d_frames_run; a.pair_ci = d_ci_run; a.pair_cj = d_cj_run; a.poses = d_poses_run;
         a.local_tables = local ? 1 : 0;
@@ -2820,9 +2751,9 @@ static int bassoc_run(glio_bassoc* b, const double* poses, int n_pairs, const in
                                    d_frames_run, d_ci_run, p0, b->d_pair_off, b->d_q_cp, b->d_q_nc, b->d_q_score, b->d_cp, b->d_nc, b->d_score);
         }
     }
-    BA_CHECK(hipGetLastError());
-    if (n_pairs > 0) BA_CHECK(hipMemcpyAsync(b->h_pair_off, b->d_pair_off, (size_t)(n_pairs + 1) * 8, hipMemcpyDeviceToHost, b->stream));
-    BA_CHECK(hipMemcpyAsync(b->h_tail, b->d_run, 16, hipMemcpyDeviceToHost, b->stream));
+    GLIO_HIP_CHECK(hipGetLastError());
+    if (n_pairs > 0) GLIO_HIP_CHECK(hipMemcpyAsync(b->h_pair_off, b->d_pair_off, (size_t)(n_pairs + 1) * 8, hipMemcpyDeviceToHost, b->stream));
+    GLIO_HIP_CHECK(hipMemcpyAsync(b->h_tail, b->d_run, 16, hipMemcpyDeviceToHost, b->stream));
     b->pending_pairs = n_pairs;
     b->pending_first = first_before;
     b->pending_selected = 0;
@@ -2839,15 +2770,15 @@ int glio_bassoc_run_append_async(glio_bassoc* b, const double* poses, int n_pair
 }
 int glio_bassoc_finish(glio_bassoc* b, int64_t* pair_count_out, int64_t* total_out) {
     if (!b) return GLIO_E_ARG;
-    BA_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     return bassoc_finish(b, pair_count_out, total_out);
 }
 int glio_bassoc_reset(glio_bassoc* b) {
     if (!b) return GLIO_E_ARG;
-    BA_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rf = bassoc_drain(b); if (rf != GLIO_OK) return rf; }
     b->done_pairs = -1; b->done_overflow = 0;              // (a reset drops the records, and with them what an uncollected run had to say)
-    BA_CHECK(hipMemsetAsync(b->d_run, 0, 16, b->stream));
+    GLIO_HIP_CHECK(hipMemsetAsync(b->d_run, 0, 16, b->stream));
     b->h_tail[0] = b->h_tail[1] = 0;
     return GLIO_OK;
 }
@@ -2860,12 +2791,12 @@ int glio_bassoc_set_frame_from_scan(glio_bassoc* b, int k, glio_ctx* c, int slot
     if (!b || !c || !lidar_offset || k < 0 || k >= b->K || slot < 0 || slot >= c->W || c->device != b->device) return GLIO_E_ARG;
     const int n = c->h_scan_count[slot];
     if (n > b->cap) { glio_set_error("scan of %d points, the batch association holds %d per keyframe", n, b->cap); return GLIO_E_ARG; }
-    BA_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rf = bassoc_drain(b); if (rf != GLIO_OK) return rf; }
     // the upload of the scan (and its presort) ran on the context's stream: this stream waits for that point, the host does not
-    if (!b->ev_scan) BA_CHECK(hipEventCreateWithFlags(&b->ev_scan, hipEventDisableTiming));
-    BA_CHECK(hipEventRecord(b->ev_scan, c->stream));
-    BA_CHECK(hipStreamWaitEvent(b->stream, b->ev_scan, 0));
+    if (!b->ev_scan) GLIO_HIP_CHECK(hipEventCreateWithFlags(&b->ev_scan, hipEventDisableTiming));
+    GLIO_HIP_CHECK(hipEventRecord(b->ev_scan, c->stream));
+    GLIO_HIP_CHECK(hipStreamWaitEvent(b->stream, b->ev_scan, 0));
     { const int re = bassoc_behind_external_read(b); if (re != GLIO_OK) return re; }
     // the context presorted this scan when it was uploaded: its presorted copy (same points, w = index in the scan) is taken over with the same offset instead
     // of presorting the cloud a second time (any spatially compact order serves: results are written at the original indices)
@@ -2878,11 +2809,11 @@ int glio_bassoc_set_frame_from_scan(glio_bassoc* b, int k, glio_ctx* c, int slot
                                b->d_local_ps + (size_t)k * b->cap);
         else enqueue_presort(b->stream, b->kb, b->d_local + (size_t)k * b->cap, n, b->d_local_ps + (size_t)k * b->cap);
         // ... and the context must not overwrite the row (glio_set_scan after W slides of the ring), nor be destroyed, before these copies have read it
-        if (!c->ev_ext_read) BA_CHECK(hipEventCreateWithFlags(&c->ev_ext_read, hipEventDisableTiming));
-        BA_CHECK(hipEventRecord(c->ev_ext_read, b->stream));
+        if (!c->ev_ext_read) GLIO_HIP_CHECK(hipEventCreateWithFlags(&c->ev_ext_read, hipEventDisableTiming));
+        GLIO_HIP_CHECK(hipEventRecord(c->ev_ext_read, b->stream));
         c->ext_read_pending = 1;
     }
-    BA_CHECK(hipGetLastError());
+    GLIO_HIP_CHECK(hipGetLastError());
     b->h_n[k] = n;
     b->frames[k].local_valid = 0;
     return GLIO_OK;
@@ -3013,37 +2944,37 @@ __global__ void k_bassoc_draw_put(const long long* __restrict__ sel_off, const i
 int glio_bassoc_select_tail_draws_async(glio_bassoc* b, int res_num, const uint64_t* raws) {
     if (!b || res_num < 1 || res_num > 64 || !raws) return GLIO_E_ARG;
     if (b->pending_pairs < 0) { glio_set_error("glio_bassoc_select_tail_draws_async: no asynchronous run is pending"); return GLIO_E_STATE; }
-    BA_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     const int n_pairs = b->pending_pairs;
     if (n_pairs == 0) return GLIO_OK;
     const long long need = (long long)n_pairs * res_num;
     if (need > b->raws_cap) {
-        if (b->raws_in_flight) { BA_CHECK(hipEventSynchronize(b->ev_raws)); b->raws_in_flight = 0; }
+        if (b->raws_in_flight) { GLIO_HIP_CHECK(hipEventSynchronize(b->ev_raws)); b->raws_in_flight = 0; }
         if (b->h_raws) hipHostFree(b->h_raws);
         if (b->d_raws) hipFree(b->d_raws);
         if (b->d_sel_off) hipFree(b->d_sel_off);
         b->h_raws = nullptr; b->d_raws = nullptr; b->d_sel_off = nullptr; b->raws_cap = 0;
         const long long cap = need + need / 2 + 1024;
-        BA_CHECK(hipHostMalloc((void**)&b->h_raws, (size_t)cap * 8)); BA_CHECK(hipMalloc((void**)&b->d_raws, (size_t)cap * 16));      // (device: the raws, then the source indices)
-        BA_CHECK(hipMalloc((void**)&b->d_sel_off, (size_t)(cap + 2) * 8 + (size_t)cap * 4));                                            // (the offsets, then the kept counts)
+        GLIO_HIP_CHECK(hipHostMalloc((void**)&b->h_raws, (size_t)cap * 8)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_raws, (size_t)cap * 16));      // (device: the raws, then the source indices)
+        GLIO_HIP_CHECK(hipMalloc((void**)&b->d_sel_off, (size_t)(cap + 2) * 8 + (size_t)cap * 4));                                            // (the offsets, then the kept counts)
         b->raws_cap = cap;
     }
     // the staging arrays of the selection (grow-only, shared with glio_bassoc_select_range)
     if (need > b->sel_cap || !b->d_sel_idx) {
-        BA_CHECK(hipStreamSynchronize(b->stream));
+        GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
         void** old[] = {(void**)&b->d_sel_cp, (void**)&b->d_sel_nc, (void**)&b->d_sel_score, (void**)&b->d_sel_idx};
         for (void** q : old) { if (*q) hipFree(*q); *q = nullptr; }
         b->sel_cap = 0;
         const int64_t cap = need + need / 2 + 1024;
-        BA_CHECK(hipMalloc((void**)&b->d_sel_cp, (size_t)cap * 16)); BA_CHECK(hipMalloc((void**)&b->d_sel_nc, (size_t)cap * 48));
-        BA_CHECK(hipMalloc((void**)&b->d_sel_score, (size_t)cap * 8)); BA_CHECK(hipMalloc((void**)&b->d_sel_idx, (size_t)(cap + 1) * 8));
+        GLIO_HIP_CHECK(hipMalloc((void**)&b->d_sel_cp, (size_t)cap * 16)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_sel_nc, (size_t)cap * 48));
+        GLIO_HIP_CHECK(hipMalloc((void**)&b->d_sel_score, (size_t)cap * 8)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_sel_idx, (size_t)(cap + 1) * 8));
         b->sel_cap = cap;
     }
-    if (!b->ev_raws) BA_CHECK(hipEventCreateWithFlags(&b->ev_raws, hipEventDisableTiming));
-    if (b->raws_in_flight) { BA_CHECK(hipEventSynchronize(b->ev_raws)); b->raws_in_flight = 0; }
+    if (!b->ev_raws) GLIO_HIP_CHECK(hipEventCreateWithFlags(&b->ev_raws, hipEventDisableTiming));
+    if (b->raws_in_flight) { GLIO_HIP_CHECK(hipEventSynchronize(b->ev_raws)); b->raws_in_flight = 0; }
     memcpy(b->h_raws, raws, (size_t)need * 8);
-    BA_CHECK(hipMemcpyAsync(b->d_raws, b->h_raws, (size_t)need * 8, hipMemcpyHostToDevice, b->stream));
-    BA_CHECK(hipEventRecord(b->ev_raws, b->stream));
+    GLIO_HIP_CHECK(hipMemcpyAsync(b->d_raws, b->h_raws, (size_t)need * 8, hipMemcpyHostToDevice, b->stream));
+    GLIO_HIP_CHECK(hipEventRecord(b->ev_raws, b->stream));
     b->raws_in_flight = 1;
     long long* d_src = reinterpret_cast<long long*>(b->d_raws + b->raws_cap);
     int* d_kept = reinterpret_cast<int*>(b->d_sel_off + b->raws_cap + 2);
@@ -3058,9 +2989,9 @@ int glio_bassoc_select_tail_draws_async(glio_bassoc* b, int res_num, const uint6
     hipLaunchKernelGGL(k_bassoc_draw_put, dim3((unsigned)((need + 255) / 256)), dim3(256), 0, b->stream, b->d_sel_off, n_pairs, b->pending_first, b->d_sel_cp, b->d_sel_nc, b->d_sel_score,
                        b->d_cp, b->d_nc, b->d_score);
     }
-    BA_CHECK(hipGetLastError());
+    GLIO_HIP_CHECK(hipGetLastError());
     // the running total as the selection left it (the copy the run enqueued carried the total BEFORE the selection; the pair counts stay the FOUND ones)
-    BA_CHECK(hipMemcpyAsync(b->h_tail, b->d_run, 8, hipMemcpyDeviceToHost, b->stream));
+    GLIO_HIP_CHECK(hipMemcpyAsync(b->h_tail, b->d_run, 8, hipMemcpyDeviceToHost, b->stream));
     b->pending_selected = res_num;
     return GLIO_OK;
 }
@@ -3107,7 +3038,7 @@ __global__ void k_bassoc_put(const long long first, const long long n, const flo
 // src_index names (absolute indices >= first); the object then holds first + n_keep records
 int glio_bassoc_select_range(glio_bassoc* b, int64_t first, int64_t n_keep, const int64_t* src_index, int64_t n_current) {
     if (!b || first < 0 || n_keep < 0 || n_current < first || n_current > b->max_con || n_keep > n_current - first || (n_keep > 0 && !src_index)) return GLIO_E_ARG;
-    BA_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rf = bassoc_drain(b); if (rf != GLIO_OK) return rf; }
     for (int64_t k = 0; k < n_keep; ++k) if (src_index[k] < first || src_index[k] >= n_current) { glio_set_error("selection index %lld out of range", (long long)src_index[k]); return GLIO_E_ARG; }
     // ONE pinned block [new running total | the indices] -> one copy, the gather into the staging arrays, one kernel that puts the records (and the total) in
@@ -3116,48 +3047,48 @@ int glio_bassoc_select_range(glio_bassoc* b, int64_t first, int64_t n_keep, cons
     if (n_keep > b->sel_cap || !b->d_sel_idx) {
         // (pointers nulled and the capacity reset before the new allocations: a failed hipMalloc must not leave dangling pointers
         //  behind a capacity that claims room -- advisor finding of round 2)
-        BA_CHECK(hipStreamSynchronize(b->stream));
+        GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));
         void** old[] = {(void**)&b->d_sel_cp, (void**)&b->d_sel_nc, (void**)&b->d_sel_score, (void**)&b->d_sel_idx};
         for (void** q : old) { if (*q) hipFree(*q); *q = nullptr; }
         b->sel_cap = 0;
         const int64_t cap = n_keep + n_keep / 2 + 1024;
-        BA_CHECK(hipMalloc((void**)&b->d_sel_cp, (size_t)cap * 16)); BA_CHECK(hipMalloc((void**)&b->d_sel_nc, (size_t)cap * 48));
-        BA_CHECK(hipMalloc((void**)&b->d_sel_score, (size_t)cap * 8)); BA_CHECK(hipMalloc((void**)&b->d_sel_idx, (size_t)(cap + 1) * 8));
+        GLIO_HIP_CHECK(hipMalloc((void**)&b->d_sel_cp, (size_t)cap * 16)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_sel_nc, (size_t)cap * 48));
+        GLIO_HIP_CHECK(hipMalloc((void**)&b->d_sel_score, (size_t)cap * 8)); GLIO_HIP_CHECK(hipMalloc((void**)&b->d_sel_idx, (size_t)(cap + 1) * 8));
         b->sel_cap = cap;
     }
-    if (b->sel_in_flight) { BA_CHECK(hipEventSynchronize(b->ev_sel)); b->sel_in_flight = 0; }      // (the previous selection's block has left the pinned copy)
+    if (b->sel_in_flight) { GLIO_HIP_CHECK(hipEventSynchronize(b->ev_sel)); b->sel_in_flight = 0; }      // (the previous selection's block has left the pinned copy)
     if (n_keep + 1 > b->h_sel_cap) {
         if (b->h_sel) hipHostFree(b->h_sel);
         b->h_sel = nullptr; b->h_sel_cap = 0;
         const int64_t cap = n_keep + n_keep / 2 + 1024;
-        BA_CHECK(hipHostMalloc((void**)&b->h_sel, (size_t)cap * 8));
+        GLIO_HIP_CHECK(hipHostMalloc((void**)&b->h_sel, (size_t)cap * 8));
         b->h_sel_cap = cap;
     }
-    if (!b->ev_sel) BA_CHECK(hipEventCreateWithFlags(&b->ev_sel, hipEventDisableTiming));
+    if (!b->ev_sel) GLIO_HIP_CHECK(hipEventCreateWithFlags(&b->ev_sel, hipEventDisableTiming));
     b->h_tail[0] = first + n_keep;
     b->h_sel[0] = first + n_keep;
     if (n_keep > 0) memcpy(b->h_sel + 1, src_index, (size_t)n_keep * 8);
-    BA_CHECK(hipMemcpyAsync(b->d_sel_idx, b->h_sel, (size_t)(n_keep + 1) * 8, hipMemcpyHostToDevice, b->stream));
-    BA_CHECK(hipEventRecord(b->ev_sel, b->stream));
+    GLIO_HIP_CHECK(hipMemcpyAsync(b->d_sel_idx, b->h_sel, (size_t)(n_keep + 1) * 8, hipMemcpyHostToDevice, b->stream));
+    GLIO_HIP_CHECK(hipEventRecord(b->ev_sel, b->stream));
     b->sel_in_flight = 1;
     if (n_keep > 0)
         hipLaunchKernelGGL(k_bassoc_gather, dim3((unsigned)((n_keep + 255) / 256)), dim3(256), 0, b->stream, b->d_sel_idx + 1, (long long)n_keep, b->d_cp, b->d_nc, b->d_score,
                            b->d_sel_cp, b->d_sel_nc, b->d_sel_score);
     hipLaunchKernelGGL(k_bassoc_put, dim3((unsigned)((std::max<int64_t>(n_keep, 1) + 255) / 256)), dim3(256), 0, b->stream, (long long)first, (long long)n_keep, b->d_sel_cp, b->d_sel_nc,
                        b->d_sel_score, b->d_cp, b->d_nc, b->d_score, b->d_sel_idx, b->d_run);
-    BA_CHECK(hipGetLastError());
+    GLIO_HIP_CHECK(hipGetLastError());
     return GLIO_OK;
 }
 
 int glio_bassoc_read(glio_bassoc* b, int64_t first, int64_t n, float* cp, double* norm_cent, double* score) {
     if (!b || first < 0 || n < 0 || first + n > b->max_con) return GLIO_E_ARG;
-    BA_CHECK(hipSetDevice(b->device));
+    GLIO_HIP_CHECK(hipSetDevice(b->device));
     { const int rf = bassoc_drain(b); if (rf != GLIO_OK) return rf; }
-    BA_CHECK(hipStreamSynchronize(b->stream));                       // (a selection may still be compacting the arrays)
+    GLIO_HIP_CHECK(hipStreamSynchronize(b->stream));                       // (a selection may still be compacting the arrays)
     if (n == 0) return GLIO_OK;
-    if (cp) BA_CHECK(hipMemcpy(cp, b->d_cp + first, (size_t)n * 16, hipMemcpyDeviceToHost));
-    if (norm_cent) BA_CHECK(hipMemcpy(norm_cent, b->d_nc + 6 * first, (size_t)n * 48, hipMemcpyDeviceToHost));
-    if (score) BA_CHECK(hipMemcpy(score, b->d_score + first, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if (cp) GLIO_HIP_CHECK(hipMemcpy(cp, b->d_cp + first, (size_t)n * 16, hipMemcpyDeviceToHost));
+    if (norm_cent) GLIO_HIP_CHECK(hipMemcpy(norm_cent, b->d_nc + 6 * first, (size_t)n * 48, hipMemcpyDeviceToHost));
+    if (score) GLIO_HIP_CHECK(hipMemcpy(score, b->d_score + first, (size_t)n * 8, hipMemcpyDeviceToHost));
     return GLIO_OK;
 }
 

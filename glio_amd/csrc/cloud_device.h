@@ -1,6 +1,6 @@
 // cloud_device.h -- the device routines that the point-cloud stages share (localmap_kernels.hip, globalmap_kernels.hip, loop_kernels.hip,
-// feature_kernels.hip, keyframe_cloud_kernels.hip): transformCloud of one point, the de-skew's ratio and slerp, the bounding box of a workgroup, the
-// workgroup scan and ballot rank, one pass of the stable radix sort.  Each has ONE definition here: the stages are held to the reference, the oracle or
+// feature_kernels.hip, keyframe_cloud_kernels.hip, assoc_kernels.hip): transformCloud of one point, the cell key of the voxel tables, the de-skew's ratio
+// and slerp, the bounding box of a workgroup, the wavefront and workgroup scan and ballot rank, one pass of the stable radix sort.  Each has ONE definition here: the stages are held to the reference, the oracle or
 // each other bit for bit, so a rounding or an ordering is changed in one place or not at all.  The integer routines are exact whatever the order of their
 // additions; cloud_transform, cloud_deskew_ratio and cloud_slerp_identity are the only arithmetic.
 #pragma once
@@ -10,12 +10,38 @@
 
 // transformCloud of one point (reference Estimator.cpp:1517-1546): double q * v + t, float store.  Eigen's q * v is v + w * (2 u x v) + u x (2 u x v) with
 // the products kept separate (d_qrot_nc); the translation is added last, (v + q0 uv + uuv) + t.  No contraction whatever the including file says.
-__device__ __forceinline__ float4 cloud_transform(const double q[4], const double t[3], const float4 p) {
+// cloud_transform_d: the sums before the float store (k_qbin_tile carries them on into a second frame).
+__device__ __forceinline__ void cloud_transform_d(const double q[4], const double t[3], const float4 p, double o[3]) {
 #pragma clang fp contract(off)
     const double v[3] = {(double)p.x, (double)p.y, (double)p.z};
+    double r[3];
+    d_qrot_nc(q, v, r);
+    o[0] = r[0] + t[0]; o[1] = r[1] + t[1]; o[2] = r[2] + t[2];
+}
+__device__ __forceinline__ float4 cloud_transform(const double q[4], const double t[3], const float4 p) {
     double o[3];
-    d_qrot_nc(q, v, o);
-    return make_float4((float)(o[0] + t[0]), (float)(o[1] + t[1]), (float)(o[2] + t[2]), p.w);
+    cloud_transform_d(q, t, p, o);
+    return make_float4((float)o[0], (float)o[1], (float)o[2], p.w);
+}
+
+// ---- the cell key of the open-addressing voxel tables (assoc_kernels.hip: the map's and the keyframes' hashes and the query grouping; localmap_kernels.hip:
+// the ring's voxel table): 21 bits per axis, biased by 2^20, x in the HIGH bits; the all-ones word is no key (the tables' EMPTY).  globalmap_kernels.hip packs
+// x into the LOW bits -- its sort order depends on that -- and keeps its own packing.
+__device__ __forceinline__ unsigned long long cloud_cell_key(const int ix, const int iy, const int iz) {
+    return ((unsigned long long)(unsigned)(ix + (1 << 20)) << 42) | ((unsigned long long)(unsigned)(iy + (1 << 20)) << 21) |
+           (unsigned long long)(unsigned)(iz + (1 << 20));
+}
+__device__ __forceinline__ void cloud_cell_of_key(const unsigned long long key, int& ix, int& iy, int& iz) {
+    ix = (int)((key >> 42) & 0x1fffffu) - (1 << 20); iy = (int)((key >> 21) & 0x1fffffu) - (1 << 20); iz = (int)(key & 0x1fffffu) - (1 << 20);
+}
+// a key as the two ints (lo, hi) a 16 B table entry or unit record carries, and back
+__device__ __forceinline__ int cloud_key_lo(const unsigned long long key) { return (int)(unsigned)(key & 0xffffffffull); }
+__device__ __forceinline__ int cloud_key_hi(const unsigned long long key) { return (int)(unsigned)(key >> 32); }
+__device__ __forceinline__ unsigned long long cloud_key_join(const int lo, const int hi) { return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo; }
+// the tables' hash of a key (the 64-bit finaliser of MurmurHash3)
+__device__ __forceinline__ unsigned cloud_key_hash(unsigned long long k) {
+    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
+    return (unsigned)k;
 }
 
 // ---- the de-skew of one point by its intensity (reference Preprocessing.cpp:176-200, LidarOdometry.cpp:180-201: the same body twice)
@@ -81,11 +107,12 @@ struct CloudBox {
 };
 
 // ---- workgroup scan and rank (NW wavefronts, every thread of the workgroup calls; s_w: NW ints of LDS, free again on return)
-__device__ __forceinline__ int cloud_wave_incl_scan(const int v) {
-    const int lane = threadIdx.x & 63;
+// inclusive scan inside every aligned group of W lanes of a wavefront (W a power of two; 64 = the whole wavefront)
+template <int W = 64> __device__ __forceinline__ int cloud_wave_incl_scan(const int v) {
+    const int lane = threadIdx.x & (W - 1);
     int incl = v;
 #pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(incl, off, 64); if (lane >= off) incl += o; }
+    for (int off = 1; off < W; off <<= 1) { const int o = __shfl_up(incl, off, W); if (lane >= off) incl += o; }
     return incl;
 }
 // the sum of the wavefronts' totals before this thread's wavefront; total = all of them

@@ -131,20 +131,14 @@ __global__ void k_lm_bbox_union(const int* __restrict__ slot_bbox, const int* __
     for (int k = 0; k < width; ++k) if (ns[k] > 0) v = c < 3 ? min(v, slot_bbox[6 * k + c]) : max(v, slot_bbox[6 * k + c]);
     bbox[c] = v;
 }
-__device__ __forceinline__ unsigned lm_hash(unsigned long long k) {
-    k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
-    return (unsigned)k;
-}
-__device__ __forceinline__ unsigned long long lm_key(int ix, int iy, int iz) {        // absolute voxel coordinates, 21 bits each, biased
-    return ((unsigned long long)(unsigned)(ix + (1 << 20)) << 42) | ((unsigned long long)(unsigned)(iy + (1 << 20)) << 21) | (unsigned long long)(unsigned)(iz + (1 << 20));
-}
+// (the voxel's key = cloud_cell_key of its absolute voxel coordinates, hashed by cloud_key_hash: cloud_device.h)
 // add (sign = +1) or remove (sign = -1) one point.
 // A removal may assume that its key is in the table only while every insertion since the last table reset found a place.  After an overflow (bit 30 of
 // *nkeys) some points of a keyframe were never inserted: their removal meets an empty slot, or walks a table without one, and then leaves every slot
 // as it is -- the table is no longer what the ring holds anyway, and the host reconstructs it from the ring at the next build (lm_voxelize).
 __device__ __forceinline__ void lm_table_add(const float4 p, const float inv_leaf, const int sign, unsigned long long* keys, long long* sum, int* cnt, const int cap, int* nkeys) {
-    const unsigned long long key = lm_key((int)floorf(p.x * inv_leaf), (int)floorf(p.y * inv_leaf), (int)floorf(p.z * inv_leaf));
-    unsigned s = lm_hash(key) & (cap - 1);
+    const unsigned long long key = cloud_cell_key((int)floorf(p.x * inv_leaf), (int)floorf(p.y * inv_leaf), (int)floorf(p.z * inv_leaf));
+    unsigned s = cloud_key_hash(key) & (cap - 1);
     int probes = 0;
     for (;;) {
         const unsigned long long k = sign > 0 ? atomicCAS(keys + s, LM_EMPTY, key) : keys[s];
@@ -182,7 +176,8 @@ __global__ __launch_bounds__(1024) void k_lm_list(const unsigned long long* __re
 #pragma unroll
     for (int c = 0; c < 3; ++c) { min_b[c] = (int)floorf(ord2f(bbox[c]) * inv_leaf); div_b[c] = (int)floorf(ord2f(bbox[3 + c]) * inv_leaf) - min_b[c] + 1; }
     const unsigned long long k = keys[s];
-    const int ix = (int)((k >> 42) & 0x1fffff) - (1 << 20), iy = (int)((k >> 21) & 0x1fffff) - (1 << 20), iz = (int)(k & 0x1fffff) - (1 << 20);
+    int ix, iy, iz;
+    cloud_cell_of_key(k, ix, iy, iz);
     const unsigned long long lin = (unsigned long long)((long long)(ix - min_b[0]) + (long long)(iy - min_b[1]) * div_b[0] + (long long)(iz - min_b[2]) * div_b[0] * (long long)div_b[1]);
     const int v = s_base + rk;
     if (v < max_vox) { vkey[v] = lin; vslot[v] = s; }
@@ -323,8 +318,8 @@ __global__ void k_lm_scatter_idx(const float4* __restrict__ ring, const int* __r
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= ns[slot]) return;
     const float4 p = ring[(size_t)slot * cap + j];
-    const unsigned long long key = lm_key((int)floorf(p.x * inv_leaf), (int)floorf(p.y * inv_leaf), (int)floorf(p.z * inv_leaf));
-    unsigned s = lm_hash(key) & (table_cap - 1);
+    const unsigned long long key = cloud_cell_key((int)floorf(p.x * inv_leaf), (int)floorf(p.y * inv_leaf), (int)floorf(p.z * inv_leaf));
+    unsigned s = cloud_key_hash(key) & (table_cap - 1);
     while (keys[s] != key) s = (s + 1) & (table_cap - 1);              // (every ring point's voxel is in the table)
     const int pos = atomicAdd(fill + s, 1);
     plist[slot_start[s] + pos] = age * cap + j;
